@@ -15,8 +15,8 @@ step k + 1 starts on the compute units step k has already left; the chains of th
 (include/aacgpu.h; --serial: aacg_decode_device on one stream, every launch behind the one before it, the method of rounds
 1-4).  ONE plan, ONE set of 256 streams continued launch after launch either way (`config.pipelines` 1).
 
-Timing: W untimed warm-up steps, then the timed region of exactly K steps — R times back to back (--repeats, default 25;
-regions shorter than 80 steps are repeated until about 2000 launches are timed, and timed in runs of consecutive repeats of at
+Timing: W untimed warm-up steps, then the timed region of exactly K steps (--steps).  --repeats R runs that region R times back
+to back (default 1: K timed steps in all; with R > 1, regions shorter than 100 steps are timed in runs of consecutive repeats of at
 least 100 launches — the marks go behind every G-th repeat, G x K >= 100: region_stats says why the median wants such runs, and
 marks as dense as three per twenty launches cost the overlapped route up to 1.5 us per launch).  A timed run ends when its last launches —
 one per pipeline stream: they run side by side — are complete: HIP events bound to those dispatches' completion
@@ -32,6 +32,9 @@ config.preconditioning): a few hundred steps are over before the clocks have ram
 
 After the timed region (untimed): every stream is reset, one more step runs, and its PCM is compared with the
 oracle on the whole batch (`parity_rms`, `parity_rel`; gate 1e-5 / 5e-6 — the run fails if it is missed).
+--dump-outputs DIR: the PCM the last timed step wrote (what a caller of the path receives) as DIR/pcm.npy in float32 (int16
+PCM as its integer values), written before the parity step; above DUMP_MAX_BYTES a fixed, seeded sample of it, with the sample's
+positions in DIR/pcm_index.npy.  The inputs depend on the arguments alone, so two builds can be compared output for output.
 
 N > 1: one rank per GPU under torch.distributed.run (the driver's launch line); started without it, `--gpus N`
 launches the N ranks itself as a child process before touching the GPU.  Streams are sharded over ranks (every
@@ -50,6 +53,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec peak (6.29 TB/s measured copy)
 STREAMS, FRAMES = 256, 16      # config 2: 4096 stereo frames per batch per GPU
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 
 
 def workload_shape(workload):
@@ -81,6 +85,27 @@ def region_stats(region_ms, steps, group=1):
     if g > 1:
         out["median_over"] = "%d runs of %d consecutive repeats (%d launches each)" % (m, g, g * steps)
     return out
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Writes {name: array} as out_dir/<name>.npy in float32, within max_bytes in all: an array whose share is too large is
+    replaced by a fixed, seeded sample of its elements (in order), and the sample's flat positions go to <name>_index.npy
+    (float64, exact).  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = max_bytes // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).astype(np.float32).ravel()
+        if a.nbytes > share:
+            n = (share - 1024) // (4 + 8)                        # the sample and its positions, room for the two headers
+            idx = np.sort(np.random.default_rng(0xAAC0D).choice(a.size, size=n, replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            written[name + "_index.npy"] = idx.shape
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = a.shape
+    return written
 
 
 def whole_job_value(world, frames_per_step, ms_per_step):
@@ -126,14 +151,26 @@ def measured_traffic(kernel):
     return None, None
 
 
+def load_oracle():
+    """The oracle library as build() left it, opened without writing into the tree (which may be read-only to whoever runs the
+    bench); made through orc's own build step only when it is missing, or out of date in a directory that can be written."""
+    import subprocess
+    import orc
+    odir = os.path.join(ROOT, "oracle")
+    path = os.path.join(odir, "liboracle.so")
+    if os.path.exists(path) and (not os.access(odir, os.W_OK) or subprocess.run(
+            ["make", "-q", "-C", odir, "liboracle.so"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode == 0):
+        return orc.Oracle(path)
+    return orc.load()
+
+
 def cpu_baseline(kind, mix, layout, n_chan, budget_s=10.0, all_cores=True):
     """The oracle (plain C restatement of the reference algorithm, bit-exact with aac.js) on the host cores, on a
     bounded sample of the same workload: batches of 4 streams x 16 frames for ~budget_s on ONE core, then one such
     stream set per thread on ALL the cores this process may use for ~budget_s / 2 (oracle/orc_bench.c)."""
     import numpy as np
     import aacgpu_workload
-    import orc
-    o = orc.load()
+    o = load_oracle()
     wl = aacgpu_workload.make_batch(n_streams=4, n_frames=FRAMES, mix=mix, layout=layout, seed=0xAAC00002)
     ov = np.zeros((4, n_chan, 1024), np.float32)
     coeffs = wl["q"]
@@ -178,7 +215,6 @@ def parity_check(eng, plan, step0, bufs, host_in0, base, units, tns, n_streams, 
     buffer set 0 and compare the whole batch with the oracle.  Returns (rms error, rms error / signal rms)."""
     import numpy as np
     import torch
-    import orc
     torch.cuda.synchronize()
     for s in range(n_streams):
         eng.reset_stream(s)
@@ -191,7 +227,7 @@ def parity_check(eng, plan, step0, bufs, host_in0, base, units, tns, n_streams, 
     if got.dtype == np.int16:                              # AACG_OUTPUT_I16: compared on the float scale (half a step of rounding on top)
         got = got.astype(np.float32) / np.float32(32768.0)
     ov = np.zeros((n_streams, n_chan + (1 if cce is not None else 0), 1024), np.float32)
-    ref = orc.load().decode_batch(units, host_in0, base["meta"] if host_in0.dtype == np.int16 else None, base["n_pcm"], ov, tns=tns, cce=cce)
+    ref = load_oracle().decode_batch(units, host_in0, base["meta"] if host_in0.dtype == np.int16 else None, base["n_pcm"], ov, tns=tns, cce=cce)
     if d_out.dtype == torch.int16:                         # int16 PCM saturates (TNS SPEC filters have gain): so does the yardstick
         ref = np.clip(ref, -1.0, 32767.0 / 32768.0)
     d = got.astype(np.float64) - ref
@@ -216,8 +252,9 @@ def main():
                          "(supplementary; the reference parses coupling elements and never applies them)")
     ap.add_argument("--output", choices=["f32", "i16"], default="f32",
                     help="i16: AACG_OUTPUT_I16 engine (supplementary; the reference returns float PCM, which is what the headline measures)")
-    ap.add_argument("--repeats", type=int, default=25,
-                    help="R: the K-step timed region is run R times back to back, each bracketed by its own HIP events; ms_per_step is the median")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="R: the K-step timed region is run R times back to back, each bracketed by its own HIP events; ms_per_step is the median "
+                         "(default 1: exactly K timed steps)")
     ap.add_argument("--default-events", action="store_true",
                     help="time with torch.cuda.Event (default HIP events: a system-scope fence per record) instead of timing-only events")
     ap.add_argument("--strict-backend", action="store_true",
@@ -239,6 +276,8 @@ def main():
     ap.add_argument("--wait-mode", type=int, default=-1, choices=[-1, 0, 1, 2, 3],
                     help="measurement only (aacg_debug_set_wait_mode): how the engine's host waits wait — 0 poll without pause (round 5), 1 yield, 2 the shipped "
                          "policy spelled out, 3 blocking events; -1 (default): whatever the library ships")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the PCM of the last timed step to DIR/pcm.npy (float32; a seeded sample above 64 MB; rank 0)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing on a box with fewer GPUs than ranks: rank r uses device r mod device_count (use with --dist-backend gloo)")
     args = ap.parse_args()
@@ -358,11 +397,11 @@ def main():
     # so a few hundred warm-up steps are over before the clocks have ramped (measured: 15.9 us per step after 40
     # warm-up steps, 14.2 us after 4000).  Untimed preconditioning, reported in the JSON line; then the W warm-up
     # steps of the contract; the timed region is exactly K steps.
-    # R repeats of the K-step region.  With overlapped launches a repeat's end is the completion of launches that run side by
-    # side with the next repeat's first ones, so short regions scatter by a launch or so either way around the same mean
-    # (K = 20: 9.2-12.8 us per step over 25 repeats, mean 11.43 both times, medians 11.22 and 11.89 in two runs): short
-    # regions are repeated more often, until about 2000 launches are timed — the median settles, the run stays short.
-    R = max(1, args.repeats, min(200, -(-2000 // max(1, args.steps))) if args.repeats == 25 else args.repeats)
+    # R repeats of the K-step region (default 1: the timed steps are exactly --steps).  With overlapped launches a repeat's end is
+    # the completion of launches that run side by side with the next repeat's first ones, so short regions scatter by a launch or
+    # so either way around the same mean (K = 20: 9.2-12.8 us per step over 25 repeats, mean 11.43 both times, medians 11.22 and
+    # 11.89 in two runs): a short K wants --repeats for a settled median.
+    R = max(1, args.repeats)
     # Timing marks: HIP events that only measure time (hipEventDisableSystemFence, aacg_timer_*).  A default event's record is
     # a system-scope fence — cache write-back and invalidation — and the launch behind it starts on cold caches: at the
     # driver's K = 20 that is one fence per 240 us of launches (12.45 against 12.13 us per step at K = 2000 on one box).
@@ -388,7 +427,7 @@ def main():
     # every twenty launches cost the overlapped route 1.1-1.5 us per launch on a box whose default line reads 11.0 (12.2-12.6 at the
     # driver's K = 20; with K = 100, three marks per hundred launches: 10.9-11.0; `--default-events`: 11.3): the same K-step region,
     # the same R x K launches back to back, fewer time stamps taken inside them.
-    group = -(-100 // args.steps) if (bound and args.steps < 100) else 1
+    group = min(R, -(-100 // args.steps)) if (bound and args.steps < 100) else 1
     if group > 1:
         R = -(-R // group) * group
     n_marked = R // group
@@ -404,6 +443,9 @@ def main():
             step(n_pre, flat_marks[n_pre] if n_pre < len(flat_marks) else None)
             n_pre += 1
         torch.cuda.synchronize()
+    while n_pre % args.nbuf:                             # whole rounds of the buffer sets: the last timed step's buffers do not depend on the clock
+        step(n_pre)
+        n_pre += 1
     for i in range(args.warmup):
         step(n_pre + i)
     def timed_steps():
@@ -458,13 +500,16 @@ def main():
 
     abytes_step = algorithmic_bytes_per_channel_frame(args.input, n_frames, args.output) * n_streams * n_frames * n_chan
     copy_reps = max(20, min(args.steps, 400))
-    copy_gbs, copy_stats = copy_rate(abytes_step / 2, max(2, args.nbuf), copy_reps, R)
+    copy_gbs, copy_stats = copy_rate(abytes_step / 2, max(2, args.nbuf), copy_reps, max(R, 25))
     copy_ms = copy_stats["ms_per_step_median"]
     copy_large_gbs, _ = copy_rate(1 << 29, 2, 20, 1)
 
     # untimed: the last output is finite and non-trivial; then the oracle comparison on the bench's own batch
     out = bufs[(n_pre + args.warmup + R * args.steps - 1) % args.nbuf][1]
     ok = bool(torch.isfinite(out.float()).all().item()) and float(out.float().abs().max().item()) > 0
+    if args.dump_outputs and rank == 0:                  # before the parity step, which reuses buffer set 0
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {"pcm": out.cpu().numpy()})
     parity = None
     if not args.no_parity:
         err, rel, finite = parity_check(eng, plans[0], lambda: step(0), bufs, host_in0, base, units, tns, n_streams, n_chan, tstream, cce)
@@ -527,7 +572,7 @@ def main():
                      "copy_ceiling_GBs": copy_gbs, "frac_of_copy": achieved / copy_gbs, "copy_ms": copy_ms,
                      "copy_timing": copy_stats,
                      "copy_ceiling_note": "aacg_calib_copy: float4 copy of the step's algorithmic byte volume (half read, half written) with the run "
-                                          "kernel's launch shape, %d x %d launches right behind the timed region on the same stream (median repeat); 1 GiB copy: %.0f GB/s" % (R, copy_reps, copy_large_gbs),
+                                          "kernel's launch shape, %d x %d launches right behind the timed region on the same stream (median repeat); 1 GiB copy: %.0f GB/s" % (max(R, 25), copy_reps, copy_large_gbs),
                      "copy_ceiling_large_GBs": copy_large_gbs,
                      "kernel": kernel_names,
                      "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": abytes,

@@ -4,8 +4,8 @@
  *
  *   node tests/js/test_frontend.js [outdir]
  *
- * Runs anywhere (the codebooks ship in aac.js_amd/data/); the parts that compare with the reference run where its
- * checkout is (the build container).
+ * Runs anywhere (the codebooks ship in aac.js_amd/data/); the parts that compare with the reference run only when
+ * AACJS_REFERENCE_SRC names the src/ directory of an aac.js checkout.
  *
  *  1. codebooks: the shipped books' lookup tables decode every code word back; with the reference present, the shipped
  *     books equal what walking the prefix trees of its huffman.js decoder recovers (probe_provider.js)
@@ -13,11 +13,11 @@
  *     back bit-exactly — all window sequences, groupings, section escapes, the three scalefactor classes,
  *     M/S masks, pulse and TNS side info, DSE / FIL / CCE elements in between, ADTS with and without CRC, raw
  *     packets, several sample rates and channel layouts; the reference's error messages for malformed input
- *  3. with the reference checkout present: the same bytes go through the reference's own readChunk()
- *     (decoder.js:125-216, its real Bitstream calls, Huffman, ICS, CPE, CCE parsers), and what it parsed
- *     (window info, band types, scalefactors, every quantised integer) must equal what FrontEnd produced;
- *     its PCM is written to `outdir` next to the engine inputs FrontEnd + GpuAACDecoder produced, for
- *     tests/test_frontend.py to decode through the oracle / the emulated kernels / the GPU.
+ *  3. the engine inputs FrontEnd + GpuAACDecoder produce from the written streams go to `outdir`, for
+ *     tests/test_frontend.py to compare with the committed tests/golden/streams; with the reference checkout present
+ *     the same bytes also go through the reference's own readChunk() (decoder.js:125-216, its real Bitstream calls,
+ *     Huffman, ICS, CPE, CCE parsers), what it parsed (window info, band types, scalefactors, every quantised
+ *     integer) must equal what FrontEnd produced, and its PCM is written beside them (.refpcm).
  */
 'use strict';
 const fs = require('fs'), path = require('path'), assert = require('assert');
@@ -30,8 +30,8 @@ const { FrontEnd, swbOffsets, tnsCoefTable } = require(path.join(root, 'aac.js_a
 const { Writer, BitWriter, Rng } = require('./aac_writer.js');
 const { randomFrame, layoutChannels, CASES, PATTERN } = require('./stream_cases.js');
 
-const REF = '/root/reference/src/';
-const haveRef = fs.existsSync(REF + 'decoder.js');
+const REF = process.env.AACJS_REFERENCE_SRC ? path.resolve(process.env.AACJS_REFERENCE_SRC) + path.sep : null;
+const haveRef = REF !== null && fs.existsSync(REF + 'decoder.js');
 const outdir = process.argv[2] || null;
 
 /* ---- 0. bit reader ------------------------------------------------------------------------------------ */
@@ -197,29 +197,33 @@ for (const c of CASES) {
     assert.throws(() => fe.parseFrame({ config: config }), /Invalid ADTS header\./);
 }
 
-/* ---- 3. the same bytes through the reference ---------------------------------------------------------- */
+/* ---- 3. the engine inputs of the written streams; the same bytes through the reference ------------------------------ */
 let compared = 0;
-if (haveRef) {
-    process.env.NODE_PATH = path.join(root, 'tests', 'golden', 'gen', 'stubs');
-    require('module').Module._initPaths();
-    const AACDecoder = require(REF + 'decoder.js'), FilterBank = require(REF + 'filter_bank.js'), refTables = require(REF + 'tables.js');
-    const refHuffman = require(REF + 'huffman.js');
-    let ints = null;
-    const inner = refHuffman.decodeSpectralData;
-    refHuffman.decodeSpectralData = function (stream, book, data, off) {               // ics.js:247 calls through the module object
-        inner.call(this, stream, book, data, off);
-        for (let j = 0; j < (book < 5 ? 4 : 2); j++) ints.push(data[off + j]);
-    };
+{
+    let AACDecoder = null, FilterBank = null, refTables = null, ints = null;
+    if (haveRef) {
+        process.env.NODE_PATH = path.join(root, 'tests', 'golden', 'gen', 'stubs');
+        require('module').Module._initPaths();
+        AACDecoder = require(REF + 'decoder.js'); FilterBank = require(REF + 'filter_bank.js'); refTables = require(REF + 'tables.js');
+        const refHuffman = require(REF + 'huffman.js');
+        const inner = refHuffman.decodeSpectralData;
+        refHuffman.decodeSpectralData = function (stream, book, data, off) {               // ics.js:247 calls through the module object
+            inner.call(this, stream, book, data, off);
+            for (let j = 0; j < (book < 5 ? 4 : 2); j++) ints.push(data[off + j]);
+        };
+    }
     const manifest = [];
     for (const c of CASES) {
         if (c.o.quirks === false) continue;                    // standard-syntax coupling elements: the reference parses those differently
         const wr = new Writer(cb, c.si), C = layoutChannels(c.layout), usable = !c.o.pns && !c.o.pulse;
-        const ref = new AACDecoder();
-        ref.format = {};
-        ref.config = { profile: 2, sampleIndex: c.si, sampleRate: host.SAMPLE_RATES[c.si], chanConfig: C, frameLength: 1024 };
-        ref.filter_bank = new FilterBank(false, C);
-        let refElements = null;
-        ref.process = function (elements) { refElements = elements; if (usable) AACDecoder.prototype.process.call(this, elements); else this.data = []; };
+        let ref = null, refElements = null;
+        if (haveRef) {
+            ref = new AACDecoder();
+            ref.format = {};
+            ref.config = { profile: 2, sampleIndex: c.si, sampleRate: host.SAMPLE_RATES[c.si], chanConfig: C, frameLength: 1024 };
+            ref.filter_bank = new FilterBank(false, C);
+            ref.process = function (elements) { refElements = elements; if (usable) AACDecoder.prototype.process.call(this, elements); else this.data = []; };
+        }
 
         /* mine: the whole stream through GpuAACDecoder.readChunk with an engine that records its input */
         const captured = {}, fe = new FrontEnd({ codebooks: cb });
@@ -233,6 +237,7 @@ if (haveRef) {
             fe1.push(bytes);
             const f = fe1.parseFrame(dec);
             mine.push(f);
+            if (!haveRef) return;
             ints = [];
             ref.bitstream = new BitStream(bytes);
             let pcm = null;
@@ -301,7 +306,7 @@ if (haveRef) {
         fs.writeFileSync(path.join(outdir, c.name + '.units'), Buffer.from(captured.units));
         fs.writeFileSync(path.join(outdir, c.name + '.q'), Buffer.from(captured.q.buffer));
         fs.writeFileSync(path.join(outdir, c.name + '.meta'), Buffer.from(captured.meta.buffer));
-        fs.writeFileSync(path.join(outdir, c.name + '.refpcm'), Buffer.from(refPcm.buffer));
+        if (haveRef) fs.writeFileSync(path.join(outdir, c.name + '.refpcm'), Buffer.from(refPcm.buffer));
         manifest.push({ name: c.name, sampleIndex: c.si, channels: C, frames: c.frames });
     }
     if (outdir) fs.writeFileSync(path.join(outdir, 'manifest.json'), JSON.stringify(manifest));

@@ -113,3 +113,29 @@ def test_rank_local_arithmetic_of_the_config4_line_at_8_gpus():
     assert bench.backend_fields("nccl", None)["dist_world_size"] == 1
     # per-GPU algorithmic bytes of config 4: 128-frame chains
     assert bench.algorithmic_bytes_per_channel_frame("quant", n_frames) == 2048 + 240 + 4096 + 64
+
+
+def test_dump_outputs_float32_within_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as float32 .npy; one that does not fit its share of the cap is replaced by the same
+    seeded sample of its elements every time, with the sample's positions beside it, and the files stay within the cap."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    pcm = (np.arange(50000, dtype=np.int16) - 25000).astype(np.int16)
+    small = np.linspace(-1, 1, 1000, dtype=np.float64)
+    cap = 200000
+    written = bench.dump_outputs(str(tmp_path / "a"), {"pcm": pcm, "small": small}, max_bytes=cap)
+    assert sorted(written) == ["pcm.npy", "pcm_index.npy", "small.npy"]
+    files = sorted((tmp_path / "a").iterdir())
+    assert [f.name for f in files] == sorted(written) and sum(f.stat().st_size for f in files) <= cap
+    got, idx, s = (np.load(tmp_path / "a" / n) for n in ("pcm.npy", "pcm_index.npy", "small.npy"))
+    assert got.dtype == np.float32 and s.dtype == np.float32 and idx.dtype == np.float64
+    assert np.array_equal(s, small.astype(np.float32))
+    assert 0 < got.size < pcm.size and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got, pcm[idx.astype(np.int64)].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "b"), {"pcm": pcm, "small": small}, max_bytes=cap)
+    for n in written:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    whole = bench.dump_outputs(str(tmp_path / "c"), {"pcm": pcm})
+    assert whole == {"pcm.npy": (pcm.size,)}

@@ -41,10 +41,12 @@ def test_launch_command_is_the_drivers_line():
 
 
 def test_bench_refuses_to_run_without_a_gpu():
-    """bench.py --gpus 2 here (no GPU): it must start two ranks by itself and each must fail loudly — no CPU fallback."""
+    """bench.py --gpus 2 with no GPU (any present are hidden from it): it must start two ranks by itself and each must fail
+    loudly — no CPU fallback."""
     import subprocess
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo"],
-                       capture_output=True, text=True, timeout=600)
+                       capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode != 0
     assert "bench.py needs a GPU" in r.stdout + r.stderr
 

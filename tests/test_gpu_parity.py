@@ -642,6 +642,30 @@ def test_bench_launches_its_own_ranks():
     assert abs(line["value"] - 2 * 4096 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
 
 
+def test_bench_dumps_its_last_timed_step(tmp_path, oracle):
+    """`bench.py --steps K --dump-outputs DIR`: the line times exactly K steps (one run of the region), and DIR/pcm.npy is the PCM
+    of the last of them.  With one buffer set every step decodes the same config-2 batch, so that PCM is the batch decoded
+    behind itself: the oracle's second pass over it, chained through the overlap state."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "37", "--warmup", "3", "--precondition-ms", "20", "--nbuf", "1",
+                        "--no-cpu-baseline", "--no-parity", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 37 and line["timing"]["repeats"] == 1 and line["output_ok"]
+    assert sorted(os.listdir(tmp_path)) == ["pcm.npy"]
+    pcm = np.load(tmp_path / "pcm.npy")
+    wl = aacgpu_workload.make_batch(n_streams=256, n_frames=16, seed=0xAAC00002)
+    ov = np.zeros((256, 2, 1024), np.float32)
+    first = oracle.decode_batch(wl["units"], wl["q"], wl["meta"], wl["n_pcm"], ov)
+    ref = oracle.decode_batch(wl["units"], wl["q"], wl["meta"], wl["n_pcm"], ov)
+    assert pcm.dtype == np.float32 and pcm.shape == (wl["n_pcm"],)
+    assert rms(pcm, ref) < RMS_TOL and not np.allclose(first, ref)
+
+
 def test_plan_refresh_units_keeps_one_plan(oracle):
     """aacg_plan_refresh_units: batch after batch of the same streams — new window sequences, shapes, grouping, M/S and block
     offsets every time (the config-3 mix at different phases) — runs on ONE plan whose unit records are replaced from the
