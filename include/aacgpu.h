@@ -227,7 +227,10 @@ enum {                          /* aacg_config.output_kind (ABI version 4)      
     AACG_OUTPUT_I16 = 1         /* the same samples as int16: round-to-nearest(x * 32768), saturated — half the
                                    bytes of the path's dominant stream, for hosts that feed 16-bit sinks.  Every
                                    `pcm` pointer of such an engine is an int16_t*, every PCM count is in samples.
-                                   Not aac.js behaviour: an explicit output format              */
+                                   Not aac.js behaviour: an explicit output format.  A NaN
+                                   sample (the reference's out-of-range IQ read, |q| >= 8191) becomes -32768: the
+                                   clamp is v_med3_f32, whose result with a NaN operand is the least of the other
+                                   two (tests/test_output_edges.py pins it on the device and in the emulator)     */
 };
 
 typedef struct aacg_config {

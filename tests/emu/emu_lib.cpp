@@ -76,6 +76,8 @@ int g_out_kind = AACG_OUTPUT_F32;          /* emu_set_output_kind: the next deco
 int g_unfused = 0;                         /* emu_set_unfused: independent coupling as the separate pass over the PCM even where the engine fuses it */
 int g_rv = 1;                              /* emu_set_rv: chains longer than a run through the run-to-run rendezvous (the engine's route; 2: blocks in reverse); 0: recomputed frames */
 int g_staged = 0;                          /* emu_set_staged: optional stages as a launch of their own even where the engine would not */
+int g_pipelined = 0;                       /* emu_set_pipelined: the route aacg_decode_pipelined takes for the plan, as one launch */
+std::vector<unsigned> g_keys;              /* emu_last_keys: the run kernels (AACG_RK_* keys, NT bit included) the last decode launched, in order */
 
 /* one workgroup of a launch, its lanes as threads */
 void run_block(const aacg_kparams& P, int kind, unsigned key, int block, int waves, size_t lds_bytes, int n_units = 0, const aacg_parse_params* PP = nullptr,
@@ -118,6 +120,7 @@ void run_block(const aacg_kparams& P, int kind, unsigned key, int block, int wav
 void launch(const aacg_kparams& P, int kind, unsigned key, int grid, int waves, size_t lds_bytes, int n_units = 0, const aacg_parse_params* PP = nullptr,
             const aacg_couple_params* Q = nullptr, const aacg_rv_args* V = nullptr)
 {
+    if (kind == 1) g_keys.push_back(key);
     for (int b = 0; b < grid; b++) run_block(P, kind, key, b, waves, lds_bytes, n_units, PP, Q, V);
 }
 
@@ -138,6 +141,14 @@ extern "C" {
 
 const char* emu_last_error() { return g_err.c_str(); }
 void emu_set_staged(int on) { g_staged = on; }
+void emu_set_pipelined(int on) { g_pipelined = on; }
+/* the keys of the run kernels the last emu_decode* launched (a coupling elements' pass included), in launch order: how many there
+ * were; the first `cap` of them into `keys` */
+int emu_last_keys(unsigned* keys, int cap)
+{
+    for (int i = 0; i < cap && i < (int)g_keys.size(); i++) keys[i] = g_keys[(size_t)i];
+    return (int)g_keys.size();
+}
 void emu_set_rv(int on) { g_rv = on; }
 void emu_set_unfused(int on) { g_unfused = on; }
 void emu_set_output_kind(int kind) { g_out_kind = kind; }       /* AACG_OUTPUT_*: the pcm buffer of later decodes is int16 */
@@ -237,10 +248,11 @@ int emu_decode_cce(int input_kind, int sample_index, int max_streams, int max_ch
     aacg_plan_host ph;
     int rc = aacg_plan_build(units, n_units, sample_index, max_streams, max_channels, parity, &ph, &g_err, tns, n_tns, cce, n_cce);
     if (rc) return rc;
+    g_keys.clear();
     if (ph.pcm_floats > n_pcm_floats) { g_err = "pcm buffer too small"; return AACG_ERR_CAPACITY; }
     if (ph.zero_fill) std::memset(pcm, 0, n_pcm_floats * (g_out_kind == AACG_OUTPUT_I16 ? 2 : 4));
     if (ph.any_pns && (pns_mode != AACG_PNS_SPEC || input_kind != AACG_INPUT_QUANT_I16)) { g_err = "PNS unit in a batch without AACG_PNS_SPEC"; return AACG_ERR_UNSUPPORTED; }
-    aacg_route R = aacg_pick_route(input_kind, g_out_kind, (g_unfused ? AACG_DEBUG_ROUTE_UNFUSED_COUPLING : 0) | (g_rv ? 0 : AACG_DEBUG_ROUTE_RECOMPUTE), false, ph, false);
+    aacg_route R = aacg_pick_route(input_kind, g_out_kind, (g_unfused ? AACG_DEBUG_ROUTE_UNFUSED_COUPLING : 0) | (g_rv ? 0 : AACG_DEBUG_ROUTE_RECOMPUTE), false, ph, g_pipelined != 0);
     if (g_staged && R.has_run && (R.run_key & AACG_RK_EX)) {     /* test switch: the optional stages as a launch of their own even where the engine runs them inside */
         R.stage = AACG_STAGE_SPECTRAL_EX; R.stage_quant = input_kind == AACG_INPUT_QUANT_I16;
         R.run_key = ph.needs_scratch ? AACG_RK_DD : 0; R.rv = false;
@@ -350,6 +362,7 @@ int emu_decode_pipelined(int input_kind, int sample_index, int max_streams, int 
     if (rc) return rc;
     if (ph.pcm_floats > n_pcm_floats) { g_err = "pcm buffer too small"; return AACG_ERR_CAPACITY; }
     const aacg_route R = aacg_pick_route(input_kind, AACG_OUTPUT_F32, 0, false, ph, true);
+    g_keys.clear();
     if (!R.overlappable) { g_err = "not a plain batch"; return AACG_ERR_UNSUPPORTED; }
     static unsigned long long epoch = 5000;
     const int NS = streams > 0 ? streams : aacg_pipeline_streams(ph, R.run_key);          /* streams the sequence takes in turn (0: the engine's choice) */
@@ -413,6 +426,7 @@ int emu_decode_pipelined(int input_kind, int sample_index, int max_streams, int 
             remaining--;
         }
     }
+    for (int j = 0; j < n_launches; j++) g_keys.push_back(R.run_key);
     for (auto& jb : sched)
         run_block(P[(size_t)jb.first], 1, R.run_key, jb.second, AACG_WG_WAVES, run_lds_bytes(R.run_key), 0, nullptr, nullptr, &V[(size_t)jb.first]);
     for (auto& c : ph.chains)

@@ -45,24 +45,31 @@ class Emu:
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int]
         L.emu_get_windows.argtypes = [C.c_int, C.c_void_p]
         L.emu_get_iq_sf.argtypes = [C.c_void_p, C.c_void_p]
+        L.emu_last_keys.argtypes = [C.c_void_p, C.c_int]
 
     def error(self):
         return self.lib.emu_last_error().decode()
 
-    def decode(self, units, coeffs, meta, n_pcm, pool, parity, sample_index=3, tns=None, pns=False, int16_out=False, cce=None, staged=False, unfused=False, rv=1):
+    def decode(self, units, coeffs, meta, n_pcm, pool, parity, sample_index=3, tns=None, pns=False, int16_out=False, cce=None, staged=False, unfused=False, rv=1,
+               pipelined=False, poison=None):
         """staged: the optional stages (TNS, PNS) as a launch of their own even where the engine would run them inside the run kernel.
         unfused: independent coupling as the separate pass over the PCM (what plans with double-duty runs take) even where the
-        engine applies it in the targets' epilogues."""
+        engine applies it in the targets' epilogues.  pipelined: the route aacg_decode_pipelined takes for the plan (the rendezvous
+        kernels for plain batches and batches with optional stages), as one launch.  poison: what the output holds before the
+        decode (default NaN, int16 -32768)."""
         units = np.ascontiguousarray(units)
         coeffs = np.ascontiguousarray(coeffs)
         kind = 1 if coeffs.dtype == np.int16 else 0
         meta = np.ascontiguousarray(meta, np.uint16) if meta is not None else None
-        pcm = np.full(n_pcm, -32768, np.int16) if int16_out else np.full(n_pcm, np.nan, np.float32)
+        if poison is None:
+            poison = -32768 if int16_out else np.nan
+        pcm = np.full(n_pcm, poison, np.int16 if int16_out else np.float32)
         tns = np.ascontiguousarray(tns) if tns is not None else None
         self.lib.emu_set_output_kind(1 if int16_out else 0)
         self.lib.emu_set_staged(1 if staged else 0)
         self.lib.emu_set_unfused(1 if unfused else 0)
         self.lib.emu_set_rv(rv)           # 1: chains longer than a run through the run-to-run rendezvous (the engine's route); 2: blocks in reverse; 0: recomputed frames
+        self.lib.emu_set_pipelined(1 if pipelined else 0)
         cce = np.ascontiguousarray(cce) if cce is not None else None
         rc = self.lib.emu_decode_cce(kind, sample_index, pool.shape[0], pool.shape[1], units.ctypes.data, len(units),
                                      coeffs.ctypes.data, meta.ctypes.data if meta is not None else None,
@@ -73,9 +80,18 @@ class Emu:
         self.lib.emu_set_staged(0)
         self.lib.emu_set_unfused(0)
         self.lib.emu_set_rv(1)
+        self.lib.emu_set_pipelined(0)
         if rc:
             raise RuntimeError("emu_decode rc=%d: %s" % (rc, self.error()))
         return pcm
+
+    def last_keys(self):
+        """The switches (AACG_RK_*, the non-temporal bit included) of every run kernel the last decode launched, in launch order:
+        the keys the emulator dispatched by (a coupling elements' pass of the plain kernel included)."""
+        n = self.lib.emu_last_keys(None, 0)
+        a = np.zeros(max(n, 1), np.uint32)
+        self.lib.emu_last_keys(a.ctypes.data, n)
+        return [int(k) for k in a[:n]]
 
     def spectral(self, units, q, meta, sample_index=3):
         units = np.ascontiguousarray(units)

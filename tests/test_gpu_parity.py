@@ -880,12 +880,24 @@ def test_rendezvous_between_runs_equals_recomputed_frames(oracle, layout, S, T, 
     rendezvous cell; aacg_imdct_run_*_rv) against the old one (later runs recompute the frame before them: _dd / predecessor
     waves; forced with AACG_DEBUG_ROUTE_RECOMPUTE) — the same bits, PCM and overlap state, over two chained batches, with more
     workgroups than the chip holds at once (so that both sides of a rendezvous arrive first somewhere) — and the oracle's values."""
+    _rendezvous_against_recompute(oracle, layout, S, T, seam, "f32")
+
+
+@pytest.mark.parametrize("layout,S,T,seam", [(("cpe",), 300, 48, "q"), (("cpe", "cpe", "cpe", "sce"), 24, 32, "f")])
+def test_rendezvous_between_runs_equals_recomputed_frames_int16(oracle, layout, S, T, seam):
+    """The same with int16 PCM: _rv_i16 (_rv_i16_nt) against _dd_i16 (a later run of 16 frames: T >= 32, not 33..47), the same
+    bits; and the oracle's PCM rounded, at most one step off."""
+    _rendezvous_against_recompute(oracle, layout, S, T, seam, "i16")
+
+
+def _rendezvous_against_recompute(oracle, layout, S, T, seam, out):
     wl0 = aacgpu_workload.make_batch(n_streams=S, n_frames=T, layout=layout, mix=True, intensity=True, seed=5200)
     C = wl0["C"]
     kind = aacgpu.INPUT_QUANT_I16 if seam == "q" else aacgpu.INPUT_SPEC_F32
+    i16 = out == "i16"
     outs, states, routes = [], [], []
     for route in (0, aacgpu.DEBUG_ROUTE_RECOMPUTE):                  # the engine's route, and the old one
-        eng = aacgpu.Engine(kind, max_streams=S, max_channels=C)
+        eng = aacgpu.Engine(kind, max_streams=S, max_channels=C, output_kind=aacgpu.OUTPUT_I16 if i16 else aacgpu.OUTPUT_F32)
         eng.debug_set_route(route)
         got = []
         for batch in range(2):
@@ -903,10 +915,21 @@ def test_rendezvous_between_runs_equals_recomputed_frames(oracle, layout, S, T, 
         states.append(overlaps(eng, S, C))
         eng.close()
     # (multichannel frames: the rendezvous kernels' variant with non-temporal loads of the spectra)
-    assert routes[0].endswith("_rv_nt" if C > 2 else "_rv") and "_rv" not in routes[1]
-    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
+    assert routes[0].endswith(("_rv" + ("_i16" if i16 else "")) + ("_nt" if C > 2 else "")) and "_rv" not in routes[1]
+    if i16:
+        assert routes[1].endswith("_dd_i16")
+    assert outs[0].dtype == (np.int16 if i16 else np.float32)
+    assert np.array_equal(outs[0].view(np.uint16 if i16 else np.uint32), outs[1].view(np.uint16 if i16 else np.uint32))
     assert np.array_equal(states[0].view(np.uint32), states[1].view(np.uint32))
-    if S * T <= 12000:
+    if i16:
+        ov = np.zeros((S, C, 1024), np.float32)
+        for batch in range(2):
+            wl = aacgpu_workload.make_batch(n_streams=S, n_frames=T, layout=layout, mix=True, intensity=True, seed=5200 + batch, frame_base=batch * T)
+            ref = oracle.decode_batch(wl["units"], wl["q"], wl["meta"], wl["n_pcm"], ov)
+            d = outs[0][batch * wl["n_pcm"]:(batch + 1) * wl["n_pcm"]].astype(np.int32) - _pcm16(ref)
+            assert np.abs(d).max() <= 1 and np.count_nonzero(d) <= 1e-2 * d.size
+        assert np.abs(states[0] - ov).max() <= 1e-5 * max(1.0, float(np.abs(ov).max()))
+    elif S * T <= 12000:
         ov = np.zeros((S, C, 1024), np.float32)
         ref = []
         for batch in range(2):
