@@ -285,4 +285,13 @@ typedef struct aacg_parse_params {
     const uint32_t* order;     /* lane i parses frame order[i] (frames of similar length share a wave), or NULL: frame i */
 } aacg_parse_params;
 
+/* aacg_parse_walk_spans: P.frames = the spans, P.n_frames = their count, P.order = the lane order over the spans; P.bytes, P.tab,
+ * P.options and P.wg_threads as for the frame parser; the record pointers of P are not used */
+typedef struct aacg_walk_params {
+    aacg_parse_params P;
+    aacg_parse_frame* blocks;  /* [span][max_frames] */
+    aacg_walk_result* results; /* [span] */
+    uint32_t max_frames;
+} aacg_walk_params;
+
 #endif

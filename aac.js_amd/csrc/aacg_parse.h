@@ -384,18 +384,22 @@ DP_DEVICE void parse_cce(bit_reader& r, const lane_ctx& c)
     }
 }
 
-/* one frame: raw_data_block, after an optional ADTS header (decoder.js:129-200) */
-DP_DEVICE void parse_frame(const lane_ctx& c, uint32_t frame)
+/* one frame: raw_data_block, after an optional ADTS header (decoder.js:129-200).
+ * WALK = true (aacg_parse_walk_spans): the same syntax with every output store off — the block at w_off, up to w_len bytes, read
+ * in place; only its status and bits_used, into *w_res.  The switches below are compile-time constants, so that the frame
+ * parser's instantiation is the code it was before the walk existed. */
+template <bool WALK = false>
+DP_DEVICE void parse_frame(const lane_ctx& c, uint32_t frame, uint32_t w_off = 0, uint32_t w_len = 0, aacg_parse_result* w_res = nullptr)
 {
     const aacg_parse_params& P = *c.P;
     /* The frame's bytes go to LDS first (16-byte pieces, 8 bytes of look-ahead included), so that refilling the bit
      * window is a ds_read instead of a global load somewhere in the wave at nearly every code word (measured: about
      * 20 % off the time per launch).  A frame that does not fit any more is read in place. */
-    const uint32_t off = P.frames[frame].byte_offset, len = P.frames[frame].byte_length;
+    const uint32_t off = WALK ? w_off : P.frames[frame].byte_offset, len = WALK ? w_len : P.frames[frame].byte_length;
     const uint32_t first = off & ~15u, span = ((off + len + 8u + 15u) & ~15u) - first;
     const unsigned char* src = (const unsigned char*)P.bytes + first;
     int staged = -1;
-    const int slot = dp_lds_atomic_add(c.arena_top, (int)span);
+    const int slot = WALK ? -1 : dp_lds_atomic_add(c.arena_top, (int)span);
     if (slot >= 0 && slot + (int)span <= c.arena_bytes) {
         dpi4* dst = (dpi4*)(c.arena + slot);
         for (uint32_t k = 0; k < span / 16u; k++) dst[k] = ((const dpi4*)src)[k];
@@ -418,9 +422,9 @@ DP_DEVICE void parse_frame(const lane_ctx& c, uint32_t frame)
         if (type == 0 || type == 3 || type == 1) {
             const int n_ch = type == 1 ? 2 : 1;
             /* beyond what the caller allowed for: the element is still parsed (its own errors come first), nothing is written */
-            if (n_units >= (int)P.max_units || channel + n_ch > (int)P.max_channels) over = true;
+            if (!WALK && (n_units >= (int)P.max_units || channel + n_ch > (int)P.max_channels)) over = true;
             const uint32_t block = frame * P.max_channels + (uint32_t)channel;
-            aacg_unit_desc* u = over ? nullptr : &P.units[frame * P.max_units + (uint32_t)n_units];
+            aacg_unit_desc* u = WALK || over ? nullptr : &P.units[frame * P.max_units + (uint32_t)n_units];
             ics_info info;
             int unit_flags = 0, fl = 0;
             bool ms = false;
@@ -437,11 +441,11 @@ DP_DEVICE void parse_frame(const lane_ctx& c, uint32_t frame)
             }
             for (int k = 0; k < n_ch && !r.status; k++) {
                 const ics_out none = {nullptr, nullptr, nullptr, nullptr};
-                const ics_out o = over ? none : ics_out{ P.q + (size_t)(block + k) * 1024u, P.meta[block + k].band, P.tns ? &P.tns[block + k] : nullptr, &u->ch[k] };
+                const ics_out o = WALK || over ? none : ics_out{ P.q + (size_t)(block + k) * 1024u, P.meta[block + k].band, P.tns ? &P.tns[block + k] : nullptr, &u->ch[k] };
                 fl |= parse_ics(r, c, (unit_flags & AACG_UNIT_COMMON_WINDOW) != 0, info, o, ms && k == 0);
             }
             if (r.status) break;
-            if (over) continue;
+            if (WALK || over) continue;
             if (n_ch == 1) { aacg_chan_info* z = &u->ch[1]; for (int i = 0; i < 16; i++) ((uint8_t*)z)[i] = 0; }
             u->stream = 0; u->pcm_offset = 0; u->channel = (uint16_t)channel; u->n_out_ch = 0;
             u->n_ch = (uint8_t)n_ch; u->flags = (uint8_t)(unit_flags | ((fl & 1) ? AACG_UNIT_HAS_PNS : 0)); u->reserved0 = (uint16_t)((type << 4) | id);
@@ -467,7 +471,7 @@ DP_DEVICE void parse_frame(const lane_ctx& c, uint32_t frame)
     if (!r.status) br_skip(r, (0u - r.pos) & 7u);
     if (r.deferred) br_fail(r, r.deferred);
     if (over) br_fail(r, AACG_PARSE_CAPACITY);
-    aacg_parse_result* res = &P.results[frame];
+    aacg_parse_result* res = WALK ? w_res : &P.results[frame];
     res->status = (uint8_t)r.status; res->n_units = (uint8_t)(r.status ? 0 : n_units); res->n_channels = (uint8_t)(r.status ? 0 : channel);
     res->flags = (uint8_t)any;
     res->bits_used = r.pos - start;
@@ -494,6 +498,45 @@ DP_DEVICE void parse_body(const aacg_parse_params& P)
     if (frame >= P.n_frames) return;
     const lane_ctx c = { &P, dp_lds_addr(lds), dp_lds_addr(swb), dp_lds_addr(swb + 64), dp_lds_addr(bands + tid), threads, arena, top, (int)P.arena_bytes };
     parse_frame(c, frame);
+}
+
+/* kernel body of aacg_parse_walk_spans: lane t of block b walks span W.P.order[b * threads + t] (spans sorted by length, longest
+ * first, like the frames of parse_body).  A span holds raw_data_blocks back to back (an MP4 sample run, Aurora's feedPacket
+ * buffer); only a parse of block k tells where block k + 1 starts, so the lane parses them one after the other with the frame
+ * parser's syntax and its stores off, and records each block's (byte_offset, byte_length).  It stops at the span's end, after
+ * W.max_frames blocks, or at a block that does not parse: that block is recorded too, with the rest of the span as its length
+ * (exactly what the frame parser will then be given, so it refuses it with the same status).  The bytes are read in place: a
+ * span may be far larger than a lane's share of LDS. */
+DP_DEVICE void walk_body(const aacg_walk_params& W)
+{
+    const aacg_parse_params& P = W.P;
+    uint32_t* lds = (uint32_t*)dp_lds();
+    const aacg_parse_tables* T = P.tab;
+    const int tid = dp_tid(), words = (int)T->lut_words, threads = (int)P.wg_threads;
+    for (int i = tid; i < words; i += threads) lds[i] = T->lut[i];
+    uint16_t* swb = (uint16_t*)(lds + words);
+    for (int i = tid; i < 64 + 16; i += threads) swb[i] = i < 64 ? T->swb_long[i] : T->swb_short[i - 64];
+    unsigned char* bands = (unsigned char*)(swb + 80);
+    dp_block_sync();
+    const uint32_t lane = (uint32_t)dp_block() * (uint32_t)threads + (uint32_t)tid;
+    const uint32_t span = P.order ? P.order[lane] : lane;        /* 0xffffffff = idle */
+    if (span >= P.n_frames) return;
+    const lane_ctx c = { &P, dp_lds_addr(lds), dp_lds_addr(swb), dp_lds_addr(swb + 64), dp_lds_addr(bands + tid), threads, nullptr, nullptr, 0 };
+    const uint32_t first = P.frames[span].byte_offset, end = first + P.frames[span].byte_length;
+    aacg_parse_frame* out = W.blocks + (size_t)span * W.max_frames;
+    uint32_t at = first, n = 0, status = AACG_PARSE_OK;
+    while (at < end && n < W.max_frames) {
+        aacg_parse_result res;
+        parse_frame<true>(c, 0u, at, end - at, &res);
+        const uint32_t used = res.bits_used >> 3;                /* byte-aligned when the block parsed, and >= 1 byte then */
+        out[n].byte_offset = at;
+        out[n].byte_length = res.status ? end - at : used;
+        n++;
+        if (res.status) { status = res.status; break; }
+        at += used;
+    }
+    aacg_walk_result* wr = &W.results[span];
+    wr->n_frames = n; wr->status = status; wr->bytes_consumed = at - first; wr->reserved = 0;
 }
 
 }  // namespace aacg_parse

@@ -18,6 +18,12 @@
 extern "C" DP_KERNEL(AACG_PARSE_WG_LARGE, 1)
 void aacg_parse_frames(const aacg_parse_params P) { aacg_parse::parse_body(P); }
 
+/* one wave per workgroup: a span is a few thousand serial code words, and a walk of a few hundred spans should spread over as
+ * many CUs as it has waves */
+#define AACG_WALK_WG 64
+extern "C" DP_KERNEL(AACG_WALK_WG, 1)
+void aacg_parse_walk_spans(const aacg_walk_params W) { aacg_parse::walk_body(W); }
+
 /* Lane order: a counting sort of the frames by length, longest first (8-byte buckets).  Three small launches. */
 __device__ __forceinline__ uint32_t length_bucket(uint32_t bytes)
 {
@@ -129,8 +135,8 @@ struct aacg_parser {
     size_t order_cap = 0;
     hipEvent_t order_free = nullptr;  /* recorded behind every launch: the scratch above may be rewritten after it */
     hipStream_t last_stream = nullptr;
-    void* d_buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[7] = {0, 0, 0, 0, 0, 0, 0};
+    void* d_buf[11] = {};             /* 0..6 aacg_parse_batch's, 7..10 aacg_parse_walk's (bytes, spans, blocks, results) */
+    size_t cap[11] = {};
     aacg_wait_policy wait;            /* aacg_parse_batch's host waits are bounded (aacg_wait.h): AACG_ERR_TIMEOUT */
     std::string err;
 };
@@ -215,6 +221,53 @@ int launch(aacg_parser* p, aacg_parse_params& P, hipStream_t s)
     return AACG_OK;
 }
 
+/* The walk: spans sorted by length, longest first (aacg_parse_prepare with nothing to clear, or the three sorting kernels for
+ * very many spans), then one lane per span.  Spans of 8 KiB and more share the longest bucket. */
+int walk_launch(aacg_parser* p, aacg_walk_params& W, hipStream_t s)
+{
+    aacg_parse_params& P = W.P;
+    P.wg_threads = AACG_WALK_WG;
+    P.arena_bytes = 0;
+    const unsigned grid = (P.n_frames + AACG_WALK_WG - 1) / AACG_WALK_WG;
+    const size_t lanes = (size_t)grid * AACG_WALK_WG;
+    const bool sorted = P.n_frames > 64u;
+    if (sorted && lanes + AACG_PARSE_BUCKETS > p->order_cap) {
+        if (p->d_order) (void)hipFree(p->d_order);
+        p->d_order = nullptr; p->order_cap = 0;
+        if (hipMalloc((void**)&p->d_order, (lanes + AACG_PARSE_BUCKETS) * sizeof(uint32_t)) != hipSuccess) return fail(p, AACG_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+        p->order_cap = lanes + AACG_PARSE_BUCKETS;
+    }
+    if (p->last_stream && p->last_stream != s) HIPCHECK(hipStreamWaitEvent(s, p->order_free, 0));
+    P.order = sorted ? p->d_order : nullptr;
+    if (sorted && P.n_frames <= AACG_PARSE_PREPARE_MAX) {
+        aacg_clear_regions C;
+        for (int i = 0; i < 4; i++) { C.at[i] = nullptr; C.n16[i] = 0; }
+        hipLaunchKernelGGL(aacg_parse_prepare, dim3(1), dim3(1024), 0, s, C, P.frames, P.n_frames, p->d_order, (uint32_t)lanes, grid, 1u);
+    } else if (sorted) {
+        uint32_t* hist = p->d_order + lanes;
+        const unsigned blocks = (P.n_frames + 255u) / 256u;
+        HIPCHECK(hipMemsetAsync(p->d_order, 0xff, lanes * sizeof(uint32_t), s));
+        HIPCHECK(hipMemsetAsync(hist, 0, AACG_PARSE_BUCKETS * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(aacg_parse_order_count, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist);
+        hipLaunchKernelGGL(aacg_parse_order_scan, dim3(1), dim3(AACG_PARSE_BUCKETS), 0, s, hist);
+        hipLaunchKernelGGL(aacg_parse_order_fill, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist, p->d_order, grid, 1u);
+    }
+    hipLaunchKernelGGL(aacg_parse_walk_spans, dim3(grid), dim3(AACG_WALK_WG), AACG_PARSE_LDS_FIXED(p->lut_words, AACG_WALK_WG), s, W);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(p->order_free, s));
+    p->last_stream = s;
+    return AACG_OK;
+}
+
+void walk_params(aacg_parser* p, aacg_walk_params& W, const void* d_bytes, const aacg_parse_frame* d_spans, uint32_t n_spans,
+                 uint32_t max_frames, uint32_t options, aacg_parse_frame* d_frames, aacg_walk_result* d_results)
+{
+    std::memset(&W, 0, sizeof W);
+    W.P.bytes = (const uint32_t*)d_bytes; W.P.frames = d_spans; W.P.tab = p->d_tab; W.P.n_frames = n_spans;
+    W.P.options = options & ~AACG_PARSE_SKIP_ZERO_FILL;
+    W.blocks = d_frames; W.results = d_results; W.max_frames = max_frames;
+}
+
 }  // namespace
 
 extern "C" {
@@ -252,7 +305,9 @@ int aacg_parser_create(int device_ordinal, int sample_index, const aacg_code_ent
             hipEventCreateWithFlags(&p->order_free, hipEventDisableTiming) != hipSuccess ||
             hipMalloc((void**)&p->d_tab, sizeof(aacg_parse_tables)) != hipSuccess ||
             hipMemcpy(p->d_tab, tab.data(), sizeof(aacg_parse_tables), hipMemcpyHostToDevice) != hipSuccess ||
-            hipFuncSetAttribute((const void*)aacg_parse_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes) != hipSuccess)
+            hipFuncSetAttribute((const void*)aacg_parse_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes) != hipSuccess ||
+            hipFuncSetAttribute((const void*)aacg_parse_walk_spans, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)AACG_PARSE_LDS_FIXED(p->lut_words, AACG_WALK_WG)) != hipSuccess)
             rc = fail(p, AACG_ERR_NO_DEVICE, "HIP setup of the parser failed");
     }
     /* on failure the object is still returned, so that aacg_parser_last_error() can say why */
@@ -274,7 +329,7 @@ void aacg_parser_destroy(aacg_parser* p)
     (void)hipGetLastError();
     if (p->order_free) (void)hipEventDestroy(p->order_free);
     if (p->d_order) (void)hipFree(p->d_order);
-    for (int i = 0; i < 7; i++) if (p->d_buf[i]) (void)hipFree(p->d_buf[i]);
+    for (int i = 0; i < 11; i++) if (p->d_buf[i]) (void)hipFree(p->d_buf[i]);
     if (p->d_tab) (void)hipFree(p->d_tab);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
@@ -336,6 +391,55 @@ int aacg_parse_batch(aacg_parser* p, const uint8_t* bytes, size_t n_bytes, const
     HIPCHECK(hipMemcpyAsync(results, p->d_buf[6], sizes[6], hipMemcpyDeviceToHost, s));
     { const hipError_t st = aacg_wait_stream(s, p->wait);
       if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_batch: the copies back did not complete within the wait limit");
+      HIPCHECK(st); }
+    return AACG_OK;
+}
+
+int aacg_parse_walk_device(aacg_parser* p, const void* d_bytes, const aacg_parse_frame* d_spans, uint32_t n_spans,
+                           uint32_t max_frames, uint32_t options, aacg_parse_frame* d_frames, aacg_walk_result* d_results,
+                           void* hip_stream)
+{
+    if (!p || !p->d_tab) return AACG_ERR_INVALID_ARG;
+    if (!n_spans) return AACG_OK;
+    if (!d_bytes || !d_spans || !d_frames || !d_results || !max_frames || ((uintptr_t)d_bytes & 15u))
+        return fail(p, AACG_ERR_INVALID_ARG, "aacg_parse_walk_device: null, zero or misaligned argument");
+    HIPCHECK(hipSetDevice(p->device));
+    aacg_walk_params W;
+    walk_params(p, W, d_bytes, d_spans, n_spans, max_frames, options, d_frames, d_results);
+    return walk_launch(p, W, hip_stream ? (hipStream_t)hip_stream : p->stream);
+}
+
+int aacg_parse_walk(aacg_parser* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* spans, uint32_t n_spans,
+                    uint32_t max_frames, uint32_t options, aacg_parse_frame* frames, aacg_walk_result* results)
+{
+    if (!p || !p->d_tab) return AACG_ERR_INVALID_ARG;
+    if (!n_spans) return AACG_OK;
+    if (!bytes || !spans || !frames || !results || !max_frames) return fail(p, AACG_ERR_INVALID_ARG, "aacg_parse_walk: null or zero argument");
+    if (n_bytes >= (1u << 29)) return fail(p, AACG_ERR_INVALID_ARG, "aacg_parse_walk: 2^29 bytes or more (bit positions are 32-bit)");
+    for (uint32_t f = 0; f < n_spans; f++)
+        if ((size_t)spans[f].byte_offset + spans[f].byte_length > n_bytes) return fail(p, AACG_ERR_INVALID_ARG, "span " + std::to_string(f) + " lies outside the byte buffer");
+    HIPCHECK(hipSetDevice(p->device));
+    const size_t padded = (n_bytes + 15u) / 16u * 16u + AACG_PARSE_PAD_BYTES;
+    const size_t sizes[4] = { padded, n_spans * sizeof(aacg_parse_frame), (size_t)n_spans * max_frames * sizeof(aacg_parse_frame),
+                              n_spans * sizeof(aacg_walk_result) };
+    for (int i = 0; i < 4; i++) { int rc = grow(p, 7 + i, sizes[i]); if (rc) return rc; }
+    hipStream_t s = p->stream;
+    const size_t tail = padded < AACG_PARSE_PAD_BYTES + 16u ? padded : AACG_PARSE_PAD_BYTES + 16u;      /* zeros behind the last byte */
+    HIPCHECK(hipMemsetAsync((char*)p->d_buf[7] + padded - tail, 0, tail, s));
+    HIPCHECK(hipMemcpyAsync(p->d_buf[7], bytes, n_bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(p->d_buf[8], spans, sizes[1], hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(p->d_buf[9], 0, sizes[2], s));        /* the slots beyond a span's count read as zero */
+    aacg_walk_params W;
+    walk_params(p, W, p->d_buf[7], (const aacg_parse_frame*)p->d_buf[8], n_spans, max_frames, options, (aacg_parse_frame*)p->d_buf[9], (aacg_walk_result*)p->d_buf[10]);
+    int rc = walk_launch(p, W, s);
+    if (rc) return rc;
+    { const hipError_t st = aacg_wait_stream(s, p->wait);
+      if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_walk: the walk kernel did not complete within the wait limit (" + std::to_string(n_spans) + " spans)");
+      HIPCHECK(st); }
+    HIPCHECK(hipMemcpyAsync(frames, p->d_buf[9], sizes[2], hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(results, p->d_buf[10], sizes[3], hipMemcpyDeviceToHost, s));
+    { const hipError_t st = aacg_wait_stream(s, p->wait);
+      if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_walk: the copies back did not complete within the wait limit");
       HIPCHECK(st); }
     return AACG_OK;
 }

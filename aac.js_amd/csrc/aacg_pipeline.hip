@@ -96,6 +96,22 @@ struct aacg_pipeline {
         std::vector<uint32_t> unlearnt;   /* streams of the batch (by position) whose layout was not known: nothing of them was decoded */
     } lane[AACG_PIPELINE_MAX_LANES];
     uint64_t submitted = 0;
+    /* span walks (aacg_pipeline_walk_submit): two slots, made at the first walk — a stream more at set-up would shift the
+     * runtime's stream -> hardware queue assignment under the lanes' streams.  Bytes up and results down by aacg_pipe_copy through
+     * page-locked staging, as a batch's; buffers grow, never shrink. */
+    struct walk_t {
+        aacg_parser* parser = nullptr;
+        hipStream_t st = nullptr;
+        hipEvent_t done = nullptr;
+        void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+        size_t in_cap = 0, out_cap = 0;
+        bool busy = false;
+        uint64_t ticket = 0;
+        aacg_parse_frame* user_frames = nullptr; aacg_walk_result* user_results = nullptr;
+        size_t frames_bytes = 0, results_bytes = 0, results_at = 0;
+    } walk[2];
+    uint64_t walks_submitted = 0;
+    std::vector<aacg_code_entry> entries; uint32_t counts[12] = {};
     size_t res_cap16 = 0;               /* a lane's h_res: results of up to max_streams x max_frames frames, then (16-byte aligned) the refusal count */
     aacg_wait_policy wait;
     std::string err;
@@ -298,6 +314,14 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         return;
     }
     drop_plans(p);
+    for (auto& W : p->walk) {
+        if (W.st) (void)aacg_wait_stream(W.st, p->wait);
+        for (void* d : {W.d_in, W.d_out}) if (d) (void)hipFree(d);
+        for (void* h : {W.h_in, W.h_out}) if (h) (void)hipHostFree(h);
+        if (W.done) (void)hipEventDestroy(W.done);
+        if (W.parser) aacg_parser_destroy(W.parser);
+        if (W.st) (void)hipStreamDestroy(W.st);
+    }
     for (auto& L : p->lane) {
         for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
         for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
@@ -327,6 +351,11 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     p->Cp = p->learn ? AACG_MAX_CHANNELS : p->C;
     p->U = p->learn ? 8u : 1u;
     p->layout.resize((size_t)cfg->max_streams);
+    {   /* the codebooks again for the walk's parsers, made at the first walk */
+        size_t n_entries = 0;
+        for (int b = 0; b < 12; b++) { p->counts[b] = counts[b]; n_entries += counts[b]; }
+        p->entries.assign(entries, entries + n_entries);
+    }
     aacg_config ec;
     std::memset(&ec, 0, sizeof ec);
     ec.abi_version = AACG_ABI_VERSION; ec.device_ordinal = cfg->device_ordinal; ec.sample_index = cfg->sample_index;
@@ -375,6 +404,7 @@ int aacg_pipeline_set_wait_limit_ms(aacg_pipeline* p, uint32_t ms)
     (void)aacg_set_wait_limit_ms(p->engine, ms);
     (void)aacg_parser_set_wait_limit_ms(p->parser, ms);
     for (int k = 0; k < p->n_lanes; k++) (void)aacg_parser_set_wait_limit_ms(p->lane[k].parser, ms);
+    for (auto& W : p->walk) if (W.parser) (void)aacg_parser_set_wait_limit_ms(W.parser, ms);
     return AACG_OK;
 }
 
@@ -497,6 +527,87 @@ int aacg_pipeline_collect(aacg_pipeline* p, uint64_t ticket)
     if (L.ticket != ticket) return AACG_OK;              /* a later batch has taken the lane: this one was finished then */
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     return finish_lane(p, L);
+}
+
+namespace {
+
+/* the walk in a slot is complete: its results go to the caller */
+int finish_walk(aacg_pipeline* p, aacg_pipeline::walk_t& W)
+{
+    if (!W.busy) return AACG_OK;
+    const hipError_t st = aacg_wait_event(W.done, p->wait);
+    if (st == hipErrorNotReady) return timed_out(p, "aacg_pipeline_walk_collect");
+    P_TRY(p, st, AACG_ERR_NO_DEVICE);
+    std::memcpy(W.user_frames, W.h_out, W.frames_bytes);
+    std::memcpy(W.user_results, (char*)W.h_out + W.results_at, W.results_bytes);
+    W.busy = false;
+    return AACG_OK;
+}
+
+/* page-locked and device buffers of at least `need` bytes (grown by half again: a steady state allocates nothing) */
+int grow_pair(aacg_pipeline* p, void** h, void** d, size_t* cap, size_t need)
+{
+    if (need <= *cap) return AACG_OK;
+    if (*h) (void)hipHostFree(*h);
+    if (*d) (void)hipFree(*d);
+    *h = *d = nullptr; *cap = 0;
+    const size_t want = need * 3 / 2 + 4096;
+    P_TRY(p, hipHostMalloc(h, want, hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
+    P_TRY(p, hipMalloc(d, want), AACG_ERR_OUT_OF_MEMORY);
+    *cap = want;
+    return AACG_OK;
+}
+
+}  // namespace
+
+int aacg_pipeline_walk_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* spans, uint32_t n_spans,
+                              uint32_t max_frames, aacg_parse_frame* frames, aacg_walk_result* results, uint64_t* ticket)
+{
+    if (!p || !bytes || !spans || !n_spans || !max_frames || !frames || !results || !ticket) return AACG_ERR_INVALID_ARG;
+    if (n_bytes >= (1u << 29)) { p->err = "aacg_pipeline_walk_submit: 2^29 bytes or more"; return AACG_ERR_INVALID_ARG; }
+    for (uint32_t i = 0; i < n_spans; i++)
+        if ((size_t)spans[i].byte_offset + spans[i].byte_length > n_bytes) { p->err = "a span points outside the byte buffer"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    aacg_pipeline::walk_t& W = p->walk[p->walks_submitted % 2];
+    int rc = finish_walk(p, W);                          /* the walk two submissions ago, if nobody has collected it */
+    if (rc) return rc;
+    if (!W.parser) {
+        int least = 0, greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+        rc = aacg_parser_create(p->cfg.device_ordinal, p->cfg.sample_index, p->entries.data(), p->counts, &W.parser);
+        if (rc) { p->err = std::string("aacg_parser_create (walk): ") + (W.parser ? aacg_parser_last_error(W.parser) : ""); if (W.parser) aacg_parser_destroy(W.parser); W.parser = nullptr; return rc; }
+        (void)aacg_parser_set_wait_limit_ms(W.parser, (uint32_t)(p->wait.limit_s * 1e3));
+        P_TRY(p, hipStreamCreateWithPriority(&W.st, hipStreamNonBlocking, least), AACG_ERR_NO_DEVICE);
+        P_TRY(p, hipEventCreateWithFlags(&W.done, hipEventDisableTiming), AACG_ERR_NO_DEVICE);
+    }
+    /* up: the bytes (16-byte aligned, zeros behind them) and the spans; down: the block table, then the per-span results */
+    const size_t padded = ((n_bytes + 15) & ~(size_t)15) + 64, table = ((size_t)n_spans * sizeof(aacg_parse_frame) + 15) & ~(size_t)15;
+    const size_t fr = (size_t)n_spans * max_frames * sizeof(aacg_parse_frame), fr16 = (fr + 15) & ~(size_t)15, rs = (size_t)n_spans * sizeof(aacg_walk_result);
+    if ((rc = grow_pair(p, &W.h_in, &W.d_in, &W.in_cap, padded + table))) return rc;
+    if ((rc = grow_pair(p, &W.h_out, &W.d_out, &W.out_cap, fr16 + rs))) return rc;
+    std::memcpy(W.h_in, bytes, n_bytes);
+    std::memset((char*)W.h_in + n_bytes, 0, padded - n_bytes);
+    std::memcpy((char*)W.h_in + padded, spans, (size_t)n_spans * sizeof(aacg_parse_frame));
+    pipe_copy(W.h_in, W.d_in, padded + table, W.st);
+    rc = aacg_parse_walk_device(W.parser, W.d_in, (const aacg_parse_frame*)((char*)W.d_in + padded), n_spans, max_frames, (uint32_t)p->cfg.parse_options,
+                                (aacg_parse_frame*)W.d_out, (aacg_walk_result*)((char*)W.d_out + fr16), W.st);
+    if (rc) { p->err = std::string("aacg_parse_walk_device: ") + aacg_parser_last_error(W.parser); return rc; }
+    pipe_copy(W.d_out, W.h_out, fr16 + ((rs + 15) & ~(size_t)15), W.st);
+    P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    P_TRY(p, hipEventRecord(W.done, W.st), AACG_ERR_NO_DEVICE);
+    W.busy = true; W.ticket = ++p->walks_submitted; W.user_frames = frames; W.user_results = results;
+    W.frames_bytes = fr; W.results_bytes = rs; W.results_at = fr16;
+    *ticket = W.ticket;
+    return AACG_OK;
+}
+
+int aacg_pipeline_walk_collect(aacg_pipeline* p, uint64_t ticket)
+{
+    if (!p || !ticket || ticket > p->walks_submitted) return AACG_ERR_INVALID_ARG;
+    aacg_pipeline::walk_t& W = p->walk[(ticket - 1) % 2];
+    if (W.ticket != ticket) return AACG_OK;              /* a later walk has taken the slot: this one was finished then */
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    return finish_walk(p, W);
 }
 
 int aacg_pipeline_decode(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,

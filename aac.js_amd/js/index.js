@@ -436,7 +436,11 @@ GpuAACDecoder.prototype.feed = function (bytes) {
     }
     this.frontend.push(bytes);
 };
-GpuAACDecoder.prototype.feedPacket = function (bytes, multi) { this.frontend.pushPacket(bytes.data || bytes, multi); };   // multi: the buffer may hold several samples
+GpuAACDecoder.prototype.feedPacket = function (bytes, multi) {          // multi: the buffer may hold several samples
+    bytes = bytes.data || bytes;
+    if (this.resident && this.packets) { this.shared.pushPacket(this, bytes, !!multi); return; }   // SharedEngine({ residentPackets: true })
+    this.frontend.pushPacket(bytes, multi);
+};
 
 module.exports = { Engine, GpuAACDecoder, BitReader, packUnits, unpackUnits, packBandWord, packTns, unpackTns, packCce, CCE_REFERENCE, CCE_SPEC, CCE_BYTES, applyPulses, loadAddon,
                    INPUT_SPEC_F32, INPUT_QUANT_I16, OUTPUT_F32, OUTPUT_I16, TNS_REFERENCE, TNS_SPEC, PNS_REFERENCE, PNS_SPEC, UNIT_BYTES, META_WORDS, TNS_BYTES, SAMPLE_RATES };

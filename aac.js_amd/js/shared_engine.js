@@ -24,7 +24,10 @@
  * pipeline per sample rate and channel count; a stream's element layout — SCE + CPE + CPE + LFE, say — is learnt on the device
  * from its first frame, coupling elements are parsed and dropped), as the reference executes them (TNS identity, no PNS /
  * coupling modes).  MP4 samples ('mp4a': packets without ADTS headers, several to a buffer, whose boundaries only a parse
- * finds) and decoders with spec modes take the parsing route above on the same SharedEngine.
+ * finds) and decoders with spec modes take the parsing route above on the same SharedEngine — unless
+ * { residentPackets: true }: then an 'mp4a' decoder takes the resident route too.  A single-sample packet is a frame; the blocks
+ * of a multi-sample packet are found on the device (aacg_pipeline_walk_submit: one GPU lane walks one packet), a flush ahead of
+ * the flush that decodes them, and then travel like ADTS frames.
  * Replaces, per batch, what src/decoder.js:125-216 does per frame.
  */
 'use strict';
@@ -37,6 +40,7 @@ function SharedEngine(opts) {
     this.maxChannels = opts.maxChannels || 8;
     this.groups = new Map();                              // sampleIndex -> { engine, decoders: [], free: [] }
     this.resident = !!opts.resident;                      // bytes -> PCM in one native call per flush (aacg_pipeline_*)
+    this.residentPackets = !!opts.residentPackets;        // resident: 'mp4a' decoders too (their blocks found by a walk on the device)
     this.lookahead = opts.lookahead || 16;                // resident: frames per stream and flush
     /* resident: where a flush's PCM lives.  0 (default): memory of its own, the caller's for as long as it keeps any frame of the
      * flush (what the reference's readChunk() promises: a fresh array per frame) — a page-locked allocation per flush.  K > 0: K
@@ -65,11 +69,7 @@ SharedEngine.prototype.attach = function (dec) {
     const cfg = dec.config;
     if (cfg.chanConfig + dec.maxCoupling > this.maxChannels) throw new Error('SharedEngine: ' + cfg.chanConfig + ' channels exceed maxChannels ' + this.maxChannels);
     if (dec.group) this.detach(dec);                       // a new cookie: a new stream
-    /* the resident route reads ADTS frame lengths itself: an 'mp4a' track's samples have none (aurora.js feeds them through
-     * feedPacket, which the device route never sees — ADVICE round 5: such a decoder used to deliver nothing, without an error) */
-    const adts = !dec.format || dec.format.formatID === undefined || dec.format.formatID === 'aac ';
-    if (this.resident && adts && cfg.profile === 2 && cfg.chanConfig >= 1 && cfg.chanConfig <= 8 && !dec.tnsMode && !dec.pnsMode && !dec.cceMode && !dec.carryWindowShape)
-        return this.attachResident(dec);
+    if (this.takesResident(dec)) return this.attachResident(dec);
     let g = this.groups.get(cfg.sampleIndex);
     if (!g) {
         const o = this.opts;
@@ -87,6 +87,15 @@ SharedEngine.prototype.attach = function (dec) {
     g.decoders.push(dec);
 };
 
+/* whether a decoder (its cookie read) takes the resident route: the resident route reads ADTS frame lengths itself, and an 'mp4a'
+ * track's samples have none (aurora.js feeds them through feedPacket — ADVICE round 5: such a decoder used to deliver nothing,
+ * without an error); with residentPackets its packets are walked on the device instead */
+SharedEngine.prototype.takesResident = function (dec) {
+    const cfg = dec.config, id = dec.format ? dec.format.formatID : undefined;
+    const adts = id === undefined || id === 'aac ', mp4a = this.residentPackets && id === 'mp4a';
+    return this.resident && (adts || mp4a) && cfg.profile === 2 && cfg.chanConfig >= 1 && cfg.chanConfig <= 8 && !dec.tnsMode && !dec.pnsMode && !dec.cceMode && !dec.carryWindowShape;
+};
+
 /* resident route: one pipeline (engine + parser on the device) per (sample rate, channel count) */
 SharedEngine.prototype.attachResident = function (dec) {
     const cfg = dec.config, key = 'r' + cfg.sampleIndex + '/' + cfg.chanConfig;
@@ -97,13 +106,16 @@ SharedEngine.prototype.attachResident = function (dec) {
         const pipeline = addon.pipelineCreate({ deviceOrdinal: this.opts.deviceOrdinal | 0, sampleIndex: cfg.sampleIndex, maxStreams: this.maxStreams,
                                                 channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
                                                 parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0) }, rec.entries, rec.counts);
-        g = { resident: true, addon: addon, pipeline: pipeline, channels: cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0 };
+        g = { resident: true, addon: addon, pipeline: pipeline, channels: cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }
     const slot = g.free.length ? g.free.pop() : g.next++;
     if (slot >= this.maxStreams) { g.next--; throw new Error('SharedEngine: more than ' + this.maxStreams + ' streams at one sample rate'); }
     dec.stream = slot; dec.group = g; dec.resident = true;
     dec.rbuf = new Uint8Array(0); dec.rpos = 0;
+    /* 'mp4a': the packets in order, each { bytes, at: first byte not walked yet, ready: its blocks found and not yet taken, done,
+     * inflight }; a new object per stream, so that a walk still in flight for the stream before is dropped when it comes back */
+    dec.packets = dec.format && dec.format.formatID === 'mp4a' ? { q: [] } : null;
     dec.engine = { resetStream: function (s) { g.addon.pipelineResetStream(g.pipeline, s); } };
     g.decoders.push(dec);
 };
@@ -114,6 +126,89 @@ SharedEngine.prototype.detach = function (dec) {
     g.decoders.splice(g.decoders.indexOf(dec), 1);
     g.free.push(dec.stream);
     dec.group = null;
+    if (dec.packets) dec.packets = { q: [] };              // a walk in flight for this stream is dropped when it comes back
+};
+
+/* GpuAACDecoder.feedPacket on the resident route: a single-sample packet is a frame; a multi-sample packet waits for a walk */
+SharedEngine.prototype.pushPacket = function (dec, bytes, multi) {
+    dec.packets.q.push(multi ? { bytes: bytes, at: 0, ready: [], done: bytes.length === 0, inflight: false } : { bytes: bytes, at: bytes.length, ready: [bytes], done: true, inflight: false });
+};
+
+/* the blocks a stream can hand to a batch now (at most `max`, into `out`): packets in order, up to the first one not walked to its end */
+function packetFrames(pk, max, out) {
+    let n = 0;
+    for (const e of pk.q) {
+        for (let i = 0; i < e.ready.length && n < max; i++) out[n++] = e.ready[i];
+        if (n >= max || !e.done) break;
+    }
+    return n;
+}
+function takePacketFrames(pk, n) {
+    while (pk.q.length) {
+        const e = pk.q[0], k = Math.min(n, e.ready.length);
+        e.ready.splice(0, k); n -= k;
+        if (e.done && !e.ready.length) pk.q.shift(); else break;
+    }
+}
+
+/* one walk over every packet not walked yet of the group's 'mp4a' streams (up to lookahead blocks each: a longer packet resumes at
+ * bytes_consumed in the next walk), enqueued on the device (pipelineWalkSubmit) */
+SharedEngine.prototype.walkSubmit = function (g) {
+    const list = [];
+    let total = 0;
+    for (const dec of g.decoders) {
+        if (!dec.packets) continue;
+        for (const e of dec.packets.q) if (!e.done && !e.inflight) { list.push({ dec: dec, pk: dec.packets, e: e, from: e.at, base: total }); total += e.bytes.length - e.at; }
+    }
+    if (!list.length) return false;
+    const M = this.lookahead, bytes = new Uint8Array(total), spans = new Uint32Array(2 * list.length);
+    list.forEach(function (w, k) { bytes.set(w.e.bytes.subarray(w.from), w.base); spans[2 * k] = w.base; spans[2 * k + 1] = w.e.bytes.length - w.from; });
+    const frames = new Uint32Array(2 * list.length * M), results = new Uint32Array(4 * list.length);
+    try { g.addon.pipelineWalkSubmit(g.pipeline, bytes, spans, M, frames, results); }
+    catch (err) { this.walkFailed(list, err); return false; }
+    for (const w of list) w.e.inflight = true;
+    g.walks.push({ list: list, frames: frames, results: results, M: M });
+    return true;
+};
+
+/* the oldest walk in flight: its blocks to their packets, in order; a block that does not parse is kept with the rest of its packet
+ * as its length — the pipeline refuses it with the same status and the reference's message is thrown where the frame is reached —
+ * and the packet ends there (as on the parsing route) */
+SharedEngine.prototype.walkCollect = function (g) {
+    const w = g.walks.shift();
+    try { g.addon.pipelineWalkCollect(g.pipeline); }
+    catch (err) { this.walkFailed(w.list, err); return; }
+    w.list.forEach(function (x, k) {
+        const e = x.e;
+        e.inflight = false;
+        if (x.dec.packets !== x.pk) return;               // the stream was detached or reset since
+        const n = w.results[4 * k], status = w.results[4 * k + 1], used = w.results[4 * k + 2];
+        for (let f = 0, i = 2 * k * w.M; f < n; f++, i += 2) {
+            const off = w.frames[i] - x.base + x.from;
+            e.ready.push(e.bytes.subarray(off, off + w.frames[i + 1]));
+        }
+        e.at = x.from + used;
+        e.done = status !== 0 || e.at >= e.bytes.length;
+    });
+};
+
+SharedEngine.prototype.walkFailed = function (list, err) {
+    const e = err instanceof Error ? err : new Error(String(err));
+    for (const x of list) {
+        x.e.inflight = false; x.e.done = true;
+        if (x.dec.packets === x.pk && x.dec.queue.indexOf(e) < 0) x.dec.queue.push(e);
+    }
+};
+
+/* before a batch is put together: the walks in flight come back, and a stream with no block ready but packets not walked yet is
+ * walked now, synchronously (a readChunk() must not return null while a complete block is buffered) */
+SharedEngine.prototype.walkReady = function (g, room) {
+    while (g.walks.length) this.walkCollect(g);
+    const want = new Array(1);
+    const starving = g.decoders.some(function (dec) {
+        return dec.packets && dec.queue.length < room && packetFrames(dec.packets, 1, want) === 0 && dec.packets.q.some(function (e) { return !e.done; });
+    });
+    if (starving && this.walkSubmit(g)) this.walkCollect(g);
 };
 
 /* how many complete ADTS frames (at most `max`) start at byte `at` of `b`: their lengths into `lens`; -1 where the bytes at a
@@ -139,6 +234,13 @@ SharedEngine.prototype.prepareResident = function (g, room) {
     for (const dec of g.decoders) {
         if (dec.queue.length >= room) continue;            // a slow reader's queue does not grow with every flush of its peers
         if (!dec.rlens) dec.rlens = new Uint32Array(L);
+        if (dec.packets) {                                 // 'mp4a': the blocks its walks have found
+            if (!dec.rblocks) dec.rblocks = new Array(L);
+            const n = packetFrames(dec.packets, L, dec.rblocks);
+            for (let f = 0; f < n; f++) dec.rlens[f] = dec.rblocks[f].length;
+            if (n) { part.push(dec); F = Math.min(F, n); }
+            continue;
+        }
         const n = scanFrames(dec.rbuf, dec.rpos, L, dec.rlens);
         if (n < 0) { if (!dec.badHeader) { dec.badHeader = true; dec.queue.push(new Error('Invalid ADTS header.')); } continue; }
         if (n === 0) continue;
@@ -156,6 +258,11 @@ SharedEngine.prototype.prepareResident = function (g, room) {
     const bytes = new Uint8Array(total);
     for (let s = 0; s < S; s++) {
         const dec = part[s], len = starts[s + 1] - starts[s];
+        if (dec.packets) {
+            for (let f = 0, at = starts[s]; f < F; f++) { bytes.set(dec.rblocks[f], at); at += dec.rblocks[f].length; dec.rblocks[f] = null; }
+            takePacketFrames(dec.packets, F);
+            continue;
+        }
         bytes.set(dec.rbuf.subarray(dec.rpos, dec.rpos + len), starts[s]);
         dec.rpos += len;
     }
@@ -191,6 +298,7 @@ SharedEngine.prototype.flushResident = function (g) {
         b = g.pending; g.pending = null;
         try { out = g.addon.pipelineCollect(g.pipeline); } catch (err) { failed = err instanceof Error ? err : new Error(String(err)); }
     } else {
+        this.walkReady(g, L);
         b = this.prepareResident(g, L);
         if (!b) return;
         try { out = g.addon.pipelineDecode.apply(null, args(b)); } catch (err) { failed = err instanceof Error ? err : new Error(String(err)); }
@@ -198,12 +306,14 @@ SharedEngine.prototype.flushResident = function (g) {
     this.stats.engineNs += process.hrtime.bigint() - t0;
     this.deliverResident(g, b, out, failed);
     if (this.overlap && !failed) {                         // ... and the one after it: decoded while the caller reads this one
+        this.walkReady(g, 2 * L);
         const nb = this.prepareResident(g, 2 * L);
         if (nb) {
             try { g.addon.pipelineSubmit.apply(null, args(nb)); g.pending = nb; }
             catch (err) { this.deliverResident(g, nb, null, err instanceof Error ? err : new Error(String(err))); }
         }
     }
+    if (!g.walks.length) this.walkSubmit(g);               // the packets not walked yet: on the device while the caller reads this flush
 };
 
 /* every registered decoder parses ahead what it has buffered; one batch per engine */

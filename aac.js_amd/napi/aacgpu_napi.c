@@ -52,6 +52,9 @@ static struct {
     int  (*pipeline_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, uint32_t,
                             void*, aacg_parse_result*, uint32_t*, uint64_t*);
     int  (*pipeline_collect)(aacg_pipeline*, uint64_t);
+    int  (*pipeline_walk_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, uint32_t, uint32_t, aacg_parse_frame*,
+                                 aacg_walk_result*, uint64_t*);
+    int  (*pipeline_walk_collect)(aacg_pipeline*, uint64_t);
     void* (*host_alloc)(size_t);
     void (*host_free)(void*);
 } L;
@@ -87,6 +90,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_create, "aacg_pipeline_create"); SYM(pipeline_destroy, "aacg_pipeline_destroy"); SYM(pipeline_last_error, "aacg_pipeline_last_error");
     SYM(pipeline_reset_stream, "aacg_pipeline_reset_stream"); SYM(pipeline_decode, "aacg_pipeline_decode");
     SYM(pipeline_submit, "aacg_pipeline_submit"); SYM(pipeline_collect, "aacg_pipeline_collect");
+    SYM(pipeline_walk_submit, "aacg_pipeline_walk_submit"); SYM(pipeline_walk_collect, "aacg_pipeline_walk_collect");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
     return 1;
@@ -112,7 +116,9 @@ typedef struct { uint32_t kind; void* ptr; pthread_mutex_t lock; int out_i16; /*
                  /* pipeline, { pcmRing: K }: K page-locked PCM buffers made once and handed out in turn (pipelineDecode) */
                  napi_ref ring_ab[PCM_RING_MAX]; void* ring_ptr[PCM_RING_MAX]; size_t ring_bytes; int ring_n; unsigned ring_next;
                  /* pipeline: the batches submitted and not yet collected, oldest first (pipelineSubmit / pipelineCollect) */
-                 void* jobs[4]; int n_jobs; } handle_box;
+                 void* jobs[4]; int n_jobs;
+                 /* pipeline: the span walks submitted and not yet collected, oldest first (pipelineWalkSubmit / pipelineWalkCollect) */
+                 void* walks[2]; int n_walks; } handle_box;
 
 static handle_box* box_new(uint32_t kind, void* ptr)
 {
@@ -479,6 +485,7 @@ static napi_value js_parse_batch(napi_env env, napi_callback_info info)
 static void ring_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; if (data && L.host_free) L.host_free(data); }
 
 static void pipe_abandon(napi_env env, void* job);    /* a submitted batch nobody collected: wait for it, drop it */
+static void walk_abandon(napi_env env, void* job);    /* a submitted walk nobody collected: dropped behind the pipeline (whose destroy waits for it) */
 static void pipeline_finalize(napi_env env, void* data, void* hint)
 {
     (void)hint;
@@ -487,6 +494,8 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     for (int i = 0; i < b->n_jobs; i++) pipe_abandon(env, b->jobs[i]);
     b->n_jobs = 0;
     if (b->ptr && L.pipeline_destroy) L.pipeline_destroy((aacg_pipeline*)b->ptr);
+    for (int i = 0; i < b->n_walks; i++) walk_abandon(env, b->walks[i]);
+    b->n_walks = 0;
     for (int i = 0; i < b->ring_n; i++) if (b->ring_ab[i]) napi_delete_reference(env, b->ring_ab[i]);   /* (the buffers go with their ArrayBuffers: ring_finalize) */
     b->kind = 0;
     pthread_mutex_destroy(&b->lock);
@@ -829,6 +838,72 @@ static napi_value js_pipeline_collect(napi_env env, napi_callback_info info)
     return pipe_finish(env, j);
 }
 
+/* pipelineWalkSubmit(pipeline, bytes:Uint8Array, spans:Uint32Array(2 * n) [offset, length]..., maxFrames,
+ *                    frames:Uint32Array(2 * n * maxFrames), results:Uint32Array(4 * n) [n_frames, status, bytes_consumed, 0]...)
+ * aacg_pipeline_walk_submit: the bytes and spans may be reused at once; frames / results belong to the walk until
+ * pipelineWalkCollect(pipeline) has returned the OLDEST submitted walk (it waits for it, bounded).  Two walks in flight at most. */
+typedef struct { handle_box* pb; uint64_t ticket; napi_ref keep[2]; } walk_job;
+
+static void walk_release(napi_env env, walk_job* w)
+{
+    for (int k = 0; k < 2; k++) if (w->keep[k]) napi_delete_reference(env, w->keep[k]);
+    free(w);
+}
+
+static void walk_abandon(napi_env env, void* job) { walk_release(env, (walk_job*)job); }
+
+static napi_value js_pipeline_walk_submit(napi_env env, napi_callback_info info)
+{
+    size_t argc = 6; napi_value argv[6];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 6) { napi_throw_error(env, NULL, "aacgpu: pipelineWalkSubmit takes 6 arguments"); return NULL; }
+    handle_box* pb = box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle");
+    if (!pb) return NULL;
+    if (pb->n_walks >= 2) { napi_throw_error(env, NULL, "aacgpu: pipelineWalkSubmit: two walks are in flight already (pipelineWalkCollect)"); return NULL; }
+    napi_typedarray_type t; size_t nb, ns, nf, nr; void *db, *ds, *df, *dr; uint32_t M = 0;
+    napi_get_value_uint32(env, argv[3], &M);
+    if (!typed(env, argv[1], &t, &nb, &db) || t != napi_uint8_array || !typed(env, argv[2], &t, &ns, &ds) || t != napi_uint32_array ||
+        !typed(env, argv[4], &t, &nf, &df) || t != napi_uint32_array || !typed(env, argv[5], &t, &nr, &dr) || t != napi_uint32_array ||
+        !M || !ns || (ns & 1) || nf != ns * M || nr != 2 * ns) {
+        napi_throw_type_error(env, NULL, "pipelineWalkSubmit(pipeline, Uint8Array bytes, Uint32Array spans (2 per span), maxFrames, Uint32Array frames (2 * maxFrames per span), Uint32Array results (4 per span))");
+        return NULL;
+    }
+    walk_job* w = (walk_job*)calloc(1, sizeof *w);
+    if (!w) { napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
+    w->pb = pb;
+    pthread_mutex_lock(&pb->lock);
+    const int rc = L.pipeline_walk_submit((aacg_pipeline*)pb->ptr, (const uint8_t*)db, nb, (const aacg_parse_frame*)ds, (uint32_t)(ns / 2), M,
+                                          (aacg_parse_frame*)df, (aacg_walk_result*)dr, &w->ticket);
+    char msg[1024] = "";
+    if (rc) snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_walk_submit failed (%d): %.800s", rc, L.pipeline_last_error((aacg_pipeline*)pb->ptr));
+    pthread_mutex_unlock(&pb->lock);
+    if (rc) { free(w); napi_throw_error(env, NULL, msg); return NULL; }
+    napi_create_reference(env, argv[4], 1, &w->keep[0]);
+    napi_create_reference(env, argv[5], 1, &w->keep[1]);
+    pb->walks[pb->n_walks++] = w;
+    return NULL;
+}
+
+static napi_value js_pipeline_walk_collect(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1];
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_box* pb = box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle");
+    if (!pb) return NULL;
+    if (!pb->n_walks) { napi_throw_error(env, NULL, "aacgpu: pipelineWalkCollect: nothing has been submitted"); return NULL; }
+    walk_job* w = (walk_job*)pb->walks[0];
+    for (int i = 1; i < pb->n_walks; i++) pb->walks[i - 1] = pb->walks[i];
+    pb->n_walks--;
+    pthread_mutex_lock(&pb->lock);
+    const int rc = L.pipeline_walk_collect((aacg_pipeline*)pb->ptr, w->ticket);
+    char msg[1024] = "";
+    if (rc) snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_walk_collect failed (%d): %.800s", rc, L.pipeline_last_error((aacg_pipeline*)pb->ptr));
+    pthread_mutex_unlock(&pb->lock);
+    walk_release(env, w);
+    if (rc) napi_throw_error(env, NULL, msg);
+    return NULL;
+}
+
 static napi_value js_pipeline_reset_stream(napi_env env, napi_callback_info info)
 {
     size_t argc = 2; napi_value argv[2]; uint32_t slot = 0;
@@ -872,6 +947,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelineSubmit", NULL, js_pipeline_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineCollect", NULL, js_pipeline_collect, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineResetStream", NULL, js_pipeline_reset_stream, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelineWalkCollect", NULL, js_pipeline_walk_collect, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;

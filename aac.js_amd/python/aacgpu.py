@@ -32,7 +32,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_create", "aacg_pipeline_destroy", "aacg_pipeline_last_error", "aacg_pipeline_reset_stream", "aacg_pipeline_decode",
                "aacg_pipeline_submit", "aacg_pipeline_collect", "aacg_pipeline_set_wait_limit_ms", "aacg_pipeline_stream_layout",
                "aacg_set_wait_limit_ms", "aacg_parser_set_wait_limit_ms", "aacg_pipeline_info",
-               "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex"]
+               "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_parse_walk", "aacg_parse_walk_device",
+               "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -195,6 +196,8 @@ def load_library(path=LIB_PATH):
     L.aacg_parse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.aacg_standard_codebooks.argtypes = [C.c_void_p, C.c_void_p]
+    L.aacg_parse_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.aacg_parse_walk_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.aacg_decode_batch_ex.argtypes = [C.c_void_p, C.POINTER(Batch)]
     L.aacg_submit_ex.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(C.c_uint64)]
     L.aacg_plan_create_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
@@ -226,6 +229,7 @@ def load_library(path=LIB_PATH):
 CODE_ENTRY_DTYPE = np.dtype([("code", "<u4"), ("len", "u1"), ("v", "i1", (4,)), ("reserved", "u1", (3,))])
 PARSE_FRAME_DTYPE = np.dtype([("byte_offset", "<u4"), ("byte_length", "<u4")])
 PARSE_RESULT_DTYPE = np.dtype([("status", "u1"), ("n_units", "u1"), ("n_channels", "u1"), ("flags", "u1"), ("bits_used", "<u4")])
+WALK_RESULT_DTYPE = np.dtype([("n_frames", "<u4"), ("status", "<u4"), ("bytes_consumed", "<u4"), ("reserved", "<u4")])
 META_DTYPE = np.dtype(("<u2", (120,)))
 PARSE_APPLY_PULSES, PARSE_REFERENCE_QUIRKS, PARSE_SKIP_ZERO_FILL = 1, 2, 4
 
@@ -378,6 +382,23 @@ class Parser:
         """Device pointers (ints); asynchronous on `stream`."""
         self._check(self.lib.aacg_parse_device(self.handle, d_bytes, d_frames, n_frames, max_units, max_channels, options,
                                                d_units, d_q, d_meta, d_tns, d_results, stream))
+
+    def walk(self, data, spans, max_frames, options=PARSE_REFERENCE_QUIRKS):
+        """aacg_parse_walk: where the raw_data_blocks of each span lie.  spans: PARSE_FRAME_DTYPE byte ranges in `data`, each
+        starting at a block boundary.  Returns (frames [n_spans][max_frames] PARSE_FRAME_DTYPE, zero beyond a span's count;
+        results [n_spans] WALK_RESULT_DTYPE)."""
+        data = np.ascontiguousarray(data, np.uint8)
+        spans = np.ascontiguousarray(spans)
+        assert spans.dtype == PARSE_FRAME_DTYPE
+        frames = np.zeros((len(spans), max_frames), PARSE_FRAME_DTYPE)
+        results = np.zeros(len(spans), WALK_RESULT_DTYPE)
+        self._check(self.lib.aacg_parse_walk(self.handle, data.ctypes.data, data.size, spans.ctypes.data, len(spans), max_frames,
+                                             options, frames.ctypes.data, results.ctypes.data))
+        return frames, results
+
+    def walk_device(self, d_bytes, d_spans, n_spans, max_frames, options, d_frames, d_results, stream=0):
+        """Device pointers (ints); asynchronous on `stream`."""
+        self._check(self.lib.aacg_parse_walk_device(self.handle, d_bytes, d_spans, n_spans, max_frames, options, d_frames, d_results, stream))
 
     def status_string(self, status):
         return self.lib.aacg_parse_status_string(int(status)).decode()

@@ -512,6 +512,32 @@ int aacg_parse_device(aacg_parser* p, const void* d_bytes, const aacg_parse_fram
                       aacg_parse_result* d_results, void* hip_stream);
 const char* aacg_parse_kernel_name(void);
 
+/* Where the raw_data_blocks lie in MP4 sample runs (decoder.js:125-133,199: a chunk buffer holds several samples back to
+ * back, and only a parse of block k finds where block k + 1 starts).  A span is one such run: it starts at a block boundary
+ * and holds whole blocks (a block it cuts off is refused: AACG_PARSE_INSUFFICIENT_DATA).  One GPU lane walks one span with the
+ * frame parser's syntax and every store off; span s's blocks land in frames[s * max_frames + k], k < results[s].n_frames, as
+ * (byte_offset in `bytes`, byte_length) — the frame table aacg_parse_batch / aacg_pipeline_decode take.  A lane stops at the
+ * span's end, after max_frames blocks, or at the first block that does not parse: that block is listed too, with the rest of
+ * the span as its length (what the frame parser is then given: it refuses the block with the same status), and its status
+ * becomes the span's.  A block that starts with 0xFFF is read as an ADTS frame, as by the frame parser (decoder.js:129-130).
+ * options: AACG_PARSE_APPLY_PULSES / AACG_PARSE_REFERENCE_QUIRKS as for the parse that follows (they decide which blocks parse).
+ *
+ * aacg_parse_walk: host pointers, returns when the results are there (bounded wait: AACG_ERR_TIMEOUT).
+ * aacg_parse_walk_device: DEVICE pointers, asynchronous on hip_stream; d_bytes 16-byte aligned with >= 32 readable bytes after
+ * the last span and fewer than 2^29 bytes in all.  Shares the lane-order scratch (and its rules) with aacg_parse_device. */
+typedef struct aacg_walk_result {
+    uint32_t n_frames;         /* blocks listed for the span, a refused one included                          */
+    uint32_t status;           /* AACG_PARSE_OK: the span's end or max_frames was reached; else the last block's */
+    uint32_t bytes_consumed;   /* from the span's start to the end of its last block that parsed: a span that
+                                  stopped at max_frames resumes at byte_offset + bytes_consumed                 */
+    uint32_t reserved;
+} aacg_walk_result;
+int aacg_parse_walk(aacg_parser* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* spans, uint32_t n_spans,
+                    uint32_t max_frames, uint32_t options, aacg_parse_frame* frames, aacg_walk_result* results);
+int aacg_parse_walk_device(aacg_parser* p, const void* d_bytes, const aacg_parse_frame* d_spans, uint32_t n_spans,
+                           uint32_t max_frames, uint32_t options, aacg_parse_frame* d_frames, aacg_walk_result* d_results,
+                           void* hip_stream);
+
 /* Parser -> transform without the host in between.  A plan's run tables depend on which streams bring how many frames
  * of which element layout, not on what the frames contain; batch after batch of the same streams can therefore keep
  * ONE plan (built once from unit records that carry the structure: stream, pcm_offset, channel, n_out_ch, n_ch and the
@@ -612,6 +638,16 @@ int  aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes
                           void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket);
 int  aacg_pipeline_collect(aacg_pipeline* p, uint64_t ticket);
 int  aacg_pipeline_set_wait_limit_ms(aacg_pipeline* p, uint32_t ms);
+/* Span walks on the pipeline's device (aacg_parse_walk's semantics and outputs, the pipeline's parse_options): where the blocks of
+ * MP4 sample runs lie, ahead of the batches that decode them.  aacg_pipeline_walk_submit stages the bytes (they may be reused when
+ * it returns) and enqueues the walk on a stream of its own — bytes up and results down through page-locked staging, no synchronous
+ * copy and, once the buffers have grown, no allocation; frames[s * max_frames + k] (k < results[s].n_frames; the slots behind
+ * are unspecified) and results are written by the time aacg_pipeline_walk_collect(ticket) returns and must stay valid until
+ * then.  Up to two walks in flight: submitting a third first finishes the oldest.  Tickets count from 1, apart from the
+ * batches'.  aacg_pipeline_walk_collect waits at most the wait limit: AACG_ERR_TIMEOUT with the lanes' and the engine's state. */
+int  aacg_pipeline_walk_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* spans, uint32_t n_spans,
+                               uint32_t max_frames, aacg_parse_frame* frames, aacg_walk_result* results, uint64_t* ticket);
+int  aacg_pipeline_walk_collect(aacg_pipeline* p, uint64_t ticket);
 /* The element layout learnt for a stream slot: returns the number of SCE / CPE / LFE elements of its frames (0: not learnt
  * yet), their channel counts in element_channels[0..7] and how many of them (the first ones) fit `channels` in *kept. */
 int  aacg_pipeline_stream_layout(aacg_pipeline* p, uint32_t slot, uint8_t element_channels[8], uint32_t* kept);

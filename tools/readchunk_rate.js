@@ -9,6 +9,10 @@
  *   - GpuAACDecoder with the JavaScript front end (parse on the CPU, transform on the GPU),
  *   - GpuAACDecoder with the device front end (parse and transform on the GPU),
  *   - the reference's own AACDecoder.readChunk() when the reference checkout is present (build container only; CPU).
+ *   node tools/readchunk_rate.js --mp4a [--samples-per-packet 16] [--streams 256] [repeats]
+ *                                                            the same streams as MP4 chunks (ADTS headers cut off, N samples per
+ *                                                            feedPacket buffer) on a SharedEngine: the parsing route, and the
+ *                                                            resident route with { residentPackets: true }; one checksum
  * The GPU lines need the built engine and a GPU; without one they are reported as null. */
 'use strict';
 const fs = require('fs'), path = require('path');
@@ -17,7 +21,9 @@ const host = require(path.join(root, 'aac.js_amd', 'js'));
 const argv0 = process.argv.slice(2);
 /* --file NAME: another of the committed streams (tests/golden/streams/NAME.aac; surround48 = SCE + CPE + CPE + LFE, six channels) */
 const fileAt = argv0.indexOf('--file'), fileName = fileAt >= 0 ? argv0[fileAt + 1] : 'stereo48';
-const argv = argv0.filter(function (a, i) { return fileAt < 0 || (i !== fileAt && i !== fileAt + 1); });
+const mp4aMode = argv0.indexOf('--mp4a') >= 0, perAt = argv0.indexOf('--samples-per-packet');
+const perPacket = perAt >= 0 ? parseInt(argv0[perAt + 1], 10) : 16;
+const argv = argv0.filter(function (a, i) { return (fileAt < 0 || (i !== fileAt && i !== fileAt + 1)) && a !== '--mp4a' && (perAt < 0 || (i !== perAt && i !== perAt + 1)); });
 const nStreams = argv[0] === '--streams' ? parseInt(argv[1], 10) : 0;
 const repeats = parseInt((nStreams ? argv[2] : argv[0]) || (nStreams ? '4' : '400'), 10);
 const one = new Uint8Array(fs.readFileSync(path.join(root, 'tests', 'golden', 'streams', fileName + '.aac')));
@@ -101,7 +107,51 @@ function many(shared, lookahead, pcmRing, overlap, yieldEvery, done) {
         return finish(t0, n, sum);
     } catch (e) { const r = { error: String(e.message || e).slice(0, 200) }; if (done) done(r); return r; }
 }
-if (nStreams && process.env.READCHUNK_ONLY === 'event_loop') {
+/* --mp4a: N decoders fed MP4 chunks (perPacket bare blocks per feedPacket buffer), read round robin */
+function mp4a(resident) {
+    try {
+        const list = host.adts.frames(bytes), cookie = host.adts.cookie(list[0].header);
+        const blocks = list.map(function (f) { return bytes.subarray(f.offset + f.header.headerBytes, f.offset + f.length); });
+        const chunks = [];
+        for (let i = 0; i < blocks.length; i += perPacket) {
+            const part = blocks.slice(i, i + perPacket), c = new Uint8Array(part.reduce(function (a, b) { return a + b.length; }, 0));
+            let at = 0; for (const b of part) { c.set(b, at); at += b.length; }
+            chunks.push(c);
+        }
+        const S = nStreams || 256;
+        const sh = new host.SharedEngine({ maxStreams: S, maxChannels: Math.max(2, nChannels), resident: true, residentPackets: resident, lookahead: 16 });
+        const decs = [];
+        for (let i = 0; i < S; i++) {
+            const d = new host.GpuAACDecoder({ frontend: new host.FrontEnd(), lookahead: 16, shared: sh, format: { formatID: 'mp4a' } });
+            d.init(); d.setCookie(cookie);
+            if (!!d.resident !== resident) throw new Error('routing: resident ' + !!d.resident);
+            decs.push(d);
+        }
+        const t0 = process.hrtime.bigint();
+        for (const d of decs) for (const c of chunks) d.feedPacket(c, true);          // the demuxer's chunks, as the ADTS lines push all bytes first
+        let n = 0, sum = 0;
+        for (let live = S; live;) {
+            live = 0;
+            for (let i = 0; i < S; i++) {
+                const d = decs[i];
+                const pcm = d.readChunk();
+                if (pcm) { n++; sum += pcm[17]; live++; }
+            }
+        }
+        const s = Number(process.hrtime.bigint() - t0) / 1e9;
+        return { route: resident ? 'resident (residentPackets)' : 'parsing', streams: S, samples_per_packet: perPacket, frames: n, seconds: +s.toFixed(3),
+                 frames_per_s: Math.round(n / s), engine_seconds: +(Number(sh.stats.engineNs) / 1e9).toFixed(3), batches: sh.stats.batches, checksum: sum };
+    } catch (e) { return { error: String(e.message || e).slice(0, 200) }; }
+}
+
+if (mp4aMode) {
+    out.stream = fileName + '.aac x ' + repeats + ' as MP4 chunks of ' + perPacket + ' samples x ' + (nStreams || 256) + ' streams';
+    out.mp4a_parsing_route = mp4a(false);
+    out.mp4a_resident_route = mp4a(true);
+    out.same_checksum = out.mp4a_parsing_route.checksum === out.mp4a_resident_route.checksum;
+    console.log(JSON.stringify(out, null, 1));
+    process.exit(0);
+} else if (nStreams && process.env.READCHUNK_ONLY === 'event_loop') {
     many('resident', 16, process.env.READCHUNK_RING | 0, true, parseInt(process.env.READCHUNK_YIELD || '16', 10), function (r) { console.log(JSON.stringify(r)); process.exit(0); });
 } else if (nStreams) {
     out.stream = fileName + '.aac x ' + repeats + ' x ' + nStreams + ' streams';
