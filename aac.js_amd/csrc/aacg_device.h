@@ -53,6 +53,9 @@ struct aacg_tables {
 #define AACG_TAB_OFF_BAND_LONG    (AACG_TAB_OFF_IQ_SMALL + 1024)
 #define AACG_TAB_OFF_BAND_SHORT   (AACG_TAB_OFF_BAND_LONG + 256)
 #define AACG_TAB_QUANT_FLOATS     (AACG_TAB_OFF_BAND_SHORT + 32)
+/* floats an LDS copy of the quant part leaves out when its signed IQ table covers only q = -iqh..iqh-1 (the band maps move down
+ * by as much; larger magnitudes take the full table in global memory, as they do beyond 512) */
+#define AACG_TAB_IQ_CUT(iqh)      (1024 - 2 * (iqh))
 
 /* ---- LDS map of the run kernel -------------------------------------------------------- */
 /* [tables][slot 0] ... [slot 15]; slot = two 1024-float areas, one per channel.  An area
@@ -64,6 +67,16 @@ struct aacg_tables {
  * strided two-address LDS reads (ds_read2st64_b64) count their offsets in units of 512 bytes */
 #define AACG_TAB_SLOT_BASE(tab_floats) (((tab_floats) + 127) & ~127)
 #define AACG_LDS_FLOATS(tab_floats) (AACG_TAB_SLOT_BASE(tab_floats) + AACG_WG_WAVES * AACG_SLOT_FLOATS + AACG_WG_WAVES)   /* + one hand-off flag per wave */
+/* Eight-wave run workgroups (imdct_run_body<..., NW = AACG_HALF_WAVES>): a run of 16 frames on 8 waves, two per wave, in at most
+ * 80 KiB so that two workgroups share a CU (160 KiB of LDS).  The signed IQ table in LDS covers q = -256..255 (larger magnitudes
+ * read the full table in global memory) and SEVEN slots serve the sixteen frames: frame t works in slot t mod 7, after frame
+ * t - 6 has read the tails frame t - 7 left there.  Then two flags per frame: tails ready, predecessor's tails read. */
+#define AACG_HALF_WAVES   8
+#define AACG_HALF_SLOTS   7
+#define AACG_HALF_IQH     256
+#define AACG_HALF_LDS_BYTES(tab_floats) (4 * (AACG_TAB_SLOT_BASE(tab_floats) + AACG_HALF_SLOTS * AACG_SLOT_FLOATS + 2 * AACG_WG_WAVES))
+#define AACG_HALF_LDS_BYTES_QUANT AACG_HALF_LDS_BYTES(AACG_TAB_QUANT_FLOATS - AACG_TAB_IQ_CUT(AACG_HALF_IQH))
+static_assert(AACG_HALF_LDS_BYTES_QUANT <= 81920, "two eight-wave run workgroups per CU");
 #define AACG_LDS_BYTES_F32    (4 * AACG_LDS_FLOATS(AACG_TAB_F32_FLOATS))
 #define AACG_LDS_BYTES_QUANT  (4 * AACG_LDS_FLOATS(AACG_TAB_QUANT_FLOATS))
 

@@ -29,6 +29,8 @@
 #ifndef AACG_KERNELS_H
 #define AACG_KERNELS_H
 
+#include <type_traits>
+
 #include "devport.h"
 #include "aacg_device.h"
 
@@ -170,6 +172,29 @@ DP_DEVICE void stage_tables_store(float* lds, int n_floats, const dpf4& t0, cons
     const int n4 = n_floats >> 2, tid = dp_tid();
     if (tid < n4) dst[tid] = t0;
     if (tid + AACG_WG_THREADS < n4) dst[tid + AACG_WG_THREADS] = t1;
+}
+/* the same for eight-wave workgroups (AACG_HALF_WAVES): three 16-byte pieces per lane, and the quant part's signed IQ table cut to
+ * q = -AACG_HALF_IQH..AACG_HALF_IQH-1 on the way (the f32 part ends before it and is copied as it is) */
+DP_DEVICE int stage_tables_half_src(int i)
+{
+    const int iq4 = AACG_TAB_OFF_IQ_SMALL / 4, cut4 = AACG_TAB_IQ_CUT(AACG_HALF_IQH) / 4;
+    return i < iq4 ? i : i < iq4 + AACG_HALF_IQH / 2 ? i + cut4 / 2 : i + cut4;
+}
+DP_DEVICE void stage_tables_load_half(const aacg_tables* T, int n_floats, dpf4& t0, dpf4& t1, dpf4& t2)
+{
+    const dpf4* src = (const dpf4*)T;
+    const int n4 = n_floats >> 2, tid = dp_tid(), nt = AACG_HALF_WAVES * 64;
+    t0 = src[stage_tables_half_src(tid < n4 ? tid : n4 - 1)];
+    t1 = src[stage_tables_half_src(tid + nt < n4 ? tid + nt : n4 - 1)];
+    t2 = src[stage_tables_half_src(tid + 2 * nt < n4 ? tid + 2 * nt : n4 - 1)];
+}
+DP_DEVICE void stage_tables_store_half(float* lds, int n_floats, const dpf4& t0, const dpf4& t1, const dpf4& t2)
+{
+    dpf4* dst = (dpf4*)lds;
+    const int n4 = n_floats >> 2, tid = dp_tid(), nt = AACG_HALF_WAVES * 64;
+    if (tid < n4) dst[tid] = t0;
+    if (tid + nt < n4) dst[tid + nt] = t1;
+    if (tid + 2 * nt < n4) dst[tid + 2 * nt] = t2;
 }
 DP_DEVICE void stage_tables(const aacg_tables* T, float* lds, int n_floats)
 {
@@ -922,11 +947,13 @@ struct chan_ctx {
  * 8 lane + 512 i + 4 h).  The maps hold one byte per coefficient, so one 8-byte read covers the two groups of
  * an i; both the long and the short map are read unconditionally (no branch between the loads). */
 struct band_raw { dpf2 lng[2], sht; };
+/* IQH: the signed IQ table in LDS covers q = -IQH..IQH-1 (AACG_TAB_IQ_CUT: the band maps sit that much earlier) */
+template <int IQH = 512>
 DP_DEVICE void band_raw_load(const float* tab, band_raw& r)
 {
     const int lane = dp_lane();
-    const unsigned char* bl = (const unsigned char*)(tab + AACG_TAB_OFF_BAND_LONG);
-    const unsigned char* bs = (const unsigned char*)(tab + AACG_TAB_OFF_BAND_SHORT);
+    const unsigned char* bl = (const unsigned char*)(tab + AACG_TAB_OFF_BAND_LONG - AACG_TAB_IQ_CUT(IQH));
+    const unsigned char* bs = (const unsigned char*)(tab + AACG_TAB_OFF_BAND_SHORT - AACG_TAB_IQ_CUT(IQH));
     r.lng[0] = *(const dpf2*)(bl + 8 * lane);
     r.lng[1] = *(const dpf2*)(bl + 8 * lane + 512);
     r.sht = *(const dpf2*)(bs + ((8 * lane) & 127));   /* pos & 127 does not depend on i */
@@ -1002,9 +1029,10 @@ DP_DEVICE void prepare_bands(const quant_regs& r, const float* tab, bool two, bo
  *   dead band:  x = IQ[q] * 0  + (+0) = +0   (uncoded, ZERO or INTENSITY band, ics.js:222-227)
  * Larger magnitudes read some other LDS word (or 0 outside the allocation); `oor` collects the packed
  * q + 512 so that the caller can detect them afterwards and patch those elements (dequant4_big). */
+template <int IQH = 512>
 DP_DEVICE void dequant4(int iq0, float sf_eff, float z_eff, int p01, int p23, float (&x)[4], int& oor)
 {
-    oor |= dp_pk_add_u16(p01, 0x02000200) | dp_pk_add_u16(p23, 0x02000200);
+    oor |= dp_pk_add_u16(p01, IQH * 0x00010001) | dp_pk_add_u16(p23, IQH * 0x00010001);
     dpv2 a, b, sf, z;
     a[0] = dp_lds_read_f32(dp_mad4_i16_lo(p01, iq0)); a[1] = dp_lds_read_f32(dp_mad4_i16_hi(p01, iq0));
     b[0] = dp_lds_read_f32(dp_mad4_i16_lo(p23, iq0)); b[1] = dp_lds_read_f32(dp_mad4_i16_hi(p23, iq0));
@@ -1013,17 +1041,18 @@ DP_DEVICE void dequant4(int iq0, float sf_eff, float z_eff, int p01, int p23, fl
     b = dp_fma2(b, sf, z);
     x[0] = a[0]; x[1] = a[1]; x[2] = b[0]; x[3] = b[1];
 }
-#define AACG_OOR_MASK ((int)0xFC00FC00)                /* some q + 512 outside 0..1023 */
+#define AACG_OOR_MASK(IQH) ((int)(0xFFFFFFFFu ^ ((2u * (IQH) - 1u) * 0x00010001u)))   /* some q + IQH outside 0..2 IQH - 1 */
 
 /* the rare magnitudes outside the LDS table: full IQ_TABLE in global memory; [8191] = NaN like the JS
  * out-of-range read */
+template <int IQH = 512>
 DP_DEVICE void dequant4_big(const aacg_tables* T, bool live, float sf, int p01, int p23, float (&x)[4])
 {
     const int q[4] = {(int)(short)(p01 & 0xffff), p01 >> 16, (int)(short)(p23 & 0xffff), p23 >> 16};
 #pragma unroll
     for (int e = 0; e < 4; e++) {
         const int a = q[e] < 0 ? -q[e] : q[e];
-        if ((q[e] + 512) & ~1023) {
+        if ((q[e] + IQH) & ~(2 * IQH - 1)) {
             const float v = T->iq[a > 8191 ? 8191 : a];
             x[e] = live ? (q[e] > 0 ? v : -v) * sf : 0.0f;
         }
@@ -1112,7 +1141,7 @@ DP_DEVICE void pns_channel(const aacg_pns_tables* T, const float* tab, const cha
 
 /* Produces xl / xr[16]: element 8 i + e is coefficient 8 lane + 512 i + e of the left / right
  * (or single) channel after dequant, MS and IS. */
-template <bool PNS = false>
+template <bool PNS = false, int IQH = 512>
 DP_DEVICE void spectral_quant(const aacg_kparams& P, const float* tab, const unit_view& u, int n_ch,
                               const quant_regs& qreg, float* bt, float (&xl)[16], float (&xr)[16])
 {
@@ -1126,7 +1155,7 @@ DP_DEVICE void spectral_quant(const aacg_kparams& P, const float* tab, const uni
     const bool ms_on = two && (u.flags & AACG_UNIT_COMMON_WINDOW) && (u.flags & AACG_UNIT_MASK_PRESENT);
     const bool mask  = (u.flags & AACG_UNIT_MASK_PRESENT) != 0;
     band_raw braw;
-    band_raw_load(tab, braw);
+    band_raw_load<IQH>(tab, braw);
     /* band indices g * maxSFB + sfb reach 64 and beyond only with window groups (8 x 15 sections); a long window has
      * at most 51 bands, so its frames prepare one band per lane and the "no band" record (wave-uniform) */
     if (ccL.cls | ccR.cls) {
@@ -1160,7 +1189,7 @@ DP_DEVICE void spectral_quant(const aacg_kparams& P, const float* tab, const uni
     bool  liveL[4], liveR[4], isR[4];
     float g_isc[4], sfL[4], sfR[4];
     int big = 0;
-    const int iq0 = dp_lds_addr(tab + AACG_TAB_OFF_IQ_SMALL + 512);
+    const int iq0 = dp_lds_addr(tab + AACG_TAB_OFF_IQ_SMALL + IQH);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int i = k >> 1, h = k & 1;
@@ -1174,16 +1203,16 @@ DP_DEVICE void spectral_quant(const aacg_kparams& P, const float* tab, const uni
         g_isc[k] = recR[k].x;
         sfR[k] = isR[k] ? 0.0f : recR[k].x;
         /* the addend is -0 on a band that carries coefficients, +0 elsewhere: the flag's sign bit */
-        dequant4(iq0, sfL[k], __builtin_bit_cast(float, fl & AACG_BR_LIVE), h ? ql[i].z : ql[i].x, h ? ql[i].w : ql[i].y, *(float (*)[4])&xl[4 * k], big);
-        dequant4(iq0, sfR[k], __builtin_bit_cast(float, fr & AACG_BR_LIVE), h ? qr[i].z : qr[i].x, h ? qr[i].w : qr[i].y, *(float (*)[4])&xr[4 * k], big);
+        dequant4<IQH>(iq0, sfL[k], __builtin_bit_cast(float, fl & AACG_BR_LIVE), h ? ql[i].z : ql[i].x, h ? ql[i].w : ql[i].y, *(float (*)[4])&xl[4 * k], big);
+        dequant4<IQH>(iq0, sfR[k], __builtin_bit_cast(float, fr & AACG_BR_LIVE), h ? qr[i].z : qr[i].x, h ? qr[i].w : qr[i].y, *(float (*)[4])&xr[4 * k], big);
     }
 
-    if (dp_any((big & AACG_OOR_MASK) != 0)) {          /* escape-coded magnitudes: rare */
+    if (dp_any((big & AACG_OOR_MASK(IQH)) != 0)) {          /* escape-coded magnitudes: rare */
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int i = k >> 1, h = k & 1;
-            dequant4_big(P.tab, liveL[k], sfL[k], h ? ql[i].z : ql[i].x, h ? ql[i].w : ql[i].y, *(float (*)[4])&xl[4 * k]);
-            dequant4_big(P.tab, liveR[k], sfR[k], h ? qr[i].z : qr[i].x, h ? qr[i].w : qr[i].y, *(float (*)[4])&xr[4 * k]);
+            dequant4_big<IQH>(P.tab, liveL[k], sfL[k], h ? ql[i].z : ql[i].x, h ? ql[i].w : ql[i].y, *(float (*)[4])&xl[4 * k]);
+            dequant4_big<IQH>(P.tab, liveR[k], sfR[k], h ? qr[i].z : qr[i].x, h ? qr[i].w : qr[i].y, *(float (*)[4])&xr[4 * k]);
         }
     }
 
@@ -2018,23 +2047,31 @@ DP_DEVICE int ov_buffer(int rot, int add) { int r = rot + add; r = r >= AACG_OV_
 #define AACG_LDS_BYTES_QUANT_EX (AACG_LDS_BYTES_QUANT + 4 * AACG_WG_WAVES * AACG_RUN_XCH_FLOATS)
 /* RV = true builds (aacg_engine_rv.hip): chains longer than a run without a recomputed frame — the plan's runs all start from
  * what the run before them hands over through a rendezvous cell (aacg_rv_args), never from a recomputed predecessor. */
-template <int KIND, int OUT = AACG_OUTPUT_F32, bool DD = false, bool EX = false, bool CPL = false, bool RV = false, bool NTL = false, bool PRE = false>
+/* NW < AACG_WG_WAVES builds (aacg_engine_rv.hip: the int16-seam rendezvous kernel): a run of 16 frames on NW = 8 waves, two
+ * frames ("tasks") per wave, so that two workgroups fit on a CU (AACG_HALF_LDS_BYTES, at most 128 VGPRs) — see AACG_HALF_*. */
+template <int KIND, int OUT = AACG_OUTPUT_F32, bool DD = false, bool EX = false, bool CPL = false, bool RV = false, bool NTL = false, bool PRE = false,
+          int NW = AACG_WG_WAVES>
 DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nullptr, const aacg_run* runs_pre = nullptr, const aacg_tables* tab_pre = nullptr, const aacg_rv_link* links_pre = nullptr,
                               const aacg_dev_unit* units_pre = nullptr, const void* coeffs_pre = nullptr, const aacg_band_meta* meta_pre = nullptr)
 {
+    constexpr bool HALF = NW != AACG_WG_WAVES;
+    static_assert(!HALF || (NW == AACG_HALF_WAVES && RV && !DD && !EX && !CPL), "eight-wave runs: the rendezvous kernels without optional stages only");
+    constexpr int TPW = AACG_WG_WAVES / NW;            /* tasks (frames of the run) per wave */
+    constexpr int IQH = (HALF && KIND == AACG_INPUT_QUANT_I16) ? AACG_HALF_IQH : 512;
     const aacg_run* const k_runs = PRE ? runs_pre : P.runs;
     const aacg_tables* const k_tab = PRE ? tab_pre : P.tab;
     const aacg_dev_unit* const k_units = PRE ? units_pre : P.units;
     const void* const k_coeffs = PRE ? coeffs_pre : P.coeffs;
     const aacg_band_meta* const k_meta = PRE ? meta_pre : P.meta;
-    const int TAB_FLOATS = (KIND == AACG_INPUT_QUANT_I16) ? AACG_TAB_QUANT_FLOATS : AACG_TAB_F32_FLOATS;
+    const int TAB_FLOATS = (KIND == AACG_INPUT_QUANT_I16) ? AACG_TAB_QUANT_FLOATS - AACG_TAB_IQ_CUT(IQH) : AACG_TAB_F32_FLOATS;
     const int lane = dp_lane(), wave = dp_wave();
     const aacg_run* run = k_runs + dp_block();
-    float* lds = (float*)dp_lds_fixed<4 * AACG_LDS_FLOATS(TAB_FLOATS) + (EX ? 4 * AACG_WG_WAVES * AACG_RUN_XCH_FLOATS : 0)>();
+    float* lds = (float*)dp_lds_fixed<HALF ? AACG_HALF_LDS_BYTES(TAB_FLOATS) : 4 * AACG_LDS_FLOATS(TAB_FLOATS) + (EX ? 4 * AACG_WG_WAVES * AACG_RUN_XCH_FLOATS : 0)>();
     const float* tab = lds;
     float* slots = lds + AACG_TAB_SLOT_BASE(TAB_FLOATS);
-    float* slot = slots + wave * AACG_SLOT_FLOATS;
-    int* flags = (int*)(slots + AACG_WG_WAVES * AACG_SLOT_FLOATS);
+    float* slot = slots + (HALF ? wave % AACG_HALF_SLOTS : wave) * AACG_SLOT_FLOATS;
+    /* one flag per task: its tails are in its slot; HALF builds: then one per task: it has read its predecessor's tails */
+    int* flags = (int*)(slots + (HALF ? AACG_HALF_SLOTS : AACG_WG_WAVES) * AACG_SLOT_FLOATS);
     float* xch = EX ? (float*)(flags + AACG_WG_WAVES) + wave * AACG_RUN_XCH_FLOATS : nullptr;
 
     /* The start of a run is dependent memory round trips and nothing else (aacg_run, aacg_device.h): behind the kernel
@@ -2047,22 +2084,25 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
     unsigned w_unit = dp_sload1(run, (int)__builtin_offsetof(aacg_run, wave_unit) + 4 * wave);
     unsigned w_coef = dp_sload1(run, (int)__builtin_offsetof(aacg_run, wave_coef) + 4 * wave);
     unsigned w_meta = dp_sload1(run, (int)__builtin_offsetof(aacg_run, wave_meta) + 4 * wave);
-    dpf4 tr0, tr1;
-    stage_tables_load(k_tab, TAB_FLOATS, tr0, tr1);
+    dpf4 tr0, tr1, tr2;
+    if (HALF) stage_tables_load_half(k_tab, TAB_FLOATS, tr0, tr1, tr2);
+    else      stage_tables_load(k_tab, TAB_FLOATS, tr0, tr1);
     dp_swait(rh, lkw, w_unit, w_coef, w_meta);
 
     const int pred_unit = (int)rh[0], n_units = (int)rh[1];
-    const bool run_is_last = rh[2] != 0;
-    const int w_nch = (int)((rh[3] >> (2 * wave)) & 3u);
-    const int run_ov0[2] = {(int)rh[4], (int)rh[5]}, run_rot[2] = {(int)rh[6], (int)rh[7]};
+    bool run_is_last = rh[2] != 0;
+    int w_nch = (int)((rh[3] >> (2 * wave)) & 3u);
+    int run_ov0[2] = {(int)rh[4], (int)rh[5]}, run_rot[2] = {(int)rh[6], (int)rh[7]};
     const bool has_pred = !RV && pred_unit >= 0;
     aacg_rv_link lk; lk.link_in = lk.link_out = lk.succ_unit = -1; lk.reserved = 0;
     if (RV) { lk.link_in = (int)lkw[0]; lk.link_out = (int)lkw[1]; lk.succ_unit = (int)lkw[2]; }
     /* pipelined launches (aacg_decode_pipelined): the two ends of a chain meet the plan's neighbouring LAUNCHES in cross-launch
      * cells (aacg_xl_cell) exactly as its runs meet each other in the in-launch ones */
     const bool xl = RV && V->xl_cells != nullptr;
+    /* the frame of the run this wave works on (HALF builds: wave w takes frame w, then frame w + NW) */
+    int task = wave;
     /* the frame another workgroup may be waiting for: a run's last, when its chain goes on — in this launch or in the next */
-    const bool hands_over = RV && wave == n_units - 1 && (lk.link_out >= 0 || xl);
+    bool hands_over = RV && task == n_units - 1 && (lk.link_out >= 0 || xl);
     const bool hurry = hands_over;
     /* this launch's overlap buffers of the run's channels (float offsets in the pool), evaluated where a chain's first or last wave needs them */
 #define AACG_OV_IN(c)  (run_ov0[c] + 1024 * ov_buffer(run_rot[c], P.flip))
@@ -2074,7 +2114,7 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
      * (aacg_run_wave_unit is the same rule on the planner's side: wave_unit / wave_coef / wave_meta are per WAVE.) */
     const bool dd = DD && has_pred && n_units == AACG_WG_WAVES;
     const bool is_pred_wave = has_pred && !dd && wave == 0;
-    const bool active = (has_pred && !dd) ? (wave == 0 || wave - 1 < n_units) : wave < n_units;     /* this wave has a frame */
+    bool active = (has_pred && !dd) ? (wave == 0 || wave - 1 < n_units) : wave < n_units;     /* this wave has a frame */
     const int n_pass = (DD && dd && wave == 0) ? 2 : 1;
     float* scratch = DD ? P.scratch + (size_t)dp_block() * AACG_SLOT_FLOATS : nullptr;
 
@@ -2090,7 +2130,7 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
     if (AACG_ABL(P, 64)) dp_setprio(0); else if (AACG_ABL(P, 32)) dp_setprio(1 - (wave >> 3)); else dp_setprio(hurry ? 3 : 3 - (wave >> 2));
     const unsigned long long t_start = AACG_ABL(P, 16) ? dp_clock() : 0;
     /* (the coupling builds carry their side buffer in spec_out, aacg_set_cpl: never a trace there) */
-    unsigned long long* trace = (!CPL && AACG_ABL(P, 16)) ? (unsigned long long*)P.spec_out + ((size_t)dp_block() * AACG_WG_WAVES + wave) * 8 : nullptr;
+    unsigned long long* trace = (!CPL && AACG_ABL(P, 16)) ? (unsigned long long*)P.spec_out + ((size_t)dp_block() * AACG_WG_WAVES + wave) * 8 : nullptr;   /* per task */
     if (trace && lane == 0) trace[0] = t_start;
 
     /* This wave's spectrum: only the tables are waited for before the barrier.  All loads are
@@ -2101,10 +2141,10 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
     dpf4 xa[4], xb[4];
     int n_ch = 0, cls0 = 0, cls1 = 0;                  /* from the unit record, whose first use is behind the table barrier */
     bool pair_path = false;
-    auto issue_loads = [&](uint32_t coef_block, uint32_t meta_block, int nch) {
-        if (KIND == AACG_INPUT_QUANT_I16) quant_load<NTL>(k_coeffs, k_meta, coef_block, meta_block, nch, qreg);
+    auto issue_loads = [&](uint32_t coef_block, uint32_t meta_block, int nch, const void* coeffs, const aacg_band_meta* metas) {
+        if (KIND == AACG_INPUT_QUANT_I16) quant_load<NTL>(coeffs, metas, coef_block, meta_block, nch, qreg);
         else {
-            const float* xsrc = (const float*)k_coeffs + (size_t)coef_block * 1024u;
+            const float* xsrc = (const float*)coeffs + (size_t)coef_block * 1024u;
             const float* xsrc1 = xsrc + (nch == 2 ? 1024 : 0);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -2138,12 +2178,50 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
      * its data after ~1.7 us instead of queueing behind the whole chip's 33 MB, and the later groups' data
      * arrives while the SIMD is still busy with the earlier ones. */
     const bool early = wave < (KIND == AACG_INPUT_QUANT_I16 ? 2 : 4) || hurry || AACG_ABL(P, 128);
-    if (early) issue_loads(w_coef, w_meta, w_nch);
-    stage_tables_store(lds, TAB_FLOATS, tr0, tr1);
-    if (lane == 0) flags[wave] = 0;
+    if (early) issue_loads(w_coef, w_meta, w_nch, k_coeffs, k_meta);
+    if (HALF) stage_tables_store_half(lds, TAB_FLOATS, tr0, tr1, tr2);
+    else      stage_tables_store(lds, TAB_FLOATS, tr0, tr1);
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < (HALF ? 2 * TPW : 1); j++) flags[wave + NW * j] = 0;
+    }
     dp_block_sync_lds();                               /* tables and flags are in LDS */
-    if (!early) issue_loads(w_coef, w_meta, w_nch);
+    if (!early) issue_loads(w_coef, w_meta, w_nch, k_coeffs, k_meta);
     if (trace && lane == 0) trace[1] = dp_clock();
+    /* HALF builds: the second task's requests go out when the first task's transform is done (with them live across the
+     * transform the body spills), so that their latency hides behind the first task's epilogue; its unit record follows when the
+     * task starts (held from here, it spills SGPRs).  Unconditional (a second task without a frame reads unit 0's blocks like
+     * an idle wave): a load under a condition would make hipcc wait for it at the join. */
+    const int task2 = HALF ? wave + NW : 0;
+    auto next_loads = [&]() {
+        w_nch = (int)(((unsigned)dp_uniform((int)run->wave_nch) >> (2 * task2)) & 3u);
+        issue_loads((unsigned)dp_uniform((int)run->wave_coef[task2]), (unsigned)dp_uniform((int)run->wave_meta[task2]), w_nch, P.coeffs, P.meta);
+    };
+
+    /* one task: dequantise / stage, transform, hand over, overlap-add and store one frame of the run */
+    auto do_task = [&](auto K) {
+    constexpr int k = decltype(K)::value;
+    if (k > 0) {
+        task = wave + NW * k;
+        slot = slots + (task % AACG_HALF_SLOTS) * AACG_SLOT_FLOATS;
+        active = task < n_units;
+        if (!active) return;
+        u = load_unit(P.units + dp_uniform(run->wave_unit[task2]));
+        /* (read again rather than held across the first task: held, they spill SGPRs) */
+        run_is_last = dp_uniform(run->is_last) != 0;
+        for (int c = 0; c < 2; c++) { run_ov0[c] = dp_uniform(run->ov0[c]); run_rot[c] = dp_uniform(run->rot[c]); }
+        if (RV) {
+            const aacg_rv_link* lp = (PRE ? links_pre : V->links) + dp_block();
+            lk.link_in = dp_uniform(lp->link_in); lk.link_out = dp_uniform(lp->link_out); lk.succ_unit = dp_uniform(lp->succ_unit);
+        }
+        hands_over = RV && task == n_units - 1 && (lk.link_out >= 0 || xl);
+        /* second tasks issue first: the older of two workgroups on a CU finishes first, so its LDS goes to the next one */
+        if (!AACG_ABL(P, 64) && !AACG_ABL(P, 32)) dp_setprio(3);
+        if (trace) {
+            trace = (unsigned long long*)P.spec_out + ((size_t)dp_block() * AACG_WG_WAVES + task) * 8;
+            if (lane == 0) trace[0] = trace[1] = dp_clock();
+        }
+    }
     n_ch = active ? u.n_ch : 0;
     cls0 = u.seq[0] == AACG_EIGHT_SHORT_SEQUENCE;
     cls1 = u.seq[1] == AACG_EIGHT_SHORT_SEQUENCE;
@@ -2151,7 +2229,7 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
 
     /* dequantise / stage this wave's loaded spectrum and run the filterbank on it: tails into the slot, the
      * windowed first half into hx / hy */
-    auto front = [&](bool want_head) {
+    auto front = [&](bool want_head, bool prefetch = false) {
         if (trace) { dp_vm_drain(); if (lane == 0) trace[6] = dp_clock(); }     /* profiling: this wave's loads have landed */
         if (AACG_ABL(P, 1) && KIND != AACG_INPUT_QUANT_I16) {
 #pragma unroll
@@ -2169,7 +2247,7 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
                     xr[8 * i + 4] = xr[8 * i]; xr[8 * i + 5] = xr[8 * i + 1]; xr[8 * i + 6] = xr[8 * i + 2]; xr[8 * i + 7] = xr[8 * i + 3];
                 }
             } else
-            spectral_quant<EX>(P, tab, u, n_ch, qreg, slot + 1024, xl, xr);
+            spectral_quant<EX, IQH>(P, tab, u, n_ch, qreg, slot + 1024, xl, xr);
             /* TNS runs here (decoder.js:309-313): identity as the reference executes it (tns.js:106,122), so the plain
              * kernels have nothing to do; the EX builds apply the filters AACG_TNS_SPEC asks for */
             if (EX && P.tns && (u.tns[0] || (n_ch == 2 && u.tns[1]))) {
@@ -2223,9 +2301,12 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
         dp_wave_sync();
         if (trace && lane == 0) trace[2] = dp_clock();     /* spectrum arrived and staged */
         filter_unit<AACG_VM_KIND(KIND)>(tab, u, n_ch, pair_path, want_head, slot, hx0, hy0, hx1, hy1);
+        if (HALF && prefetch) next_loads();
     };
 
-    if (active) front(!is_pred_wave && n_pass == 1);
+    /* HALF builds: a slot serves tasks t and t + AACG_HALF_SLOTS; task t's tails stay there until task t + 1 has read them */
+    if (HALF && active && task >= AACG_HALF_SLOTS) dp_flag_wait(&flags[AACG_WG_WAVES + task - AACG_HALF_SLOTS + 1], 1);
+    if (active) front(!is_pred_wave && n_pass == 1, k + 1 < TPW);
     if (DD && n_pass == 2) {
         /* double duty (cold: only the first wave of a full later run): park the predecessor's tails, then fetch
          * and process this wave's own frame with a second copy of the code above */
@@ -2237,14 +2318,14 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
         cls0 = u.seq[0] == AACG_EIGHT_SHORT_SEQUENCE;
         cls1 = u.seq[1] == AACG_EIGHT_SHORT_SEQUENCE;
         pair_path = n_ch == 2 && u.seq[0] == u.seq[1] && u.shape[0] == u.shape[1] && u.shape_prev[0] == u.shape_prev[1];
-        issue_loads(u.coef_offset, u.meta_offset, u.n_ch);
+        issue_loads(u.coef_offset, u.meta_offset, u.n_ch, k_coeffs, k_meta);
         dp_wave_sync();                                /* the slot is free again */
         front(true);
     }
 
     /* this wave's tails are complete in its slot: release them to the next wave */
     dp_wave_sync();
-    if (lane == 0) dp_flag_set(&flags[wave], 1);
+    if (lane == 0) dp_flag_set(&flags[task], 1);
     if (trace && lane == 0) trace[3] = dp_clock();         /* IMDCT done, tail released */
 
     typedef typename pcm_elem<OUT>::type pcm_t;
@@ -2295,7 +2376,7 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
     } else if (active && !is_pred_wave) {
         /* the long paths of the int16 seam deal their columns out by long_col (filter_unit<VM>) */
         const int lcol = AACG_VM_KIND(KIND) ? long_col(lane) : lane;
-        if (wave == 0) {
+        if (task == 0) {
             /* first frame of its chain in this launch: overlap state from HBM (filter_bank.js:38-41,
              * `overlap = this.overlaps[channel]`); a double-duty wave: the tails it parked itself */
             const float* ov0 = n_pass == 2 ? scratch : P.overlap + AACG_OV_IN(0);
@@ -2336,20 +2417,32 @@ DP_DEVICE void imdct_run_body(const aacg_kparams& P, const aacg_rv_args* V = nul
         } else {
             cpl_prefetch pre;
             couple_prefetch<CPL>(P, u, pre);
-            dp_flag_wait(&flags[wave - 1], 1);         /* the previous frame's tails (acquire) */
+            dp_flag_wait(&flags[task - 1], 1);         /* the previous frame's tails (acquire) */
             if (trace && lane == 0) trace[4] = dp_clock();
-            epilogue<true, OUT, CPL>(P, pre, slot - AACG_SLOT_FLOATS, slot - AACG_SLOT_FLOATS, u, n_ch, cls0, cls1, P.pcm, hx0, hy0, hx1, hy1, lcol);
+            float* const pslot = HALF ? slots + ((task - 1) % AACG_HALF_SLOTS) * AACG_SLOT_FLOATS : slot - AACG_SLOT_FLOATS;
+            epilogue<true, OUT, CPL>(P, pre, pslot, pslot, u, n_ch, cls0, cls1, P.pcm, hx0, hy0, hx1, hy1, lcol);
         }
         if (trace && lane == 0) trace[5] = dp_clock();     /* PCM stores issued */
         /* the chain's last frame in this launch: its tail is the new overlap state (planar in HBM) */
         const int last_wave = (has_pred && !dd) ? n_units : n_units - 1;
-        if (wave == last_wave && run_is_last && !xl)      /* (pipelined: the hand-over above has put it there, or the next launch has taken it) */
+        if (task == last_wave && run_is_last && !xl)      /* (pipelined: the hand-over above has put it there, or the next launch has taken it) */
             save_tails(P.overlap + AACG_OV_OUT(0), P.overlap + AACG_OV_OUT(1));
+    }
+    if (HALF && active && task >= 1) {
+        /* the previous frame's slot is free (release: its reads are complete) — on every path: a later frame waits for this
+         * flag before it works in that slot.  The profiling path without an epilogue (AACG_ABL 2) takes the tails' flag first,
+         * so that the slot is still handed on only once they are there. */
+        if (AACG_ABL(P, 2)) dp_flag_wait(&flags[task - 1], 1);
+        dp_wave_sync();
+        if (lane == 0) dp_flag_set(&flags[AACG_WG_WAVES + task], 1);
     }
     if (trace) {                                           /* profiling: when this wave's stores were acknowledged (a wave ends no earlier), and on which CU it ran */
         dp_vm_drain();
         if (lane == 0) trace[7] = ((unsigned long long)dp_cu_id() << 52) | (dp_clock() & 0xfffffffffffffull);
     }
+    };
+    do_task(std::integral_constant<int, 0>());
+    if constexpr (TPW > 1) do_task(std::integral_constant<int, 1>());
 }
 
 #undef AACG_OV_IN

@@ -30,6 +30,7 @@ struct aacg_run_kernel {
     bool preloaded = false; /* AACG_RUN_KERNEL_PRE signature: six leading pointer arguments (run table, tables, links, units, spectra,
                                band words) that arrive in SGPRs with the wave (-amdgpu-kernarg-preload-count), then the two
                                argument records */
+    unsigned threads = AACG_WG_THREADS;   /* workgroup size it is launched with: 16 waves, or AACG_HALF_WAVES for the eight-wave body */
 };
 /* The signature of a run kernel whose early pointers are preloaded: by-value struct arguments are not preloaded, so the pointers
  * a wave needs for its first loads travel once more as leading scalar arguments — the table loads and the run record's batch go
@@ -39,6 +40,13 @@ struct aacg_run_kernel {
     void name(const aacg_run* runs, const aacg_tables* tab, const aacg_rv_link* links, const aacg_dev_unit* units, const void* coeffs, \
               const aacg_band_meta* meta, const aacg_kparams P, const aacg_rv_args V) \
     { imdct_run_body<__VA_ARGS__, true>(P, &V, runs, tab, links, units, coeffs, meta); }
+/* the same with the eight-wave run body (imdct_run_body<..., NW = AACG_HALF_WAVES>): launched with 512 threads, and bounded so that
+ * it keeps to 128 VGPRs — four waves per SIMD, two workgroups per CU with its 80 KiB of LDS */
+#define AACG_RUN_KERNEL_PRE_HALF(name, ...) \
+    extern "C" __global__ __launch_bounds__(AACG_HALF_WAVES * 64, 4) \
+    void name(const aacg_run* runs, const aacg_tables* tab, const aacg_rv_link* links, const aacg_dev_unit* units, const void* coeffs, \
+              const aacg_band_meta* meta, const aacg_kparams P, const aacg_rv_args V) \
+    { imdct_run_body<__VA_ARGS__, true, AACG_HALF_WAVES>(P, &V, runs, tab, links, units, coeffs, meta); }
 
 /* one table per translation unit */
 extern const aacg_run_kernel aacg_run_kernels_plain[];  extern const int aacg_run_kernels_plain_n;    /* aacg_engine.hip */

@@ -70,6 +70,35 @@ if PIPE:
         print("   last stores issued -> acknowledged: median %.2f us (p10 %.2f, p90 %.2f);  acknowledged -> next workgroup's first wave: median %.2f (p10 %.2f, p90 %.2f);  together %.2f" % (
             *(np.percentile(r[:, 1] - r[:, 0], q) for q in (50, 10, 90)), *(np.percentile(r[:, 2] - r[:, 1], q) for q in (50, 10, 90)), np.median(r[:, 2] - r[:, 0])))
     print("this launch: last stores issued -> acknowledged, per workgroup: median %.2f us, p90 %.2f" % tuple(np.percentile(ack_l - el, q) for q in (50, 90)))
+    # co-residence over the last four launches: which workgroups share a CU at the same time, and of which launches
+    # (a workgroup lives from its first wave's start to its last wave's acknowledged stores; the record of every frame carries the CU)
+    life = []
+    for li, part in enumerate(parts):
+        r = part.view(np.uint64)[: 256 * 16 * 8].reshape(256, 16, 8)[:NB, :NW]
+        cu = (r[:, 0, 7] >> np.uint64(52)).astype(int)
+        st = (r[:, :, 0].astype(np.float64) * 0.01).min(axis=1)
+        en = ((r[:, :, 7] & np.uint64(M)).astype(np.float64) * 0.01).max(axis=1)
+        life += [(int(cu[b]), li, float(st[b]), float(en[b])) for b in range(NB)]
+    per_cu = {}
+    for c, li, a0, a1 in life:
+        per_cu.setdefault(c, []).append((a0, a1, li))
+    same = other = 0
+    for c, iv in per_cu.items():
+        for i in range(len(iv)):
+            for j in range(i + 1, len(iv)):
+                if min(iv[i][1], iv[j][1]) > max(iv[i][0], iv[j][0]):
+                    if iv[i][2] == iv[j][2]: same += 1
+                    else: other += 1
+    lo, hi = max(min(a0 for _, _, a0, _ in life), 0.0), max(a1 for _, _, _, a1 in life)
+    grid = np.linspace(lo, hi, 400)
+    occ = np.array([[sum(1 for a0, a1, _ in iv if a0 <= g < a1) for g in grid] for iv in per_cu.values()])
+    mid = occ[:, 100:300]                              # away from the window's edges (launches before and after are not recorded)
+    print("co-residence, last four launches: %d workgroups on %d CUs; overlapping pairs on one CU: %d of different launches, %d of the same launch" % (
+        len(life), len(per_cu), other, same))
+    print("   workgroups resident per CU over the middle of the window: " + "  ".join("%d: %.1f %%" % (k, 100.0 * np.mean(mid == k)) for k in range(int(mid.max()) + 1)))
+    if same:
+        idle_at = [(g, int(np.sum(occ[:, gi] == 0))) for gi, g in enumerate(grid) if 100 <= gi < 300]
+        print("   (the same launch doubled up on a CU) CUs holding no workgroup at some moment in the middle of the window: max %d" % max(n for _, n in idle_at))
 
 # distribution over workgroups: where do the stragglers come from?
 end = t[:, :, 5].max(axis=1) - t0                     # last stores issued per workgroup
