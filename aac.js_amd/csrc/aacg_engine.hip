@@ -28,21 +28,9 @@
 #include "aacg_wait.h"
 
 /* ---- kernels ----------------------------------------------------------------------- */
-/* 1024 threads = 16 waves, one workgroup per CU: 4 waves per SIMD -> 128 VGPRs per lane */
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_quant(const aacg_kparams P) { imdct_run_body<AACG_INPUT_QUANT_I16>(P); }
-
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_f32(const aacg_kparams P) { imdct_run_body<AACG_INPUT_SPEC_F32>(P); }
-
-/* Every other variant of the run kernel lives in a translation unit of its own (aacg_engine_{rv,nt,ext,i16,exrun,couple}.hip:
- * their own code objects, so that adding to them never moves the two kernels above); each exports a table of its kernels
- * (aacg_routes.h). */
-const aacg_run_kernel aacg_run_kernels_plain[] = {
-    {AACG_RK_QUANT, "aacg_imdct_run_quant", (const void*)aacg_imdct_run_quant},
-    {0, "aacg_imdct_run_f32", (const void*)aacg_imdct_run_f32}
-};
-const int aacg_run_kernels_plain_n = 2;
+/* The two plain run kernels (aacg_run_kernels.h).  Every other variant lives in a translation unit of its own
+ * (aacg_engine_{rv,nt,ext,i16,exrun,couple}.hip: their own code objects, so that adding to them never moves these two). */
+AACG_RUN_KERNEL_UNIT(plain, AACG_RUN_KERNELS_PLAIN)
 
 /* aacg_engine_refresh.hip: a kept plan's unit records from the device parser's output */
 void aacg_refresh_launch(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg_parse_result* results, const aacg_refresh_map* map, uint32_t n_units,
@@ -345,16 +333,18 @@ void note_stream(aacg_engine* e, hipStream_t s)
 }  // namespace
 
 /* ---- the route: ONE decision (aacg_pick_route, aacg_routes.cpp), executed by launch_run, printed by aacg_plan_kernels ---- */
-/* the registered kernel with these switches; its symbol is what aacg_run_kernel_name composes (checked at aacg_create) */
+/* the tables of the registered run kernels, one per translation unit */
+struct run_kernel_set { const aacg_run_kernel* k; const int& n; };
+#define AACG_RUN_KERNEL_SET(set, ROWS) {aacg_run_kernels_##set, aacg_run_kernels_##set##_n},
+static const run_kernel_set run_kernel_sets[] = { AACG_RUN_KERNEL_SETS(AACG_RUN_KERNEL_SET) };
+#undef AACG_RUN_KERNEL_SET
+
+/* the registered kernel with these switches */
 const aacg_run_kernel* aacg_find_run_kernel(unsigned key)
 {
-    const aacg_run_kernel* const tabs[] = {aacg_run_kernels_plain, aacg_run_kernels_rv, aacg_run_kernels_nt, aacg_run_kernels_ext,
-                                           aacg_run_kernels_i16, aacg_run_kernels_exrun, aacg_run_kernels_couple};
-    const int counts[] = {aacg_run_kernels_plain_n, aacg_run_kernels_rv_n, aacg_run_kernels_nt_n, aacg_run_kernels_ext_n,
-                          aacg_run_kernels_i16_n, aacg_run_kernels_exrun_n, aacg_run_kernels_couple_n};
-    for (size_t t = 0; t < sizeof tabs / sizeof tabs[0]; t++)
-        for (int i = 0; i < counts[t]; i++)
-            if (tabs[t][i].key == key) return &tabs[t][i];
+    for (const run_kernel_set& s : run_kernel_sets)
+        for (int i = 0; i < s.n; i++)
+            if (s.k[i].key == key) return &s.k[i];
     return nullptr;
 }
 
@@ -378,7 +368,7 @@ int launch_kernel(aacg_engine* e, const aacg_run_kernel* k, unsigned blocks, hip
     void* args[8] = {&p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (k->key & AACG_RK_RV) { v = *V; args[1] = &v; }
     const void *a_runs = p.runs, *a_tab = p.tab, *a_links = V ? V->links : nullptr, *a_units = p.units, *a_coeffs = p.coeffs, *a_meta = p.meta;
-    if (k->preloaded) { args[0] = &a_runs; args[1] = &a_tab; args[2] = &a_links; args[3] = &a_units; args[4] = &a_coeffs; args[5] = &a_meta; args[6] = &p; args[7] = &v; }   /* AACG_RUN_KERNEL_PRE (aacg_routes.h) */
+    if (k->preloaded) { args[0] = &a_runs; args[1] = &a_tab; args[2] = &a_links; args[3] = &a_units; args[4] = &a_coeffs; args[5] = &a_meta; args[6] = &p; args[7] = &v; }   /* the PRE signature (aacg_run_kernels.h) */
     const dim3 block(k->threads);
     if (stop) HIP_TRY(e, hipExtLaunchKernel(k->fn, dim3(blocks), block, args, 0, s, nullptr, stop, 0), AACG_ERR_NO_DEVICE);
     else      HIP_TRY(e, hipLaunchKernel(k->fn, dim3(blocks), block, args, 0, s), AACG_ERR_NO_DEVICE);
@@ -591,20 +581,16 @@ int aacg_debug_pipeline_order(unsigned long long n, int streams, int* stream, lo
 }
 
 /* The registered run kernels: `index`-th symbol into dst; returns its switches (AACG_RK_*), or < 0 past the end.  Every
- * symbol must be what aacg_run_kernel_name composes from its switches (tests/test_routes.py; aacg_create checks it too). */
+ * symbol must be what aacg_run_kernel_name composes from its switches (tests/test_routes.py). */
 int aacg_debug_run_kernel(int index, char* dst, size_t n)
 {
-    const aacg_run_kernel* const tabs[] = {aacg_run_kernels_plain, aacg_run_kernels_rv, aacg_run_kernels_nt, aacg_run_kernels_ext,
-                                           aacg_run_kernels_i16, aacg_run_kernels_exrun, aacg_run_kernels_couple};
-    const int counts[] = {aacg_run_kernels_plain_n, aacg_run_kernels_rv_n, aacg_run_kernels_nt_n, aacg_run_kernels_ext_n,
-                          aacg_run_kernels_i16_n, aacg_run_kernels_exrun_n, aacg_run_kernels_couple_n};
-    for (size_t t = 0; t < sizeof tabs / sizeof tabs[0]; t++) {
-        if (index < counts[t]) {
-            if (!dst || std::strlen(tabs[t][index].name) + 1 > n) return AACG_ERR_INVALID_ARG;
-            std::strcpy(dst, tabs[t][index].name);
-            return (int)tabs[t][index].key;
+    for (const run_kernel_set& s : run_kernel_sets) {
+        if (index < s.n) {
+            if (!dst || std::strlen(s.k[index].name) + 1 > n) return AACG_ERR_INVALID_ARG;
+            std::strcpy(dst, s.k[index].name);
+            return (int)s.k[index].key;
         }
-        index -= counts[t];
+        index -= s.n;
     }
     return AACG_ERR_INVALID_ARG;
 }
@@ -655,13 +641,6 @@ int aacg_create(const aacg_config* cfg, aacg_engine** out)
         return AACG_ERR_NO_DEVICE;
     }
     e->parity.assign((size_t)cfg->max_streams * (size_t)cfg->max_channels, 0);
-    /* every registered run kernel carries the symbol its switches compose: what aacg_plan_kernels prints is what launches */
-    for (int i = 0;; i++) {
-        char name[96];
-        const int key = aacg_debug_run_kernel(i, name, sizeof name);
-        if (key < 0) break;
-        if (aacg_run_kernel_name((unsigned)key) != name) { std::fprintf(stderr, "aacgpu: run kernel table: %s registered with switches %d\n", name, key); aacg_destroy(e); return AACG_ERR_INVALID_ARG; }
-    }
     if (cfg->pns_mode == AACG_PNS_SPEC) {
         aacg_pns_tables* pt = new (std::nothrow) aacg_pns_tables;
         const bool ok = pt && aacg_build_pns_tables(cfg->sample_index, pt) == AACG_OK &&

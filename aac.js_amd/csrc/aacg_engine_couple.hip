@@ -17,25 +17,9 @@ extern "C" __global__ __launch_bounds__(AACG_COUPLE_WAVES * 64)
 void aacg_couple_pcm(const aacg_couple_params Q) { couple_pcm_body(Q, AACG_COUPLE_WAVES); }
 
 /* the run kernels with the independent coupling in their epilogue (plans whose every run is a first run or a run with a
- * wave of its own for the predecessor: no double duty) */
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_quant_cpl(const aacg_kparams P) { imdct_run_body<AACG_INPUT_QUANT_I16, AACG_OUTPUT_F32, false, false, true>(P); }
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_f32_cpl(const aacg_kparams P) { imdct_run_body<AACG_INPUT_SPEC_F32, AACG_OUTPUT_F32, false, false, true>(P); }
-
-/* batches of multichannel frames (where coupling lives): non-temporal loads of the spectra (aacg_engine_nt.hip says why) */
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_quant_cpl_nt(const aacg_kparams P) { imdct_run_body<AACG_INPUT_QUANT_I16, AACG_OUTPUT_F32, false, false, true, false, true>(P); }
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_f32_cpl_nt(const aacg_kparams P) { imdct_run_body<AACG_INPUT_SPEC_F32, AACG_OUTPUT_F32, false, false, true, false, true>(P); }
-
-const aacg_run_kernel aacg_run_kernels_couple[] = {
-    {AACG_RK_CPL | AACG_RK_QUANT, "aacg_imdct_run_quant_cpl", (const void*)aacg_imdct_run_quant_cpl},
-    {AACG_RK_CPL, "aacg_imdct_run_f32_cpl", (const void*)aacg_imdct_run_f32_cpl},
-    {AACG_RK_CPL | AACG_RK_NT | AACG_RK_QUANT, "aacg_imdct_run_quant_cpl_nt", (const void*)aacg_imdct_run_quant_cpl_nt},
-    {AACG_RK_CPL | AACG_RK_NT, "aacg_imdct_run_f32_cpl_nt", (const void*)aacg_imdct_run_f32_cpl_nt}
-};
-const int aacg_run_kernels_couple_n = 4;
+ * wave of its own for the predecessor: no double duty); the _nt ones for batches of multichannel frames (where coupling
+ * lives): non-temporal loads of the spectra (aacg_engine_nt.hip says why) */
+AACG_RUN_KERNEL_UNIT(couple, AACG_RUN_KERNELS_COUPLE)
 
 void aacg_couple_launch(bool pcm, hipStream_t s, const aacg_couple_params& Q)
 {

@@ -13,14 +13,4 @@
 #include "aacg_kernels.h"
 #include "aacg_routes.h"
 
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_quant_nt(const aacg_kparams P) { imdct_run_body<AACG_INPUT_QUANT_I16, AACG_OUTPUT_F32, false, false, false, false, true>(P); }
-
-extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
-void aacg_imdct_run_f32_nt(const aacg_kparams P) { imdct_run_body<AACG_INPUT_SPEC_F32, AACG_OUTPUT_F32, false, false, false, false, true>(P); }
-
-const aacg_run_kernel aacg_run_kernels_nt[] = {
-    {AACG_RK_NT | AACG_RK_QUANT, "aacg_imdct_run_quant_nt", (const void*)aacg_imdct_run_quant_nt},
-    {AACG_RK_NT, "aacg_imdct_run_f32_nt", (const void*)aacg_imdct_run_f32_nt}
-};
-const int aacg_run_kernels_nt_n = 2;
+AACG_RUN_KERNEL_UNIT(nt, AACG_RUN_KERNELS_NT)

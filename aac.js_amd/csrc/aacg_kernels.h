@@ -33,6 +33,7 @@
 
 #include "devport.h"
 #include "aacg_device.h"
+#include "aacg_run_kernels.h"
 
 /* Work-skipping / tracing switches for tools/ (timeline, ablations).  They exist only in a build made with
  * -DAACG_PROFILE (`make profile` -> variants/profile.so): the library that ships has no such branches and ignores

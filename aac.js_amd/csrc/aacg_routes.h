@@ -1,8 +1,8 @@
 /*
- * aacg_routes.h — the run kernels as a registry, and the ONE decision which of them a plan takes.
+ * aacg_routes.h — the ONE decision which of the registered run kernels (aacg_run_kernels.h) a plan takes.
  *
- * imdct_run_body (aacg_kernels.h) is instantiated per variant in translation units of their own (each its own code object, so
- * that adding to one never moves another's code); every such unit exports a table of {switches, symbol, host stub}.  The
+ * imdct_run_body (aacg_kernels.h) is instantiated per row of aacg_run_kernels.h in translation units of their own (each its
+ * own code object, so that adding to one never moves another's code); every such unit exports a table of its kernels.  The
  * engine turns a plan into a route — the staging launches in front, the run kernel by its switches, the launches behind —
  * in one function (aacg_pick_route, aacg_engine.hip): launch_run executes that descriptor, aacg_plan_kernels prints it.
  * Reference for what every route computes: src/decoder.js:218-248 + src/filter_bank.js:88-204.
@@ -10,52 +10,7 @@
 #ifndef AACG_ROUTES_H
 #define AACG_ROUTES_H
 
-#include "aacg_device.h"
-
-/* template switches of imdct_run_body = key of a run kernel */
-enum {
-    AACG_RK_QUANT = 1,      /* KIND = AACG_INPUT_QUANT_I16 (else f32 spectra) */
-    AACG_RK_I16   = 2,      /* OUT = AACG_OUTPUT_I16 */
-    AACG_RK_DD    = 4,      /* double duty: the first wave of a full later run recomputes the frame before it */
-    AACG_RK_EX    = 8,      /* the optional stages (AACG_TNS_SPEC, AACG_PNS_SPEC) inside the run */
-    AACG_RK_CPL   = 16,     /* independent coupling applied where the target's PCM is formed */
-    AACG_RK_RV    = 32,     /* rendezvous cells between the runs of a chain (and, pipelined, between launches); takes aacg_rv_args */
-    AACG_RK_NT    = 64      /* non-temporal loads of the spectra: batches of multichannel frames */
-};
-
-struct aacg_run_kernel {
-    unsigned    key;        /* AACG_RK_* */
-    const char* name;       /* the symbol a rocprofv3 kernel trace shows */
-    const void* fn;         /* host stub, for hipLaunchKernel */
-    bool preloaded = false; /* AACG_RUN_KERNEL_PRE signature: six leading pointer arguments (run table, tables, links, units, spectra,
-                               band words) that arrive in SGPRs with the wave (-amdgpu-kernarg-preload-count), then the two
-                               argument records */
-    unsigned threads = AACG_WG_THREADS;   /* workgroup size it is launched with: 16 waves, or AACG_HALF_WAVES for the eight-wave body */
-};
-/* The signature of a run kernel whose early pointers are preloaded: by-value struct arguments are not preloaded, so the pointers
- * a wave needs for its first loads travel once more as leading scalar arguments — the table loads and the run record's batch go
- * out with the wave's first instructions, one dependent round trip earlier (0.2 us per launch on the headline route). */
-#define AACG_RUN_KERNEL_PRE(name, ...) \
-    extern "C" __global__ __launch_bounds__(AACG_WG_THREADS) \
-    void name(const aacg_run* runs, const aacg_tables* tab, const aacg_rv_link* links, const aacg_dev_unit* units, const void* coeffs, \
-              const aacg_band_meta* meta, const aacg_kparams P, const aacg_rv_args V) \
-    { imdct_run_body<__VA_ARGS__, true>(P, &V, runs, tab, links, units, coeffs, meta); }
-/* the same with the eight-wave run body (imdct_run_body<..., NW = AACG_HALF_WAVES>): launched with 512 threads, and bounded so that
- * it keeps to 128 VGPRs — four waves per SIMD, two workgroups per CU with its 80 KiB of LDS */
-#define AACG_RUN_KERNEL_PRE_HALF(name, ...) \
-    extern "C" __global__ __launch_bounds__(AACG_HALF_WAVES * 64, 4) \
-    void name(const aacg_run* runs, const aacg_tables* tab, const aacg_rv_link* links, const aacg_dev_unit* units, const void* coeffs, \
-              const aacg_band_meta* meta, const aacg_kparams P, const aacg_rv_args V) \
-    { imdct_run_body<__VA_ARGS__, true, AACG_HALF_WAVES>(P, &V, runs, tab, links, units, coeffs, meta); }
-
-/* one table per translation unit */
-extern const aacg_run_kernel aacg_run_kernels_plain[];  extern const int aacg_run_kernels_plain_n;    /* aacg_engine.hip */
-extern const aacg_run_kernel aacg_run_kernels_rv[];     extern const int aacg_run_kernels_rv_n;       /* aacg_engine_rv.hip */
-extern const aacg_run_kernel aacg_run_kernels_nt[];     extern const int aacg_run_kernels_nt_n;       /* aacg_engine_nt.hip */
-extern const aacg_run_kernel aacg_run_kernels_ext[];    extern const int aacg_run_kernels_ext_n;      /* aacg_engine_ext.hip */
-extern const aacg_run_kernel aacg_run_kernels_i16[];    extern const int aacg_run_kernels_i16_n;      /* aacg_engine_i16.hip */
-extern const aacg_run_kernel aacg_run_kernels_exrun[];  extern const int aacg_run_kernels_exrun_n;    /* aacg_engine_exrun.hip */
-extern const aacg_run_kernel aacg_run_kernels_couple[]; extern const int aacg_run_kernels_couple_n;   /* aacg_engine_couple.hip */
+#include "aacg_run_kernels.h"
 
 /* what launch_run does for a plan: the single statement of the route */
 enum { AACG_STAGE_NONE = 0, AACG_STAGE_SPECTRAL_EX = 1, AACG_STAGE_DEPENDENT_COUPLING = 2 };

@@ -43,7 +43,7 @@ WAIT_SPIN, WAIT_YIELD, WAIT_SLEEP, WAIT_BLOCK = 0, 1, 2, 3
 DEBUG_ROUTE_UNFUSED_COUPLING, DEBUG_ROUTE_RECOMPUTE = 1, 8
 ROUTE_PLAN_TNS, ROUTE_PLAN_PNS, ROUTE_PLAN_LONG_CHAINS, ROUTE_PLAN_FULL_LATER_RUNS = 1, 2, 4, 8
 ROUTE_PLAN_WIDE_FRAMES, ROUTE_PLAN_CCE_INDEPENDENT, ROUTE_PLAN_CCE_DEPENDENT, ROUTE_PLAN_NO_RUNS = 0x10, 0x20, 0x40, 0x80
-# switches of a run kernel (aacg_routes.h), as aacg_debug_run_kernel returns them
+# switches of a run kernel (aacg_run_kernels.h), as aacg_debug_run_kernel returns them
 RK_QUANT, RK_I16, RK_DD, RK_EX, RK_CPL, RK_RV, RK_NT = 1, 2, 4, 8, 16, 32, 64
 
 UNIT_DTYPE = np.dtype([

@@ -29,32 +29,18 @@ struct launch_arg {
     const aacg_rv_args* V;
 };
 
-/* the run kernel with these switches: the same instantiations the engine's translation units make (the non-temporal variants
- * load through the same emulated instruction, so AACG_RK_NT is dropped here) */
+/* the run kernel with these switches: one case per registered kernel (aacg_run_kernels.h).  The non-temporal variants load through
+ * the same emulated instruction, so AACG_RK_NT is dropped from the body's key; every kernel runs on the emulator's sixteen waves. */
 void run_kernel(unsigned key, const aacg_kparams& P, const aacg_rv_args* V)
 {
-    constexpr int Q = AACG_INPUT_QUANT_I16, F = AACG_INPUT_SPEC_F32, O16 = AACG_OUTPUT_I16, O32 = AACG_OUTPUT_F32;
-    switch (key & ~(unsigned)AACG_RK_NT) {
-    case 0:                                         imdct_run_body<F>(P); break;
-    case AACG_RK_QUANT:                             imdct_run_body<Q>(P); break;
-    case AACG_RK_DD:                                imdct_run_body<F, O32, true>(P); break;
-    case AACG_RK_DD | AACG_RK_QUANT:                imdct_run_body<Q, O32, true>(P); break;
-    case AACG_RK_I16:                               imdct_run_body<F, O16>(P); break;
-    case AACG_RK_I16 | AACG_RK_QUANT:               imdct_run_body<Q, O16>(P); break;
-    case AACG_RK_I16 | AACG_RK_DD:                  imdct_run_body<F, O16, true>(P); break;
-    case AACG_RK_I16 | AACG_RK_DD | AACG_RK_QUANT:  imdct_run_body<Q, O16, true>(P); break;
-    case AACG_RK_EX:                                imdct_run_body<F, O32, false, true>(P); break;
-    case AACG_RK_EX | AACG_RK_QUANT:                imdct_run_body<Q, O32, false, true>(P); break;
-    case AACG_RK_CPL:                               imdct_run_body<F, O32, false, false, true>(P); break;
-    case AACG_RK_CPL | AACG_RK_QUANT:               imdct_run_body<Q, O32, false, false, true>(P); break;
-    case AACG_RK_RV:                                imdct_run_body<F, O32, false, false, false, true>(P, V); break;
-    case AACG_RK_RV | AACG_RK_QUANT:                imdct_run_body<Q, O32, false, false, false, true>(P, V); break;
-    case AACG_RK_RV | AACG_RK_EX:                   imdct_run_body<F, O32, false, true, false, true>(P, V); break;
-    case AACG_RK_RV | AACG_RK_EX | AACG_RK_QUANT:   imdct_run_body<Q, O32, false, true, false, true>(P, V); break;
-    case AACG_RK_RV | AACG_RK_I16:                  imdct_run_body<F, O16, false, false, false, true>(P, V); break;
-    case AACG_RK_RV | AACG_RK_I16 | AACG_RK_QUANT:  imdct_run_body<Q, O16, false, false, false, true>(P, V); break;
+#define EMU_RUN_KERNEL(suffix, k, waves, args) case k: imdct_run_body<AACG_RUN_BODY_ARGS((k) & ~AACG_RK_NT)>(P, V); break;
+#define EMU_RUN_KERNEL_SET(set, ROWS) ROWS(EMU_RUN_KERNEL)
+    switch (key) {
+    AACG_RUN_KERNEL_SETS(EMU_RUN_KERNEL_SET)
     default: std::abort();                          /* a route without a kernel */
     }
+#undef EMU_RUN_KERNEL_SET
+#undef EMU_RUN_KERNEL
 }
 
 void* lane_main(void* p)

@@ -15,16 +15,16 @@ namespace half_emu {
 
 int g_ablate = 0;
 
-template <int KIND, int OUT = AACG_OUTPUT_F32, bool DD = false, bool EX = false, bool CPL = false, bool RV = false>
+template <int KIND, int OUT = AACG_OUTPUT_F32, bool DD = false, bool EX = false, bool CPL = false, bool RV = false, bool NTL = false>
 void run_body(const aacg_kparams& P, const aacg_rv_args* V = nullptr)
 {
     if constexpr (RV && !DD && !EX && !CPL && OUT == AACG_OUTPUT_F32) {
         if (dp_wave() >= AACG_HALF_WAVES) { dp_block_sync_lds(); return; }
         aacg_kparams Q = P;
         Q.ablate = g_ablate;
-        imdct_run_body<KIND, OUT, false, false, false, true, false, false, AACG_HALF_WAVES>(Q, V);
+        imdct_run_body<KIND, OUT, false, false, false, true, NTL, false, AACG_HALF_WAVES>(Q, V);
     } else {
-        imdct_run_body<KIND, OUT, DD, EX, CPL, RV>(P, V);
+        imdct_run_body<KIND, OUT, DD, EX, CPL, RV, NTL>(P, V);
     }
 }
 

@@ -3,10 +3,16 @@ in the build container: a toolchain change (or an edit) that spills, drops occup
 to tests/test_disasm_guard.py, instead of showing up as a slower or failing launch on the GPU box.
 
 The budgets are what the design rests on: the 16-wave run kernels hold one workgroup per CU — 4 waves per SIMD,
-so at most 128 VGPRs, no scratch (a scratch reload waits for the PCM stores in flight), at most 160 KiB of LDS."""
+so at most 128 VGPRs, no scratch (a scratch reload waits for the PCM stores in flight), at most 160 KiB of LDS; the eight-wave
+ones hold two workgroups per CU, so the same registers and at most 80 KiB of LDS each.
+
+Every registered run kernel is checked: the rows of aac.js_amd/csrc/aacg_run_kernels.h, in the translation unit that expands
+their list (AACG_RUN_KERNEL_UNIT), built with the flags the Makefile builds that unit with."""
 import concurrent.futures
+import glob
 import os
 import re
+import shlex
 import subprocess
 
 import pytest
@@ -14,23 +20,43 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "aac.js_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
-SCHED = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-# translation unit -> (extra flags as the Makefile builds it, {kernel: (max VGPRs, min waves/SIMD, max LDS bytes)})
-WIDE = (128, 4, 160 * 1024)
-TUS = {
-    "aacg_engine_rv.hip": (SCHED, {"aacg_imdct_run_quant_rv": WIDE, "aacg_imdct_run_f32_rv": WIDE, "aacg_imdct_run_quant_rv_nt": WIDE, "aacg_imdct_run_f32_rv_nt": WIDE}),
-    "aacg_engine_nt.hip": (SCHED, {"aacg_imdct_run_quant_nt": WIDE, "aacg_imdct_run_f32_nt": WIDE}),
-    "aacg_engine.hip": (SCHED, {"aacg_imdct_run_quant": WIDE, "aacg_imdct_run_f32": WIDE}),
-    "aacg_engine_ext.hip": (SCHED, {"aacg_imdct_run_quant_dd": WIDE, "aacg_imdct_run_f32_dd": WIDE}),
-    "aacg_engine_i16.hip": (SCHED, {"aacg_imdct_run_quant_i16": WIDE, "aacg_imdct_run_f32_i16": WIDE, "aacg_imdct_run_quant_i16_nt": WIDE, "aacg_imdct_run_f32_i16_nt": WIDE}),
-    "aacg_engine_exrun.hip": (SCHED, {"aacg_imdct_run_quant_ex": WIDE, "aacg_imdct_run_f32_ex": WIDE}),
-    "aacg_engine_couple.hip": ([], {"aacg_imdct_run_quant_cpl": WIDE, "aacg_imdct_run_f32_cpl": WIDE, "aacg_imdct_run_quant_cpl_nt": WIDE, "aacg_imdct_run_f32_cpl_nt": WIDE}),
-}
+BUDGET = {"AACG_WG_WAVES": (128, 4, 160 * 1024), "AACG_HALF_WAVES": (128, 4, 80 * 1024)}   # (max VGPRs, min waves/SIMD, max LDS bytes)
 
 
-def resource_report(tu, flags):
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function"] + flags +
-                       ["-Rpass-analysis=kernel-resource-usage", "-c", tu, "-o", "/dev/null"], cwd=CSRC, capture_output=True, text=True, timeout=900)
+def registry():
+    """{list macro: [(kernel, wave count macro)]} from the rows of aacg_run_kernels.h"""
+    with open(os.path.join(CSRC, "aacg_run_kernels.h")) as f:
+        text = f.read().replace("\\\n", " ")
+    lists = {}
+    for m in re.finditer(r"^#define (AACG_RUN_KERNELS_\w+)\(X\)(.*)$", text, re.M):
+        rows = re.findall(r"X\(\s*(\w+)\s*,[^,()]*,\s*(\w+)\s*,\s*\w+\s*\)", m.group(2))
+        lists[m.group(1)] = [("aacg_imdct_run_" + suffix, waves) for suffix, waves in rows]
+    return lists
+
+
+def units():
+    """{translation unit: [(kernel, wave count macro)]}: the file that expands each list"""
+    lists, out = registry(), {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        with open(path) as f:
+            for name in re.findall(r"^AACG_RUN_KERNEL_UNIT\(\w+, (AACG_RUN_KERNELS_\w+)\)", f.read(), re.M):
+                out.setdefault(os.path.basename(path), []).extend(lists.pop(name))
+    assert not lists, "registered but expanded nowhere: %s" % sorted(lists)
+    return out
+
+
+TUS = units()
+
+
+def make_var(name):
+    r = subprocess.run(["make", "-s", "-C", CSRC, "print-" + name], capture_output=True, text=True, timeout=60, check=True)
+    return shlex.split(r.stdout)
+
+
+def resource_report(tu):
+    flags = make_var("CXXFLAGS") + make_var("FLAGS_" + tu[:-len(".hip")])
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950"] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", tu, "-o", "/dev/null"],
+                       cwd=CSRC, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out, name = {}, None
     for line in r.stderr.splitlines():
@@ -50,19 +76,31 @@ def reports():
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
     with concurrent.futures.ThreadPoolExecutor(max_workers=4) as ex:
-        futs = {tu: ex.submit(resource_report, tu, flags) for tu, (flags, _) in TUS.items()}
+        futs = {tu: ex.submit(resource_report, tu) for tu in TUS}
         return {tu: f.result() for tu, f in futs.items()}
+
+
+def test_rows_read_here_are_the_registered_kernels(engine_lib):
+    import aacgpu
+    kernels = [k for rows in TUS.values() for k, _ in rows]
+    assert sorted(kernels) == sorted(aacgpu.run_kernels()), kernels
+    assert all(w in BUDGET for rows in TUS.values() for _, w in rows), TUS
+
+
+def sgpr_spill_allowance(kernel):
+    # scalar spills go to VGPR lanes (no memory traffic); the plain kernels have none, the optional-stage builds a handful
+    return 48 if kernel.endswith("_ex_rv") else 32 if kernel.endswith("_ex") else 0
 
 
 @pytest.mark.parametrize("tu", sorted(TUS))
 def test_hot_kernels_keep_their_register_and_lds_budget(reports, tu):
-    for kernel, (max_vgpr, min_occ, max_lds) in TUS[tu][1].items():
+    for kernel, waves in TUS[tu]:
+        max_vgpr, min_occ, max_lds = BUDGET[waves]
         rep = reports[tu].get(kernel)
         assert rep, "%s: kernel %s not in the resource report (%s)" % (tu, kernel, sorted(reports[tu]))
         assert int(rep["VGPRs"]) + int(rep["AGPRs"]) <= max_vgpr, (kernel, rep)
         assert int(rep["ScratchSize [bytes/lane]"]) == 0 and int(rep["VGPRs Spill"]) == 0, (kernel, rep)
-        # scalar spills go to VGPR lanes (no memory traffic); the plain kernels have none, the optional-stage builds a handful
-        assert int(rep["SGPRs Spill"]) <= (32 if kernel.endswith("_ex") else 0), (kernel, rep)
+        assert int(rep["SGPRs Spill"]) <= sgpr_spill_allowance(kernel), (kernel, rep)
         assert int(rep["Occupancy [waves/SIMD]"]) >= min_occ, (kernel, rep)
         assert int(rep["LDS Size [bytes/block]"]) <= max_lds, (kernel, rep)
         assert rep["Dynamic Stack"] == "False", (kernel, rep)
