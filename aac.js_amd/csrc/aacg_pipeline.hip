@@ -23,7 +23,11 @@
  *     first frame (one small synchronous parse when a stream is new), the kept plan lists exactly those elements, and a
  *     later frame with other elements is refused as a whole (AACG_PARSE_LAYOUT).
  *
- * Host code only (the kernels are the parser's and the engine's); it uses nothing but the public ABI of those two.
+ * Ragged batches (aacg_pipeline_submit_ragged): each stream brings its own frame count, packed stream after stream; the
+ * rectangular call is the case of equal counts.  A batch's refresh map is expanded on the lane's stream (aacg_pipe_map) from a
+ * per-stream table staged with the bytes, so a new shape costs the submit path no allocation and no synchronous copy.
+ *
+ * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine.
  */
 #include <hip/hip_runtime.h>
 
@@ -35,6 +39,7 @@
 
 #include "../../include/aacgpu.h"
 #include "../../include/aacgpu_tools.h"
+#include "aacg_pipe_map.h"
 #include "aacg_wait.h"
 
 #define AACG_PIPELINE_MAX_LANES 8
@@ -62,6 +67,14 @@ void aacg_pipe_copy(const uint4* src, uint4* dst, size_t n16, int clear_last)
     }
 }
 
+/* A batch's refresh map from its per-stream table (aacg_pipe_map.h), on the lane's stream in front of the refresh that reads it:
+ * a new batch shape costs the lane no device allocation and no synchronous copy. */
+extern "C" __global__ __launch_bounds__(AACG_PIPE_MAP_THREADS)
+void aacg_pipe_map(const aacg_pipe_stream* tab, uint32_t n_streams, uint32_t U, aacg_refresh_map* map)
+{
+    aacg_pipe::map_body(tab, n_streams, U, map, gridDim.x);
+}
+
 struct aacg_pipeline {
     aacg_pipeline_config cfg;
     aacg_engine* engine = nullptr;
@@ -70,13 +83,15 @@ struct aacg_pipeline {
     uint32_t C = 2;                     /* channels of a frame's PCM (chanConfig) */
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
-    /* a stream's element layout: channels of every SCE / LFE / CPE of a frame in order; kept = how many of them fit into C channels */
-    struct layout_t { uint8_t n = 0, kept = 0; uint8_t nch[8] = {}; };
+    /* a stream's element layout (aacg_pipe_map.h): channels of every SCE / LFE / CPE of a frame in order; kept = how many of them fit into C channels */
+    typedef aacg_pipe_layout layout_t;
     std::vector<layout_t> layout;       /* per slot; n = 0: not learnt yet */
-    /* kept plans, by batch shape: (frames per stream, the stream slots in order); the layouts are the slots' */
-    struct kept { uint32_t frames; std::vector<uint32_t> slots; aacg_plan* plan; void* d_map; uint32_t n_units; uint64_t used; };
+    /* kept plans, by batch shape: (the stream slots in order, each one's frame count); the layouts are the slots' */
+    struct kept { std::vector<uint32_t> frames; std::vector<uint32_t> slots; aacg_plan* plan; uint32_t n_units; uint64_t used; };
     std::vector<kept> plans;
-    uint64_t tick = 0;
+    uint64_t tick = 0, plan_builds = 0;
+    std::vector<layout_t> batch_layout; /* the submitting batch's streams' layouts, as its plan lists them */
+    std::vector<uint32_t> rect_counts;  /* aacg_pipeline_submit's counts: every stream frames_per_stream */
     struct lane_t {
         /* A parser of its own per lane: a parser's launches are ordered one behind the other (they share its lane-order scratch),
          * and a batch's parse is the longest single step of the route — one GPU lane walks one frame's bits, so 4096 frames keep a
@@ -86,13 +101,15 @@ struct aacg_pipeline {
         hipStream_t st = nullptr;
         hipEvent_t done = nullptr;
         void *d_bytes = nullptr, *d_frames = nullptr, *d_units = nullptr, *d_q = nullptr, *d_meta = nullptr, *d_res = nullptr, *d_pcm = nullptr, *d_refused = nullptr;
+        void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         void *h_in = nullptr, *h_pcm = nullptr, *h_res = nullptr;
         size_t bytes_cap = 0, h_in_cap = 0;
         /* the batch in flight */
         bool busy = false, count_stale = false;
         uint64_t ticket = 0;
         void* user_pcm = nullptr; bool direct = false; size_t pcm_bytes = 0;
-        aacg_parse_result* user_results = nullptr; uint32_t* user_refused = nullptr; uint32_t n = 0, F = 0;
+        aacg_parse_result* user_results = nullptr; uint32_t* user_refused = nullptr; uint32_t n = 0;
+        std::vector<uint32_t> first, frames_of;   /* the batch's streams: first packed frame, frame count */
         std::vector<uint32_t> unlearnt;   /* streams of the batch (by position) whose layout was not known: nothing of them was decoded */
     } lane[AACG_PIPELINE_MAX_LANES];
     uint64_t submitted = 0;
@@ -149,60 +166,35 @@ void pipe_copy(const void* src, void* dst, size_t bytes, hipStream_t s, bool cle
 void drop_plan(aacg_pipeline* p, size_t i)
 {
     aacg_plan_destroy(p->plans[i].plan);                 /* waits (bounded) for the launches that read it */
-    if (p->plans[i].d_map) (void)hipFree(p->plans[i].d_map);
     p->plans.erase(p->plans.begin() + (long)i);
 }
 void drop_plans(aacg_pipeline* p) { while (!p->plans.empty()) drop_plan(p, p->plans.size() - 1); }
 
-/* The plan for a batch of this shape.  Frame f of stream s is parsed frame i = s * F + f; the parser (max_units U, max_channels
- * Cp) puts its element e at record i * U + e and its running channel c at block i * Cp + c.  The plan lists, frame by frame,
- * the elements of the stream's layout that fit into the C output channels. */
-int plan_for(aacg_pipeline* p, const uint32_t* slots, uint32_t S, uint32_t F, aacg_pipeline::kept** out)
+/* The plan for a batch of this shape: stream s brings frames_of[s] frames, parsed frames first_s .. first_s + frames_of[s] - 1
+ * (aacg_pipe::plan_list: the units the plan lists; the map they are refreshed through is the lane's, aacg_pipe_map).  The
+ * batch's layouts are in p->batch_layout. */
+int plan_for(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t S, aacg_pipeline::kept** out)
 {
     for (auto& k : p->plans)
-        if (k.frames == F && k.slots.size() == S && std::memcmp(k.slots.data(), slots, S * sizeof(uint32_t)) == 0) { k.used = ++p->tick; *out = &k; return AACG_OK; }
-    const uint32_t C = p->C, Cp = p->Cp, U = p->U;
+        if (k.slots.size() == S && std::memcmp(k.slots.data(), slots, S * sizeof(uint32_t)) == 0 &&
+            std::memcmp(k.frames.data(), frames_of, S * sizeof(uint32_t)) == 0) { k.used = ++p->tick; *out = &k; return AACG_OK; }
     std::vector<aacg_unit_desc> u;
-    std::vector<aacg_refresh_map> map;
-    u.reserve((size_t)S * F * (p->learn ? 4 : 1));
-    for (uint32_t s = 0; s < S; s++) {
-        aacg_pipeline::layout_t lay = p->layout[slots[s]];
-        if (!p->learn) { lay.n = lay.kept = 1; lay.nch[0] = (uint8_t)C; }
-        for (uint32_t f = 0; f < F; f++) {
-            const uint32_t i = s * F + f;
-            uint32_t chan = 0;
-            for (uint32_t e = 0; e < lay.kept; e++) {
-                aacg_unit_desc d;
-                std::memset(&d, 0, sizeof d);
-                d.stream = slots[s]; d.pcm_offset = i * 1024u * C; d.channel = (uint16_t)chan; d.n_out_ch = (uint16_t)C; d.n_ch = lay.nch[e];
-                d.coef_offset = d.meta_offset = i * Cp + chan;
-                for (uint32_t c = 0; c < d.n_ch; c++) { d.ch[c].group_count = 1; d.ch[c].group_len[0] = 1; }
-                u.push_back(d);
-                map.push_back({i * U + e, (uint32_t)lay.n | ((uint32_t)lay.kept << 8)});
-                chan += lay.nch[e];
-            }
-        }
-    }
+    uint32_t total = 0;
+    for (uint32_t s = 0; s < S; s++) total += frames_of[s];
+    u.reserve((size_t)total * (p->learn ? 4 : 1));
+    aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, S, p->C, p->Cp, p->U, &u, nullptr, nullptr);
     if (u.empty()) { *out = nullptr; return AACG_OK; }     /* no stream of the batch has a layout yet: nothing to transform, every frame is refused */
     aacg_plan* plan = nullptr;
     int rc = aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
     if (rc == AACG_OK && (rc = aacg_plan_set_unit_sets(p->engine, plan, (uint32_t)p->n_lanes))) { aacg_plan_destroy(plan); plan = nullptr; }
     if (rc) { p->err = std::string("aacg_plan_create: ") + aacg_last_error(p->engine); return rc; }
-    void* d_map = nullptr;
-    if (hipMalloc(&d_map, map.size() * sizeof(aacg_refresh_map)) != hipSuccess ||
-        hipMemcpy(d_map, map.data(), map.size() * sizeof(aacg_refresh_map), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_map) (void)hipFree(d_map);
-        aacg_plan_destroy(plan);
-        p->err = "hipMalloc (plan map)";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
+    p->plan_builds++;
     if (p->plans.size() >= 8) {                          /* the least recently used shape makes room */
         size_t lru = 0;
         for (size_t i = 1; i < p->plans.size(); i++) if (p->plans[i].used < p->plans[lru].used) lru = i;
         drop_plan(p, lru);
     }
-    p->plans.push_back({F, std::vector<uint32_t>(slots, slots + S), plan, d_map, (uint32_t)u.size(), ++p->tick});
+    p->plans.push_back({std::vector<uint32_t>(frames_of, frames_of + S), std::vector<uint32_t>(slots, slots + S), plan, (uint32_t)u.size(), ++p->tick});
     *out = &p->plans.back();
     return AACG_OK;
 }
@@ -243,7 +235,7 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
     aacg_parse_result* res = (aacg_parse_result*)L.h_res;
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
     for (uint32_t s : L.unlearnt)
-        for (uint32_t f = 0; f < L.F; f++) { aacg_parse_result& r = res[(size_t)s * L.F + f]; if (r.status == AACG_PARSE_OK) r.status = AACG_PARSE_LAYOUT; (*refused)++; }
+        for (uint32_t f = 0; f < L.frames_of[s]; f++) { aacg_parse_result& r = res[(size_t)L.first[s] + f]; if (r.status == AACG_PARSE_OK) r.status = AACG_PARSE_LAYOUT; (*refused)++; }
     if (L.user_results) std::memcpy(L.user_results, res, (size_t)L.n * sizeof(aacg_parse_result));
     if (L.user_refused) std::memcpy(L.user_refused, refused, 4);
     L.busy = false;
@@ -251,16 +243,16 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
 }
 
 /* the element layouts of streams that are new: their first frames through one small synchronous parse (host pointers) */
-int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames, const uint32_t* slots, uint32_t S, uint32_t F)
+int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames, const uint32_t* slots, uint32_t S, const uint32_t* frames_of)
 {
-    std::vector<uint32_t> who;
-    for (uint32_t s = 0; s < S; s++) if (!p->layout[slots[s]].n) who.push_back(s);
+    std::vector<uint32_t> who, first;
+    for (uint32_t s = 0, i = 0; s < S; i += frames_of[s], s++) if (!p->layout[slots[s]].n) { who.push_back(s); first.push_back(i); }
     if (who.empty()) return AACG_OK;
     /* gather those frames' bytes (they lie anywhere in the caller's buffer) */
     std::vector<aacg_parse_frame> fr(who.size());
     std::vector<uint8_t> buf;
     for (size_t k = 0; k < who.size(); k++) {
-        const aacg_parse_frame& f = frames[(size_t)who[k] * F];
+        const aacg_parse_frame& f = frames[first[k]];
         fr[k].byte_offset = (uint32_t)buf.size(); fr[k].byte_length = f.byte_length;
         buf.insert(buf.end(), bytes + f.byte_offset, bytes + f.byte_offset + f.byte_length);
         buf.resize((buf.size() + 15) & ~(size_t)15);
@@ -323,7 +315,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (W.st) (void)hipStreamDestroy(W.st);
     }
     for (auto& L : p->lane) {
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_map}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
         for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.parser) aacg_parser_destroy(L.parser);
@@ -383,6 +375,7 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
         good = ok(p, hipStreamCreateWithPriority(&L.st, hipStreamNonBlocking, prio), "hipStreamCreate") &&
                ok(p, hipEventCreateWithFlags(&L.done, hipEventDisableTiming), "hipEventCreate") &&
                ok(p, hipMalloc(&L.d_units, n * U * sizeof(aacg_unit_desc)), "hipMalloc") &&
+               ok(p, hipMalloc(&L.d_map, n * U * sizeof(aacg_refresh_map)), "hipMalloc") &&
                ok(p, hipMalloc(&L.d_q, n * Cp * 2048), "hipMalloc") && ok(p, hipMemsetAsync(L.d_q, 0, n * Cp * 2048, L.st), "hipMemset") &&
                ok(p, hipMalloc(&L.d_meta, n * Cp * sizeof(aacg_band_meta)), "hipMalloc") &&
                ok(p, hipMalloc(&L.d_res, p->res_cap16 + 16), "hipMalloc") &&      /* the refusal count lies behind the results: one copy brings both down */
@@ -427,13 +420,20 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     return AACG_OK;
 }
 
-int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
-                         const uint32_t* slots, uint32_t n_streams, uint32_t frames_per_stream,
-                         void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
+int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
 {
-    if (!p || !bytes || !frames || !slots || !pcm_out || !n_streams || !frames_per_stream || !ticket) return AACG_ERR_INVALID_ARG;
-    if ((int)n_streams > p->cfg.max_streams || (int)frames_per_stream > p->cfg.max_frames) { p->err = "batch larger than the pipeline was created for"; return AACG_ERR_CAPACITY; }
-    const uint32_t n = n_streams * frames_per_stream, C = p->C, Cp = p->Cp, U = p->U;
+    if (!p || !bytes || !frames || !slots || !frames_of || !pcm_out || !n_streams || !ticket) return AACG_ERR_INVALID_ARG;
+    if ((int)n_streams > p->cfg.max_streams) { p->err = "batch larger than the pipeline was created for"; return AACG_ERR_CAPACITY; }
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        if (!frames_of[s]) { p->err = "a stream of the batch brings no frame (frames_of[s] == 0)"; return AACG_ERR_INVALID_ARG; }
+        if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "a stream brings more frames than max_frames"; return AACG_ERR_CAPACITY; }
+        total += frames_of[s];
+    }
+    if (total > (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames) { p->err = "the batch's frames exceed max_streams x max_frames"; return AACG_ERR_CAPACITY; }
+    const uint32_t n = (uint32_t)total, C = p->C, Cp = p->Cp, U = p->U;
     for (uint32_t s = 0; s < n_streams; s++) if ((int)slots[s] >= p->cfg.max_streams) { p->err = "stream slot out of range"; return AACG_ERR_CAPACITY; }
     {   /* a slot is one stream's overlap state: a batch brings each at most once (its frames are consecutive ones of that stream) */
         std::vector<bool> seen((size_t)p->cfg.max_streams, false);
@@ -446,9 +446,18 @@ int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
     const uint32_t set = (uint32_t)(p->submitted % (uint64_t)p->n_lanes);
     int rc = finish_lane(p, L);                          /* the batch `lanes` submissions ago, if nobody has collected it */
     if (rc) return rc;
-    if (p->learn && (rc = learn_layouts(p, bytes, n_bytes, frames, slots, n_streams, frames_per_stream))) return rc;
-    /* staging: the bytes (16-byte aligned, AACG_PARSE_PAD readable bytes behind them) and the frame table in one page-locked block */
-    const size_t padded = ((n_bytes + 15) & ~(size_t)15) + 64, table = (size_t)n * sizeof(aacg_parse_frame), up = padded + ((table + 15) & ~(size_t)15);
+    if (p->learn && (rc = learn_layouts(p, bytes, n_bytes, frames, slots, n_streams, frames_of))) return rc;
+    /* the batch's layouts as its plan lists them (a stream without one has no unit in the plan) */
+    p->batch_layout.resize(n_streams);
+    for (uint32_t s = 0; s < n_streams; s++) {
+        aacg_pipeline::layout_t lay = p->layout[slots[s]];
+        if (!p->learn) { lay.n = lay.kept = 1; lay.nch[0] = (uint8_t)C; }
+        p->batch_layout[s] = lay;
+    }
+    /* staging: the bytes (16-byte aligned, AACG_PARSE_PAD readable bytes behind them), the frame table and the per-stream table
+     * that aacg_pipe_map expands into the refresh map, in one page-locked block */
+    const size_t padded = ((n_bytes + 15) & ~(size_t)15) + 64, table = (size_t)n * sizeof(aacg_parse_frame), table16 = (table + 15) & ~(size_t)15;
+    const size_t up = padded + table16 + (size_t)n_streams * sizeof(aacg_pipe_stream);
     if (up > L.h_in_cap) {
         if (L.h_in) (void)hipHostFree(L.h_in);
         L.h_in = nullptr; L.h_in_cap = 0;
@@ -467,8 +476,9 @@ int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
     std::memcpy(L.h_in, bytes, n_bytes);
     std::memset((char*)L.h_in + n_bytes, 0, padded - n_bytes);
     std::memcpy((char*)L.h_in + padded, frames, table);
+    aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, n_streams, C, Cp, U, nullptr, nullptr, (aacg_pipe_stream*)((char*)L.h_in + padded + table16));
     aacg_pipeline::kept* kp = nullptr;
-    if ((rc = plan_for(p, slots, n_streams, frames_per_stream, &kp))) return rc;
+    if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
     const size_t pcm_bytes = (size_t)n * C * 1024u * pcm_elem(p);
     /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
      * lane's own page-locked staging and one host copy at collect */
@@ -478,6 +488,9 @@ int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
     hipStream_t st = L.st;
     L.unlearnt.clear();
     if (p->learn) for (uint32_t s = 0; s < n_streams; s++) if (!p->layout[slots[s]].kept) L.unlearnt.push_back(s);
+    L.frames_of.assign(frames_of, frames_of + n_streams);
+    L.first.resize(n_streams);
+    for (uint32_t s = 0, i = 0; s < n_streams; i += frames_of[s], s++) L.first[s] = i;
     if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(L.d_pcm, 0, pcm_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
     pipe_copy(L.h_in, L.d_bytes, up, st);                 /* aacg_pipe_copy: not the SDMA engines, where it would queue behind other lanes' PCM */
     if (L.count_stale) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* a submission that failed half-way left its count behind */
@@ -487,12 +500,17 @@ int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
     rc = aacg_parse_device(L.parser, L.d_bytes, (const aacg_parse_frame*)L.d_frames, n, U, Cp, (uint32_t)p->cfg.parse_options | AACG_PARSE_SKIP_ZERO_FILL,
                            (aacg_unit_desc*)L.d_units, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, nullptr, (aacg_parse_result*)L.d_res, st);
     if (rc) { p->err = std::string("aacg_parse_device: ") + aacg_parser_last_error(L.parser); return rc; }
+    if (kp) {                                            /* the map the refresh reads: behind the staging's copy, on the lane's stream */
+        const uint32_t blocks = n_streams < 256 ? n_streams : 256;
+        hipLaunchKernelGGL(aacg_pipe_map, dim3(blocks), dim3(AACG_PIPE_MAP_THREADS), 0, st, (const aacg_pipe_stream*)((char*)L.d_bytes + padded + table16),
+                           n_streams, U, (aacg_refresh_map*)L.d_map);
+    }
     for (int attempt = 0; kp; attempt++) {
         /* this lane's set of the plan's unit records: the launch that read it last was this lane's previous batch, whose PCM has
          * come down on this stream since */
         if (attempt) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* the stale plan's refresh has counted this batch's refusals already */
         rc = aacg_plan_refresh_from_parse_ex(p->engine, kp->plan, (const aacg_unit_desc*)L.d_units, (aacg_parse_result*)L.d_res, U,
-                                             (const aacg_refresh_map*)kp->d_map, set, (uint32_t*)L.d_refused, st);
+                                             (const aacg_refresh_map*)L.d_map, set, (uint32_t*)L.d_refused, st);
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
         if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, st);
@@ -500,7 +518,7 @@ int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
         if (rc != AACG_ERR_STALE_PLAN || attempt) break;
         /* another shape's plan has advanced these streams since this one was used: plans are made from the engine's current state */
         drop_plans(p);
-        if ((rc = plan_for(p, slots, n_streams, frames_per_stream, &kp))) return rc;
+        if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
     }
     if (rc == AACG_OK && kp) rc = aacg_pipeline_join(p->engine, st);
     if (rc) { p->err = std::string("transform: ") + aacg_last_error(p->engine); return rc; }
@@ -515,9 +533,19 @@ int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
     P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
     P_TRY(p, hipEventRecord(L.done, st), AACG_ERR_NO_DEVICE);
     L.busy = true; L.ticket = ++p->submitted; L.user_pcm = pcm_out; L.direct = direct; L.pcm_bytes = pcm_bytes;
-    L.user_results = results; L.user_refused = n_refused; L.n = n; L.F = frames_per_stream;
+    L.user_results = results; L.user_refused = n_refused; L.n = n;
     *ticket = L.ticket;
     return AACG_OK;
+}
+
+int aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                         const uint32_t* slots, uint32_t n_streams, uint32_t frames_per_stream,
+                         void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
+{
+    if (!p || !bytes || !frames || !slots || !pcm_out || !n_streams || !frames_per_stream || !ticket) return AACG_ERR_INVALID_ARG;
+    if ((int)n_streams > p->cfg.max_streams || (int)frames_per_stream > p->cfg.max_frames) { p->err = "batch larger than the pipeline was created for"; return AACG_ERR_CAPACITY; }
+    p->rect_counts.assign(n_streams, frames_per_stream);      /* the rectangle: every stream the same count */
+    return aacg_pipeline_submit_ragged(p, bytes, n_bytes, frames, slots, n_streams, p->rect_counts.data(), pcm_out, results, n_refused, ticket);
 }
 
 int aacg_pipeline_collect(aacg_pipeline* p, uint64_t ticket)
@@ -619,6 +647,18 @@ int aacg_pipeline_decode(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
     if (rc) return rc;
     return aacg_pipeline_collect(p, t);
 }
+
+int aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                void* pcm_out, aacg_parse_result* results, uint32_t* n_refused)
+{
+    uint64_t t = 0;
+    int rc = aacg_pipeline_submit_ragged(p, bytes, n_bytes, frames, slots, n_streams, frames_of, pcm_out, results, n_refused, &t);
+    if (rc) return rc;
+    return aacg_pipeline_collect(p, t);
+}
+
+uint64_t aacg_pipeline_plan_builds(const aacg_pipeline* p) { return p ? p->plan_builds : 0; }
 
 int aacg_pipeline_stream_layout(aacg_pipeline* p, uint32_t slot, uint8_t element_channels[8], uint32_t* kept)
 {

@@ -28,6 +28,9 @@
  * { residentPackets: true }: then an 'mp4a' decoder takes the resident route too.  A single-sample packet is a frame; the blocks
  * of a multi-sample packet are found on the device (aacg_pipeline_walk_submit: one GPU lane walks one packet), a flush ahead of
  * the flush that decodes them, and then travel like ADTS frames.
+ * { resident: true, ragged: true } — a flush takes from each stream what it has buffered, up to lookahead frames, instead of
+ * cutting every stream to the count of the one with the fewest (aacg_pipeline_submit_ragged: per-stream frame counts, frames and
+ * PCM packed stream after stream); one stream with a single frame buffered no longer makes the whole flush a one-frame batch.
  * Replaces, per batch, what src/decoder.js:125-216 does per frame.
  */
 'use strict';
@@ -42,6 +45,7 @@ function SharedEngine(opts) {
     this.resident = !!opts.resident;                      // bytes -> PCM in one native call per flush (aacg_pipeline_*)
     this.residentPackets = !!opts.residentPackets;        // resident: 'mp4a' decoders too (their blocks found by a walk on the device)
     this.lookahead = opts.lookahead || 16;                // resident: frames per stream and flush
+    this.ragged = !!opts.ragged;                          // resident: each stream's own frame count per flush (at most lookahead)
     /* resident: where a flush's PCM lives.  0 (default): memory of its own, the caller's for as long as it keeps any frame of the
      * flush (what the reference's readChunk() promises: a fresh array per frame) — a page-locked allocation per flush.  K > 0: K
      * page-locked buffers made once and used in turn: a frame is valid until its SharedEngine has flushed K more times, i.e. for
@@ -53,7 +57,7 @@ function SharedEngine(opts) {
      * (lookahead frames) further ahead than they are consumed, and with pcmRing a frame is valid for one flush less.  On by
      * default since round 6 ({ overlap: false } for a flush that decodes what it returns). */
     this.overlap = opts.overlap === undefined ? this.resident : !!opts.overlap;
-    this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0 };
+    this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0, flushNs: 0n };   // flushNs: resident flushes, host side and native calls
 }
 
 /* error codes the engine raises before it has launched anything (include/aacgpu.h): a batch refused with one of these has
@@ -101,7 +105,7 @@ SharedEngine.prototype.attachResident = function (dec) {
     const cfg = dec.config, key = 'r' + cfg.sampleIndex + '/' + cfg.chanConfig;
     let g = this.groups.get(key);
     if (!g) {
-        const addon = host.loadAddon(), rec = require('./codebooks.js').load(this.opts).toEntryRecords();
+        const addon = this.opts.addon || host.loadAddon(), rec = require('./codebooks.js').load(this.opts).toEntryRecords();
         const outI16 = (this.opts.outputKind | 0) === host.OUTPUT_I16;
         const pipeline = addon.pipelineCreate({ deviceOrdinal: this.opts.deviceOrdinal | 0, sampleIndex: cfg.sampleIndex, maxStreams: this.maxStreams,
                                                 channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
@@ -228,8 +232,8 @@ function scanFrames(b, at, max, lens) {
 
 /* resident flush: the next frames of every stream that has run dry or has room, ONE native call, views of its PCM handed out */
 SharedEngine.prototype.prepareResident = function (g, room) {
-    const L = this.lookahead;
-    const part = [];
+    const L = this.lookahead, ragged = this.ragged;
+    const part = [], own = [];                             // own[s]: what participant s has buffered (at most L frames)
     let F = L;
     for (const dec of g.decoders) {
         if (dec.queue.length >= room) continue;            // a slow reader's queue does not grow with every flush of its peers
@@ -238,47 +242,52 @@ SharedEngine.prototype.prepareResident = function (g, room) {
             if (!dec.rblocks) dec.rblocks = new Array(L);
             const n = packetFrames(dec.packets, L, dec.rblocks);
             for (let f = 0; f < n; f++) dec.rlens[f] = dec.rblocks[f].length;
-            if (n) { part.push(dec); F = Math.min(F, n); }
+            if (n) { part.push(dec); own.push(n); F = Math.min(F, n); }
             continue;
         }
         const n = scanFrames(dec.rbuf, dec.rpos, L, dec.rlens);
         if (n < 0) { if (!dec.badHeader) { dec.badHeader = true; dec.queue.push(new Error('Invalid ADTS header.')); } continue; }
         if (n === 0) continue;
-        part.push(dec); F = Math.min(F, n);
+        part.push(dec); own.push(n); F = Math.min(F, n);
     }
     if (!part.length) return null;
-    const S = part.length, frames = new Uint32Array(2 * S * F), slots = new Uint32Array(S), starts = new Uint32Array(S + 1);
+    /* counts[s]: stream s's frames in this batch — its own (ragged) or the fewest any participant has; first[s]: where they begin
+     * in the batch's packed order (frames, results and PCM alike) */
+    const S = part.length, counts = new Uint32Array(S), first = new Uint32Array(S + 1), slots = new Uint32Array(S), starts = new Uint32Array(S + 1);
+    for (let s = 0; s < S; s++) { counts[s] = ragged ? own[s] : F; first[s + 1] = first[s] + counts[s]; }
+    const N = first[S], frames = new Uint32Array(2 * N);
     let total = 0;
     for (let s = 0; s < S; s++) {
         const lens = part[s].rlens;
         starts[s] = total; slots[s] = part[s].stream;
-        for (let f = 0, i = 2 * s * F; f < F; f++, i += 2) { frames[i] = total; frames[i + 1] = lens[f]; total += lens[f]; }
+        for (let f = 0, i = 2 * first[s]; f < counts[s]; f++, i += 2) { frames[i] = total; frames[i + 1] = lens[f]; total += lens[f]; }
     }
     starts[S] = total;
     const bytes = new Uint8Array(total);
     for (let s = 0; s < S; s++) {
-        const dec = part[s], len = starts[s + 1] - starts[s];
+        const dec = part[s], len = starts[s + 1] - starts[s], n = counts[s];
         if (dec.packets) {
-            for (let f = 0, at = starts[s]; f < F; f++) { bytes.set(dec.rblocks[f], at); at += dec.rblocks[f].length; dec.rblocks[f] = null; }
-            takePacketFrames(dec.packets, F);
+            for (let f = 0, at = starts[s]; f < n; f++) { bytes.set(dec.rblocks[f], at); at += dec.rblocks[f].length; }
+            for (let f = 0; f < own[s]; f++) dec.rblocks[f] = null;
+            takePacketFrames(dec.packets, n);
             continue;
         }
         bytes.set(dec.rbuf.subarray(dec.rpos, dec.rpos + len), starts[s]);
         dec.rpos += len;
     }
-    return { part: part, S: S, F: F, frames: frames, slots: slots, bytes: bytes, results: new Uint8Array(8 * S * F) };
+    return { part: part, S: S, F: F, N: N, ragged: ragged, counts: counts, first: first, frames: frames, slots: slots, bytes: bytes, results: new Uint8Array(8 * N) };
 };
 
 /* the batch's PCM: one array on page-locked memory the device wrote into; a frame is a view of it (the memory returns to the
  * addon's pool when the last of the batch's frames has been collected) */
 SharedEngine.prototype.deliverResident = function (g, b, out, failed) {
-    const C = g.channels, part = b.part, S = b.S, F = b.F, results = b.results;
-    this.stats.batches++; this.stats.units += S * F;
+    const C = g.channels, part = b.part, S = b.S, results = b.results;
+    this.stats.batches++; this.stats.units += b.N;
     if (failed) { for (const dec of part) dec.queue.push(failed); return; }
     const pcm = out.pcm, refused = out.refused, per = 1024 * C;
     for (let s = 0; s < S; s++) {
         const q = part[s].queue;
-        for (let f = 0, i = s * F; f < F; f++, i++) {
+        for (let f = 0, i = b.first[s]; f < b.counts[s]; f++, i++) {
             /* a frame the device refused: the reference's message for its status where the frame is reached (it was decoded as
              * silence: the stream goes on); a frame whose elements are not the ones its stream began with has a status of its own
              * (AACG_PARSE_LAYOUT, set where the plan's records are refreshed) */
@@ -286,12 +295,24 @@ SharedEngine.prototype.deliverResident = function (g, b, out, failed) {
             else q.push(pcm.subarray(i * per, (i + 1) * per));
         }
     }
-    this.stats.frames += S * F;
+    this.stats.frames += b.N;
 };
 
 SharedEngine.prototype.flushResident = function (g) {
+    const t = process.hrtime.bigint();
+    try { this.flushResidentTimed(g); } finally { this.stats.flushNs += process.hrtime.bigint() - t; }
+};
+
+/* how many plans the resident pipelines have built (one per batch shape a pipeline had not kept) */
+SharedEngine.prototype.planBuilds = function () {
+    let n = 0;
+    for (const g of this.groups.values()) if (g.resident && g.addon.pipelinePlanBuilds) n += g.addon.pipelinePlanBuilds(g.pipeline);
+    return n;
+};
+
+SharedEngine.prototype.flushResidentTimed = function (g) {
     const L = this.lookahead, C = g.channels, ringElems = this.pcmRing ? this.maxStreams * L * 1024 * C : 0;
-    const args = (b) => [g.pipeline, b.bytes, b.frames, b.slots, b.F, b.results, C, this.pcmRing, ringElems];
+    const args = (b) => [g.pipeline, b.bytes, b.frames, b.slots, b.ragged ? b.counts : b.F, b.results, C, this.pcmRing, ringElems];
     const t0 = process.hrtime.bigint();
     let b = null, out = null, failed = null;
     if (this.overlap && g.pending) {                       // the batch the flush before this one submitted

@@ -52,6 +52,11 @@ static struct {
     int  (*pipeline_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, uint32_t,
                             void*, aacg_parse_result*, uint32_t*, uint64_t*);
     int  (*pipeline_collect)(aacg_pipeline*, uint64_t);
+    int  (*pipeline_decode_ragged)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, const uint32_t*,
+                                   void*, aacg_parse_result*, uint32_t*);
+    int  (*pipeline_submit_ragged)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, const uint32_t*,
+                                   void*, aacg_parse_result*, uint32_t*, uint64_t*);
+    uint64_t (*pipeline_plan_builds)(const aacg_pipeline*);
     int  (*pipeline_walk_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, uint32_t, uint32_t, aacg_parse_frame*,
                                  aacg_walk_result*, uint64_t*);
     int  (*pipeline_walk_collect)(aacg_pipeline*, uint64_t);
@@ -90,6 +95,8 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_create, "aacg_pipeline_create"); SYM(pipeline_destroy, "aacg_pipeline_destroy"); SYM(pipeline_last_error, "aacg_pipeline_last_error");
     SYM(pipeline_reset_stream, "aacg_pipeline_reset_stream"); SYM(pipeline_decode, "aacg_pipeline_decode");
     SYM(pipeline_submit, "aacg_pipeline_submit"); SYM(pipeline_collect, "aacg_pipeline_collect");
+    SYM(pipeline_decode_ragged, "aacg_pipeline_decode_ragged"); SYM(pipeline_submit_ragged, "aacg_pipeline_submit_ragged");
+    SYM(pipeline_plan_builds, "aacg_pipeline_plan_builds");
     SYM(pipeline_walk_submit, "aacg_pipeline_walk_submit"); SYM(pipeline_walk_collect, "aacg_pipeline_walk_collect");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
@@ -664,12 +671,15 @@ static void* pcm_take(size_t bytes, size_t* got)
 /* pipelineDecode(pipeline, bytes:Uint8Array, frames:Uint32Array(2 * S * F) [offset, length]..., slots:Uint32Array(S), framesPerStream,
  *                results:Uint8Array(8 * S * F), channels [, ring, ringElems])
  *   -> { pcm: Float32Array|Int16Array(S * F * 1024 * channels) on page-locked memory, refused }
+ * framesPerStream may be a Uint32Array(S) of per-stream counts instead (aacg_pipeline_decode_ragged / _submit_ragged): stream s
+ * brings counts[s] frames, and S * F above reads as the counts' sum — frames, results and PCM are packed stream after stream.
  * ring = 0 / absent: the PCM array's memory is the caller's for as long as any view of it lives (a buffer per call, recycled by
  * the garbage collector's finalizer).  ring = K: the pipeline's K buffers of ringElems elements, made at the first call, are
  * handed out in turn — what a call returns is overwritten by the K-th call after it. */
 typedef struct {
     handle_box* pb;
     const uint8_t* db; size_t nb; const aacg_parse_frame* df; const uint32_t* ds; size_t ns; uint32_t F; aacg_parse_result* dr;
+    const uint32_t* counts;                            /* ragged: per-stream frame counts (read during the call only), else NULL */
     void* pcm; size_t got, elems; int slot;
     napi_ref keep[4];                                  /* the four argument arrays: theirs is the memory the native call reads and writes */
     int n_keep;
@@ -689,16 +699,28 @@ static pipe_job* pipe_prepare(napi_env env, napi_callback_info info, int keep_ar
     if (!pb) return NULL;
     if (pb->n_jobs && !keep_args) { napi_throw_error(env, NULL, "aacgpu: submitted batches have not been collected yet (pipelineCollect)"); return NULL; }
     if (pb->n_jobs >= 3) { napi_throw_error(env, NULL, "aacgpu: pipelineSubmit: three batches are in flight already (pipelineCollect)"); return NULL; }
-    napi_typedarray_type t; size_t nb, nf, ns, nr; void *db, *df, *ds, *dr; uint32_t F = 0, C = 0;
-    napi_get_value_uint32(env, argv[4], &F);
+    napi_typedarray_type t; size_t nb, nf, ns, nr, nc = 0; void *db, *df, *ds, *dr, *dc = NULL; uint32_t F = 0, C = 0;
     napi_get_value_uint32(env, argv[6], &C);
-    if (!typed(env, argv[1], &t, &nb, &db) || t != napi_uint8_array || !typed(env, argv[2], &t, &nf, &df) || t != napi_uint32_array ||
-        !typed(env, argv[3], &t, &ns, &ds) || t != napi_uint32_array || !F || nf != 2 * ns * F || C < 1 || C > AACG_MAX_CHANNELS ||
-        !typed(env, argv[5], &t, &nr, &dr) || t != napi_uint8_array || nr != ns * F * sizeof(aacg_parse_result)) {
-        napi_throw_type_error(env, NULL, "pipelineDecode(pipeline, Uint8Array bytes, Uint32Array frames (2 per frame), Uint32Array slots, framesPerStream, Uint8Array results (8 per frame), channels)");
+    int ragged = 0, counts_ok = 1;
+    {
+        bool is_ta = false;
+        napi_is_typedarray(env, argv[4], &is_ta);
+        if (is_ta) { ragged = 1; counts_ok = typed(env, argv[4], &t, &nc, &dc) && t == napi_uint32_array; }
+        else napi_get_value_uint32(env, argv[4], &F);
+    }
+    size_t total = 0;                                  /* the batch's frames: S * F, or the counts' sum */
+    if (!typed(env, argv[3], &t, &ns, &ds) || t != napi_uint32_array) counts_ok = 0;
+    if (counts_ok && ragged) {
+        if (nc != ns) counts_ok = 0;
+        for (size_t s = 0; counts_ok && s < nc; s++) total += ((const uint32_t*)dc)[s];
+    } else total = ns * F;
+    if (!counts_ok || !typed(env, argv[1], &t, &nb, &db) || t != napi_uint8_array || !typed(env, argv[2], &t, &nf, &df) || t != napi_uint32_array ||
+        (!ragged && !F) || !total || nf != 2 * total || C < 1 || C > AACG_MAX_CHANNELS ||
+        !typed(env, argv[5], &t, &nr, &dr) || t != napi_uint8_array || nr != total * sizeof(aacg_parse_result)) {
+        napi_throw_type_error(env, NULL, "pipelineDecode(pipeline, Uint8Array bytes, Uint32Array frames (2 per frame), Uint32Array slots, framesPerStream | Uint32Array counts (one per stream), Uint8Array results (8 per frame), channels)");
         return NULL;
     }
-    const size_t elems = ns * F * 1024u * C, bytes = elems * (pb->out_i16 ? 2u : 4u);
+    const size_t elems = total * 1024u * C, bytes = elems * (pb->out_i16 ? 2u : 4u);
     size_t got = 0;
     void* pcm = NULL;
     int slot = -1;
@@ -733,7 +755,7 @@ static pipe_job* pipe_prepare(napi_env env, napi_callback_info info, int keep_ar
     pipe_job* j = (pipe_job*)calloc(1, sizeof *j);
     if (!j) { if (slot < 0 && !pool_put(pcm, got)) pcm_discard(pcm); napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
     j->pb = pb; j->db = (const uint8_t*)db; j->nb = nb; j->df = (const aacg_parse_frame*)df; j->ds = (const uint32_t*)ds; j->ns = ns; j->F = F;
-    j->dr = (aacg_parse_result*)dr; j->pcm = pcm; j->got = got; j->elems = elems; j->slot = slot;
+    j->dr = (aacg_parse_result*)dr; j->pcm = pcm; j->got = got; j->elems = elems; j->slot = slot; j->counts = (const uint32_t*)dc;
     if (keep_args) {
         const int which[4] = {1, 2, 3, 5};
         for (int k = 0; k < 4; k++)
@@ -749,10 +771,14 @@ static void pipe_run(pipe_job* j, int submit_only)
     pthread_mutex_lock(&j->pb->lock);
     aacg_pipeline* p = (aacg_pipeline*)j->pb->ptr;
     if (submit_only) {
-        j->rc = L.pipeline_submit(p, j->db, j->nb, j->df, j->ds, (uint32_t)j->ns, j->F, j->pcm, j->dr, &j->refused, &j->ticket);
+        j->rc = j->counts ? L.pipeline_submit_ragged(p, j->db, j->nb, j->df, j->ds, (uint32_t)j->ns, j->counts, j->pcm, j->dr, &j->refused, &j->ticket)
+                          : L.pipeline_submit(p, j->db, j->nb, j->df, j->ds, (uint32_t)j->ns, j->F, j->pcm, j->dr, &j->refused, &j->ticket);
         j->submitted = j->rc == 0;
-    } else j->rc = L.pipeline_decode(p, j->db, j->nb, j->df, j->ds, (uint32_t)j->ns, j->F, j->pcm, j->dr, &j->refused);
-    if (j->rc) snprintf(j->msg, sizeof j->msg, "aacgpu: %s failed (%d): %.800s", submit_only ? "aacg_pipeline_submit" : "aacg_pipeline_decode", j->rc, L.pipeline_last_error(p));
+    } else j->rc = j->counts ? L.pipeline_decode_ragged(p, j->db, j->nb, j->df, j->ds, (uint32_t)j->ns, j->counts, j->pcm, j->dr, &j->refused)
+                             : L.pipeline_decode(p, j->db, j->nb, j->df, j->ds, (uint32_t)j->ns, j->F, j->pcm, j->dr, &j->refused);
+    j->counts = NULL;                                  /* the counts are read by the call only (the pipeline keeps a copy) */
+    if (j->rc) snprintf(j->msg, sizeof j->msg, "aacgpu: %s%s failed (%d): %.800s", submit_only ? "aacg_pipeline_submit" : "aacg_pipeline_decode",
+                        j->F ? "" : "_ragged", j->rc, L.pipeline_last_error(p));
     pthread_mutex_unlock(&j->pb->lock);
 }
 static void pipe_wait(pipe_job* j)
@@ -918,6 +944,20 @@ static napi_value js_pipeline_reset_stream(napi_env env, napi_callback_info info
     return NULL;
 }
 
+/* pipelinePlanBuilds(pipeline) -> how many plans the pipeline has built (one per batch shape it had not kept; aacgpu_tools.h) */
+static napi_value js_pipeline_plan_builds(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1], out;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_box* pb = box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle");
+    if (!pb) return NULL;
+    pthread_mutex_lock(&pb->lock);
+    const uint64_t n = L.pipeline_plan_builds((const aacg_pipeline*)pb->ptr);
+    pthread_mutex_unlock(&pb->lock);
+    CHECK(env, napi_create_double(env, (double)n, &out));
+    return out;
+}
+
 /* parseStatusString(code) -> the reference's message for a per-frame status */
 static napi_value js_parse_status_string(napi_env env, napi_callback_info info)
 {
@@ -947,6 +987,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelineSubmit", NULL, js_pipeline_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineCollect", NULL, js_pipeline_collect, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineResetStream", NULL, js_pipeline_reset_stream, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelinePlanBuilds", NULL, js_pipeline_plan_builds, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkCollect", NULL, js_pipeline_walk_collect, NULL, NULL, NULL, napi_default, NULL},
     };

@@ -33,11 +33,12 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_submit", "aacg_pipeline_collect", "aacg_pipeline_set_wait_limit_ms", "aacg_pipeline_stream_layout",
                "aacg_set_wait_limit_ms", "aacg_parser_set_wait_limit_ms", "aacg_pipeline_info",
                "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_parse_walk", "aacg_parse_walk_device",
-               "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect"]
+               "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
-                 "aacg_debug_pipeline_order", "aacg_pipeline_streams_used", "aacg_debug_set_wait_mode", "aacg_debug_in_flight", "aacg_debug_stall"]
+                 "aacg_debug_pipeline_order", "aacg_pipeline_streams_used", "aacg_debug_set_wait_mode", "aacg_debug_in_flight", "aacg_debug_stall",
+                 "aacg_pipeline_plan_builds"]
 WAIT_SPIN, WAIT_YIELD, WAIT_SLEEP, WAIT_BLOCK = 0, 1, 2, 3
 # aacg_debug_set_route / aacg_debug_route flags
 DEBUG_ROUTE_UNFUSED_COUPLING, DEBUG_ROUTE_RECOMPUTE = 1, 8
@@ -219,6 +220,11 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.aacg_pipeline_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     L.aacg_pipeline_collect.argtypes = [C.c_void_p, C.c_uint64]
+    L.aacg_pipeline_decode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.aacg_pipeline_submit_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_uint64)]
+    L.aacg_pipeline_plan_builds.argtypes = [C.c_void_p]
+    L.aacg_pipeline_plan_builds.restype = C.c_uint64
     L.aacg_pipeline_set_wait_limit_ms.argtypes = [C.c_void_p, C.c_uint32]
     L.aacg_pipeline_stream_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     _lib = L
@@ -468,30 +474,49 @@ class Pipeline:
             raise AacgError(n, "aacg_pipeline_stream_layout")
         return [int(c) for c in ch[:n]], int(kept.value)
 
+    def plan_builds(self):
+        """how many plans the pipeline has built (one per batch shape it had not kept)"""
+        return int(self.lib.aacg_pipeline_plan_builds(self.handle))
+
     def _args(self, data, frames, slots, frames_per_stream, pcm):
         data = np.ascontiguousarray(data, np.uint8)
         frames = np.ascontiguousarray(frames)
         slots = np.ascontiguousarray(slots, np.uint32)
-        assert frames.dtype == PARSE_FRAME_DTYPE and len(frames) == len(slots) * frames_per_stream
+        if np.ndim(frames_per_stream):
+            counts = np.ascontiguousarray(frames_per_stream, np.uint32)
+            assert len(counts) == len(slots)
+            total = int(counts.sum())
+        else:
+            counts, total = None, len(slots) * int(frames_per_stream)
+        assert frames.dtype == PARSE_FRAME_DTYPE and len(frames) == total
         n = len(frames)
         if pcm is None:
             pcm = np.zeros(n * 1024 * self.channels, np.int16 if self.i16 else np.float32)
         assert pcm.size >= n * 1024 * self.channels
-        return data, frames, slots, pcm, np.zeros(n, PARSE_RESULT_DTYPE), C.c_uint32(0)
+        return data, frames, slots, counts, pcm, np.zeros(n, PARSE_RESULT_DTYPE), C.c_uint32(0)
 
     def decode(self, data, frames, slots, frames_per_stream, pcm=None):
-        """Synchronous: (pcm, results, n_refused).  frames[s * F + f] = frame f of stream s in `data`."""
-        data, frames, slots, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
-        self._check(self.lib.aacg_pipeline_decode(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
-                                                  frames_per_stream, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
+        """Synchronous: (pcm, results, n_refused).  frames[s * F + f] = frame f of stream s in `data`.  frames_per_stream may be a
+        sequence of per-stream counts (aacg_pipeline_decode_ragged): frames, PCM and results are then packed stream after stream."""
+        data, frames, slots, counts, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
+        if counts is None:
+            self._check(self.lib.aacg_pipeline_decode(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
+                                                      frames_per_stream, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
+        else:
+            self._check(self.lib.aacg_pipeline_decode_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
+                                                             counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
         return pcm, res, int(refused.value)
 
     def submit(self, data, frames, slots, frames_per_stream, pcm=None):
-        """Asynchronous: returns a ticket; collect(ticket) -> (pcm, results, n_refused)."""
-        data, frames, slots, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
+        """Asynchronous: returns a ticket; collect(ticket) -> (pcm, results, n_refused).  frames_per_stream as for decode."""
+        data, frames, slots, counts, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
         t = C.c_uint64()
-        self._check(self.lib.aacg_pipeline_submit(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
-                                                  frames_per_stream, pcm.ctypes.data, res.ctypes.data, C.byref(refused), C.byref(t)))
+        if counts is None:
+            self._check(self.lib.aacg_pipeline_submit(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
+                                                      frames_per_stream, pcm.ctypes.data, res.ctypes.data, C.byref(refused), C.byref(t)))
+        else:
+            self._check(self.lib.aacg_pipeline_submit_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
+                                                             counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused), C.byref(t)))
         self._keep[t.value] = (pcm, res, refused)
         return t.value
 

@@ -637,6 +637,21 @@ int  aacg_pipeline_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes
                           const uint32_t* slots, uint32_t n_streams, uint32_t frames_per_stream,
                           void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket);
 int  aacg_pipeline_collect(aacg_pipeline* p, uint64_t ticket);
+/* Ragged batches: each stream brings its own number of frames (what one decoder per stream decodes of whatever its stream has,
+ * decoder.js:125-216).  Stream s brings frames_of[s] consecutive frames (1 <= frames_of[s] <= max_frames), listed at
+ * frames[first_s .. first_s + frames_of[s]), first_s = frames_of[0] + ... + frames_of[s - 1]; pcm_out is
+ * [first_s + f][1024][channels] and results one record per frame, both in that same packed order.  The batch's frames, the
+ * sum of the counts, are at most max_streams x max_frames.  A count of 0 or a slot listed twice is AACG_ERR_INVALID_ARG, a count
+ * over max_frames or a total over capacity AACG_ERR_CAPACITY: nothing is enqueued then, no ticket is taken and
+ * aacg_pipeline_last_error says why.  Otherwise as aacg_pipeline_decode / aacg_pipeline_submit, which are the case of every
+ * count equal to frames_per_stream (frames[s * F + f] is frames[first_s + f] then) and give the same bits.  A kept plan serves
+ * the batches of one shape: the same slots in the same order with the same counts. */
+int  aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                 const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                 void* pcm_out, aacg_parse_result* results, uint32_t* n_refused);
+int  aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                 const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                 void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket);
 int  aacg_pipeline_set_wait_limit_ms(aacg_pipeline* p, uint32_t ms);
 /* Span walks on the pipeline's device (aacg_parse_walk's semantics and outputs, the pipeline's parse_options): where the blocks of
  * MP4 sample runs lie, ahead of the batches that decode them.  aacg_pipeline_walk_submit stages the bytes (they may be reused when

@@ -33,6 +33,8 @@ uint64_t aacg_pipeline_chained(const aacg_engine* e);
 /* 1 if the engine's internal streams were seen to run side by side, each pair of them, when the pipeline was set up (HIP multiplexes
  * streams onto a few hardware queues; two streams on one queue serialise): 0 = pipelined launches are correct but do not overlap. */
 int aacg_pipeline_concurrent(const aacg_engine* e);
+/* How many plans the resident pipeline has built since it was made (one per batch shape it had not kept: aacg_pipeline_submit_ragged). */
+uint64_t aacg_pipeline_plan_builds(const aacg_pipeline* p);
 /* how many of the engine's streams the current pipelined sequence takes in turn (aacg_pipeline_streams, aacg_routes.h); 0 before the first */
 int aacg_pipeline_streams_used(const aacg_engine* e);
 /* How the host waits once a wait has lasted spin_us microseconds of polling (aacg_wait.h): 0 keep polling (round 5), 1 sched_yield

@@ -13,6 +13,14 @@
  *                                                            the same streams as MP4 chunks (ADTS headers cut off, N samples per
  *                                                            feedPacket buffer) on a SharedEngine: the parsing route, and the
  *                                                            resident route with { residentPackets: true }; one checksum
+ *   node tools/readchunk_rate.js --arrival jitter [--ragged] [--streams 256] [--rounds 60] [--seed 7] [--ring K]
+ *                                                            jittered arrival (tests/js/jitter_feed.js): N stereo decoders on one
+ *                                                            resident SharedEngine (overlap on), each fed a seeded random 1..16
+ *                                                            frames per round, one reader in ten paused for a few rounds, streams
+ *                                                            ending and starting over now and then; frames/s, flushes, frames per
+ *                                                            flush, plans built per 1000 flushes, host time per flush, and a
+ *                                                            checksum of every stream's PCM (equal with and without --ragged for
+ *                                                            one seed).  --ragged: SharedEngine({ ragged: true })
  * The GPU lines need the built engine and a GPU; without one they are reported as null. */
 'use strict';
 const fs = require('fs'), path = require('path');
@@ -21,6 +29,30 @@ const host = require(path.join(root, 'aac.js_amd', 'js'));
 const argv0 = process.argv.slice(2);
 /* --file NAME: another of the committed streams (tests/golden/streams/NAME.aac; surround48 = SCE + CPE + CPE + LFE, six channels) */
 const fileAt = argv0.indexOf('--file'), fileName = fileAt >= 0 ? argv0[fileAt + 1] : 'stereo48';
+const arrivalAt = argv0.indexOf('--arrival');
+if (arrivalAt >= 0) {
+    if (argv0[arrivalAt + 1] !== 'jitter') throw new Error('--arrival: jitter is the one arrival mode');
+    const opt = function (name, dflt) { const i = argv0.indexOf(name); return i >= 0 ? parseInt(argv0[i + 1], 10) : dflt; };
+    const ragged = argv0.indexOf('--ragged') >= 0, S = opt('--streams', 256), rounds = opt('--rounds', 60), seed = opt('--seed', 7), ring = opt('--ring', 0);
+    const jitter = require(path.join(root, 'tests', 'js', 'jitter_feed.js'));
+    const one = new Uint8Array(fs.readFileSync(path.join(root, 'tests', 'golden', 'streams', fileName + '.aac'))), reps = 64;
+    const bytes = new Uint8Array(one.length * reps);
+    for (let i = 0; i < reps; i++) bytes.set(one, i * one.length);
+    const res = { mode: 'arrival jitter', ragged: ragged, stream: fileName + '.aac x ' + reps, streams: S, rounds: rounds, seed: seed, pcm_ring: ring };
+    try {
+        const sh = new host.SharedEngine({ maxStreams: S, maxChannels: 8, resident: true, ragged: ragged, lookahead: 16, pcmRing: ring });
+        const r = jitter.run({ host: host, shared: sh, sources: [{ bytes: bytes, list: host.adts.frames(bytes) }], streams: S, rounds: rounds, seed: seed });
+        const flushes = sh.stats.batches, builds = sh.planBuilds();
+        Object.assign(res, { frames: r.frames, seconds: +r.seconds.toFixed(3), frames_per_s: Math.round(r.frames / r.seconds), decoders_made: r.instances,
+                             flushes: flushes, frames_per_flush: +(sh.stats.frames / flushes).toFixed(1), plan_builds: builds,
+                             plan_builds_per_1000_flushes: +(1000 * builds / flushes).toFixed(1),
+                             host_ms_per_flush: +(Number(sh.stats.flushNs) / 1e6 / flushes).toFixed(3),
+                             native_call_ms_per_flush: +(Number(sh.stats.engineNs) / 1e6 / flushes).toFixed(3),
+                             checksum: r.sums.reduce(function (a, b) { return a + b; }, 0) });
+    } catch (e) { res.error = String(e.message || e).slice(0, 300); }
+    console.log(JSON.stringify(res, null, 1));
+    process.exit(0);
+}
 const mp4aMode = argv0.indexOf('--mp4a') >= 0, perAt = argv0.indexOf('--samples-per-packet');
 const perPacket = perAt >= 0 ? parseInt(argv0[perAt + 1], 10) : 16;
 const argv = argv0.filter(function (a, i) { return (fileAt < 0 || (i !== fileAt && i !== fileAt + 1)) && a !== '--mp4a' && (perAt < 0 || (i !== perAt && i !== perAt + 1)); });
