@@ -16,6 +16,12 @@ f32-output twins), worst block seen:
                                       lane emulator (CPU)          MI355X
   routes without optional stages:     RMS 2.22e-7  max 5.19e-7     RMS 2.09e-7  max 4.16e-7
   TNS / PNS / coupling elements:      RMS 5.40e-7  max 1.19e-6     RMS 5.46e-7  max 8.86e-7
+  edges (tests/edge_cases.py, every band table; same gates):
+    routes without optional stages:   RMS 3.78e-7  max 7.12e-7     RMS 3.78e-7  max 5.65e-7
+    TNS / PNS / coupling elements:    RMS 1.04e-6  max 2.13e-6     RMS 1.04e-6  max 2.13e-6
+The edge rows are higher because a block's scale is its own level while its first half is the previous frame's tail: after a
+frame louder than itself (escape values, TNS gains) a block carries that frame's error.  The workload keeps single-band and
+silent frames away from the seam where batch 1 follows batch 0 for that reason.
 The excess of the second row is in the channels that carry TNS filters (their blocks twice the error of the others in the same
 batch): the kernels run the all-pole filters through double-precision transition matrices, the oracle runs the reference's
 float32 recursion, and the filter's gain amplifies the rounding.  Each gate is about three times the worst block seen.

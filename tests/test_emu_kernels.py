@@ -315,24 +315,25 @@ def test_long_chains_double_duty(emu, oracle, T, want):
 @pytest.mark.parametrize("sample_index,max_long", [(5, 49), (6, 47), (8, 43), (0, 41)])
 def test_other_sample_rates_vs_oracle(emu, oracle, sample_index, max_long):
     """The band tables depend on the sampling rate (tables.js:34-155): 32, 24, 16 and 96 kHz layouts against the
-    oracle (the golden vectors pin 48 kHz).  The generator's long windows are clamped to the rate's band count."""
+    oracle (the golden vectors pin 48 kHz).  The generator's max_sfb is stretched onto the rate's own band counts, long and
+    short (max_long: the cap below the table these tests once applied), and held to the per-block gate as well."""
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "aac.js_amd", "python"))
     import aacgpu_workload
+    import edge_cases
+    import parity
     wl = aacgpu_workload.random_batch(500 + sample_index, n_streams=2, max_frames=5)
-    units = wl["units"].copy()
-    for i in range(len(units)):
-        for c in range(2):
-            short = int(units[i]["ch"][c]["window_sequence"]) == 2
-            units[i]["ch"][c]["max_sfb"] = min(int(units[i]["ch"][c]["max_sfb"]), 12 if short else max_long)
-    # grouped shorts index their bands by g * maxSFB + sfb: rebuild nothing, the oracle and the kernels read the
-    # same words through the same formula
+    units, meta = edge_cases.stretch_max_sfb(oracle, wl, sample_index, max_long)
     S, C = wl["n_streams"], wl["max_channels"]
     ov = np.zeros((S, C, 1024), np.float32)
-    ref, spec_ref = oracle.decode_batch(units, wl["q"], wl["meta"], wl["n_pcm"], ov, sample_index=sample_index, want_spec=True)
+    ref, spec_ref = oracle.decode_batch(units, wl["q"], meta, wl["n_pcm"], ov, sample_index=sample_index, want_spec=True)
+    exact = parity.exact_reference(oracle, units, wl["q"], meta, wl["n_pcm"], np.zeros((S, C, 1024), np.float32), sample_index=sample_index)
     pool = np.zeros((S, C, emu_lib.OV_BUFFERS, 1024), np.float32)
     par = np.zeros(S * C, np.uint8)
-    pcm = emu.decode(units, wl["q"], wl["meta"], wl["n_pcm"], pool, par, sample_index=sample_index)
+    pcm = emu.decode(units, wl["q"], meta, wl["n_pcm"], pool, par, sample_index=sample_index)
     rms(pcm, ref)
-    spec = emu.spectral(units, wl["q"], wl["meta"], sample_index=sample_index)
+    w = parity.assert_blocks(pcm, exact, units, what="sample index %d" % sample_index)
+    print("per-block worst si %d: rms %.3e max %.3e" % (sample_index, w[0], w[1]))
+    spec = emu.spectral(units, wl["q"], meta, sample_index=sample_index)
     assert np.array_equal(spec.view(np.uint32), spec_ref.view(np.uint32))
+

@@ -483,21 +483,65 @@ def test_long_chains_double_duty(oracle, T):
     eng.close()
 
 
+@pytest.mark.parametrize("sample_index", [8, 5])
+def test_extremes_at_the_tables_maxima(oracle, sample_index):
+    """The real maxima next to test_extremes: at sample index 8 eight one-window groups of 15 bands (120 band records, the
+    whole of aacg_band_meta), at 5 long windows of 51 bands; every band escape-coded, magnitudes up to 8190, MS on every band
+    of the first CPE; rms() and the per-block gate against the exact-roots oracle."""
+    import edge_cases
+    import parity
+    S = 1
+    wl = aacgpu_workload.make_batch(n_streams=S, n_frames=8, layout=("cpe", "cpe", "cpe", "cpe"), mix=True, seed=19)
+    u, q, meta = wl["units"].copy(), wl["q"].copy(), wl["meta"].copy()
+    lo, so = edge_cases.tables(oracle, sample_index)
+    short = u["ch"]["window_sequence"][:, 0] == 2
+    for c in range(2):
+        gl = u["ch"]["group_len"][:, c].copy()
+        gl[short] = 1
+        u["ch"]["group_len"][:, c] = gl
+        u["ch"]["group_count"][short, c] = 8
+        u["ch"]["max_sfb"][:, c] = np.where(short, len(so) - 1, len(lo) - 1)
+    nb = np.where(short, 8 * (len(so) - 1), len(lo) - 1)
+    assert nb.max() == (120 if sample_index == 8 else 112) and (sample_index != 5 or (nb == 51).any())
+    bt = np.full(120, 11 << 12, np.uint16) | 236
+    for i in range(len(u)):
+        for c in range(2):
+            meta[u["meta_offset"][i] + c] = np.where(np.arange(120) < nb[i], bt | (0x400 if c == 0 and i % 4 == 0 else 0), 0)
+    q[::7, ::13] = 8190
+    q[3::11, 5::17] = -8190
+    q[1::5, 1016:] = 8190                                      # the top of the top band
+    ov = np.zeros((S, 8, 1024), np.float32)
+    ref = oracle.decode_batch(u, q, meta, wl["n_pcm"], ov, sample_index=sample_index)
+    exact = parity.exact_reference(oracle, u, q, meta, wl["n_pcm"], np.zeros((S, 8, 1024), np.float32), sample_index=sample_index)
+    eng = aacgpu.Engine(aacgpu.INPUT_QUANT_I16, S, 8, sample_index=sample_index)
+    pcm = eng.decode_batch(u, q, meta, wl["n_pcm"])
+    assert np.isfinite(ref).all()
+    rms(pcm, ref)
+    w = parity.assert_blocks(pcm, exact, u, what="sample index %d" % sample_index)
+    print("per-block worst si %d: rms %.3e max %.3e" % (sample_index, w[0], w[1]))
+    assert np.abs(overlaps(eng, S, 8) - ov).max() < 1e-5 * max(1.0, float(np.abs(ov).max()))
+    eng.close()
+
+
 @pytest.mark.parametrize("sample_index,max_long", [(5, 49), (6, 47), (8, 43), (0, 41)])
 def test_other_sample_rates(oracle, sample_index, max_long):
-    """Band tables of other sampling rates (tables.js:34-155) through the real engine: 32, 24, 16, 96 kHz."""
+    """Band tables of other sampling rates (tables.js:34-155) through the real engine: 32, 24, 16, 96 kHz, max_sfb stretched
+    onto each table's own long and short counts (edge_cases.stretch_max_sfb; max_long: the cap below the table once applied),
+    the per-block gate against the exact-roots oracle next to rms()."""
+    import edge_cases
+    import parity
     wl = aacgpu_workload.random_batch(600 + sample_index, n_streams=3, max_frames=12)
-    units = wl["units"].copy()
-    for i in range(len(units)):
-        for c in range(2):
-            short = int(units[i]["ch"][c]["window_sequence"]) == 2
-            units[i]["ch"][c]["max_sfb"] = min(int(units[i]["ch"][c]["max_sfb"]), 12 if short else max_long)
+    units, meta = edge_cases.stretch_max_sfb(oracle, wl, sample_index, max_long)
     S, C = wl["n_streams"], wl["max_channels"]
     ov = np.zeros((S, C, 1024), np.float32)
-    ref = oracle.decode_batch(units, wl["q"], wl["meta"], wl["n_pcm"], ov, sample_index=sample_index)
+    ref = oracle.decode_batch(units, wl["q"], meta, wl["n_pcm"], ov, sample_index=sample_index)
+    exact = parity.exact_reference(oracle, units, wl["q"], meta, wl["n_pcm"], np.zeros((S, C, 1024), np.float32),
+                                   sample_index=sample_index)
     eng = aacgpu.Engine(aacgpu.INPUT_QUANT_I16, S, C, sample_index=sample_index)
-    pcm = eng.decode_batch(units, wl["q"], wl["meta"], wl["n_pcm"])
+    pcm = eng.decode_batch(units, wl["q"], meta, wl["n_pcm"])
     rms(pcm, ref)
+    w = parity.assert_blocks(pcm, exact, units, what="sample index %d" % sample_index)
+    print("per-block worst si %d: rms %.3e max %.3e" % (sample_index, w[0], w[1]))
     assert np.abs(overlaps(eng, S, C) - ov).max() < 1e-5 * max(1.0, float(np.abs(ov).max()))
     eng.close()
 

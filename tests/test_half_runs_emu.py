@@ -128,6 +128,79 @@ def _check_cells(layout, S, T, n, seam):
         assert _same(emu_lib.pool_current(pool, par), serial_state), order
 
 
+@pytest.mark.parametrize("si,T,nan", [(8, 20, False), (5, 17, False), (6, 20, True)])
+def test_eight_wave_runs_at_the_edges(emus, si, T, nan):
+    """The edge workload (tests/edge_cases.py: every q of -520..520 across the IQ table's LDS cut at +-256, +-8190, 120 band
+    records at 15-band rates, 51 long bands at sample index 5; nan: |q| = 8191 / -32768 in the last frame of the first run)
+    through the eight-wave body in both rendezvous orders: the sixteen-wave body's bits, and the exact-roots oracle block by
+    block"""
+    _in_child("_check_edges", si, T, nan)
+
+
+def _edge_batch(oracle, si, T, S=2, seed=71):
+    import edge_cases as E
+    wl = W.make_batch(n_streams=S, n_frames=T, layout=("cpe",), mix=True, intensity=True, seed=seed)
+    units, meta = E.edge_side_info(wl, si, oracle, seed + 1)
+    q, _ = E.edge_coeffs(units, meta, si, oracle, seed + 2)
+    return wl, units, meta, q
+
+
+def _check_edges(si, T, nan):
+    import edge_cases as E
+    import orc
+    import parity
+    oracle = orc.load()
+    full, half = emu_lib.Emu(), emu_lib.Emu(LIB)
+    S = 2
+    wl, units, meta, q = _edge_batch(oracle, si, T, S)
+    if nan:
+        q = E.edge_nan(q, units, meta, 1, si, oracle, [s * T + 15 for s in range(S)])
+    assert set(E.SEAM.tolist()) <= E.covered(units, meta, [q], si, oracle)
+    C = wl["C"]
+    exact = parity.exact_reference(oracle, units, q, meta, wl["n_pcm"], np.zeros((S, C, 1024), np.float32), sample_index=si)
+    assert np.isnan(exact).any() == nan
+    pool, par = emu_lib.new_pool(S, C)
+    want = full.decode(units, q, meta, wl["n_pcm"], pool, par, sample_index=si, rv=1)
+    want_state = emu_lib.pool_current(pool, par)
+    parity.assert_blocks(want, exact, units, what="sixteen waves, sample index %d" % si)
+    for rv in (1, 2):
+        pool, par = emu_lib.new_pool(S, C)
+        got = half.decode(units, q, meta, wl["n_pcm"], pool, par, sample_index=si, rv=rv)
+        assert _same(got, want), rv
+        assert _same(emu_lib.pool_current(pool, par), want_state), rv
+    return True
+
+
+def test_eight_wave_runs_through_cross_launch_cells_at_the_edges(emus):
+    """three overlapped launches of one plan on the edge workload at a 15-band rate, meeting in cross-launch cells in a random
+    interleaving: the serial sixteen-wave decode's bits"""
+    _in_child("_check_edge_cells", 8, 18, 3)
+
+
+def _check_edge_cells(si, T, n):
+    import edge_cases as E
+    import orc
+    oracle = orc.load()
+    full, half = emu_lib.Emu(), emu_lib.Emu(LIB)
+    S = 1
+    wl, units, meta, q = _edge_batch(oracle, si, T, S, seed=73)
+    C = wl["C"]
+    qs, at = [q], 0
+    for j in range(1, n):
+        x, at = E.edge_coeffs(units, meta, si, oracle, 80 + j, start=at)
+        qs.append(x)
+    pool, par = emu_lib.new_pool(S, C)
+    serial = [full.decode(units, x, meta, wl["n_pcm"], pool, par, sample_index=si) for x in qs]
+    serial_state = emu_lib.pool_current(pool, par)
+    pool, par = emu_lib.new_pool(S, C)
+    cells, heads = _cells(S, C)
+    got, _ = half.decode_pipelined(units, qs, [meta] * n, wl["n_pcm"], pool, par, cells, heads, order=7, sample_index=si)
+    for j in range(n):
+        assert _same(got[j], serial[j]), j
+    assert _same(emu_lib.pool_current(pool, par), serial_state)
+    return True
+
+
 @pytest.mark.parametrize("ablate", [2, 8, 10, 32, 64, 128])
 def test_eight_wave_profiling_paths_finish(emus, ablate):
     """tools/floor.sh and tools/timeline.py run the headline route with these switches (profiling build): no epilogue (2), no
