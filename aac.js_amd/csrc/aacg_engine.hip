@@ -41,8 +41,6 @@ void aacg_spectral_ex_launch(bool quant, int n_units, hipStream_t s, const aacg_
 void aacg_tns_matrices_launch(const aacg_dev_tns* d_recs, double* d_m, uint32_t n_records, hipStream_t s);
 /* aacg_engine_couple.hip: AACG_CCE_SPEC */
 void aacg_couple_launch(bool pcm, hipStream_t s, const aacg_couple_params& Q);
-struct cce_bufs { const aacg_run* runs; const aacg_couple_job* jobs; const float* gains; float* side; };
-struct rv_bufs { const aacg_run* runs; const aacg_rv_link* links; unsigned long long* state; float* data; };
 
 extern "C" __global__ __launch_bounds__(AACG_WG_THREADS)
 void aacg_spectral(const aacg_kparams P, int n_units) { spectral_body(P, n_units); }
@@ -60,6 +58,37 @@ extern "C" __global__ void aacg_probe_wait(const unsigned* flag, unsigned* seen,
 extern "C" __global__ void aacg_probe_set(unsigned* flag) { __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 #define AACG_LDS_BYTES_SPECTRAL ((AACG_TAB_QUANT_FLOATS + AACG_WG_WAVES * 512) * 4)
+
+/* What a planned batch owns on the device: the planner's tables (aacg_plan_host) and the work areas of its route.  Plans take
+ * the buffers from the engine's free list, the host-buffer path's slots grow theirs on demand; their sizes (batch_sizes), their
+ * upload (batch_upload) and launch_run's reading of them are the same for both. */
+struct batch_bufs {
+    enum { UNITS, RUNS,
+           TNS,                                     /* TNS records, their transition matrices behind them (tns_buffer_bytes) */
+           SCRATCH,                                 /* parked predecessor tails of double-duty runs */
+           SPEC,                                    /* staged routes: f32 spectra between the launches */
+           CCE_RUNS, CCE_JOBS, CCE_GAINS, CCE_SIDE, /* AACG_CCE_SPEC: coupling elements' runs, jobs, gains, side PCM */
+           RV_RUNS, RV_LINKS, RV_DATA, RV_STATE,    /* _rv kernels: run table, link records, in-launch cells' payload and state words
+                                                       (the state last: a slot zeroes it when its growing loop made it anew, and
+                                                       nothing may fail in between) */
+           N };
+    void* p[N] = {};
+    size_t bytes[N] = {};                           /* of each allocation: the free-list block (plans), the capacity (slots) */
+    double* tns_m = nullptr;                        /* where the TNS matrices start in p[TNS] (batch_upload) */
+    aacg_dev_unit* units() const { return (aacg_dev_unit*)p[UNITS]; }
+    aacg_run* runs() const { return (aacg_run*)p[RUNS]; }
+    aacg_dev_tns* tns() const { return (aacg_dev_tns*)p[TNS]; }
+    float* scratch() const { return (float*)p[SCRATCH]; }
+    float* spec() const { return (float*)p[SPEC]; }
+    aacg_run* cce_runs() const { return (aacg_run*)p[CCE_RUNS]; }
+    aacg_couple_job* cce_jobs() const { return (aacg_couple_job*)p[CCE_JOBS]; }
+    float* cce_gains() const { return (float*)p[CCE_GAINS]; }
+    float* cce_side() const { return (float*)p[CCE_SIDE]; }
+    aacg_run* rv_runs() const { return (aacg_run*)p[RV_RUNS]; }
+    aacg_rv_link* rv_links() const { return (aacg_rv_link*)p[RV_LINKS]; }
+    float* rv_data() const { return (float*)p[RV_DATA]; }
+    unsigned long long* rv_state() const { return (unsigned long long*)p[RV_STATE]; }
+};
 
 /* ---- engine ------------------------------------------------------------------------ */
 struct aacg_engine {
@@ -104,15 +133,9 @@ struct aacg_engine {
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr, kernel_done = nullptr;
         bool busy = false;
-        void* d_units = nullptr;  size_t units_cap = 0;
-        void* d_runs = nullptr;   size_t runs_cap = 0;
+        batch_bufs b;                       /* the batch's tables and work areas (b.bytes: capacities) */
         void* d_coeffs = nullptr; size_t coeffs_cap = 0;
         void* d_meta = nullptr;   size_t meta_cap = 0;
-        void* d_tns = nullptr;    size_t tns_cap = 0;
-        void* d_scratch = nullptr; size_t scratch_cap = 0;
-        void* d_spec = nullptr;   size_t spec_cap = 0;       /* PNS route: f32 spectra between the two kernels */
-        void* d_cce[4] = {nullptr, nullptr, nullptr, nullptr}; size_t cce_cap[4] = {0, 0, 0, 0};   /* AACG_CCE_SPEC: runs, jobs, gains, side PCM */
-        void* d_rv[4] = {nullptr, nullptr, nullptr, nullptr}; size_t rv_cap[4] = {0, 0, 0, 0};     /* _rv kernels: runs, links, rendezvous state, payload */
         void* d_pcm = nullptr;    size_t pcm_cap = 0;
         /* page-locked staging for callers that pass ordinary (pageable) memory */
         void* h_in = nullptr;     size_t h_in_cap = 0;
@@ -141,24 +164,17 @@ struct aacg_engine {
     std::string err;
 };
 
-#define AACG_PLAN_BUFFERS 13
 struct aacg_plan {
     aacg_engine* e;
     aacg_plan_host h;
     uint32_t n_units = 0;
-    aacg_dev_unit* d_units = nullptr;
-    aacg_run* d_runs = nullptr;
-    aacg_dev_tns* d_tns = nullptr;
-    float* d_scratch = nullptr;             /* parked predecessor tails of double-duty runs */
-    float* d_spec = nullptr;                /* PNS route: f32 spectra between the two kernels */
-    void*  d_cce[4] = {nullptr, nullptr, nullptr, nullptr};   /* AACG_CCE_SPEC: coupling elements' runs, jobs, gains, side PCM */
-    void*  d_rv[4] = {nullptr, nullptr, nullptr, nullptr};    /* _rv kernels: run table, link records, rendezvous state words and payload (two sets: overlapping launches) */
-    size_t bytes[AACG_PLAN_BUFFERS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  /* sizes of the buffers above, for the engine's free list */
+    batch_bufs b;                           /* the batch's tables and work areas, from the engine's free list (b.bytes: the blocks' sizes);
+                                               rendezvous cells: a set per pipeline stream (overlapping launches) */
     hipEvent_t uploaded = nullptr;          /* the tables are on the device */
     hipEvent_t last_use = nullptr;          /* recorded at destruction on last_stream: everything launched with this plan */
     hipStream_t last_stream = nullptr;      /* stream of the most recent launch (no per-launch event: it costs 3 us per step) */
-    uint32_t unit_sets = 1, cur_set = 0;    /* aacg_plan_set_unit_sets: d_units holds unit_sets copies of the records; launches read cur_set */
-    const aacg_dev_unit* units_now() const { return d_units + (size_t)cur_set * n_units; }
+    uint32_t unit_sets = 1, cur_set = 0;    /* aacg_plan_set_unit_sets: b.units() holds unit_sets copies of the records; launches read cur_set */
+    const aacg_dev_unit* units_now() const { return b.units() + (size_t)cur_set * n_units; }
     bool used = false;
     bool last_pipelined = false;            /* its most recent launch went through aacg_decode_pipelined */
     uint64_t seen_epoch = ~0ull;            /* engine epoch right after this plan's last launch */
@@ -379,16 +395,55 @@ int launch_kernel(aacg_engine* e, const aacg_run_kernel* k, unsigned blocks, hip
  * the device by aacg_tns_matrices when the records are uploaded, read by every launch that runs filters). */
 static size_t tns_record_bytes(size_t n) { return (sizeof(aacg_dev_tns) * n + 255u) & ~(size_t)255u; }
 static size_t tns_buffer_bytes(size_t n) { return n ? tns_record_bytes(n) + sizeof(double) * AACG_TNS_M_DOUBLES * n : 0; }
-static double* tns_matrices_of(const aacg_dev_tns* d_tns, size_t n) { return (double*)((char*)const_cast<aacg_dev_tns*>(d_tns) + tns_record_bytes(n)); }
+
+/* The bytes each of a batch's device buffers needs.  rv: a route the buffers serve walks the rendezvous cut; rv_sets: sets of
+ * in-launch rendezvous cells, one per launch of the batch that may be in flight at once.  The f32 spectra are what the staged
+ * kernels write, at each unit's coef_offset: h.coef_blocks blocks. */
+void batch_sizes(const aacg_engine* e, const aacg_plan_host& h, bool rv, size_t rv_sets, size_t (&want)[batch_bufs::N])
+{
+    want[batch_bufs::UNITS] = sizeof(aacg_dev_unit) * h.units.size();
+    want[batch_bufs::RUNS] = sizeof(aacg_run) * h.runs.size();
+    want[batch_bufs::TNS] = tns_buffer_bytes(h.tns.size());
+    want[batch_bufs::SCRATCH] = h.needs_scratch ? h.runs.size() * AACG_SLOT_FLOATS * sizeof(float) : 0;
+    want[batch_bufs::SPEC] = needs_spec_buffer(e, h) ? (size_t)h.coef_blocks * 1024u * sizeof(float) : 0;
+    want[batch_bufs::CCE_RUNS] = sizeof(aacg_run) * h.cce_runs.size();
+    want[batch_bufs::CCE_JOBS] = sizeof(aacg_couple_job) * h.couple_jobs.size();
+    want[batch_bufs::CCE_GAINS] = sizeof(float) * h.gains.size();
+    want[batch_bufs::CCE_SIDE] = (size_t)h.side_blocks * 4096u;
+    want[batch_bufs::RV_RUNS] = rv ? sizeof(aacg_run) * h.runs_rv.size() : 0;
+    want[batch_bufs::RV_LINKS] = rv ? sizeof(aacg_rv_link) * h.links_rv.size() : 0;
+    want[batch_bufs::RV_DATA] = rv ? rv_sets * sizeof(float) * AACG_RV_DATA_FLOATS * (size_t)h.n_links_rv : 0;
+    want[batch_bufs::RV_STATE] = rv ? rv_sets * sizeof(unsigned long long) * AACG_RV_STATE_WORDS * (size_t)h.n_links_rv : 0;
+}
+
+/* The planner's tables into buffers of at least batch_sizes' bytes, in order on stream s: unit records, run tables, TNS records
+ * (their matrices made behind them on the device), coupling side info.  zero_state, first: the rendezvous state words start
+ * from zero (they count only with a launch's epoch in them, but a buffer fresh from hipMalloc or the free list may hold another's). */
+int batch_upload(aacg_engine* e, batch_bufs& b, const aacg_plan_host& h, const size_t (&want)[batch_bufs::N], bool zero_state, hipStream_t s)
+{
+    if (zero_state && want[batch_bufs::RV_STATE])
+        HIP_TRY(e, hipMemsetAsync(b.rv_state(), 0, want[batch_bufs::RV_STATE], s), AACG_ERR_NO_DEVICE);
+    auto up = [&](void* dst, const void* src, size_t n) { return !n || hip_ok(e, hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s), "upload batch tables"); };
+    const size_t n_tns = h.tns.size();
+    b.tns_m = n_tns ? (double*)((char*)b.p[batch_bufs::TNS] + tns_record_bytes(n_tns)) : nullptr;
+    if (!up(b.units(), h.units.data(), want[batch_bufs::UNITS]) || !up(b.runs(), h.runs.data(), want[batch_bufs::RUNS]) ||
+        !up(b.tns(), h.tns.data(), sizeof(aacg_dev_tns) * n_tns))
+        return AACG_ERR_NO_DEVICE;
+    if (n_tns) aacg_tns_matrices_launch(b.tns(), b.tns_m, (uint32_t)n_tns, s);
+    if (!up(b.cce_runs(), h.cce_runs.data(), want[batch_bufs::CCE_RUNS]) || !up(b.cce_jobs(), h.couple_jobs.data(), want[batch_bufs::CCE_JOBS]) ||
+        !up(b.cce_gains(), h.gains.data(), want[batch_bufs::CCE_GAINS]) ||
+        !up(b.rv_runs(), h.runs_rv.data(), want[batch_bufs::RV_RUNS]) || !up(b.rv_links(), h.links_rv.data(), want[batch_bufs::RV_LINKS]))
+        return AACG_ERR_NO_DEVICE;
+    return AACG_OK;
+}
 
 /* what a pipelined launch adds to the rendezvous arguments: the cross-launch cells, the epoch its input state carries, and
  * which of the plan's two sets of in-launch cells it uses (overlapping launches must not share one) */
 struct xl_args { bool on; unsigned long long epoch_in; int set; int trace_part = 0; };   /* trace_part: which quarter of the profiling buffer this launch stamps */
 
-/* enqueue the launches of route R for a planned batch (device pointers) */
-int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units, const aacg_run* d_runs, const aacg_dev_tns* d_tns,
-               float* d_scratch, float* d_spec, const cce_bufs& cb, const rv_bufs& rvb, const aacg_plan_host& h, const void* d_coeffs, const aacg_band_meta* d_meta,
-               void* d_pcm, int flip, hipStream_t s, const xl_args& xl, unsigned long long* epoch_out, hipEvent_t stop = nullptr)
+/* enqueue the launches of route R for a planned batch: its unit records d_units (a plan's current set), its other buffers b */
+int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units, const batch_bufs& b, const aacg_plan_host& h, const void* d_coeffs,
+               const aacg_band_meta* d_meta, void* d_pcm, int flip, hipStream_t s, const xl_args& xl, unsigned long long* epoch_out, hipEvent_t stop = nullptr)
 {
     if (h.zero_fill)
         HIP_TRY(e, hipMemsetAsync(d_pcm, 0, h.pcm_floats * pcm_elem_size(e), s), AACG_ERR_NO_DEVICE);
@@ -398,26 +453,26 @@ int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units
     P.overlap = e->d_overlap; P.tab = e->d_tab; P.flip = flip;
     if (R.rv) {
         const size_t n_runs = h.runs_rv.size(), n_links = h.n_links_rv;
-        P.runs = rvb.runs; P.n_runs = (int32_t)n_runs;
+        P.runs = b.rv_runs(); P.n_runs = (int32_t)n_runs;
         aacg_rv_args V;
         std::memset(&V, 0, sizeof V);
-        V.links = rvb.links;
-        V.state = rvb.state ? rvb.state + (size_t)xl.set * AACG_RV_STATE_WORDS * n_links : nullptr;
-        V.data = rvb.data ? rvb.data + (size_t)xl.set * AACG_RV_DATA_FLOATS * n_links : nullptr;
+        V.links = b.rv_links();
+        V.state = b.rv_state() ? b.rv_state() + (size_t)xl.set * AACG_RV_STATE_WORDS * n_links : nullptr;
+        V.data = b.rv_data() ? b.rv_data() + (size_t)xl.set * AACG_RV_DATA_FLOATS * n_links : nullptr;
         V.epoch = ++e->rv_epoch;
         if (xl.on) { V.xl_cells = e->d_xl_cells; V.xl_head = e->d_xl_head; V.epoch_in = xl.epoch_in; }
         if (R.run_key & AACG_RK_EX) {                    /* optional stages inside the run kernel */
-            P.tns = h.any_tns ? d_tns : nullptr; P.pns = e->d_pns;
-            if (h.any_tns) aacg_set_tns_m(&P, tns_matrices_of(d_tns, h.tns.size()));
+            P.tns = h.any_tns ? b.tns() : nullptr; P.pns = e->d_pns;
+            if (h.any_tns) aacg_set_tns_m(&P, b.tns_m);
         }
         if (epoch_out) *epoch_out = V.epoch;
         P.ablate = e->d_trace ? e->ablate : (e->ablate & ~16);                                       /* profiling builds only (0 in the library that ships) */
         if (e->d_trace) P.spec_out = (float*)e->d_trace + (size_t)xl.trace_part * (1u << 18);       /* ... the last four launches keep their stamps */
         return launch_kernel(e, aacg_find_run_kernel(R.run_key), (unsigned)n_runs, s, P, &V, stop);
     }
-    P.runs = d_runs; P.n_runs = (int32_t)h.runs.size();
-    P.tns = h.any_tns ? d_tns : nullptr;
-    P.scratch = h.needs_scratch ? d_scratch : nullptr;
+    P.runs = b.runs(); P.n_runs = (int32_t)h.runs.size();
+    P.tns = h.any_tns ? b.tns() : nullptr;
+    P.scratch = h.needs_scratch ? b.scratch() : nullptr;
     P.ablate = e->d_trace ? e->ablate : (e->ablate & ~16);
     if (e->d_trace) P.spec_out = (float*)e->d_trace;
     auto couple = [&](int point) {                      /* the coupling launches of one coupling point, round by round */
@@ -425,8 +480,8 @@ int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units
             const uint32_t first = h.couple_first[(size_t)point * h.couple_rounds + r], last = h.couple_first[(size_t)point * h.couple_rounds + r + 1];
             if (last <= first) continue;
             aacg_couple_params Q;
-            Q.jobs = cb.jobs + first; Q.n_jobs = (int32_t)(last - first); Q.units = d_units; Q.meta = d_meta; Q.tab = e->d_tab;
-            Q.gains = cb.gains; Q.spec = d_spec; Q.side = cb.side; Q.pcm = (float*)d_pcm; Q.reserved = 0;
+            Q.jobs = b.cce_jobs() + first; Q.n_jobs = (int32_t)(last - first); Q.units = d_units; Q.meta = d_meta; Q.tab = e->d_tab;
+            Q.gains = b.cce_gains(); Q.spec = b.spec(); Q.side = b.cce_side(); Q.pcm = (float*)d_pcm; Q.reserved = 0;
             aacg_couple_launch(point == AACG_CCE_AFTER_IMDCT, s, Q);
         }
     };
@@ -435,37 +490,37 @@ int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units
          * then decoder.js:258-266 / 304-316 in stages: coupling before TNS, the TNS filters, coupling after TNS — each its
          * own small launch, in place.  (Independent coupling alone leaves the spectral route as it is.) */
         float* trace_or_null = P.spec_out;
-        P.spec_out = d_spec; P.pns = e->d_pns; P.tns = nullptr;
+        P.spec_out = b.spec(); P.pns = e->d_pns; P.tns = nullptr;
         if (R.stage_quant) aacg_spectral_ex_launch(true, (int)h.units.size(), s, P);
-        else HIP_TRY(e, hipMemcpyAsync(d_spec, d_coeffs, (size_t)h.coef_blocks * 4096u, hipMemcpyDeviceToDevice, s), AACG_ERR_NO_DEVICE);
+        else HIP_TRY(e, hipMemcpyAsync(b.spec(), d_coeffs, (size_t)h.coef_blocks * 4096u, hipMemcpyDeviceToDevice, s), AACG_ERR_NO_DEVICE);
         couple(AACG_CCE_BEFORE_TNS);
         if (h.any_tns) {
-            P.coeffs = d_spec; P.meta = nullptr; P.tns = d_tns;
-            { aacg_kparams Q = P; aacg_set_tns_m(&Q, tns_matrices_of(d_tns, h.tns.size())); aacg_spectral_ex_launch(false, (int)h.units.size(), s, Q); }
+            P.coeffs = b.spec(); P.meta = nullptr; P.tns = b.tns();
+            { aacg_kparams Q = P; aacg_set_tns_m(&Q, b.tns_m); aacg_spectral_ex_launch(false, (int)h.units.size(), s, Q); }
         }
         couple(AACG_CCE_AFTER_TNS);
-        P.spec_out = trace_or_null; P.coeffs = d_spec; P.meta = nullptr; P.tns = nullptr;
+        P.spec_out = trace_or_null; P.coeffs = b.spec(); P.meta = nullptr; P.tns = nullptr;
     } else if (R.stage == AACG_STAGE_SPECTRAL_EX) {
         /* the optional stages first, as a launch of their own that leaves f32 spectra, which the f32 run kernel takes from there */
         float* trace_or_null = P.spec_out;
-        P.spec_out = d_spec; P.pns = e->d_pns;
-        { aacg_kparams Q = P; if (h.any_tns) aacg_set_tns_m(&Q, tns_matrices_of(d_tns, h.tns.size())); aacg_spectral_ex_launch(R.stage_quant, (int)h.units.size(), s, Q); }
-        P.spec_out = trace_or_null; P.coeffs = d_spec; P.meta = nullptr; P.tns = nullptr;
+        P.spec_out = b.spec(); P.pns = e->d_pns;
+        { aacg_kparams Q = P; if (h.any_tns) aacg_set_tns_m(&Q, b.tns_m); aacg_spectral_ex_launch(R.stage_quant, (int)h.units.size(), s, Q); }
+        P.spec_out = trace_or_null; P.coeffs = b.spec(); P.meta = nullptr; P.tns = nullptr;
     } else if (R.has_run && (R.run_key & AACG_RK_EX)) {
         P.pns = e->d_pns;                                /* optional stages (noise bands, TNS filters) inside the run kernel: one launch */
-        if (h.any_tns) aacg_set_tns_m(&P, tns_matrices_of(d_tns, h.tns.size()));
+        if (h.any_tns) aacg_set_tns_m(&P, b.tns_m);
     }
     int rc = AACG_OK;
     auto side_pass = [&]() {                            /* the independently switched coupling elements' own filterbank pass */
         aacg_kparams C = P;
-        C.runs = cb.runs; C.n_runs = (int32_t)h.cce_runs.size(); C.pcm = cb.side; C.scratch = nullptr;
+        C.runs = b.cce_runs(); C.n_runs = (int32_t)h.cce_runs.size(); C.pcm = b.cce_side(); C.scratch = nullptr;
         return launch_kernel(e, aacg_find_run_kernel(R.side_key), (unsigned)h.cce_runs.size(), s, C, nullptr);
     };
     if (R.has_side && R.side_first && (rc = side_pass())) return rc;
     if (R.has_run) {
         /* independent coupling in the targets' epilogues: the run kernel adds gain * side where it forms the PCM — no
          * read-modify-write pass over the interleaved PCM */
-        if (R.run_key & AACG_RK_CPL) aacg_set_cpl(&P, cb.jobs + h.fused_first, cb.gains, cb.side);
+        if (R.run_key & AACG_RK_CPL) aacg_set_cpl(&P, b.cce_jobs() + h.fused_first, b.cce_gains(), b.cce_side());
         if ((rc = launch_kernel(e, aacg_find_run_kernel(R.run_key), (unsigned)h.runs.size(), s, P, nullptr))) return rc;
     }
     if (R.has_side && !R.side_first && (rc = side_pass())) return rc;
@@ -726,9 +781,8 @@ void aacg_destroy(aacg_engine* e)
     for (hipStream_t st : e->pipe.stream) if (st) (void)hipStreamDestroy(st);
     if (e->d_overlap) (void)hipFree(e->d_overlap);
     for (auto& sl : e->slot) {
-        for (void* p : {sl.d_units, sl.d_runs, sl.d_coeffs, sl.d_meta, sl.d_tns, sl.d_scratch, sl.d_spec, sl.d_pcm}) if (p) (void)hipFree(p);
-        for (void* p : sl.d_cce) if (p) (void)hipFree(p);
-        for (void* p : sl.d_rv) if (p) (void)hipFree(p);
+        for (void* p : sl.b.p) if (p) (void)hipFree(p);
+        for (void* p : {sl.d_coeffs, sl.d_meta, sl.d_pcm}) if (p) (void)hipFree(p);
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_pcm) (void)hipHostFree(sl.h_pcm);
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -829,56 +883,45 @@ int aacg_plan_create_tns(aacg_engine* e, const aacg_unit_desc* units, uint32_t n
     return aacg_plan_create_ex(e, units, n_units, tns, n_tns, nullptr, 0, out);
 }
 
+/* The host side of a batch, for plans and the host-buffer path alike: REFERENCE modes drop the TNS and coupling side info,
+ * aacg_plan_build, and the refusal of noise bands that an AACG_PNS_REFERENCE engine cannot decode. */
+static int plan_host(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units, const aacg_tns_info* tns, uint32_t n_tns,
+                     const aacg_cce_info* cce, uint32_t n_cce, aacg_plan_host* h)
+{
+    if (e->cfg.tns_mode != AACG_TNS_SPEC) { tns = nullptr; n_tns = 0; }   /* REFERENCE mode: TNS is the identity */
+    if (e->cfg.cce_mode != AACG_CCE_SPEC) { cce = nullptr; n_cce = 0; }   /* REFERENCE mode: a coupling element in the batch is refused */
+    const int rc = aacg_plan_build(units, n_units, e->cfg.sample_index, e->cfg.max_streams, e->cfg.max_channels,
+                                   e->parity.data(), h, &e->err, tns, n_tns, cce, n_cce);
+    if (rc) return rc;
+    if (h->any_pns && e->cfg.pns_mode != AACG_PNS_SPEC) {
+        e->err = "a unit carries AACG_UNIT_HAS_PNS: NOISE_BT bands are not decodable by the reference either (AACG_PNS_SPEC engines fill them)";
+        return AACG_ERR_UNSUPPORTED;
+    }
+    return AACG_OK;
+}
+
 int aacg_plan_create_ex(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units,
                         const aacg_tns_info* tns, uint32_t n_tns, const aacg_cce_info* cce, uint32_t n_cce, aacg_plan** out)
 {
     if (!e || !units || !n_units || !out) return AACG_ERR_INVALID_ARG;
-    if (e->cfg.tns_mode != AACG_TNS_SPEC) { tns = nullptr; n_tns = 0; }   /* REFERENCE mode: TNS is the identity */
-    if (e->cfg.cce_mode != AACG_CCE_SPEC) { cce = nullptr; n_cce = 0; }   /* REFERENCE mode: a coupling element in the batch is refused */
     *out = nullptr;
     aacg_plan* p = new (std::nothrow) aacg_plan();
     if (!p) return AACG_ERR_OUT_OF_MEMORY;
     p->e = e;
     p->n_units = n_units;
-    int rc = aacg_plan_build(units, n_units, e->cfg.sample_index, e->cfg.max_streams, e->cfg.max_channels,
-                             e->parity.data(), &p->h, &e->err, tns, n_tns, cce, n_cce);
+    const int rc = plan_host(e, units, n_units, tns, n_tns, cce, n_cce, &p->h);
     if (rc) { delete p; return rc; }
-    if (p->h.any_pns && e->cfg.pns_mode != AACG_PNS_SPEC) {
-        e->err = "a unit carries AACG_UNIT_HAS_PNS: NOISE_BT bands are not decodable by the reference either (AACG_PNS_SPEC engines fill them)";
-        delete p;
-        return AACG_ERR_UNSUPPORTED;
-    }
-    const size_t ub = sizeof(aacg_dev_unit) * n_units, rb = sizeof(aacg_run) * p->h.runs.size();
-    const size_t xb = needs_spec_buffer(e, p->h) ? (size_t)p->h.coef_blocks * 1024u * sizeof(float) : 0;
-    const size_t tb = tns_buffer_bytes(p->h.tns.size());
-    const size_t sb = p->h.needs_scratch ? p->h.runs.size() * AACG_SLOT_FLOATS * sizeof(float) : 0;
-    const size_t cb[4] = {sizeof(aacg_run) * p->h.cce_runs.size(), sizeof(aacg_couple_job) * p->h.couple_jobs.size(),
-                          sizeof(float) * p->h.gains.size(), (size_t)p->h.side_blocks * 4096u};
     bool ok = hip_ok(e, hipSetDevice(e->cfg.device_ordinal), "hipSetDevice") &&
               hip_ok(e, hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming), "hipEventCreate") &&
               hip_ok(e, hipEventCreateWithFlags(&p->last_use, hipEventDisableTiming), "hipEventCreate");
     /* the rendezvous cut of the chains, for plans that can take it (serially: long chains; through the pipeline: every plain
-     * batch): run table, links, and a set of in-launch cells per pipeline stream — overlapping launches of the plan must not share one */
-    const bool rvp = route_of(e, p->h, true).rv;
-    const size_t rvs[4] = {rvp ? sizeof(aacg_run) * p->h.runs_rv.size() : 0, rvp ? sizeof(aacg_rv_link) * p->h.links_rv.size() : 0,
-                           rvp ? (size_t)AACG_PIPE_STREAMS * sizeof(unsigned long long) * AACG_RV_STATE_WORDS * (size_t)p->h.n_links_rv : 0,
-                           rvp ? (size_t)AACG_PIPE_STREAMS * sizeof(float) * AACG_RV_DATA_FLOATS * (size_t)p->h.n_links_rv : 0};
-    const size_t want[AACG_PLAN_BUFFERS] = {ub, rb, tb, sb, xb, cb[0], cb[1], cb[2], cb[3], rvs[0], rvs[1], rvs[2], rvs[3]};
-    void** const slot[AACG_PLAN_BUFFERS] = {(void**)&p->d_units, (void**)&p->d_runs, (void**)&p->d_tns, (void**)&p->d_scratch, (void**)&p->d_spec,
-                             &p->d_cce[0], &p->d_cce[1], &p->d_cce[2], &p->d_cce[3], &p->d_rv[0], &p->d_rv[1], &p->d_rv[2], &p->d_rv[3]};
-    const void* const src[AACG_PLAN_BUFFERS] = {p->h.units.data(), p->h.runs.data(), p->h.tns.data(), nullptr, nullptr,
-                                 p->h.cce_runs.data(), p->h.couple_jobs.data(), p->h.gains.data(), nullptr,
-                                 p->h.runs_rv.data(), p->h.links_rv.data(), nullptr, nullptr};
-    for (int i = 0; i < AACG_PLAN_BUFFERS && ok; i++) {
-        if (!want[i]) continue;
-        *slot[i] = pool_take(e, want[i], &p->bytes[i]);
-        ok = *slot[i] != nullptr &&
-             (!src[i] || hip_ok(e, hipMemcpyAsync(*slot[i], src[i], i == 2 ? sizeof(aacg_dev_tns) * p->h.tns.size() : want[i], hipMemcpyHostToDevice, e->stream), "upload plan tables"));
-        if (ok && i == 2) aacg_tns_matrices_launch(p->d_tns, tns_matrices_of(p->d_tns, p->h.tns.size()), (uint32_t)p->h.tns.size(), e->stream);   /* behind the records, once */
-        /* rendezvous state words count only with a launch's epoch in them; a recycled or fresh buffer starts from zero all the same */
-        if (ok && i == 11) ok = hip_ok(e, hipMemsetAsync(*slot[i], 0, want[i], e->stream), "zero rendezvous state");
-    }
-    ok = ok && hip_ok(e, hipEventRecord(p->uploaded, e->stream), "hipEventRecord");
+     * batch), with a set of in-launch cells per pipeline stream — overlapping launches of the plan must not share one */
+    size_t want[batch_bufs::N];
+    batch_sizes(e, p->h, route_of(e, p->h, true).rv, AACG_PIPE_STREAMS, want);
+    for (int i = 0; i < batch_bufs::N && ok; i++)
+        if (want[i]) ok = (p->b.p[i] = pool_take(e, want[i], &p->b.bytes[i])) != nullptr;
+    ok = ok && batch_upload(e, p->b, p->h, want, true, e->stream) == AACG_OK &&
+         hip_ok(e, hipEventRecord(p->uploaded, e->stream), "hipEventRecord");
     if (!ok) {
         aacg_plan_destroy(p);
         return AACG_ERR_OUT_OF_MEMORY;
@@ -909,9 +952,7 @@ void aacg_plan_destroy(aacg_plan* p)
         delete p;
         return;
     }
-    void* const ptr[AACG_PLAN_BUFFERS] = {p->d_units, p->d_runs, p->d_tns, p->d_scratch, p->d_spec, p->d_cce[0], p->d_cce[1], p->d_cce[2], p->d_cce[3],
-                           p->d_rv[0], p->d_rv[1], p->d_rv[2], p->d_rv[3]};
-    for (int i = 0; i < AACG_PLAN_BUFFERS; i++) pool_give(e, ptr[i], p->bytes[i]);
+    for (int i = 0; i < batch_bufs::N; i++) pool_give(e, p->b.p[i], p->b.bytes[i]);
     if (e->pipe.plan == p) e->pipe.plan = nullptr;
     delete p;
 }
@@ -928,24 +969,41 @@ static int plan_check_parity(aacg_engine* e, const aacg_plan* p)
     return AACG_OK;
 }
 
-/* every chain of the plan has moved on by one overlap buffer */
-static void plan_advance(aacg_engine* e, aacg_plan* p)
+/* every chain of a decoded batch has moved on by one overlap buffer; returns the engine's new epoch */
+static uint64_t parity_advance(aacg_engine* e, const aacg_plan_host& h)
 {
-    for (const aacg_chain& c : p->h.chains)
+    for (const aacg_chain& c : h.chains)
         for (int k = 0; k < c.n_ch; k++) {
             uint8_t& b = e->parity[(size_t)c.stream * (size_t)e->cfg.max_channels + c.channel + k];
             b = (uint8_t)((b + 1) % AACG_OV_BUFFERS);
         }
+    return ++e->epoch;
+}
+
+static void plan_advance(aacg_engine* e, aacg_plan* p)
+{
     p->launches++;
-    p->seen_epoch = ++e->epoch;
+    p->seen_epoch = parity_advance(e, p->h);
 }
 
 /* the device buffers a route needs are the ones the plan was made with (aacg_debug_set_route may have changed since) */
 static int plan_check_route(aacg_engine* e, const aacg_plan* p, const aacg_route& R)
 {
-    if ((R.rv && !p->d_rv[0]) || (!R.rv && R.has_run && !p->d_runs) || (R.stage != AACG_STAGE_NONE && !p->d_spec)) {
+    if ((R.rv && !p->b.rv_runs()) || (!R.rv && R.has_run && !p->b.runs()) || (R.stage != AACG_STAGE_NONE && !p->b.spec())) {
         e->err = "the plan was made for another route (aacg_debug_set_route changed since)";
         return AACG_ERR_STALE_PLAN;
+    }
+    return AACG_OK;
+}
+
+/* The plan's previous launch ran on ANOTHER stream, not through the pipeline (pipe_join orders those): work on s that continues
+ * its overlap state or reuses its buffers is ordered behind it on the device (an event only when the stream changes: per launch
+ * it would cost 3 us) */
+static int plan_follow(aacg_engine* e, aacg_plan* p, hipStream_t s)
+{
+    if (p->used && p->last_stream != s && !p->last_pipelined) {
+        HIP_TRY(e, hipEventRecord(p->last_use, p->last_stream), AACG_ERR_NO_DEVICE);
+        HIP_TRY(e, hipStreamWaitEvent(s, p->last_use, 0), AACG_ERR_NO_DEVICE);
     }
     return AACG_OK;
 }
@@ -965,19 +1023,9 @@ int aacg_decode_device(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const
     note_stream(e, s);
     if (!p->used) HIP_TRY(e, hipStreamWaitEvent(s, p->uploaded, 0), AACG_ERR_NO_DEVICE);
     /* pipelined launches in flight (of this plan or of another: the caller orders PLANS, the engine its own streams) first */
-    if ((rc = pipe_join(e, s))) return rc;
-    /* the plan's previous launch ran on ANOTHER stream: this one continues its overlap state, reuses its scratch areas and
-     * rendezvous cells, so it is ordered behind it on the device (an event only when the stream changes: per launch it
-     * would cost 3 us) */
-    if (p->used && p->last_stream != s && !p->last_pipelined) {
-        HIP_TRY(e, hipEventRecord(p->last_use, p->last_stream), AACG_ERR_NO_DEVICE);
-        HIP_TRY(e, hipStreamWaitEvent(s, p->last_use, 0), AACG_ERR_NO_DEVICE);
-    }
-    const cce_bufs cb = {(const aacg_run*)p->d_cce[0], (const aacg_couple_job*)p->d_cce[1], (const float*)p->d_cce[2], (float*)p->d_cce[3]};
-    const rv_bufs rvb = {(const aacg_run*)p->d_rv[0], (const aacg_rv_link*)p->d_rv[1], (unsigned long long*)p->d_rv[2], (float*)p->d_rv[3]};
+    if ((rc = pipe_join(e, s)) || (rc = plan_follow(e, p, s))) return rc;
     const xl_args serial = {false, 0ull, 0};
-    rc = launch_run(e, R, p->units_now(), p->d_runs, p->d_tns, p->d_scratch, p->d_spec, cb, rvb, p->h, d_coeffs, d_meta, d_pcm,
-                    (int)(p->launches % AACG_OV_BUFFERS), s, serial, nullptr);
+    rc = launch_run(e, R, p->units_now(), p->b, p->h, d_coeffs, d_meta, d_pcm, (int)(p->launches % AACG_OV_BUFFERS), s, serial, nullptr);
     if (rc) return rc;
     p->last_stream = s;
     p->used = true;
@@ -1111,11 +1159,8 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
             }
         }
     } else if (!follows) {
-        if ((rc = pipe_join(e, s))) return rc;
-        if (p->used && !p->last_pipelined) {
-            HIP_TRY(e, hipEventRecord(p->last_use, p->last_stream), AACG_ERR_NO_DEVICE);
-            HIP_TRY(e, hipStreamWaitEvent(s, p->last_use, 0), AACG_ERR_NO_DEVICE);
-        }
+        /* (a stream the plan last ran on outside the pipeline is never one of the pipeline's) */
+        if ((rc = pipe_join(e, s)) || (rc = plan_follow(e, p, s))) return rc;
         if (e->last_kernel) HIP_TRY(e, hipStreamWaitEvent(s, e->last_kernel, 0), AACG_ERR_NO_DEVICE);   /* the host-buffer path's batches */
     }
     if (!p->used) HIP_TRY(e, hipStreamWaitEvent(s, p->uploaded, 0), AACG_ERR_NO_DEVICE);
@@ -1126,8 +1171,6 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
         HIP_TRY(e, hipEventRecord(pp.fork, s), AACG_ERR_NO_DEVICE);
         for (hipStream_t ps : pp.stream) if (ps != s) HIP_TRY(e, hipStreamWaitEvent(ps, pp.fork, 0), AACG_ERR_NO_DEVICE);
     }
-    const cce_bufs cb = {(const aacg_run*)p->d_cce[0], (const aacg_couple_job*)p->d_cce[1], (const float*)p->d_cce[2], (float*)p->d_cce[3]};
-    const rv_bufs rvb = {(const aacg_run*)p->d_rv[0], (const aacg_rv_link*)p->d_rv[1], (unsigned long long*)p->d_rv[2], (float*)p->d_rv[3]};
     const xl_args xl = {R.overlappable, continues ? pp.epoch : 0ull, ord.stream, (int)(pp.n & 3u)};
     unsigned long long epoch = 0;
     /* the host will wait for this one: its event rides on the dispatch itself where the route is a single launch
@@ -1139,8 +1182,7 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
     hipEvent_t const mine = (stop_mark && R.rv) ? (hipEvent_t)stop_mark : pp.mark[slot][ord.stream];
     if (ordered) pp.seen[slot][ord.stream] = mine;
     hipEvent_t bound = R.rv ? (stop_mark ? (hipEvent_t)stop_mark : (ordered ? mine : nullptr)) : nullptr;
-    rc = launch_run(e, R, p->units_now(), p->d_runs, p->d_tns, p->d_scratch, p->d_spec, cb, rvb, p->h, d_coeffs, d_meta, d_pcm,
-                    (int)(p->launches % AACG_OV_BUFFERS), s, xl, &epoch, bound);
+    rc = launch_run(e, R, p->units_now(), p->b, p->h, d_coeffs, d_meta, d_pcm, (int)(p->launches % AACG_OV_BUFFERS), s, xl, &epoch, bound);
     if (rc) return rc;
     if (ordered && bound != mine) HIP_TRY(e, hipEventRecord(mine, s), AACG_ERR_NO_DEVICE);
     if (stop_mark && bound != (hipEvent_t)stop_mark) HIP_TRY(e, hipEventRecord((hipEvent_t)stop_mark, s), AACG_ERR_NO_DEVICE);
@@ -1208,8 +1250,8 @@ int aacg_plan_set_unit_sets(aacg_engine* e, aacg_plan* p, uint32_t n_sets)
     if (!fresh) return AACG_ERR_OUT_OF_MEMORY;
     for (uint32_t k = 0; k < n_sets; k++)
         if (!hip_ok(e, hipMemcpyAsync((char*)fresh + ub * k, p->h.units.data(), ub, hipMemcpyHostToDevice, e->stream), "upload plan unit sets")) { pool_give(e, fresh, got); return AACG_ERR_NO_DEVICE; }
-    pool_give(e, p->d_units, p->bytes[0]);               /* its upload is in front of whatever takes it next on the same stream */
-    p->d_units = (aacg_dev_unit*)fresh; p->bytes[0] = got;
+    pool_give(e, p->b.p[batch_bufs::UNITS], p->b.bytes[batch_bufs::UNITS]);   /* its upload is in front of whatever takes it next on the same stream */
+    p->b.p[batch_bufs::UNITS] = fresh; p->b.bytes[batch_bufs::UNITS] = got;
     p->unit_sets = n_sets; p->cur_set = 0;
     HIP_TRY(e, hipEventRecord(p->uploaded, e->stream), AACG_ERR_NO_DEVICE);
     return AACG_OK;
@@ -1230,17 +1272,14 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
     if (p->unit_sets > 1) {
         /* a set of its own: nothing in flight reads it (the caller's word), so neither the pipeline is joined nor the plan's
          * sequence of overlapped launches ended; the next launch reads this set */
-        aacg_refresh_launch(p->d_units + (size_t)set * p->n_units, d_parsed_units, d_results, d_map, p->n_units, max_units, 1, d_refused, s);
+        aacg_refresh_launch(p->b.units() + (size_t)set * p->n_units, d_parsed_units, d_results, d_map, p->n_units, max_units, 1, d_refused, s);
         HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
         p->cur_set = set;
         return AACG_OK;
     }
     if (p->last_pipelined) { int jrc = pipe_join(e, s); if (jrc) return jrc; }
-    if (p->used && p->last_stream != s && !p->last_pipelined) {              /* the records' readers on the plan's previous stream first */
-        HIP_TRY(e, hipEventRecord(p->last_use, p->last_stream), AACG_ERR_NO_DEVICE);
-        HIP_TRY(e, hipStreamWaitEvent(s, p->last_use, 0), AACG_ERR_NO_DEVICE);
-    }
-    aacg_refresh_launch(p->d_units, d_parsed_units, d_results, d_map, p->n_units, max_units, 1, d_refused, s);
+    if (const int frc = plan_follow(e, p, s)) return frc;                      /* the records' readers on the plan's previous stream first */
+    aacg_refresh_launch(p->b.units(), d_parsed_units, d_results, d_map, p->n_units, max_units, 1, d_refused, s);
     HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
     p->last_stream = s;
     p->used = true;
@@ -1259,16 +1298,13 @@ int aacg_plan_refresh_units(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* 
     HIP_TRY(e, hipStreamWaitEvent(s, p->uploaded, 0), AACG_ERR_NO_DEVICE);
     /* the plan's previous launch on ANOTHER stream may still be reading the records this copy overwrites: order behind it */
     if (p->last_pipelined) { int jrc = pipe_join(e, s); if (jrc) return jrc; }
-    if (p->used && p->last_stream != s && !p->last_pipelined) {
-        HIP_TRY(e, hipEventRecord(p->last_use, p->last_stream), AACG_ERR_NO_DEVICE);
-        HIP_TRY(e, hipStreamWaitEvent(s, p->last_use, 0), AACG_ERR_NO_DEVICE);
-    }
+    if ((rc = plan_follow(e, p, s))) return rc;
     /* pageable source: the runtime stages it before returning, so the host copy may change again right away; in stream
      * order behind the launches that read the previous records */
-    HIP_TRY(e, hipMemcpyAsync(p->d_units, p->h.units.data(), sizeof(aacg_dev_unit) * p->h.units.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
+    HIP_TRY(e, hipMemcpyAsync(p->b.units(), p->h.units.data(), sizeof(aacg_dev_unit) * p->h.units.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
     if (p->h.runs_moved) {                                  /* the batch's blocks lie elsewhere: the run tables' copies of the offsets with them */
-        if (p->d_runs) HIP_TRY(e, hipMemcpyAsync(p->d_runs, p->h.runs.data(), sizeof(aacg_run) * p->h.runs.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
-        if (p->d_rv[0]) HIP_TRY(e, hipMemcpyAsync(p->d_rv[0], p->h.runs_rv.data(), sizeof(aacg_run) * p->h.runs_rv.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
+        if (p->b.runs()) HIP_TRY(e, hipMemcpyAsync(p->b.runs(), p->h.runs.data(), sizeof(aacg_run) * p->h.runs.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
+        if (p->b.rv_runs()) HIP_TRY(e, hipMemcpyAsync(p->b.rv_runs(), p->h.runs_rv.data(), sizeof(aacg_run) * p->h.runs_rv.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
     }
     p->last_stream = s;
     p->used = true;
@@ -1399,12 +1435,8 @@ int aacg_submit_ex(aacg_engine* e, const aacg_batch* batch, uint64_t* ticket)
     const aacg_unit_desc* units = batch->units; const uint32_t n_units = batch->n_units;
     const void* coeffs = batch->coeffs; const uint32_t n_coef_blocks = batch->n_coef_blocks;
     const aacg_band_meta* meta = batch->meta; const uint32_t n_meta = batch->n_meta;
-    const aacg_tns_info* tns = batch->tns; uint32_t n_tns = batch->n_tns;
-    const aacg_cce_info* cce = batch->cce; uint32_t n_cce = batch->n_cce;
     void* pcm_out = batch->pcm_out; const size_t n_pcm_floats = batch->n_pcm_floats;
     if (!units || !n_units || !coeffs || !pcm_out || !ticket) return AACG_ERR_INVALID_ARG;
-    if (e->cfg.tns_mode != AACG_TNS_SPEC) { tns = nullptr; n_tns = 0; }   /* REFERENCE mode: TNS is the identity */
-    if (e->cfg.cce_mode != AACG_CCE_SPEC) { cce = nullptr; n_cce = 0; }   /* REFERENCE mode: a coupling element in the batch is refused */
     const bool quant = e->cfg.input_kind == AACG_INPUT_QUANT_I16;
     if (quant && !meta) { e->err = "QUANT_I16 engine needs band meta"; return AACG_ERR_INVALID_ARG; }
     if (e->cfg.max_batch_units > 0 && (int)n_units > e->cfg.max_batch_units) {
@@ -1423,8 +1455,7 @@ int aacg_submit_ex(aacg_engine* e, const aacg_batch* batch, uint64_t* ticket)
         HIP_TRY(e, hipEventCreateWithFlags(&sl.kernel_done, hipEventDisableTiming), AACG_ERR_NO_DEVICE);
     }
 
-    int rc = aacg_plan_build(units, n_units, e->cfg.sample_index, e->cfg.max_streams, e->cfg.max_channels,
-                             e->parity.data(), &sl.h, &e->err, tns, n_tns, cce, n_cce);
+    int rc = plan_host(e, units, n_units, batch->tns, batch->n_tns, batch->cce, batch->n_cce, &sl.h);
     if (rc) return rc;
     const aacg_plan_host& h = sl.h;
     if (h.coef_blocks > n_coef_blocks || (quant && h.meta_blocks > n_meta) || h.pcm_floats > n_pcm_floats) {
@@ -1450,43 +1481,27 @@ int aacg_submit_ex(aacg_engine* e, const aacg_batch* batch, uint64_t* ticket)
                         }
                     }
             }
-        if (h.any_pns && e->cfg.pns_mode != AACG_PNS_SPEC) {
-            e->err = "a unit carries AACG_UNIT_HAS_PNS: NOISE_BT bands are not decodable by the reference either";
-            return AACG_ERR_UNSUPPORTED;
-        }
     }
 
-    const size_t ub = sizeof(aacg_dev_unit) * h.units.size(), rb = sizeof(aacg_run) * h.runs.size();
-    const size_t tb = tns_buffer_bytes(h.tns.size());
-    const size_t sb = h.needs_scratch ? h.runs.size() * AACG_SLOT_FLOATS * sizeof(float) : 0;
-    const size_t xb = needs_spec_buffer(e, h) ? (size_t)n_coef_blocks * 1024u * sizeof(float) : 0;
-    const size_t ccb[4] = {sizeof(aacg_run) * h.cce_runs.size(), sizeof(aacg_couple_job) * h.couple_jobs.size(),
-                           sizeof(float) * h.gains.size(), (size_t)h.side_blocks * 4096u};
-    const void* const cce_src[4] = {h.cce_runs.data(), h.couple_jobs.data(), h.gains.data(), nullptr};
-    for (int i = 0; i < 4; i++) if (ccb[i] && (rc = grow(e, &sl.d_cce[i], &sl.cce_cap[i], ccb[i]))) return rc;
+    /* the batch's tables and work areas, grown on demand (the launches are serial: one set of rendezvous cells) and uploaded on
+     * the slot's own stream, in front of the launch that reads them; so is the zeroing of a state buffer made anew (a plain
+     * hipMemset is ordered on the null stream, which a non-blocking stream does not wait for) */
+    hipStream_t s = sl.stream;
     const aacg_route R = route_of(e, h, false);
-    const bool rvp = R.rv;
-    const size_t rvs[4] = {rvp ? sizeof(aacg_run) * h.runs_rv.size() : 0, rvp ? sizeof(aacg_rv_link) * h.links_rv.size() : 0,
-                           rvp ? sizeof(unsigned long long) * AACG_RV_STATE_WORDS * (size_t)h.n_links_rv : 0,
-                           rvp ? sizeof(float) * AACG_RV_DATA_FLOATS * (size_t)h.n_links_rv : 0};
-    for (int i = 0; i < 4; i++) {
-        const size_t had = sl.rv_cap[i];
-        if (rvs[i] && (rc = grow(e, &sl.d_rv[i], &sl.rv_cap[i], rvs[i]))) return rc;
-        /* a new state buffer starts from zero — on the slot's own stream, in front of the launch that reads it (a plain
-         * hipMemset is ordered on the null stream, which a non-blocking stream does not wait for) */
-        if (i == 2 && sl.rv_cap[i] != had) HIP_TRY(e, hipMemsetAsync(sl.d_rv[i], 0, sl.rv_cap[i], sl.stream), AACG_ERR_NO_DEVICE);
-    }
+    size_t want[batch_bufs::N];
+    batch_sizes(e, h, R.rv, 1, want);
+    const size_t had_state = sl.b.bytes[batch_bufs::RV_STATE];
+    for (int i = 0; i < batch_bufs::N; i++) if ((rc = grow(e, &sl.b.p[i], &sl.b.bytes[i], want[i]))) return rc;
+    if ((rc = batch_upload(e, sl.b, h, want, sl.b.bytes[batch_bufs::RV_STATE] != had_state, s))) return rc;
     const size_t cb = (size_t)n_coef_blocks * 1024u * coef_elem_size(e);
     const size_t mb = quant ? (size_t)n_meta * sizeof(aacg_band_meta) : 0;
     const size_t pb = h.pcm_floats * pcm_elem_size(e);
-    if ((rc = grow(e, &sl.d_units, &sl.units_cap, ub)) || (rb && (rc = grow(e, &sl.d_runs, &sl.runs_cap, rb))) ||
-        (rc = grow(e, &sl.d_coeffs, &sl.coeffs_cap, cb)) || (quant && (rc = grow(e, &sl.d_meta, &sl.meta_cap, mb))) ||
-        (tb && (rc = grow(e, &sl.d_tns, &sl.tns_cap, tb))) || (sb && (rc = grow(e, &sl.d_scratch, &sl.scratch_cap, sb))) || (xb && (rc = grow(e, &sl.d_spec, &sl.spec_cap, xb))) || (rc = grow(e, &sl.d_pcm, &sl.pcm_cap, pb)))
+    if ((rc = grow(e, &sl.d_coeffs, &sl.coeffs_cap, cb)) || (quant && (rc = grow(e, &sl.d_meta, &sl.meta_cap, mb))) ||
+        (rc = grow(e, &sl.d_pcm, &sl.pcm_cap, pb)))
         return rc;
 
     /* Ordinary (pageable) caller memory goes through the slot's page-locked staging buffers (one host
      * memcpy each way, then truly asynchronous DMA); page-locked caller memory is used in place. */
-    hipStream_t s = sl.stream;
     const void* src_coeffs = coeffs;
     const void* src_meta = meta;
     if (!is_pinned(coeffs) || (quant && !is_pinned(meta))) {
@@ -1505,15 +1520,6 @@ int aacg_submit_ex(aacg_engine* e, const aacg_batch* batch, uint64_t* ticket)
         sl.user_pcm = pcm_out;
         sl.user_pcm_bytes = pb;
     }
-    HIP_TRY(e, hipMemcpyAsync(sl.d_units, h.units.data(), ub, hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
-    if (rb) HIP_TRY(e, hipMemcpyAsync(sl.d_runs, h.runs.data(), rb, hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
-    if (rvs[0]) HIP_TRY(e, hipMemcpyAsync(sl.d_rv[0], h.runs_rv.data(), rvs[0], hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
-    if (rvs[1]) HIP_TRY(e, hipMemcpyAsync(sl.d_rv[1], h.links_rv.data(), rvs[1], hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
-    if (tb) {
-        HIP_TRY(e, hipMemcpyAsync(sl.d_tns, h.tns.data(), sizeof(aacg_dev_tns) * h.tns.size(), hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
-        aacg_tns_matrices_launch((const aacg_dev_tns*)sl.d_tns, tns_matrices_of((const aacg_dev_tns*)sl.d_tns, h.tns.size()), (uint32_t)h.tns.size(), s);
-    }
-    for (int i = 0; i < 3; i++) if (ccb[i]) HIP_TRY(e, hipMemcpyAsync(sl.d_cce[i], cce_src[i], ccb[i], hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
     HIP_TRY(e, hipMemcpyAsync(sl.d_coeffs, src_coeffs, cb, hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
     if (quant) HIP_TRY(e, hipMemcpyAsync(sl.d_meta, src_meta, mb, hipMemcpyHostToDevice, s), AACG_ERR_NO_DEVICE);
     /* kernels chain through the overlap state: this one starts after the previous batch's kernel,
@@ -1521,21 +1527,14 @@ int aacg_submit_ex(aacg_engine* e, const aacg_batch* batch, uint64_t* ticket)
     if (e->last_kernel) HIP_TRY(e, hipStreamWaitEvent(s, e->last_kernel, 0), AACG_ERR_NO_DEVICE);
     if ((rc = pipe_join(e, s))) return rc;              /* ... and after whatever aacg_decode_pipelined has in flight */
     const xl_args serial = {false, 0ull, 0};
-    rc = launch_run(e, R, (const aacg_dev_unit*)sl.d_units, (const aacg_run*)sl.d_runs, (const aacg_dev_tns*)sl.d_tns,
-                    (float*)sl.d_scratch, (float*)sl.d_spec, cce_bufs{(const aacg_run*)sl.d_cce[0], (const aacg_couple_job*)sl.d_cce[1], (const float*)sl.d_cce[2], (float*)sl.d_cce[3]},
-                    rv_bufs{(const aacg_run*)sl.d_rv[0], (const aacg_rv_link*)sl.d_rv[1], (unsigned long long*)sl.d_rv[2], (float*)sl.d_rv[3]}, h, sl.d_coeffs,
-                    (const aacg_band_meta*)sl.d_meta, sl.d_pcm, 0, s, serial, nullptr);
+    rc = launch_run(e, R, sl.b.units(), sl.b, h, sl.d_coeffs, (const aacg_band_meta*)sl.d_meta, sl.d_pcm, 0, s, serial, nullptr);
     if (rc) return rc;
     HIP_TRY(e, hipEventRecord(sl.kernel_done, s), AACG_ERR_NO_DEVICE);
     e->last_kernel = sl.kernel_done;
     HIP_TRY(e, hipMemcpyAsync(dst_pcm, sl.d_pcm, pb, hipMemcpyDeviceToHost, s), AACG_ERR_NO_DEVICE);
     HIP_TRY(e, hipEventRecord(sl.done, s), AACG_ERR_NO_DEVICE);
     sl.busy = true;
-
-    for (const aacg_chain& c : h.chains)
-        for (int k = 0; k < c.n_ch; k++)
-            { uint8_t& b = e->parity[(size_t)c.stream * (size_t)e->cfg.max_channels + c.channel + k]; b = (uint8_t)((b + 1) % AACG_OV_BUFFERS); }
-    e->epoch++;
+    parity_advance(e, h);
     *ticket = ++e->submitted;
     return AACG_OK;
 }

@@ -468,14 +468,21 @@ def _engine(r, H, out=None, si=S_INDEX):
     return eng
 
 
-def device_run(r, saturate=False, out=None, workload=MAKE, si=S_INDEX, nan=False):
+def device_run(r, saturate=False, out=None, workload=MAKE, si=S_INDEX, nan=False, host=False):
     """both batches of recipe r through the device path (one plan; aacg_decode_device or aacg_decode_pipelined) into buffers
     poisoned first (NaN, int16 0x7F7F), out: another output kind than the recipe's: ([PCM of batch 0, 1], overlap state, the
-    plan's route)"""
+    plan's route).  host: through the host-buffer path instead (Engine.decode_batch: aacg_decode_batch / _tns / _ex, so
+    aacg_submit_ex; no plan, the route None), for recipes that are not pipelined"""
     import torch
     i16 = (out or r.out) == O16
     rec, coeffs = batches(r.name, saturate, workload, si, nan)
     eng = _engine(r, rec["H"], out, si)
+    if host:
+        assert not r.piped
+        outs = [eng.decode_batch(rec["units"], c, rec["meta"], rec["n_pcm"], tns=rec["tns"], cce=rec["cce"]) for c in coeffs]
+        state = np.stack([[eng.get_overlap(s, ch) for ch in range(rec["H"])] for s in range(S)])
+        eng.close()
+        return outs, state, None
     plan = eng.plan(rec["units"], tns=rec["tns"], cce=rec["cce"])
     route = eng.plan_kernels(plan, pipelined=r.piped)
     d_meta = torch.from_numpy(rec["meta"].view(np.int16)).cuda() if rec["meta"] is not None else None
@@ -502,13 +509,23 @@ def device_run(r, saturate=False, out=None, workload=MAKE, si=S_INDEX, nan=False
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", [r.name for r in RECIPES])
-def test_recipe_on_the_device(oracle, name):
+@pytest.mark.parametrize("name,host", [pytest.param(r.name, h, id=r.name + ("-host" if h else ""))
+                                       for r in RECIPES for h in ((False,) if r.piped else (False, True))])
+def test_recipe_on_the_device(oracle, name, host):
+    """host: the recipe's batches through the host-buffer path as well (every table of the batch through the engine's slot
+    buffers): the PCM of both batches and the overlap state bit for bit what the plan gives"""
     r = BY_NAME[name]
     outs, state, route = device_run(r)
     assert route == r.route
     w = check(name, outs, state, "device")
     print("per-block worst %s: rms %.3e max %.3e" % (name, w[0], w[1]))
+    if host:
+        h_outs, h_state, _ = device_run(r, host=True)
+        for b, (x, y) in enumerate(zip(h_outs, outs)):
+            assert x.dtype == y.dtype, name
+            same = np.array_equal(x, y) if r.out == O16 else np.array_equal(x.view(np.uint32), y.view(np.uint32))
+            assert same, "%s batch %d: the host-buffer path's PCM" % (name, b)
+        assert np.array_equal(h_state.view(np.uint32), state.view(np.uint32)), "%s: the host-buffer path's overlap state" % name
 
 
 @pytest.mark.gpu
