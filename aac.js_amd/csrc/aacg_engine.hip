@@ -25,6 +25,7 @@
 #include "aacg_kernels.h"
 #include "aacg_host.h"
 #include "aacg_routes.h"
+#include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
 /* ---- kernels ----------------------------------------------------------------------- */
@@ -35,6 +36,8 @@ AACG_RUN_KERNEL_UNIT(plain, AACG_RUN_KERNELS_PLAIN)
 /* aacg_engine_refresh.hip: a kept plan's unit records from the device parser's output */
 void aacg_refresh_launch(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg_parse_result* results, const aacg_refresh_map* map, uint32_t n_units,
                          uint32_t max_units, int refuse_pns, uint32_t* refused, hipStream_t s);
+/* aacg_engine_shape.hip: a shaped plan's set of tables from the batch's per-stream table (aacg_plan_shape.h) */
+void aacg_shape_launch(const aacg_shape_args& A, hipStream_t s);
 /* aacg_engine_spectral.hip: the optional stages (AACG_PNS_SPEC noise bands, AACG_TNS_SPEC filters) -> f32 spectra */
 int aacg_spectral_ex_set_lds_limits(void);
 void aacg_spectral_ex_launch(bool quant, int n_units, hipStream_t s, const aacg_kparams& P);
@@ -174,11 +177,29 @@ struct aacg_plan {
     hipEvent_t last_use = nullptr;          /* recorded at destruction on last_stream: everything launched with this plan */
     hipStream_t last_stream = nullptr;      /* stream of the most recent launch (no per-launch event: it costs 3 us per step) */
     uint32_t unit_sets = 1, cur_set = 0;    /* aacg_plan_set_unit_sets: b.units() holds unit_sets copies of the records; launches read cur_set */
-    const aacg_dev_unit* units_now() const { return b.units() + (size_t)cur_set * n_units; }
     bool used = false;
     bool last_pipelined = false;            /* its most recent launch went through aacg_decode_pipelined */
     uint64_t seen_epoch = ~0ull;            /* engine epoch right after this plan's last launch */
     uint32_t launches = 0;
+    /* A plan with a capacity instead of a shape (aacg_plan_create_shaped): b holds unit_sets sets of unit records, run and link
+     * tables sized for the largest batch, and every batch shapes one of them on the device (aacg_plan_shape.h).  h then holds what
+     * launch_run and the route take from a planner's output for the set shaped last — flags, pcm_floats, n_links_rv, the chains
+     * a launch advances, and ONE placeholder entry in runs_rv ("has runs") — its tables exist on the device only. */
+    struct shaped_t {
+        aacg_shape_limits lim;
+        uint32_t n_runs = 0;                        /* of the set shaped last */
+        uint32_t Cp = 0, unit0_coef = 0, unit0_nch = 0;
+        std::vector<uint32_t> set_units;            /* per set: plan units of the shape it holds */
+        std::vector<aacg_shape_stream> table;       /* the set shaped last: the host's copy of its table */
+        std::vector<aacg_shape_stream> launched;    /* ... and of the most recent launch (the sequence rule, aacg_shape_same) */
+        bool tabled = false;                        /* aacg_plan_shape_table has booked a shape, aacg_plan_shape_launch is to follow */
+        bool ready = false;                         /* the set shaped last is on its way to the device: aacg_decode_pipelined may launch it */
+        uint64_t epoch = ~0ull;                     /* the engine's epoch the rotation words were taken at */
+    };
+    shaped_t* sh = nullptr;
+    size_t unit_stride() const { return sh ? sh->lim.max_units : n_units; }
+    const aacg_dev_unit* units_now() const { return b.units() + (size_t)cur_set * unit_stride(); }
+    ~aacg_plan() { delete sh; }
 };
 
 namespace {
@@ -440,10 +461,14 @@ int batch_upload(aacg_engine* e, batch_bufs& b, const aacg_plan_host& h, const s
 /* what a pipelined launch adds to the rendezvous arguments: the cross-launch cells, the epoch its input state carries, and
  * which of the plan's two sets of in-launch cells it uses (overlapping launches must not share one) */
 struct xl_args { bool on; unsigned long long epoch_in; int set; int trace_part = 0; };   /* trace_part: which quarter of the profiling buffer this launch stamps */
+/* a shaped plan's launch (aacg_plan_shape.h): the run and link tables of the set shaped last and their count — the host has no copy
+ * to count — and the plan's capacity in links, which is what a set of in-launch cells holds */
+struct shaped_run { const aacg_run* runs; const aacg_rv_link* links; size_t n_runs, cell_links; };
 
 /* enqueue the launches of route R for a planned batch: its unit records d_units (a plan's current set), its other buffers b */
 int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units, const batch_bufs& b, const aacg_plan_host& h, const void* d_coeffs,
-               const aacg_band_meta* d_meta, void* d_pcm, int flip, hipStream_t s, const xl_args& xl, unsigned long long* epoch_out, hipEvent_t stop = nullptr)
+               const aacg_band_meta* d_meta, void* d_pcm, int flip, hipStream_t s, const xl_args& xl, unsigned long long* epoch_out, hipEvent_t stop = nullptr,
+               const shaped_run* shaped = nullptr)
 {
     if (h.zero_fill)
         HIP_TRY(e, hipMemsetAsync(d_pcm, 0, h.pcm_floats * pcm_elem_size(e), s), AACG_ERR_NO_DEVICE);
@@ -452,11 +477,11 @@ int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units
     P.units = d_units; P.coeffs = d_coeffs; P.meta = d_meta; P.pcm = (float*)d_pcm;
     P.overlap = e->d_overlap; P.tab = e->d_tab; P.flip = flip;
     if (R.rv) {
-        const size_t n_runs = h.runs_rv.size(), n_links = h.n_links_rv;
-        P.runs = b.rv_runs(); P.n_runs = (int32_t)n_runs;
+        const size_t n_runs = shaped ? shaped->n_runs : h.runs_rv.size(), n_links = shaped ? shaped->cell_links : h.n_links_rv;
+        P.runs = shaped ? shaped->runs : b.rv_runs(); P.n_runs = (int32_t)n_runs;
         aacg_rv_args V;
         std::memset(&V, 0, sizeof V);
-        V.links = b.rv_links();
+        V.links = shaped ? shaped->links : b.rv_links();
         V.state = b.rv_state() ? b.rv_state() + (size_t)xl.set * AACG_RV_STATE_WORDS * n_links : nullptr;
         V.data = b.rv_data() ? b.rv_data() + (size_t)xl.set * AACG_RV_DATA_FLOATS * n_links : nullptr;
         V.epoch = ++e->rv_epoch;
@@ -930,6 +955,107 @@ int aacg_plan_create_ex(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_
     return AACG_OK;
 }
 
+/* ---- plans shaped on the device (aacg_plan_shape.h) -------------------------------------------------------------------- */
+int aacg_plan_create_shaped(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, aacg_plan** out)
+{
+    if (!e || !out || !max_streams || !max_frames || !max_elems || max_elems > 8 || n_sets < 1 || n_sets > 8 ||
+        (uint64_t)max_streams * (uint64_t)max_frames > (1u << 22))
+        return AACG_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (e->cfg.input_kind != AACG_INPUT_QUANT_I16 || e->cfg.tns_mode == AACG_TNS_SPEC || e->cfg.pns_mode == AACG_PNS_SPEC || e->cfg.cce_mode == AACG_CCE_SPEC) {
+        e->err = "aacg_plan_create_shaped: an AACG_INPUT_QUANT_I16 engine without optional stages (TNS / PNS / coupling records are prepared on the host, per batch)";
+        return AACG_ERR_UNSUPPORTED;
+    }
+    if ((int)max_streams > e->cfg.max_streams) { e->err = "aacg_plan_create_shaped: more streams than the engine has slots"; return AACG_ERR_CAPACITY; }
+    aacg_plan* p = new (std::nothrow) aacg_plan();
+    if (p) p->sh = new (std::nothrow) aacg_plan::shaped_t();
+    if (!p || !p->sh) { delete p; return AACG_ERR_OUT_OF_MEMORY; }
+    p->e = e;
+    aacg_plan::shaped_t& sh = *p->sh;
+    sh.lim = aacg_shape_capacity(max_streams, max_frames, max_elems, (uint32_t)e->cfg.max_channels);
+    sh.set_units.assign(n_sets, 0);
+    sh.table.reserve(max_streams); sh.launched.reserve(max_streams);
+    p->unit_sets = n_sets;
+    size_t want[batch_bufs::N] = {};
+    want[batch_bufs::UNITS] = (size_t)n_sets * sh.lim.max_units * sizeof(aacg_dev_unit);
+    want[batch_bufs::RV_RUNS] = (size_t)n_sets * sh.lim.max_runs * sizeof(aacg_run);
+    want[batch_bufs::RV_LINKS] = (size_t)n_sets * sh.lim.max_runs * sizeof(aacg_rv_link);
+    /* the in-launch cells: a set per pipeline stream as for any plan (overlapping launches must not share one); epoch-tagged and
+     * never reset, so launches of different shapes may share them */
+    want[batch_bufs::RV_DATA] = (size_t)AACG_PIPE_STREAMS * sh.lim.max_links * AACG_RV_DATA_FLOATS * sizeof(float);
+    want[batch_bufs::RV_STATE] = (size_t)AACG_PIPE_STREAMS * sh.lim.max_links * AACG_RV_STATE_WORDS * sizeof(unsigned long long);
+    bool ok = hip_ok(e, hipSetDevice(e->cfg.device_ordinal), "hipSetDevice") &&
+              hip_ok(e, hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming), "hipEventCreate") &&
+              hip_ok(e, hipEventCreateWithFlags(&p->last_use, hipEventDisableTiming), "hipEventCreate");
+    for (int i = 0; i < batch_bufs::N && ok; i++)
+        if (want[i]) ok = (p->b.p[i] = pool_take(e, want[i], &p->b.bytes[i])) != nullptr;
+    if (!ok) {
+        char b[400];
+        std::snprintf(b, sizeof b, "aacg_plan_create_shaped: no room for a plan of %u streams x %u frames x %u elements in %u sets: %zu bytes of unit records, %zu of run and link "
+                      "tables, %zu of in-launch rendezvous cells (%zu links x 16 KB x %d pipeline streams) — ", max_streams, max_frames, sh.lim.max_elems, n_sets,
+                      want[batch_bufs::UNITS], want[batch_bufs::RV_RUNS] + want[batch_bufs::RV_LINKS], want[batch_bufs::RV_DATA] + want[batch_bufs::RV_STATE], sh.lim.max_links, AACG_PIPE_STREAMS);
+        const std::string why = e->err;
+        aacg_plan_destroy(p);
+        e->err = std::string(b) + why;
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    /* the cells' state words count only with a launch's epoch in them, but a block from the free list may hold another plan's */
+    if ((want[batch_bufs::RV_STATE] && !hip_ok(e, hipMemsetAsync(p->b.rv_state(), 0, want[batch_bufs::RV_STATE], e->stream), "zero the cells' state words")) ||
+        !hip_ok(e, hipEventRecord(p->uploaded, e->stream), "hipEventRecord")) {
+        aacg_plan_destroy(p);
+        return AACG_ERR_NO_DEVICE;
+    }
+    p->h.runs_rv.resize(1);                                /* "has runs" for the route decision; the tables themselves exist on the device only */
+    *out = p;
+    return AACG_OK;
+}
+
+int aacg_plan_shape_table(aacg_engine* e, aacg_plan* p, uint32_t set, aacg_shape_stream* table, uint32_t n_streams, uint32_t parse_channels, uint32_t* n_units)
+{
+    if (!e || !p || p->e != e || !table || !n_streams || !n_units) return AACG_ERR_INVALID_ARG;
+    if (!p->sh) { e->err = "aacg_plan_shape_table: not a plan made by aacg_plan_create_shaped"; return AACG_ERR_INVALID_ARG; }
+    if (set >= p->unit_sets) { e->err = "aacg_plan_shape_table: no such set"; return AACG_ERR_INVALID_ARG; }
+    aacg_plan::shaped_t& sh = *p->sh;
+    aacg_shape_info info;
+    const int rc = aacg_shape_plan(table, n_streams, (uint32_t)e->cfg.max_streams, (uint32_t)e->cfg.max_channels, parse_channels, e->parity.data(), sh.lim, &info, &e->err);
+    if (rc) return rc;                                     /* nothing touched, nothing enqueued */
+    sh.table.assign(table, table + n_streams);
+    sh.n_runs = info.n_runs; sh.Cp = parse_channels; sh.unit0_coef = info.unit0_coef; sh.unit0_nch = info.unit0_nch;
+    sh.set_units[set] = info.n_units;
+    sh.epoch = e->epoch;
+    sh.tabled = info.n_units != 0; sh.ready = false;
+    p->cur_set = set;
+    p->n_units = info.n_units;
+    p->h.zero_fill = info.zero_fill; p->h.pcm_floats = info.pcm_floats; p->h.wide_frames = info.wide_frames; p->h.long_chains = info.long_chains;
+    p->h.n_links_rv = info.n_links;
+    p->h.chains = std::move(info.chains);
+    *n_units = info.n_units;
+    return AACG_OK;
+}
+
+int aacg_plan_shape_launch(aacg_engine* e, aacg_plan* p, const aacg_shape_stream* d_table, uint32_t max_units, aacg_refresh_map* d_map, void* hip_stream)
+{
+    if (!e || !p || p->e != e || !d_table || !max_units || !d_map) return AACG_ERR_INVALID_ARG;
+    if (!p->sh || !p->sh->tabled) { e->err = "aacg_plan_shape_launch: aacg_plan_shape_table books the shape first (and a shape without units has nothing to launch)"; return AACG_ERR_INVALID_ARG; }
+    aacg_plan::shaped_t& sh = *p->sh;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    note_stream(e, s);
+    HIP_TRY(e, hipSetDevice(e->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    HIP_TRY(e, hipStreamWaitEvent(s, p->uploaded, 0), AACG_ERR_NO_DEVICE);
+    aacg_shape_args A;
+    std::memset(&A, 0, sizeof A);
+    A.tab = d_table; A.n_streams = (uint32_t)sh.table.size(); A.U = max_units; A.C = (uint32_t)e->cfg.max_channels; A.Cp = sh.Cp;
+    A.n_runs = sh.n_runs; A.unit0_coef = sh.unit0_coef; A.unit0_nch = sh.unit0_nch;
+    A.map = d_map;
+    A.units = p->b.units() + (size_t)p->cur_set * sh.lim.max_units;
+    A.runs = p->b.rv_runs() + (size_t)p->cur_set * sh.lim.max_runs;
+    A.links = p->b.rv_links() + (size_t)p->cur_set * sh.lim.max_runs;
+    aacg_shape_launch(A, s);
+    HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    sh.tabled = false; sh.ready = true;
+    return AACG_OK;
+}
+
 void aacg_plan_destroy(aacg_plan* p)
 {
     if (!p) return;
@@ -955,6 +1081,13 @@ void aacg_plan_destroy(aacg_plan* p)
     for (int i = 0; i < batch_bufs::N; i++) pool_give(e, p->b.p[i], p->b.bytes[i]);
     if (e->pipe.plan == p) e->pipe.plan = nullptr;
     delete p;
+}
+
+/* an entry point that needs what a shaped plan does not hold: its tables exist on the device only, and only the rendezvous cut */
+static int shaped_refused(aacg_engine* e, const char* who, const char* why)
+{
+    e->err = std::string(who) + ": the plan was made by aacg_plan_create_shaped and holds the rendezvous cut of one batch shape at a time, on the device only: " + why;
+    return AACG_ERR_UNSUPPORTED;
 }
 
 static int plan_check_parity(aacg_engine* e, const aacg_plan* p)
@@ -1012,6 +1145,7 @@ int aacg_decode_device(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const
                        void* d_pcm, void* hip_stream)
 {
     if (!e || !p || p->e != e || !d_coeffs || !d_pcm) return AACG_ERR_INVALID_ARG;
+    if (p->sh) return shaped_refused(e, "aacg_decode_device", "the serial route walks the cut with recomputed tails (aacg_decode_pipelined launches such a plan)");
     const bool quant = e->cfg.input_kind == AACG_INPUT_QUANT_I16;
     if (quant && !d_meta) { e->err = "QUANT_I16 engine needs band meta"; return AACG_ERR_INVALID_ARG; }
     /* relaunched back to back (nothing else advanced any stream since): the per-chain check is known to pass */
@@ -1123,10 +1257,20 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
     if (!e || !p || p->e != e || !d_coeffs || !d_pcm) return AACG_ERR_INVALID_ARG;
     const bool quant = e->cfg.input_kind == AACG_INPUT_QUANT_I16;
     if (quant && !d_meta) { e->err = "QUANT_I16 engine needs band meta"; return AACG_ERR_INVALID_ARG; }
-    int rc = p->seen_epoch == e->epoch ? AACG_OK : plan_check_parity(e, p);
+    int rc = AACG_OK;
+    if (p->sh) {
+        /* the set shaped last took its rotation words from the engine's state: it is current if nothing has advanced a stream since */
+        if (!p->sh->ready) { e->err = "aacg_decode_pipelined: no shape to launch (aacg_plan_shape_table + aacg_plan_shape_launch first; a launch uses its shape up)"; return AACG_ERR_INVALID_ARG; }
+        if (p->sh->epoch != e->epoch) { e->err = "plan is stale: a stream was advanced between aacg_plan_shape_table and the launch"; return AACG_ERR_STALE_PLAN; }
+    } else rc = p->seen_epoch == e->epoch ? AACG_OK : plan_check_parity(e, p);
     if (rc) return rc;
     const aacg_route R = route_of(e, p->h, true);
+    if (p->sh && !(R.rv && R.overlappable)) return shaped_refused(e, "aacg_decode_pipelined", "this engine's route does not take the rendezvous cut");
     if ((rc = plan_check_route(e, p, R)) || (rc = pipe_setup(e))) return rc;
+    /* launches of different shapes do not meet in the cross-launch cells: a launch that continues its predecessor leaves a chain's
+     * first half in the cell and trusts the predecessor's last wave of that chain to finish the frame — a
+     * predecessor of another shape may have no such chain */
+    const bool same_shape = !p->sh || aacg_shape_same(p->sh->launched.data(), p->sh->launched.size(), p->sh->table.data(), p->sh->table.size());
     aacg_engine::pipe_t& pp = e->pipe;
     /* a route whose launches cannot overlap (optional stages, coupling, int16 PCM: no rendezvous build) runs on the pipeline's
      * first stream, launch behind launch: the stream orders them, no event is needed between two of them */
@@ -1136,8 +1280,8 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
      * stream puts it behind launch n - AACG_PIPE_STREAMS; the event waits of aacg_pipeline_order (aacg_routes.cpp) do the rest:
      * together every launch is behind every launch up to n - AACG_OV_BUFFERS + 1, whose buffers and cells it reuses
      * (aacg_device.h).  Otherwise it starts behind everything in flight, from complete state. */
-    const bool continues = R.overlappable && pp.open && !pp.serial && pp.plan == p && p->last_pipelined && p->seen_epoch == e->epoch;
-    if (!continues) { pp.n = 0; pp.streams = aacg_pipeline_streams(p->h, R.run_key); std::memset(pp.seen, 0, sizeof pp.seen); }      /* a new sequence */
+    const bool continues = R.overlappable && pp.open && !pp.serial && pp.plan == p && p->last_pipelined && p->seen_epoch == e->epoch && same_shape;
+    if (!continues) { pp.n = 0; pp.streams = p->sh ? aacg_pipeline_streams_for(p->sh->n_runs, p->sh->set_units[p->cur_set], 0, R.run_key) : aacg_pipeline_streams(p->h, R.run_key); std::memset(pp.seen, 0, sizeof pp.seen); }      /* a new sequence */
     const aacg_pipe_order ord = aacg_pipeline_order(pp.n, pp.streams);
     hipStream_t s = R.overlappable ? pp.stream[ord.stream] : pp.stream[0];
     if (continues) {
@@ -1182,8 +1326,12 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
     hipEvent_t const mine = (stop_mark && R.rv) ? (hipEvent_t)stop_mark : pp.mark[slot][ord.stream];
     if (ordered) pp.seen[slot][ord.stream] = mine;
     hipEvent_t bound = R.rv ? (stop_mark ? (hipEvent_t)stop_mark : (ordered ? mine : nullptr)) : nullptr;
-    rc = launch_run(e, R, p->units_now(), p->b, p->h, d_coeffs, d_meta, d_pcm, (int)(p->launches % AACG_OV_BUFFERS), s, xl, &epoch, bound);
+    shaped_run sr;
+    if (p->sh) sr = shaped_run{p->b.rv_runs() + (size_t)p->cur_set * p->sh->lim.max_runs, p->b.rv_links() + (size_t)p->cur_set * p->sh->lim.max_runs, p->sh->n_runs, p->sh->lim.max_links};
+    /* (a shaped set carries the rotation it was shaped at: no flip) */
+    rc = launch_run(e, R, p->units_now(), p->b, p->h, d_coeffs, d_meta, d_pcm, p->sh ? 0 : (int)(p->launches % AACG_OV_BUFFERS), s, xl, &epoch, bound, p->sh ? &sr : nullptr);
     if (rc) return rc;
+    if (p->sh) { if (!same_shape) p->sh->launched = p->sh->table; p->sh->ready = false; }
     if (ordered && bound != mine) HIP_TRY(e, hipEventRecord(mine, s), AACG_ERR_NO_DEVICE);
     if (stop_mark && bound != (hipEvent_t)stop_mark) HIP_TRY(e, hipEventRecord((hipEvent_t)stop_mark, s), AACG_ERR_NO_DEVICE);
     if (continues) pp.chained++;
@@ -1241,6 +1389,7 @@ int aacg_plan_refresh_from_parse(aacg_engine* e, aacg_plan* p, const aacg_unit_d
 int aacg_plan_set_unit_sets(aacg_engine* e, aacg_plan* p, uint32_t n_sets)
 {
     if (!e || !p || p->e != e || n_sets < 1 || n_sets > 8) return AACG_ERR_INVALID_ARG;
+    if (p->sh) return shaped_refused(e, "aacg_plan_set_unit_sets", "its sets are made with it");
     if (p->used || p->launches) { e->err = "aacg_plan_set_unit_sets: before the plan's first launch"; return AACG_ERR_INVALID_ARG; }
     if (n_sets == p->unit_sets) return AACG_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
@@ -1269,6 +1418,14 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
     note_stream(e, s);
     HIP_TRY(e, hipStreamWaitEvent(s, p->uploaded, 0), AACG_ERR_NO_DEVICE);
+    if (p->sh) {
+        /* a shaped set: the records aacg_plan_shape_launch has just written on this stream, as many as the shape has; a set of
+         * its own like the sets of a kept plan (nothing in flight reads it: the caller's word) */
+        if (!p->sh->ready || set != p->cur_set || !d_map) { e->err = "aacg_plan_refresh_from_parse_ex: a shaped plan refreshes the set shaped last (aacg_plan_shape_launch), through its map"; return AACG_ERR_INVALID_ARG; }
+        aacg_refresh_launch(p->b.units() + (size_t)set * p->unit_stride(), d_parsed_units, d_results, d_map, p->sh->set_units[set], max_units, 1, d_refused, s);
+        HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
+        return AACG_OK;
+    }
     if (p->unit_sets > 1) {
         /* a set of its own: nothing in flight reads it (the caller's word), so neither the pipeline is joined nor the plan's
          * sequence of overlapped launches ended; the next launch reads this set */
@@ -1291,6 +1448,7 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
 int aacg_plan_refresh_units(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* units, uint32_t n_units, void* hip_stream)
 {
     if (!e || !p || p->e != e || !units) return AACG_ERR_INVALID_ARG;
+    if (p->sh) return shaped_refused(e, "aacg_plan_refresh_units", "there are no host unit records to rewrite (aacg_plan_refresh_from_parse_ex refreshes a shaped set)");
     int rc = aacg_plan_refresh_host(&p->h, units, n_units, e->cfg.sample_index, e->cfg.tns_mode == AACG_TNS_SPEC, &e->err);
     if (rc) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
@@ -1317,6 +1475,7 @@ int aacg_spectral_device(aacg_engine* e, aacg_plan* p, const void* d_coeffs, con
 {
     if (!e || !p || p->e != e || !d_coeffs || !d_meta || !d_spec_out) return AACG_ERR_INVALID_ARG;
     if (e->cfg.input_kind != AACG_INPUT_QUANT_I16) { e->err = "spectral stage needs a QUANT_I16 engine"; return AACG_ERR_INVALID_ARG; }
+    if (p->sh) return shaped_refused(e, "aacg_spectral_device", "the staged spectral launch walks a planner's unit count");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
     note_stream(e, s);
     aacg_kparams P;

@@ -27,7 +27,14 @@
  * rectangular call is the case of equal counts.  A batch's refresh map is expanded on the lane's stream (aacg_pipe_map) from a
  * per-stream table staged with the bytes, so a new shape costs the submit path no allocation and no synchronous copy.
  *
- * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine.
+ * Device plans (aacg_pipeline_config.plan_mode 1): the pipeline makes ONE plan with its own capacity at create
+ * (aacg_plan_create_shaped) and every batch shapes that plan's set of its lane on the device — aacg_plan_shape_table completes the
+ * per-stream table in the staging, aacg_plan_shape_launch runs the shaping kernel in the place of aacg_pipe_map — so a batch of a
+ * shape not seen before costs the submit path no plan build, no allocation, no upload of O(units) bytes and no eviction.  The two
+ * modes part in aacg_pipeline_submit_ragged where the plan is chosen and where the map / shaping kernel is launched, nowhere else.
+ *
+ * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
+ * (and aacg_pipe_map.h / aacg_plan_shape.h for the tables it fills).
  */
 #include <hip/hip_runtime.h>
 
@@ -39,7 +46,7 @@
 
 #include "../../include/aacgpu.h"
 #include "../../include/aacgpu_tools.h"
-#include "aacg_pipe_map.h"
+#include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
 #define AACG_PIPELINE_MAX_LANES 8
@@ -90,6 +97,11 @@ struct aacg_pipeline {
     struct kept { std::vector<uint32_t> frames; std::vector<uint32_t> slots; aacg_plan* plan; uint32_t n_units; uint64_t used; };
     std::vector<kept> plans;
     uint64_t tick = 0, plan_builds = 0;
+    /* plan_mode 1 (aacg_pipeline_config): ONE plan with the pipeline's capacity, a set per lane, shaped on the device batch by batch
+     * (aacg_plan_create_shaped) — `plans`, plan_for and the stale-plan retry are not on that path */
+    aacg_plan* shaped = nullptr;
+    kept shaped_kept;                   /* what the submit path takes from a kept plan: the plan and the batch's unit count */
+    uint64_t shaped_batches = 0, launches = 0;
     std::vector<layout_t> batch_layout; /* the submitting batch's streams' layouts, as its plan lists them */
     std::vector<uint32_t> rect_counts;  /* aacg_pipeline_submit's counts: every stream frames_per_stream */
     struct lane_t {
@@ -306,6 +318,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         return;
     }
     drop_plans(p);
+    if (p->shaped) aacg_plan_destroy(p->shaped);
     for (auto& W : p->walk) {
         if (W.st) (void)aacg_wait_stream(W.st, p->wait);
         for (void* d : {W.d_in, W.d_out}) if (d) (void)hipFree(d);
@@ -332,7 +345,7 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     *out = nullptr;
     if (cfg->abi_version != AACG_ABI_VERSION || cfg->max_streams < 1 || cfg->max_frames < 1 || cfg->channels < 1 || cfg->channels > AACG_MAX_CHANNELS ||
         (cfg->output_kind != AACG_OUTPUT_F32 && cfg->output_kind != AACG_OUTPUT_I16) || (uint64_t)cfg->max_streams * (uint64_t)cfg->max_frames > (1u << 22) ||
-        cfg->lanes < 0 || cfg->lanes > AACG_PIPELINE_MAX_LANES)
+        cfg->lanes < 0 || cfg->lanes > AACG_PIPELINE_MAX_LANES || cfg->plan_mode < 0 || cfg->plan_mode > 1)
         return AACG_ERR_INVALID_ARG;
     aacg_pipeline* p = new (std::nothrow) aacg_pipeline();
     if (!p) return AACG_ERR_OUT_OF_MEMORY;
@@ -355,6 +368,11 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     ec.tns_mode = AACG_TNS_REFERENCE; ec.pns_mode = AACG_PNS_REFERENCE; ec.output_kind = cfg->output_kind; ec.cce_mode = AACG_CCE_REFERENCE;
     int rc = aacg_create(&ec, &p->engine);
     if (rc == AACG_OK) rc = aacg_parser_create(cfg->device_ordinal, cfg->sample_index, entries, counts, &p->parser);
+    /* device plans: the one plan, made here — a failure (the in-launch cells of long chains are the large part) is the caller's to
+     * see, there is no falling back to kept plans */
+    if (rc == AACG_OK && cfg->plan_mode == 1 &&
+        (rc = aacg_plan_create_shaped(p->engine, (uint32_t)cfg->max_streams, (uint32_t)cfg->max_frames, p->U, (uint32_t)p->n_lanes, &p->shaped)))
+        std::fprintf(stderr, "aacgpu: %s\n", aacg_last_error(p->engine));
     if (rc) { aacg_pipeline_destroy(p); return rc; }
     const size_t n = (size_t)cfg->max_streams * (size_t)cfg->max_frames, C = p->C, Cp = p->Cp, U = p->U;
     p->res_cap16 = (n * sizeof(aacg_parse_result) + 15) & ~(size_t)15;
@@ -457,7 +475,8 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     /* staging: the bytes (16-byte aligned, AACG_PARSE_PAD readable bytes behind them), the frame table and the per-stream table
      * that aacg_pipe_map expands into the refresh map, in one page-locked block */
     const size_t padded = ((n_bytes + 15) & ~(size_t)15) + 64, table = (size_t)n * sizeof(aacg_parse_frame), table16 = (table + 15) & ~(size_t)15;
-    const size_t up = padded + table16 + (size_t)n_streams * sizeof(aacg_pipe_stream);
+    const bool device_plans = p->shaped != nullptr;
+    const size_t up = padded + table16 + (size_t)n_streams * (device_plans ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
     if (up > L.h_in_cap) {
         if (L.h_in) (void)hipHostFree(L.h_in);
         L.h_in = nullptr; L.h_in_cap = 0;
@@ -476,9 +495,19 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     std::memcpy(L.h_in, bytes, n_bytes);
     std::memset((char*)L.h_in + n_bytes, 0, padded - n_bytes);
     std::memcpy((char*)L.h_in + padded, frames, table);
-    aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, n_streams, C, Cp, U, nullptr, nullptr, (aacg_pipe_stream*)((char*)L.h_in + padded + table16));
     aacg_pipeline::kept* kp = nullptr;
-    if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
+    if (device_plans) {
+        /* the plan is chosen: the one there is, its set of this lane shaped from the batch's table — which the engine checks against
+         * the plan's capacity and completes (each stream's first run and link, the overlap rotation) before anything is enqueued */
+        aacg_shape_stream* tab = (aacg_shape_stream*)((char*)L.h_in + padded + table16);
+        aacg_pipe::shape_table(p->batch_layout.data(), slots, frames_of, n_streams, tab);
+        if ((rc = aacg_plan_shape_table(p->engine, p->shaped, set, tab, n_streams, Cp, &p->shaped_kept.n_units))) { p->err = std::string("aacg_plan_shape_table: ") + aacg_last_error(p->engine); return rc; }
+        p->shaped_kept.plan = p->shaped;
+        if (p->shaped_kept.n_units) kp = &p->shaped_kept;      /* (no stream of the batch has a layout yet: nothing to transform, as with kept plans) */
+    } else {
+        aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, n_streams, C, Cp, U, nullptr, nullptr, (aacg_pipe_stream*)((char*)L.h_in + padded + table16));
+        if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
+    }
     const size_t pcm_bytes = (size_t)n * C * 1024u * pcm_elem(p);
     /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
      * lane's own page-locked staging and one host copy at collect */
@@ -500,7 +529,12 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     rc = aacg_parse_device(L.parser, L.d_bytes, (const aacg_parse_frame*)L.d_frames, n, U, Cp, (uint32_t)p->cfg.parse_options | AACG_PARSE_SKIP_ZERO_FILL,
                            (aacg_unit_desc*)L.d_units, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, nullptr, (aacg_parse_result*)L.d_res, st);
     if (rc) { p->err = std::string("aacg_parse_device: ") + aacg_parser_last_error(L.parser); return rc; }
-    if (kp) {                                            /* the map the refresh reads: behind the staging's copy, on the lane's stream */
+    if (kp && device_plans) {                            /* the shaping kernel INSTEAD of aacg_pipe_map: the map, and the set's unit, run and link records */
+        if ((rc = aacg_plan_shape_launch(p->engine, p->shaped, (const aacg_shape_stream*)((char*)L.d_bytes + padded + table16), U, (aacg_refresh_map*)L.d_map, st))) {
+            p->err = std::string("aacg_plan_shape_launch: ") + aacg_last_error(p->engine); return rc;
+        }
+        p->shaped_batches++;
+    } else if (kp) {                                     /* the map the refresh reads: behind the staging's copy, on the lane's stream */
         const uint32_t blocks = n_streams < 256 ? n_streams : 256;
         hipLaunchKernelGGL(aacg_pipe_map, dim3(blocks), dim3(AACG_PIPE_MAP_THREADS), 0, st, (const aacg_pipe_stream*)((char*)L.d_bytes + padded + table16),
                            n_streams, U, (aacg_refresh_map*)L.d_map);
@@ -515,7 +549,8 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
         if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, st);
         if (rc == AACG_OK) rc = aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_pcm);
-        if (rc != AACG_ERR_STALE_PLAN || attempt) break;
+        if (rc == AACG_OK) p->launches++;
+        if (rc != AACG_ERR_STALE_PLAN || attempt || device_plans) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
         /* another shape's plan has advanced these streams since this one was used: plans are made from the engine's current state */
         drop_plans(p);
         if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
@@ -659,6 +694,15 @@ int aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
 }
 
 uint64_t aacg_pipeline_plan_builds(const aacg_pipeline* p) { return p ? p->plan_builds : 0; }
+
+int aacg_pipeline_launch_counts(const aacg_pipeline* p, uint64_t* shaped, uint64_t* chained, uint64_t* launches)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    if (shaped) *shaped = p->shaped_batches;
+    if (chained) *chained = aacg_pipeline_chained(p->engine);
+    if (launches) *launches = p->launches;
+    return AACG_OK;
+}
 
 int aacg_pipeline_stream_layout(aacg_pipeline* p, uint32_t slot, uint8_t element_channels[8], uint32_t* kept)
 {

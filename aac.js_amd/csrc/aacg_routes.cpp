@@ -110,11 +110,16 @@ aacg_pipe_order aacg_pipeline_order(uint64_t n, int streams)
     return o;
 }
 
-int aacg_pipeline_streams(const aacg_plan_host& h, unsigned run_key)
+int aacg_pipeline_streams_for(size_t n_runs, size_t n_units, uint32_t short_units, unsigned run_key)
 {
-    if (h.runs_rv.size() > 512) return 2;                                   /* several rounds of workgroups per launch */
+    if (n_runs > 512) return 2;                                             /* several rounds of workgroups per launch */
     if (run_key & AACG_RK_I16) return 2;                                    /* int16 PCM */
     if ((run_key & AACG_RK_EX) && (run_key & AACG_RK_QUANT)) return 2;      /* optional stages on the int16 seam */
-    if (2u * h.short_units > h.units.size()) return 2;                      /* mostly frames of eight short windows */
+    if (2u * short_units > n_units) return 2;                               /* mostly frames of eight short windows */
     return AACG_PIPE_STREAMS;
+}
+
+int aacg_pipeline_streams(const aacg_plan_host& h, unsigned run_key)
+{
+    return aacg_pipeline_streams_for(h.runs_rv.size(), h.units.size(), h.short_units, run_key);
 }

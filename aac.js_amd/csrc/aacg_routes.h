@@ -70,6 +70,8 @@ aacg_pipe_order aacg_pipeline_order(uint64_t n, int streams);
  * Three where a CU that is done with launch n + 1's workgroup would otherwise find nothing of launch n + 2 to run; two where the
  * launches in flight already contend for the write path more than that wait costs. */
 int aacg_pipeline_streams(const aacg_plan_host& h, unsigned run_key);
+/* the same from the figures alone: a plan shaped on the device (aacg_plan_shape.h) has no host tables to count */
+int aacg_pipeline_streams_for(size_t n_runs, size_t n_units, uint32_t short_units, unsigned run_key);
 #endif
 
 #endif

@@ -31,6 +31,9 @@
  * { resident: true, ragged: true } — a flush takes from each stream what it has buffered, up to lookahead frames, instead of
  * cutting every stream to the count of the one with the fewest (aacg_pipeline_submit_ragged: per-stream frame counts, frames and
  * PCM packed stream after stream); one stream with a single frame buffered no longer makes the whole flush a one-frame batch.
+ * { resident: true, ragged: true, devicePlans: true } — ragged flushes seldom repeat a batch shape, and a kept plan per shape then
+ * means a plan built, uploaded and evicted per flush; with devicePlans a pipeline has ONE plan, shaped on the device for every
+ * batch (aacg_pipeline_config.plan_mode 1).  Off by default: INTEGRATION.md says when to switch it on.
  * Replaces, per batch, what src/decoder.js:125-216 does per frame.
  */
 'use strict';
@@ -46,6 +49,7 @@ function SharedEngine(opts) {
     this.residentPackets = !!opts.residentPackets;        // resident: 'mp4a' decoders too (their blocks found by a walk on the device)
     this.lookahead = opts.lookahead || 16;                // resident: frames per stream and flush
     this.ragged = !!opts.ragged;                          // resident: each stream's own frame count per flush (at most lookahead)
+    this.devicePlans = !!opts.devicePlans;                // resident: one plan per pipeline, shaped on the device batch by batch (plan_mode 1)
     /* resident: where a flush's PCM lives.  0 (default): memory of its own, the caller's for as long as it keeps any frame of the
      * flush (what the reference's readChunk() promises: a fresh array per frame) — a page-locked allocation per flush.  K > 0: K
      * page-locked buffers made once and used in turn: a frame is valid until its SharedEngine has flushed K more times, i.e. for
@@ -109,7 +113,8 @@ SharedEngine.prototype.attachResident = function (dec) {
         const outI16 = (this.opts.outputKind | 0) === host.OUTPUT_I16;
         const pipeline = addon.pipelineCreate({ deviceOrdinal: this.opts.deviceOrdinal | 0, sampleIndex: cfg.sampleIndex, maxStreams: this.maxStreams,
                                                 channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
-                                                parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0) }, rec.entries, rec.counts);
+                                                parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0),
+                                                planMode: this.devicePlans ? 1 : 0 }, rec.entries, rec.counts);
         g = { resident: true, addon: addon, pipeline: pipeline, channels: cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }
@@ -307,6 +312,18 @@ SharedEngine.prototype.flushResident = function (g) {
 SharedEngine.prototype.planBuilds = function () {
     let n = 0;
     for (const g of this.groups.values()) if (g.resident && g.addon.pipelinePlanBuilds) n += g.addon.pipelinePlanBuilds(g.pipeline);
+    return n;
+};
+
+/* the resident pipelines' transform launches, summed: { shaped: batches whose plan was shaped on the device (devicePlans),
+ * chained: launches that continued their predecessor through the cross-launch cells, launches } */
+SharedEngine.prototype.launchCounts = function () {
+    const n = { shaped: 0, chained: 0, launches: 0 };
+    for (const g of this.groups.values())
+        if (g.resident && g.addon.pipelineLaunchCounts) {
+            const c = g.addon.pipelineLaunchCounts(g.pipeline);
+            n.shaped += c.shaped; n.chained += c.chained; n.launches += c.launches;
+        }
     return n;
 };
 

@@ -57,6 +57,7 @@ static struct {
     int  (*pipeline_submit_ragged)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, const uint32_t*,
                                    void*, aacg_parse_result*, uint32_t*, uint64_t*);
     uint64_t (*pipeline_plan_builds)(const aacg_pipeline*);
+    int (*pipeline_launch_counts)(const aacg_pipeline*, uint64_t*, uint64_t*, uint64_t*);
     int  (*pipeline_walk_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, uint32_t, uint32_t, aacg_parse_frame*,
                                  aacg_walk_result*, uint64_t*);
     int  (*pipeline_walk_collect)(aacg_pipeline*, uint64_t);
@@ -97,6 +98,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_submit, "aacg_pipeline_submit"); SYM(pipeline_collect, "aacg_pipeline_collect");
     SYM(pipeline_decode_ragged, "aacg_pipeline_decode_ragged"); SYM(pipeline_submit_ragged, "aacg_pipeline_submit_ragged");
     SYM(pipeline_plan_builds, "aacg_pipeline_plan_builds");
+    SYM(pipeline_launch_counts, "aacg_pipeline_launch_counts");
     SYM(pipeline_walk_submit, "aacg_pipeline_walk_submit"); SYM(pipeline_walk_collect, "aacg_pipeline_walk_collect");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
@@ -509,7 +511,8 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     free(b);
 }
 
-/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions}, entries, counts) -> external */
+/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode}, entries, counts) -> external
+ * (planMode 1: device plans, aacg_pipeline_config.plan_mode) */
 static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
 {
     size_t argc = 3; napi_value argv[3], out;
@@ -533,6 +536,7 @@ static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
     cfg.output_kind = get_i32(env, argv[0], "outputKind", AACG_OUTPUT_F32);
     cfg.parse_options = get_i32(env, argv[0], "parseOptions", AACG_PARSE_REFERENCE_QUIRKS);
     cfg.lanes = get_i32(env, argv[0], "lanes", 0);
+    cfg.plan_mode = get_i32(env, argv[0], "planMode", 0);
     aacg_pipeline* p = NULL;
     int rc = L.pipeline_create(&cfg, (const aacg_code_entry*)de, (const uint32_t*)dc, &p);
     if (rc) {
@@ -958,6 +962,28 @@ static napi_value js_pipeline_plan_builds(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* pipelineLaunchCounts(pipeline) -> { shaped, chained, launches }: batches whose plan was shaped on the device, transform launches
+ * that continued their predecessor through the cross-launch cells, transform launches in all (aacgpu_tools.h) */
+static napi_value js_pipeline_launch_counts(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1], out, v;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_box* pb = box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle");
+    if (!pb) return NULL;
+    uint64_t n[3] = {0, 0, 0};
+    pthread_mutex_lock(&pb->lock);
+    const int rc = L.pipeline_launch_counts((const aacg_pipeline*)pb->ptr, &n[0], &n[1], &n[2]);
+    pthread_mutex_unlock(&pb->lock);
+    if (rc) { napi_throw_error(env, NULL, "aacgpu: aacg_pipeline_launch_counts failed"); return NULL; }
+    static const char* const names[3] = {"shaped", "chained", "launches"};
+    CHECK(env, napi_create_object(env, &out));
+    for (int i = 0; i < 3; i++) {
+        CHECK(env, napi_create_double(env, (double)n[i], &v));
+        CHECK(env, napi_set_named_property(env, out, names[i], v));
+    }
+    return out;
+}
+
 /* parseStatusString(code) -> the reference's message for a per-frame status */
 static napi_value js_parse_status_string(napi_env env, napi_callback_info info)
 {
@@ -988,6 +1014,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelineCollect", NULL, js_pipeline_collect, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineResetStream", NULL, js_pipeline_reset_stream, NULL, NULL, NULL, napi_default, NULL},
         {"pipelinePlanBuilds", NULL, js_pipeline_plan_builds, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelineLaunchCounts", NULL, js_pipeline_launch_counts, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkCollect", NULL, js_pipeline_walk_collect, NULL, NULL, NULL, napi_default, NULL},
     };

@@ -33,12 +33,13 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_submit", "aacg_pipeline_collect", "aacg_pipeline_set_wait_limit_ms", "aacg_pipeline_stream_layout",
                "aacg_set_wait_limit_ms", "aacg_parser_set_wait_limit_ms", "aacg_pipeline_info",
                "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_parse_walk", "aacg_parse_walk_device",
-               "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged"]
+               "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged",
+               "aacg_plan_create_shaped", "aacg_plan_shape_table", "aacg_plan_shape_launch"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
                  "aacg_debug_pipeline_order", "aacg_pipeline_streams_used", "aacg_debug_set_wait_mode", "aacg_debug_in_flight", "aacg_debug_stall",
-                 "aacg_pipeline_plan_builds"]
+                 "aacg_pipeline_plan_builds", "aacg_pipeline_launch_counts"]
 WAIT_SPIN, WAIT_YIELD, WAIT_SLEEP, WAIT_BLOCK = 0, 1, 2, 3
 # aacg_debug_set_route / aacg_debug_route flags
 DEBUG_ROUTE_UNFUSED_COUPLING, DEBUG_ROUTE_RECOMPUTE = 1, 8
@@ -83,7 +84,13 @@ class Config(C.Structure):
 class PipelineConfig(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("device_ordinal", C.c_int32), ("sample_index", C.c_int32), ("max_streams", C.c_int32),
                 ("channels", C.c_int32), ("max_frames", C.c_int32), ("output_kind", C.c_int32), ("parse_options", C.c_int32),
-                ("lanes", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("lanes", C.c_int32), ("plan_mode", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
+SHAPE_STREAM_DTYPE = np.dtype([("frame_first", "<u4"), ("frames", "<u4"), ("unit_first", "<u4"), ("frame_units", "<u4"), ("slot", "<u4"),
+                               ("run_first", "<u4"), ("link_first", "<u4"), ("rot", "<u4"), ("nch", "<u4"), ("reserved", "<u4", (3,))])
+assert SHAPE_STREAM_DTYPE.itemsize == 48
 
 
 class Batch(C.Structure):
@@ -225,6 +232,10 @@ def load_library(path=LIB_PATH):
                                               C.POINTER(C.c_uint64)]
     L.aacg_pipeline_plan_builds.argtypes = [C.c_void_p]
     L.aacg_pipeline_plan_builds.restype = C.c_uint64
+    L.aacg_pipeline_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.aacg_plan_create_shaped.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.aacg_plan_shape_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.aacg_plan_shape_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.aacg_pipeline_set_wait_limit_ms.argtypes = [C.c_void_p, C.c_uint32]
     L.aacg_pipeline_stream_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     _lib = L
@@ -416,19 +427,22 @@ PARSE_LAYOUT = 16          # AACG_PARSE_LAYOUT: a frame whose elements are not i
 
 class Pipeline:
     """aacg_pipeline: bytes in, PCM out — device front end and transform behind one call per batch, `lanes` batches in flight
-    (include/aacgpu.h).  channels = the streams' chanConfig (1..8)."""
+    (include/aacgpu.h).  channels = the streams' chanConfig (1..8).  device_plans: ONE plan shaped on the device for every batch
+    (aacg_pipeline_config.plan_mode 1) instead of a kept plan per batch shape: for feeds whose batches seldom repeat a shape."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
-                 parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None):
+                 parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
         entries, counts = np.ascontiguousarray(entries), np.ascontiguousarray(counts, np.uint32)
-        cfg = PipelineConfig(self.lib.aacg_abi_version(), device, sample_index, max_streams, channels, max_frames, output_kind, parse_options, lanes)
+        cfg = PipelineConfig(self.lib.aacg_abi_version(), device, sample_index, max_streams, channels, max_frames, output_kind, parse_options, lanes,
+                             1 if device_plans else 0)
         h = C.c_void_p()
         rc = self.lib.aacg_pipeline_create(C.byref(cfg), entries.ctypes.data, counts.ctypes.data, C.byref(h))
         if rc != 0:
-            raise AacgError(rc, "aacg_pipeline_create failed (no GPU?)")
+            raise AacgError(rc, "aacg_pipeline_create failed (no GPU?%s)" % (" or no room for the device plan's buffers: see stderr" if device_plans else ""))
+        self.device_plans = bool(device_plans)
         self.handle, self.channels, self.i16 = h, channels, output_kind == OUTPUT_I16
         self._keep = {}
 
@@ -477,6 +491,13 @@ class Pipeline:
     def plan_builds(self):
         """how many plans the pipeline has built (one per batch shape it had not kept)"""
         return int(self.lib.aacg_pipeline_plan_builds(self.handle))
+
+    def launch_counts(self):
+        """{"shaped": batches whose plan was shaped on the device, "chained": transform launches that continued their predecessor
+        through the cross-launch cells, "launches": transform launches} (aacg_pipeline_launch_counts)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.aacg_pipeline_launch_counts(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return {"shaped": int(a.value), "chained": int(b.value), "launches": int(c.value)}
 
     def _args(self, data, frames, slots, frames_per_stream, pcm):
         data = np.ascontiguousarray(data, np.uint8)
@@ -670,6 +691,19 @@ class Engine:
             return Plan(self, h, len(units))
         self._check(self.lib.aacg_plan_create(self.handle, units.ctypes.data, len(units), C.byref(h)))
         return Plan(self, h, len(units))
+
+    def plan_shaped(self, max_streams, max_frames, max_elems=1, n_sets=1):
+        """aacg_plan_create_shaped: a plan with a capacity instead of a shape, shaped on the device batch by batch."""
+        h = C.c_void_p()
+        self._check(self.lib.aacg_plan_create_shaped(self.handle, max_streams, max_frames, max_elems, n_sets, C.byref(h)))
+        return Plan(self, h, 0)
+
+    def plan_shape_table(self, plan, set_index, table, parse_channels):
+        """aacg_plan_shape_table: checks and completes the batch's table (SHAPE_STREAM_DTYPE, in place); -> the shape's plan units."""
+        assert table.dtype == SHAPE_STREAM_DTYPE and table.flags["C_CONTIGUOUS"]
+        n = C.c_uint32()
+        self._check(self.lib.aacg_plan_shape_table(self.handle, plan.handle, set_index, table.ctypes.data, len(table), parse_channels, C.byref(n)))
+        return int(n.value)
 
     def decode_device(self, plan, d_coeffs, d_meta, d_pcm, stream=0):
         """d_* are raw device addresses (e.g. torch.Tensor.data_ptr()); stream a hipStream_t handle or 0."""

@@ -573,6 +573,53 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
                                     aacg_parse_result* d_results, uint32_t max_units, const aacg_refresh_map* d_map,
                                     uint32_t set, uint32_t* d_refused, void* hip_stream);
 
+/* ---- a plan with a capacity instead of a shape: shaped on the device, batch by batch --------------------------------------
+ * On the resident route a plan is a pure function of the batch's shape — the stream slots in order, each one's frame count
+ * and element layout — and of the engine's overlap-buffer rotation.  aacg_plan_create builds it on the host, uploads it and
+ * keeps it per shape; a plan made by aacg_plan_create_shaped has device buffers for the LARGEST batch instead (at most
+ * max_streams streams of at most max_frames frames, max_elems decoded elements per frame; n_sets (1..8) sets of unit records,
+ * run and link tables — a set is shaped for the next batch while launches that read another are in flight — and the in-launch
+ * rendezvous cells, 16 KB per link and pipeline stream: none at max_frames <= 16), and every batch shapes one set with ONE
+ * small launch (aacg_plan_shape) from a table of 48 bytes per stream: no host planner, no allocation, no
+ * upload of O(units) bytes, no per-shape object to evict.  AACG_ERR_OUT_OF_MEMORY, with the sizes in aacg_last_error, if the
+ * buffers cannot be had.
+ * Per batch:  1. fill the caller's words of the table, one record per stream in the batch's order;
+ *             2. aacg_plan_shape_table: the engine checks them (AACG_ERR_CAPACITY / AACG_ERR_INVALID_ARG before anything is
+ *                enqueued or changed), adds run_first / link_first / rot from its current overlap rotation and books the
+ *                shape for `set`; *n_units: the plan units of the shape (0: no stream has a layout — nothing to launch);
+ *             3. bring the completed table to the device on hip_stream (e.g. with the batch's bytes);
+ *             4. aacg_plan_shape_launch on the same stream: the refresh map into d_map (max_units: the parser's elements per
+ *                frame), the unit records' planner part, run and link records into the set;
+ *             5. aacg_plan_refresh_from_parse_ex with d_map and `set`, then aacg_decode_pipelined: it launches the set shaped
+ *                last.  The caller guarantees that no launch still reads `set` (as for aacg_plan_set_unit_sets).
+ * Such a plan holds the rendezvous cut of the run table only: aacg_decode_pipelined serves it; aacg_decode_device,
+ * aacg_plan_refresh_units, aacg_spectral_device and aacg_plan_set_unit_sets refuse it (AACG_ERR_UNSUPPORTED), and it exists
+ * on AACG_INPUT_QUANT_I16 engines without optional stages only (the resident route's).
+ * Consecutive launches overlap through the cross-launch cells only if they were shaped from identical tables (the same slots
+ * in the same order, the same counts and layouts; the rotation words apart) with nothing in between; any other launch opens a
+ * new sequence behind everything in flight, as a launch of another plan object does. */
+typedef struct aacg_shape_stream {
+    /* the caller's words */
+    uint32_t frame_first;      /* the stream's first frame in the batch's packed order: the sum of `frames` over the streams before it */
+    uint32_t frames;           /* its frames in this batch, 1..max_frames                                                       */
+    uint32_t unit_first;       /* its first plan unit: the sum of frames * kept over the streams before it                      */
+    uint32_t frame_units;      /* bits 0..7: the elements of its frames (n); bits 8..15: how many of them are decoded (kept);
+                                  kept = 0: no layout yet, no unit (aacg_refresh_map.frame_units)                              */
+    uint32_t slot;             /* the stream slot: owner of the overlap state                                                   */
+    /* the engine's words (aacg_plan_shape_table) */
+    uint32_t run_first;        /* the stream's first run in generation order (chains by slot, then channel)                     */
+    uint32_t link_first;       /* ... and its first link                                                                        */
+    uint32_t rot;              /* 4 bits per channel 0..7: the overlap buffer that holds the channel's state                    */
+    /* the caller's again */
+    uint32_t nch;              /* 2 bits per element 0..7: its channels (1 or 2), in the frame's order                          */
+    uint32_t reserved[3];      /* zero                                                                                          */
+} aacg_shape_stream;
+int aacg_plan_create_shaped(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, aacg_plan** out);
+int aacg_plan_shape_table(aacg_engine* e, aacg_plan* p, uint32_t set, aacg_shape_stream* table, uint32_t n_streams,
+                          uint32_t parse_channels, uint32_t* n_units);
+int aacg_plan_shape_launch(aacg_engine* e, aacg_plan* p, const aacg_shape_stream* d_table, uint32_t max_units,
+                           aacg_refresh_map* d_map, void* hip_stream);
+
 /* The host's counterpart of aacg_plan_refresh_from_parse, for callers that parse on the CPU (the JavaScript front end) but
  * keep spectra and PCM on the device: batch after batch of the same streams keeps ONE plan, and the next batch's unit
  * records — same streams, frames, elements and PCM positions; new window sequences, shapes, grouping, flags and block
@@ -607,7 +654,13 @@ typedef struct aacg_pipeline_config {
     int32_t output_kind;       /* AACG_OUTPUT_*                                                             */
     int32_t parse_options;     /* AACG_PARSE_* (AACG_PARSE_REFERENCE_QUIRKS for what aac.js reads)          */
     int32_t lanes;             /* batches in flight at most, 1..8; 0 = 5 (ABI version 6)                     */
-    int32_t reserved[3];       /* zero                                                                      */
+    int32_t plan_mode;         /* 0: kept plans per batch shape (aacg_plan_create per new shape).  1: device plans — ONE plan
+                                  shaped on the device for every batch (aacg_plan_create_shaped): no plan build, no allocation
+                                  and no host wait on the submit path when a batch has a shape not seen before.  A scaffold for
+                                  one round: mode 0 is what existing callers get and what the tests compare mode 1's bits
+                                  against; once mode 1 is measured the switch and mode 0's path (plan_for, its LRU, the
+                                  stale-plan retry) go.  (reserved[0] until now: zero selects today's path)                */
+    int32_t reserved[2];       /* zero                                                                      */
 } aacg_pipeline_config;
 int  aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry* entries, const uint32_t counts[12], aacg_pipeline** out);
 void aacg_pipeline_destroy(aacg_pipeline* p);

@@ -35,6 +35,10 @@ uint64_t aacg_pipeline_chained(const aacg_engine* e);
 int aacg_pipeline_concurrent(const aacg_engine* e);
 /* How many plans the resident pipeline has built since it was made (one per batch shape it had not kept: aacg_pipeline_submit_ragged). */
 uint64_t aacg_pipeline_plan_builds(const aacg_pipeline* p);
+/* The resident pipeline's transform launches, in either plan mode: *shaped = batches whose plan was shaped on the device
+ * (aacg_plan_shape; 0 with plan_mode 0), *chained = launches that continued their predecessor through the cross-launch cells (the
+ * pipeline's engine's aacg_pipeline_chained), *launches = transform launches in all.  Any pointer may be null. */
+int aacg_pipeline_launch_counts(const aacg_pipeline* p, uint64_t* shaped, uint64_t* chained, uint64_t* launches);
 /* how many of the engine's streams the current pipelined sequence takes in turn (aacg_pipeline_streams, aacg_routes.h); 0 before the first */
 int aacg_pipeline_streams_used(const aacg_engine* e);
 /* How the host waits once a wait has lasted spin_us microseconds of polling (aacg_wait.h): 0 keep polling (round 5), 1 sched_yield

@@ -5,6 +5,11 @@
  * the other 0.5 ms goes" — run it under `rocprofv3 --kernel-trace --memory-copy-trace --stats` for the per-stage durations.
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
+ *                                         [--device-plans] [--new-shapes [--seed N]]
+ *
+ * --device-plans: aacg_pipeline_config.plan_mode 1 (one plan shaped on the device per batch instead of a kept plan per shape).
+ * --new-shapes: every batch a NEW seeded shape — each stream brings 1..F frames (aacg_pipeline_submit_ragged) — which is what a
+ * jittered feed gives the route; the line then also says how long the host spent inside the submit call alone, per batch.
  *
  * The batch: S streams x F frames taken from the ADTS file's frames in rotation (any sequence of frames decodes; the rate does
  * not depend on whether it is music).  The reference does this per stream and per frame in readChunk(), src/decoder.js:125-216.
@@ -21,6 +26,7 @@
 #include <vector>
 
 #include "../../include/aacgpu.h"
+#include "../../include/aacgpu_tools.h"
 
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -29,7 +35,8 @@ int main(int argc, char** argv)
     if (argc < 2) { std::fprintf(stderr, "usage: resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]\n"); return 2; }
     uint32_t S = 256, F = 16;
     int batches = 200, lanes = 3;
-    bool i16 = false, sync = false, pageable = false;
+    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false;
+    uint64_t seed = 1;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -40,6 +47,9 @@ int main(int argc, char** argv)
         else if (a == "--i16") i16 = true;
         else if (a == "--sync") sync = true;
         else if (a == "--pageable") pageable = true;
+        else if (a == "--device-plans") device_plans = true;
+        else if (a == "--new-shapes") new_shapes = true;
+        else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     std::vector<uint8_t> file;
@@ -73,6 +83,7 @@ int main(int argc, char** argv)
     std::memset(&cfg, 0, sizeof cfg);
     cfg.abi_version = AACG_ABI_VERSION; cfg.sample_index = (int32_t)sample_index; cfg.max_streams = (int32_t)S; cfg.channels = (int32_t)channels; cfg.max_frames = (int32_t)F;
     cfg.output_kind = i16 ? AACG_OUTPUT_I16 : AACG_OUTPUT_F32; cfg.parse_options = AACG_PARSE_REFERENCE_QUIRKS; cfg.lanes = sync ? 1 : lanes;
+    cfg.plan_mode = device_plans ? 1 : 0;
     aacg_pipeline* p = nullptr;
     int rc = aacg_pipeline_create(&cfg, entries.data(), counts, &p);
     if (rc) { std::fprintf(stderr, "aacg_pipeline_create: %d\n", rc); return 2; }
@@ -83,13 +94,33 @@ int main(int argc, char** argv)
     std::vector<aacg_parse_result> results((size_t)S * F * n_out);
     uint32_t refused[n_out] = {};
     auto fail = [&](const char* what, int code) { std::fprintf(stderr, "%s: %d %s\n", what, code, aacg_pipeline_last_error(p)); std::exit(2); };
+    /* --new-shapes: the batch's counts (1..F per stream, a new draw per batch) and its frame table, packed stream after stream */
+    std::vector<uint32_t> counts_of(S);
+    std::vector<aacg_parse_frame> ragged((size_t)S * F);
+    uint64_t lcg = seed * 0x9E3779B97F4A7C15ull + 1;
+    double submit_s = 0;
+    uint64_t fed = 0;                                       /* frames submitted */
     auto run = [&](int n) {
         std::vector<uint64_t> t((size_t)n);
         const int depth = sync ? 0 : lanes - 1;                 /* batches submitted ahead of the one being collected */
         for (int b = 0; b < n + depth; b++) {
             if (b < n) {
                 const int k = b % n_out;
-                if (sync) { if ((rc = aacg_pipeline_decode(p, bytes.data(), bytes.size(), frames.data(), slots.data(), S, F, out[k], &results[(size_t)k * S * F], &refused[k]))) fail("aacg_pipeline_decode", rc); }
+                if (new_shapes) {
+                    size_t at = 0;
+                    for (uint32_t s = 0; s < S; s++) {
+                        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+                        counts_of[s] = 1u + (uint32_t)((lcg >> 33) % F);
+                        std::memcpy(&ragged[at], &frames[(size_t)s * F], counts_of[s] * sizeof(aacg_parse_frame));
+                        at += counts_of[s];
+                    }
+                    const double t0 = now_s();
+                    if (sync) { if ((rc = aacg_pipeline_decode_ragged(p, bytes.data(), bytes.size(), ragged.data(), slots.data(), S, counts_of.data(), out[k], &results[(size_t)k * S * F], &refused[k]))) fail("aacg_pipeline_decode_ragged", rc); }
+                    else if ((rc = aacg_pipeline_submit_ragged(p, bytes.data(), bytes.size(), ragged.data(), slots.data(), S, counts_of.data(), out[k], &results[(size_t)k * S * F], &refused[k], &t[(size_t)b]))) fail("aacg_pipeline_submit_ragged", rc);
+                    submit_s += now_s() - t0;
+                    fed += at;
+                }
+                else if (sync) { if ((rc = aacg_pipeline_decode(p, bytes.data(), bytes.size(), frames.data(), slots.data(), S, F, out[k], &results[(size_t)k * S * F], &refused[k]))) fail("aacg_pipeline_decode", rc); }
                 else if ((rc = aacg_pipeline_submit(p, bytes.data(), bytes.size(), frames.data(), slots.data(), S, F, out[k], &results[(size_t)k * S * F], &refused[k], &t[(size_t)b]))) fail("aacg_pipeline_submit", rc);
             }
             if (!sync && b >= depth && (rc = aacg_pipeline_collect(p, t[(size_t)(b - depth)]))) fail("aacg_pipeline_collect", rc);
@@ -97,7 +128,11 @@ int main(int argc, char** argv)
     };
     run(10);                                                /* warm: plans, staging, page-locked memory */
     std::vector<double> ms;
+    submit_s = 0; fed = 0;
     for (int r = 0; r < 5; r++) { const double t0 = now_s(); run(batches); ms.push_back((now_s() - t0) * 1e3 / batches); }
+    const double submit_ms = submit_s * 1e3 / (5.0 * batches);
+    uint64_t shaped = 0, chained = 0, launches = 0;
+    (void)aacg_pipeline_launch_counts(p, &shaped, &chained, &launches);
     std::sort(ms.begin(), ms.end());
     bool finite = true, nonzero = false;
     uint32_t bad = 0;
@@ -106,10 +141,12 @@ int main(int argc, char** argv)
     else { const int16_t* w = (const int16_t*)out[0]; for (size_t i = 0; i < pcm_bytes / 2; i += 97) nonzero = nonzero || w[i] != 0; }
     std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", "
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
-                "\"pcm_GBs\": %.2f, \"refused\": %u, \"output_ok\": %s}\n",
+                "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
+                "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                pageable ? "pageable" : "page-locked", bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (double)S * F / (ms[ms.size() / 2] * 1e-3),
-                (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, bad, (finite && nonzero && !bad) ? "true" : "false");
+                pageable ? "pageable" : "page-locked", bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
+                new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
     return (finite && nonzero && !bad) ? 0 : 1;
 }

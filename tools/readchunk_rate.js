@@ -4,7 +4,8 @@
  *   node tools/readchunk_rate.js --streams 256 [repeats]     N decoders on one SharedEngine (cross-stream batches), read round robin,
  *                                                            next to N decoders with an engine each: engine time per frame, checksum;
  *                                                            and on a RESIDENT SharedEngine (front end on the device too: one native
- *                                                            call per flush, bytes in, PCM out)
+ *                                                            call per flush, bytes in, PCM out; --device-plans: with
+ *                                                            SharedEngine({ devicePlans: true }))
  * A long ADTS stream (the committed tests/golden/streams/stereo48.aac repeated) through
  *   - GpuAACDecoder with the JavaScript front end (parse on the CPU, transform on the GPU),
  *   - GpuAACDecoder with the device front end (parse and transform on the GPU),
@@ -13,14 +14,16 @@
  *                                                            the same streams as MP4 chunks (ADTS headers cut off, N samples per
  *                                                            feedPacket buffer) on a SharedEngine: the parsing route, and the
  *                                                            resident route with { residentPackets: true }; one checksum
- *   node tools/readchunk_rate.js --arrival jitter [--ragged] [--streams 256] [--rounds 60] [--seed 7] [--ring K]
+ *   node tools/readchunk_rate.js --arrival jitter [--ragged] [--device-plans] [--streams 256] [--rounds 60] [--seed 7] [--ring K]
  *                                                            jittered arrival (tests/js/jitter_feed.js): N stereo decoders on one
  *                                                            resident SharedEngine (overlap on), each fed a seeded random 1..16
  *                                                            frames per round, one reader in ten paused for a few rounds, streams
  *                                                            ending and starting over now and then; frames/s, flushes, frames per
  *                                                            flush, plans built per 1000 flushes, host time per flush, and a
  *                                                            checksum of every stream's PCM (equal with and without --ragged for
- *                                                            one seed).  --ragged: SharedEngine({ ragged: true })
+ *                                                            one seed).  --ragged: SharedEngine({ ragged: true });
+ *                                                            --device-plans: SharedEngine({ devicePlans: true }) — one plan per
+ *                                                            pipeline, shaped on the device for every flush
  * The GPU lines need the built engine and a GPU; without one they are reported as null. */
 'use strict';
 const fs = require('fs'), path = require('path');
@@ -34,18 +37,20 @@ if (arrivalAt >= 0) {
     if (argv0[arrivalAt + 1] !== 'jitter') throw new Error('--arrival: jitter is the one arrival mode');
     const opt = function (name, dflt) { const i = argv0.indexOf(name); return i >= 0 ? parseInt(argv0[i + 1], 10) : dflt; };
     const ragged = argv0.indexOf('--ragged') >= 0, S = opt('--streams', 256), rounds = opt('--rounds', 60), seed = opt('--seed', 7), ring = opt('--ring', 0);
+    const devicePlans = argv0.indexOf('--device-plans') >= 0;
     const jitter = require(path.join(root, 'tests', 'js', 'jitter_feed.js'));
     const one = new Uint8Array(fs.readFileSync(path.join(root, 'tests', 'golden', 'streams', fileName + '.aac'))), reps = 64;
     const bytes = new Uint8Array(one.length * reps);
     for (let i = 0; i < reps; i++) bytes.set(one, i * one.length);
-    const res = { mode: 'arrival jitter', ragged: ragged, stream: fileName + '.aac x ' + reps, streams: S, rounds: rounds, seed: seed, pcm_ring: ring };
+    const res = { mode: 'arrival jitter', ragged: ragged, device_plans: devicePlans, stream: fileName + '.aac x ' + reps, streams: S, rounds: rounds, seed: seed, pcm_ring: ring };
     try {
-        const sh = new host.SharedEngine({ maxStreams: S, maxChannels: 8, resident: true, ragged: ragged, lookahead: 16, pcmRing: ring });
+        const sh = new host.SharedEngine({ maxStreams: S, maxChannels: 8, resident: true, ragged: ragged, devicePlans: devicePlans, lookahead: 16, pcmRing: ring });
         const r = jitter.run({ host: host, shared: sh, sources: [{ bytes: bytes, list: host.adts.frames(bytes) }], streams: S, rounds: rounds, seed: seed });
-        const flushes = sh.stats.batches, builds = sh.planBuilds();
+        const flushes = sh.stats.batches, builds = sh.planBuilds(), launched = sh.launchCounts();
         Object.assign(res, { frames: r.frames, seconds: +r.seconds.toFixed(3), frames_per_s: Math.round(r.frames / r.seconds), decoders_made: r.instances,
                              flushes: flushes, frames_per_flush: +(sh.stats.frames / flushes).toFixed(1), plan_builds: builds,
                              plan_builds_per_1000_flushes: +(1000 * builds / flushes).toFixed(1),
+                             batches_shaped_on_device: launched.shaped, launches_continued: launched.chained,
                              host_ms_per_flush: +(Number(sh.stats.flushNs) / 1e6 / flushes).toFixed(3),
                              native_call_ms_per_flush: +(Number(sh.stats.engineNs) / 1e6 / flushes).toFixed(3),
                              checksum: r.sums.reduce(function (a, b) { return a + b; }, 0) });
@@ -55,7 +60,7 @@ if (arrivalAt >= 0) {
 }
 const mp4aMode = argv0.indexOf('--mp4a') >= 0, perAt = argv0.indexOf('--samples-per-packet');
 const perPacket = perAt >= 0 ? parseInt(argv0[perAt + 1], 10) : 16;
-const argv = argv0.filter(function (a, i) { return (fileAt < 0 || (i !== fileAt && i !== fileAt + 1)) && a !== '--mp4a' && (perAt < 0 || (i !== perAt && i !== perAt + 1)); });
+const argv = argv0.filter(function (a, i) { return (fileAt < 0 || (i !== fileAt && i !== fileAt + 1)) && a !== '--mp4a' && a !== '--device-plans' && (perAt < 0 || (i !== perAt && i !== perAt + 1)); });
 const nStreams = argv[0] === '--streams' ? parseInt(argv[1], 10) : 0;
 const repeats = parseInt((nStreams ? argv[2] : argv[0]) || (nStreams ? '4' : '400'), 10);
 const one = new Uint8Array(fs.readFileSync(path.join(root, 'tests', 'golden', 'streams', fileName + '.aac')));
@@ -98,7 +103,8 @@ function many(shared, lookahead, pcmRing, overlap, yieldEvery, done) {
             eng.decodeBatch = function () { const t = process.hrtime.bigint(); try { return inner.apply(null, arguments); } finally { engineNs += process.hrtime.bigint() - t; batches++; } };
             return eng;
         };
-        const sh = shared ? new host.SharedEngine({ maxStreams: nStreams, maxChannels: Math.max(2, nChannels), resident: resident, lookahead: lookahead, pcmRing: pcmRing | 0, overlap: !!overlap }) : null;
+        const sh = shared ? new host.SharedEngine({ maxStreams: nStreams, maxChannels: Math.max(2, nChannels), resident: resident, lookahead: lookahead, pcmRing: pcmRing | 0, overlap: !!overlap,
+                                                 devicePlans: argv0.indexOf('--device-plans') >= 0 }) : null;
         const finish = function (t0, n, sum) {
             if (resident) { engineNs = sh.stats.engineNs; batches = sh.stats.batches; }       // wall time inside the one native call per flush
             const s = Number(process.hrtime.bigint() - t0) / 1e9, es = Number(engineNs) / 1e9;

@@ -6,7 +6,9 @@ int16 or f32 PCM all drawn per round; now and then a stream is reset and starts 
 records aacg_parse_batch parsed from the same bytes (the parser itself is pinned by the reference on the same corpus,
 tests/test_corpus.py), frame by frame with the overlap state carried along; a malformed frame must come back with the status
 whose text is the reference's message and must not disturb its neighbours in the batch.
-Usage: python tools/soak_resident.py [seconds=120]"""
+Usage: python tools/soak_resident.py [seconds=120] [kept|device|mixed]
+The second argument is the plan mode of the pipelines (aacg_pipeline_config.plan_mode): kept plans per batch shape (the default),
+device plans, or one of the two drawn per round (from a generator of its own: the rounds are the same in every mode)."""
 import os
 import subprocess
 import sys
@@ -23,6 +25,10 @@ import orc  # noqa: E402
 import test_corpus as T  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
+plans = sys.argv[2] if len(sys.argv) > 2 else "kept"
+assert plans in ("kept", "device", "mixed"), plans
+plan_rng = np.random.default_rng(8)
+shaped_rounds = 0
 o = orc.load()
 rng = np.random.default_rng(20261003)
 d = tempfile.mkdtemp()
@@ -63,8 +69,10 @@ while time.time() - t0 < budget:
     Fmax = int(rng.integers(1, 5))
     lanes = int(rng.integers(1, 7))
     i16 = bool(rng.integers(0, 3) == 0)
+    device_plans = plans == "device" or (plans == "mixed" and bool(plan_rng.integers(0, 2)))
+    shaped_rounds += device_plans
     pipe = aacgpu.Pipeline(channels=C, max_streams=S, max_frames=Fmax, sample_index=si, lanes=lanes,
-                           output_kind=aacgpu.OUTPUT_I16 if i16 else aacgpu.OUTPUT_F32)
+                           output_kind=aacgpu.OUTPUT_I16 if i16 else aacgpu.OUTPUT_F32, device_plans=device_plans)
     base = np.cumsum([0] + [len(m["data"]) for m in chosen]).astype(np.uint32)
     data = np.concatenate([m["data"] for m in chosen])
     usable = [m["e"]["decoded"] + (1 if m["e"]["error"] else 0) for m in chosen]      # frames of each stream that go in
@@ -132,5 +140,5 @@ while time.time() - t0 < budget:
             resets += 1
     pipe.close()
     rounds += 1
-print("soak_resident OK: %.0f s, %d pipelines, %d batches, %d frames (%d of them malformed: refused with the reference's message), %d resets; "
-      "worst error %.2f of the tolerance (f32: 1e-5 x max(1, 4 rms) per sample; int16: that + one step + 3e-6 of the frame's peak)" % (time.time() - t0, rounds, batches, frames, refused_frames, resets, worst))
+print("soak_resident OK (plans: %s, %d pipelines with device plans): %.0f s, %d pipelines, %d batches, %d frames (%d of them malformed: refused with the reference's message), %d resets; "
+      "worst error %.2f of the tolerance (f32: 1e-5 x max(1, 4 rms) per sample; int16: that + one step + 3e-6 of the frame's peak)" % (plans, shaped_rounds, time.time() - t0, rounds, batches, frames, refused_frames, resets, worst))
