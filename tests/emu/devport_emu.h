@@ -8,6 +8,21 @@
  * GPU (LDS is poisoned with NaN bits before every workgroup, so a read of a slot nobody wrote
  * is visible too).  What it cannot show: compiler/hardware issues (the -m gpu tests do).
  * Never compiled into the product library; selected by -DAACG_EMU_BUILD in tests/emu/Makefile.
+ *
+ * Schedule-controlled mode (emu_set_schedule, emu_lib.cpp; off by default, and then nothing here differs from the above): ONE
+ * wave runs at a time.  The primitives through which waves and workgroups interact — dp_flag_set / dp_flag_wait(_ge),
+ * dp_block_sync(_lds), dp_g_load_* / dp_g_store_* / dp_g_cas_u64, dp_vm_drain — are scheduling points: a lane that reaches one
+ * parks there BEFORE the operation takes effect; when no lane of the wave runs any more (each is parked, in the wave's barrier or
+ * has returned) the wave gives up its turn and the controller picks the next runnable wave by the policy.  A lane in
+ * dp_flag_wait is runnable once the flag holds the value: the controller evaluates that, nobody spins.
+ * What is deterministic: the order of scheduling points, and with it every value any wave can see, for a given (policy, seed).
+ * Where only lane 0 executes a dp_flag_set, the other lanes run on to their next barrier or scheduling point before the wave
+ * gives up its turn, so their plain loads and stores behind the set execute before the set takes effect — always the same ones;
+ * lockstep hardware would have issued the set first.  The order in which the OS runs the lanes of the one running wave between
+ * two such points is not deterministic, and cannot matter: lanes of a wave only interact at the wave's barrier.
+ *
+ * emu_set_fault breaks a primitive on purpose (a wait that does not wait, a compare-and-swap that does not compare): the
+ * schedule tests use it to show that they would see a broken hand-off.  The kernel source carries no such switch.
  */
 #ifndef AACG_DEVPORT_EMU_H
 #define AACG_DEVPORT_EMU_H
@@ -29,8 +44,10 @@ struct alignas(16) dpi4 { int x, y, z, w; };
 struct alignas(8)  dpu2 { uint32_t x, y; };
 typedef float dpv2 __attribute__((vector_size(8)));
 
+struct emu_sched_wave;
 struct emu_wave {
     pthread_barrier_t bar;
+    emu_sched_wave* sw;                    /* schedule-controlled mode: this wave's record with the controller; else NULL */
     float shfl[64][16];
     double shfl_d[64][16];
 };
@@ -39,6 +56,8 @@ struct emu_block {
     unsigned char* lds;
     size_t lds_bytes;
     int block_id;
+    int threads, sync_arrived, sync_gen;   /* schedule-controlled mode: the workgroup barrier as a condition the controller evaluates */
+    int flags_off;                         /* ... and where the run body's flags begin in LDS (known from the first dp_flag_set; -1 before) */
 };
 struct emu_lane_ctx {
     int lane, wave;
@@ -47,16 +66,60 @@ struct emu_lane_ctx {
 };
 extern thread_local emu_lane_ctx g_emu;
 
+/* schedule-controlled mode and fault injection (emu_lib.cpp) */
+enum { EMU_SP_NONE, EMU_SP_FLAG_SET, EMU_SP_FLAG_WAIT, EMU_SP_FLAG_WAIT_GE, EMU_SP_BLOCK_SYNC, EMU_SP_G_LOAD_U64, EMU_SP_G_CAS, EMU_SP_G_STORE,
+       EMU_SP_G_LOAD, EMU_SP_DRAIN };
+enum { EMU_FAULT_NONE, EMU_FAULT_SKIP_WAIT, EMU_FAULT_EARLY_SET, EMU_FAULT_BLIND_CAS, EMU_FAULT_LOST_SET };
+#ifdef AACG_EMU_SCHEDULER                  /* tests/emu/emu_lib.cpp, which has the controller; the other users of this header run as ever */
+extern int g_emu_fault_kind, g_emu_fault_lo, g_emu_fault_hi, g_emu_fault_wave;
+void emu_sched_wave_barrier();                                   /* the wave's barrier; the last running lane gives up the wave's turn */
+void emu_sched_point(int kind, const void* addr, long long val); /* park; returns when the wave has the turn and the lane's condition holds */
+void emu_sched_note(int kind, const void* addr);                 /* a load or swap of a rendezvous state word has taken effect */
+#define EMU_SCHEDULED() (g_emu.w->sw != nullptr)
+#else
+static const int g_emu_fault_kind = EMU_FAULT_NONE, g_emu_fault_lo = 0, g_emu_fault_hi = 0, g_emu_fault_wave = -1;
+DP_DEVICE void emu_sched_wave_barrier() {}
+DP_DEVICE void emu_sched_point(int, const void*, long long) {}
+DP_DEVICE void emu_sched_note(int, const void*) {}
+#define EMU_SCHEDULED() false
+#endif
+DP_DEVICE void emu_wave_bar() { if (EMU_SCHEDULED()) emu_sched_wave_barrier(); else pthread_barrier_wait(&g_emu.w->bar); }
+DP_DEVICE void emu_sp(int kind, const void* addr = nullptr, long long val = 0) { if (EMU_SCHEDULED()) emu_sched_point(kind, addr, val); }
+DP_DEVICE bool emu_fault_flag(const int* flag)
+{
+    const long off = (long)((const unsigned char*)flag - g_emu.b->lds);
+    return off >= g_emu_fault_lo && off < g_emu_fault_hi;
+}
+/* skip_wait: waits on flags in LDS bytes [lo, hi) return at once; early_set: the same for the one waiting wave — the flag is
+ * treated as set from the start for that waiter; lost_set: such a flag is never raised (the waiters then wait for ever: in
+ * schedule-controlled mode a deadlock report, otherwise a spin without end) */
+DP_DEVICE bool emu_fault_skips(const int* flag)
+{
+    if (g_emu_fault_kind != EMU_FAULT_SKIP_WAIT && g_emu_fault_kind != EMU_FAULT_EARLY_SET) return false;
+    if (!emu_fault_flag(flag)) return false;
+    return g_emu_fault_kind == EMU_FAULT_SKIP_WAIT || g_emu_fault_wave < 0 || g_emu_fault_wave == g_emu.wave;
+}
+
 DP_DEVICE int dp_tid()   { return g_emu.wave * 64 + g_emu.lane; }
 DP_DEVICE int dp_lane()  { return g_emu.lane; }
 DP_DEVICE int dp_wave()  { return g_emu.wave; }
 DP_DEVICE int dp_block() { return g_emu.b->block_id; }
 DP_DEVICE int dp_uniform(int v) { return v; }
-DP_DEVICE void dp_wave_sync()  { pthread_barrier_wait(&g_emu.w->bar); }
-DP_DEVICE void dp_block_sync() { pthread_barrier_wait(&g_emu.b->bar); }
-DP_DEVICE void dp_block_sync_lds() { pthread_barrier_wait(&g_emu.b->bar); }
-DP_DEVICE void dp_flag_set(int* flag, int v) { __atomic_store_n(flag, v, __ATOMIC_RELEASE); }
-DP_DEVICE void dp_flag_wait(int* flag, int v) { while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != v) sched_yield(); }
+DP_DEVICE void dp_wave_sync()  { emu_wave_bar(); }
+DP_DEVICE void dp_block_sync() { if (EMU_SCHEDULED()) emu_sched_point(EMU_SP_BLOCK_SYNC, nullptr, 0); else pthread_barrier_wait(&g_emu.b->bar); }
+DP_DEVICE void dp_block_sync_lds() { dp_block_sync(); }
+DP_DEVICE void dp_flag_set(int* flag, int v)
+{
+    emu_sp(EMU_SP_FLAG_SET, flag, v);
+    if (g_emu_fault_kind == EMU_FAULT_LOST_SET && emu_fault_flag(flag)) return;
+    __atomic_store_n(flag, v, __ATOMIC_RELEASE);
+}
+DP_DEVICE void dp_flag_wait(int* flag, int v)
+{
+    if (emu_fault_skips(flag)) { emu_sp(EMU_SP_NONE); return; }
+    if (EMU_SCHEDULED()) { emu_sched_point(EMU_SP_FLAG_WAIT, flag, v); return; }
+    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != v) sched_yield();
+}
 DP_DEVICE void dp_setprio(int) {}
 
 template <int N>
@@ -64,9 +127,9 @@ DP_DEVICE void dp_shfl(float (&v)[N], int src)
 {
     static_assert(N <= 16, "shuffle payload");
     for (int i = 0; i < N; i++) g_emu.w->shfl[g_emu.lane][i] = v[i];
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     for (int i = 0; i < N; i++) v[i] = g_emu.w->shfl[src][i];
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
 }
 
 template <int N> DP_DEVICE void dp_mirror8_valu(const float (&in)[N], float (&out)[N]) { for (int i = 0; i < N; i++) out[i] = in[i]; dp_shfl(out, g_emu.lane ^ 7); }
@@ -86,9 +149,9 @@ DP_DEVICE void dp_window_mirror(const float (&src)[8], const float (&w)[4], floa
 DP_DEVICE void dp_row_gather12(float v, float (&out)[12])
 {
     g_emu.w->shfl[g_emu.lane][0] = v;
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     for (int k = 0; k < 12; k++) out[k] = g_emu.w->shfl[(g_emu.lane & ~15) | k][0];
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
 }
 
 template <int N>
@@ -96,9 +159,9 @@ DP_DEVICE void dp_shfl(double (&v)[N], int src)
 {
     static_assert(N <= 16, "shuffle payload");
     for (int i = 0; i < N; i++) g_emu.w->shfl_d[g_emu.lane][i] = v[i];
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     for (int i = 0; i < N; i++) v[i] = g_emu.w->shfl_d[src][i];
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
 }
 
 /* one complex value per dpv2 (devport.h) */
@@ -112,20 +175,36 @@ DP_DEVICE dpv2 dp_cmul(dpv2 a, dpv2 w)
     r[1] = fmaf(a[0], w[1], a[1] * w[0]);
     return r;
 }
-DP_DEVICE void dp_flag_wait_ge(int* flag, int v) { while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) < v) sched_yield(); }
+DP_DEVICE void dp_flag_wait_ge(int* flag, int v)
+{
+    if (emu_fault_skips(flag)) { emu_sp(EMU_SP_NONE); return; }
+    if (EMU_SCHEDULED()) { emu_sched_point(EMU_SP_FLAG_WAIT_GE, flag, v); return; }
+    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) < v) sched_yield();
+}
 /* the run-to-run rendezvous through global memory (devport.h): plain host memory here */
 typedef unsigned long long dp_u64;
-DP_DEVICE dp_u64 dp_g_load_u64(const dp_u64* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
+DP_DEVICE dp_u64 dp_g_load_u64(const dp_u64* p)
+{
+    emu_sp(EMU_SP_G_LOAD_U64, p);
+    const dp_u64 v = __atomic_load_n(p, __ATOMIC_ACQUIRE);
+    if (EMU_SCHEDULED()) emu_sched_note(EMU_SP_G_LOAD_U64, p);
+    return v;
+}
 DP_DEVICE bool dp_g_cas_u64(dp_u64* p, dp_u64 expected, dp_u64 desired)
 {
-    return __atomic_compare_exchange_n(p, &expected, desired, false, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE);
+    emu_sp(EMU_SP_G_CAS, p, (long long)desired);
+    bool won = true;
+    if (g_emu_fault_kind == EMU_FAULT_BLIND_CAS) __atomic_store_n(p, desired, __ATOMIC_RELEASE);       /* blind_cas: a plain store that reports success */
+    else won = __atomic_compare_exchange_n(p, &expected, desired, false, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE);
+    if (EMU_SCHEDULED()) emu_sched_note(EMU_SP_G_CAS, p);
+    return won;
 }
-DP_DEVICE void dp_g_store_f2(float* p, float a, float b) { p[0] = a; p[1] = b; }
-DP_DEVICE dpf2 dp_g_load_f2(const float* p) { dpf2 v; v.x = p[0]; v.y = p[1]; return v; }
-DP_DEVICE float dp_g_load_f1(const float* p) { return *p; }
-DP_DEVICE void dp_g_store_u64(dp_u64* p, dp_u64 v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
-DP_DEVICE unsigned dp_g_load_u32(const unsigned* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-DP_DEVICE void dp_g_store_u32(unsigned* p, unsigned v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+DP_DEVICE void dp_g_store_f2(float* p, float a, float b) { emu_sp(EMU_SP_G_STORE, p); p[0] = a; p[1] = b; }
+DP_DEVICE dpf2 dp_g_load_f2(const float* p) { emu_sp(EMU_SP_G_LOAD, p); dpf2 v; v.x = p[0]; v.y = p[1]; return v; }
+DP_DEVICE float dp_g_load_f1(const float* p) { emu_sp(EMU_SP_G_LOAD, p); return *p; }
+DP_DEVICE void dp_g_store_u64(dp_u64* p, dp_u64 v) { emu_sp(EMU_SP_G_STORE, p); __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+DP_DEVICE unsigned dp_g_load_u32(const unsigned* p) { emu_sp(EMU_SP_G_LOAD, p); return __atomic_load_n(p, __ATOMIC_RELAXED); }
+DP_DEVICE void dp_g_store_u32(unsigned* p, unsigned v) { emu_sp(EMU_SP_G_STORE, p); __atomic_store_n(p, v, __ATOMIC_RELAXED); }
 DP_DEVICE unsigned dp_cu_id() { return 0; }
 /* scalar loads in a spelled-out batch (devport.h): here plain reads */
 struct dp_su4 { unsigned v[4]; unsigned operator[](int i) const { return v[i]; } unsigned& operator[](int i) { return v[i]; } };
@@ -135,14 +214,14 @@ DP_DEVICE dp_su4 dp_sload4(const void* p) { dp_su4 r; memcpy(r.v, p, 16); return
 DP_DEVICE dp_su8 dp_sload8(const void* p) { dp_su8 r; memcpy(r.v, p, 32); return r; }
 DP_DEVICE void dp_swait(dp_su8&, dp_su4&, unsigned&, unsigned&, unsigned&) {}
 DP_DEVICE dp_su8 dp_sload8(const void* p, const void*) { return dp_sload8(p); }
-DP_DEVICE void dp_vm_drain() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
+DP_DEVICE void dp_vm_drain() { emu_sp(EMU_SP_DRAIN); __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 /* lane 0's value in every lane */
 DP_DEVICE dp_u64 dp_first_u64(dp_u64 v)
 {
     if (g_emu.lane == 0) memcpy(&g_emu.w->shfl_d[0][0], &v, 8);
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     dp_u64 r; memcpy(&r, &g_emu.w->shfl_d[0][0], 8);
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     return r;
 }
 
@@ -151,10 +230,10 @@ DP_DEVICE int dp_lds_atomic_add(int* p, int v) { return __atomic_fetch_add(p, v,
 DP_DEVICE bool dp_any(bool p)
 {
     g_emu.w->shfl[g_emu.lane][0] = p ? 1.0f : 0.0f;
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     bool r = false;
     for (int i = 0; i < 64; i++) r = r || g_emu.w->shfl[i][0] != 0.0f;
-    pthread_barrier_wait(&g_emu.w->bar);
+    emu_wave_bar();
     return r;
 }
 

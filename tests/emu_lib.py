@@ -22,6 +22,15 @@ def new_pool(streams, channels):
     return np.zeros((streams, channels, OV_BUFFERS, 1024), np.float32), np.zeros(streams * channels, np.uint8)
 
 
+POLICIES = {"natural": 1, "reversed": 2, "straggler": 3, "sprinter": 4, "random": 5, "cell": 6}     # emu_set_schedule (tests/emu/emu_lib.cpp)
+FAULTS = {"skip_wait": 1, "early_set": 2, "blind_cas": 3, "lost_set": 4}                                             # emu_set_fault
+ERR_DEADLOCK = -9001
+
+
+class EmuDeadlock(RuntimeError):
+    """A decode in schedule-controlled mode in which no wave could run any more: the text names who waited for what."""
+
+
 class Emu:
     def __init__(self, target="libaacg_emu.so"):
         import fcntl
@@ -46,9 +55,55 @@ class Emu:
         L.emu_get_windows.argtypes = [C.c_int, C.c_void_p]
         L.emu_get_iq_sf.argtypes = [C.c_void_p, C.c_void_p]
         L.emu_last_keys.argtypes = [C.c_void_p, C.c_int]
+        L.emu_set_schedule.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.emu_sched_steps.restype = C.c_long
+        L.emu_sched_trace.argtypes = [C.c_void_p, C.c_int]
+        L.emu_sched_cells.argtypes = [C.c_void_p, C.c_void_p]
+        L.emu_set_fault.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.emu_flags_offset.argtypes = [C.c_int, C.c_int]
 
     def error(self):
         return self.lib.emu_last_error().decode()
+
+    def set_schedule(self, schedule, span=0):
+        """Schedule-controlled mode for the run kernels of later decodes (tests/emu/devport_emu.h): one wave at a time, the next
+        one picked by the policy.  schedule: None (off: the default), ("natural",), ("reversed",), ("straggler", k), ("sprinter", k),
+        ("random", seed, d) — span: the turns of a run of the same decode (sched_steps), from which the d change points are
+        drawn —, ("cell", a, variant) with variant 1..5 (emu_set_schedule in tests/emu/emu_lib.cpp)."""
+        if schedule is None:
+            self.lib.emu_set_schedule(0, 0, 0, 0, 0)
+        elif schedule[0] == "random":
+            self.lib.emu_set_schedule(POLICIES["random"], 0, schedule[2], schedule[1], span)
+        else:
+            a, b = (list(schedule[1:]) + [0, 0])[:2]
+            self.lib.emu_set_schedule(POLICIES[schedule[0]], a, b, 0, span)
+
+    def sched_steps(self):
+        """turns the controller granted in the last decode"""
+        return int(self.lib.emu_sched_steps())
+
+    def sched_cells(self):
+        """(in-launch rendezvous cells, chains) of the last decode's plan: cell(a, .) takes a below the first for decode(), below
+        chains * (launches - 1) for decode_pipelined()"""
+        a, b = C.c_int(0), C.c_int(0)
+        self.lib.emu_sched_cells(C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def set_fault(self, kind=None, lo=0, hi=0, wave=-1):
+        """Breaks an emulated primitive for later decodes (None: mends it).  "skip_wait": dp_flag_wait on flags in LDS bytes
+        [lo, hi) returns at once; "early_set": the same for waiting wave `wave` only (the flag counts as set from the start for
+        that waiter); "lost_set": dp_flag_set on such a flag does nothing; "blind_cas": dp_g_cas_u64 stores without comparing
+        and reports success."""
+        self.lib.emu_set_fault(FAULTS[kind] if kind else 0, lo, hi, wave)
+
+    def flags_offset(self, quant, half):
+        """LDS byte offset of the run body's flags (flags[task], then — eight-wave body — flags[16 + task])"""
+        return int(self.lib.emu_flags_offset(1 if quant else 0, 1 if half else 0))
+
+    def _raise(self, what, rc):
+        if rc == ERR_DEADLOCK:
+            raise EmuDeadlock(self.error())
+        raise RuntimeError("%s rc=%d: %s" % (what, rc, self.error()))
 
     def decode(self, units, coeffs, meta, n_pcm, pool, parity, sample_index=3, tns=None, pns=False, int16_out=False, cce=None, staged=False, unfused=False, rv=1,
                pipelined=False, poison=None):
@@ -82,7 +137,7 @@ class Emu:
         self.lib.emu_set_rv(1)
         self.lib.emu_set_pipelined(0)
         if rc:
-            raise RuntimeError("emu_decode rc=%d: %s" % (rc, self.error()))
+            self._raise("emu_decode", rc)
         return pcm
 
     def last_keys(self):
@@ -126,7 +181,7 @@ class Emu:
         rc = self.lib.emu_decode_pipelined(kind, sample_index, pool.shape[0], pool.shape[1], units.ctypes.data, len(units), n, cp, mp, pp, n_pcm,
                                            pool.ctypes.data, parity.ctypes.data, cells.ctypes.data, heads.ctypes.data, order, epoch_in, C.byref(last), streams)
         if rc:
-            raise RuntimeError("emu_decode_pipelined rc=%d: %s" % (rc, self.error()))
+            self._raise("emu_decode_pipelined", rc)
         return pcm, last.value
 
     def plan(self, units, max_streams, max_channels, parity=None, sample_index=3):

@@ -1,7 +1,8 @@
 /*
  * half_emu.cpp — the lane emulator (tests/emu/emu_lib.cpp, unchanged) with its rendezvous run kernels of f32 PCM on the
  * eight-wave run body (imdct_run_body<..., NW = AACG_HALF_WAVES>, the body behind aacg_imdct_run_quant_rv), for
- * tests/test_half_runs_emu.py, which compiles it (with tests/emu/devport_emu.h) into a library of its own.  TESTS ONLY.
+ * tests/test_half_runs_emu.py and tests/test_schedules_emu.py: compiled (with tests/emu/devport_emu.h) into a library of its
+ * own, libaacg_emu_half.so (tests/emu/Makefile).  TESTS ONLY.
  * The emulator launches every run kernel with sixteen waves; here waves 0..7 run the eight-wave body, each taking two frames of
  * the run, and waves 8..15 take part in its one workgroup barrier and leave, so the body sees eight working waves and touches
  * no LDS beyond AACG_HALF_LDS_BYTES.  Every other kernel is the emulator's own.
@@ -9,6 +10,7 @@
  * body then sees, so that its profiling paths are emulated too; 0, the default, is the library that ships.
  */
 #define AACG_PROFILE
+#define AACG_EMU_SCHEDULER              /* devport_emu.h: emu_lib.cpp, included below, has the schedule controller */
 #include "../aac.js_amd/csrc/aacg_kernels.h"
 
 namespace half_emu {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The run kernels' source in the lane emulator under AddressSanitizer + UBSan (CPU only: the GPU pool has no sanitizer runs): the
 run-to-run rendezvous of the 16-wave kernels (both block orders) and the launch-to-launch rendezvous of aacg_decode_pipelined
-(three workgroup orders) on exactly-sized buffers, LDS included (the emulator's LDS is a heap block).  tools/asan_emu.sh builds
+(three workgroup orders) on exactly-sized buffers, LDS included (the emulator's LDS is a heap block), and two decodes in the
+emulator's schedule-controlled mode.  tools/asan_emu.sh builds
 the library and runs this."""
 import sys, os, ctypes as C, numpy as np
 sys.path.insert(0,'tests'); sys.path.insert(0,'aac.js_amd/python')
@@ -15,7 +16,9 @@ class E(emu_lib.Emu):
         L.emu_decode_cce.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.emu_decode_pipelined.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int]
+        L.emu_set_schedule.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int]
+        L.emu_sched_steps.restype = C.c_long
 emu = E(); o = orc.load()
 def run(S,T,layout,seam,rv,seed=9):
     wl = W.make_batch(n_streams=S, n_frames=T, layout=layout, mix=True, intensity=True, seed=seed)
@@ -48,4 +51,9 @@ for rv in (1,2):
     run(2,37,("cpe",),"q",rv); run(1,33,("cpe",),"f",rv); run(1,50,("sce",),"q",rv); run(1,20,("cpe","cpe","cpe","sce"),"q",rv)
 for order in (0,1,5):
     run_pipelined(2,16,("cpe",),"q",order); run_pipelined(1,20,("cpe",),"f",order); run_pipelined(1,4,("cpe","cpe","cpe","sce"),"q",order); run_pipelined(2,7,("sce",),"q",order)
+# schedule-controlled mode (tests/test_schedules_emu.py): consumers before producers, and both sides of a cell loading before the consumer swaps
+for sch in (("reversed",), ("cell", 0, 2)):
+    emu.set_schedule(sch)
+    run(1,40,("cpe",),"q",1)
+    emu.set_schedule(None)
 print("sanitized emulator runs ok")
