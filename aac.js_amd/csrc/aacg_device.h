@@ -5,6 +5,7 @@
 #ifndef AACG_DEVICE_H
 #define AACG_DEVICE_H
 
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/aacgpu.h"
 #include "../../include/aacgpu_tools.h"
@@ -100,6 +101,11 @@ struct aacg_dev_tns {
     int32_t order[8];
     float   lpc[8][AACG_TNS_MAX_ORDER];
 };
+/* Behind a buffer's n records, 256-byte aligned, lie their transition matrices (tns_matrix_row, aacg_kernels.h: made on the
+ * device by aacg_tns_matrices, read by every launch that runs filters): per record [filter slot 0..2][row][column]. */
+#define AACG_TNS_M_DOUBLES (3 * AACG_TNS_MAX_ORDER * AACG_TNS_MAX_ORDER)
+static inline size_t aacg_tns_record_bytes(size_t n) { return (sizeof(aacg_dev_tns) * n + 255u) & ~(size_t)255u; }
+static inline size_t aacg_tns_buffer_bytes(size_t n) { return n ? aacg_tns_record_bytes(n) + sizeof(double) * AACG_TNS_M_DOUBLES * n : 0; }
 
 /* AACG_PNS_SPEC: the noise generator's whole sequence (it restarts for every channel of every frame, so it is a
  * fixed table), the running sum of its squares (a band-window's energy is a difference of two entries) and the

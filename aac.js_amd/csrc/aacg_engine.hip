@@ -26,6 +26,7 @@
 #include "aacg_host.h"
 #include "aacg_routes.h"
 #include "aacg_plan_shape.h"
+#include "aacg_tns_prep.h"
 #include "aacg_wait.h"
 
 /* ---- kernels ----------------------------------------------------------------------- */
@@ -35,13 +36,15 @@ AACG_RUN_KERNEL_UNIT(plain, AACG_RUN_KERNELS_PLAIN)
 
 /* aacg_engine_refresh.hip: a kept plan's unit records from the device parser's output */
 void aacg_refresh_launch(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg_parse_result* results, const aacg_refresh_map* map, uint32_t n_units,
-                         uint32_t max_units, int refuse_pns, uint32_t* refused, hipStream_t s);
+                         uint32_t max_units, int refuse_pns, int keep_tns, uint32_t* refused, hipStream_t s);
 /* aacg_engine_shape.hip: a shaped plan's set of tables from the batch's per-stream table (aacg_plan_shape.h) */
 void aacg_shape_launch(const aacg_shape_args& A, hipStream_t s);
 /* aacg_engine_spectral.hip: the optional stages (AACG_PNS_SPEC noise bands, AACG_TNS_SPEC filters) -> f32 spectra */
 int aacg_spectral_ex_set_lds_limits(void);
 void aacg_spectral_ex_launch(bool quant, int n_units, hipStream_t s, const aacg_kparams& P);
 void aacg_tns_matrices_launch(const aacg_dev_tns* d_recs, double* d_m, uint32_t n_records, hipStream_t s);
+/* aacg_engine_tnsprep.hip: a batch's TNS records from the device parser's outputs (aacg_tns_prep.h) */
+void aacg_tns_records_launch(const aacg_tnsprep_args& A, hipStream_t s);
 /* aacg_engine_couple.hip: AACG_CCE_SPEC */
 void aacg_couple_launch(bool pcm, hipStream_t s, const aacg_couple_params& Q);
 
@@ -67,7 +70,7 @@ extern "C" __global__ void aacg_probe_set(unsigned* flag) { __hip_atomic_store(f
  * upload (batch_upload) and launch_run's reading of them are the same for both. */
 struct batch_bufs {
     enum { UNITS, RUNS,
-           TNS,                                     /* TNS records, their transition matrices behind them (tns_buffer_bytes) */
+           TNS,                                     /* TNS records, their transition matrices behind them (aacg_tns_buffer_bytes) */
            SCRATCH,                                 /* parked predecessor tails of double-duty runs */
            SPEC,                                    /* staged routes: f32 spectra between the launches */
            CCE_RUNS, CCE_JOBS, CCE_GAINS, CCE_SIDE, /* AACG_CCE_SPEC: coupling elements' runs, jobs, gains, side PCM */
@@ -412,10 +415,6 @@ int launch_kernel(aacg_engine* e, const aacg_run_kernel* k, unsigned blocks, hip
     return AACG_OK;
 }
 
-/* A plan's TNS records and, behind them in the same buffer, their transition matrices (tns_matrix_row, aacg_kernels.h: made on
- * the device by aacg_tns_matrices when the records are uploaded, read by every launch that runs filters). */
-static size_t tns_record_bytes(size_t n) { return (sizeof(aacg_dev_tns) * n + 255u) & ~(size_t)255u; }
-static size_t tns_buffer_bytes(size_t n) { return n ? tns_record_bytes(n) + sizeof(double) * AACG_TNS_M_DOUBLES * n : 0; }
 
 /* The bytes each of a batch's device buffers needs.  rv: a route the buffers serve walks the rendezvous cut; rv_sets: sets of
  * in-launch rendezvous cells, one per launch of the batch that may be in flight at once.  The f32 spectra are what the staged
@@ -424,7 +423,7 @@ void batch_sizes(const aacg_engine* e, const aacg_plan_host& h, bool rv, size_t 
 {
     want[batch_bufs::UNITS] = sizeof(aacg_dev_unit) * h.units.size();
     want[batch_bufs::RUNS] = sizeof(aacg_run) * h.runs.size();
-    want[batch_bufs::TNS] = tns_buffer_bytes(h.tns.size());
+    want[batch_bufs::TNS] = aacg_tns_buffer_bytes(h.tns.size());
     want[batch_bufs::SCRATCH] = h.needs_scratch ? h.runs.size() * AACG_SLOT_FLOATS * sizeof(float) : 0;
     want[batch_bufs::SPEC] = needs_spec_buffer(e, h) ? (size_t)h.coef_blocks * 1024u * sizeof(float) : 0;
     want[batch_bufs::CCE_RUNS] = sizeof(aacg_run) * h.cce_runs.size();
@@ -446,7 +445,7 @@ int batch_upload(aacg_engine* e, batch_bufs& b, const aacg_plan_host& h, const s
         HIP_TRY(e, hipMemsetAsync(b.rv_state(), 0, want[batch_bufs::RV_STATE], s), AACG_ERR_NO_DEVICE);
     auto up = [&](void* dst, const void* src, size_t n) { return !n || hip_ok(e, hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s), "upload batch tables"); };
     const size_t n_tns = h.tns.size();
-    b.tns_m = n_tns ? (double*)((char*)b.p[batch_bufs::TNS] + tns_record_bytes(n_tns)) : nullptr;
+    b.tns_m = n_tns ? (double*)((char*)b.p[batch_bufs::TNS] + aacg_tns_record_bytes(n_tns)) : nullptr;
     if (!up(b.units(), h.units.data(), want[batch_bufs::UNITS]) || !up(b.runs(), h.runs.data(), want[batch_bufs::RUNS]) ||
         !up(b.tns(), h.tns.data(), sizeof(aacg_dev_tns) * n_tns))
         return AACG_ERR_NO_DEVICE;
@@ -460,7 +459,8 @@ int batch_upload(aacg_engine* e, batch_bufs& b, const aacg_plan_host& h, const s
 
 /* what a pipelined launch adds to the rendezvous arguments: the cross-launch cells, the epoch its input state carries, and
  * which of the plan's two sets of in-launch cells it uses (overlapping launches must not share one) */
-struct xl_args { bool on; unsigned long long epoch_in; int set; int trace_part = 0; };   /* trace_part: which quarter of the profiling buffer this launch stamps */
+struct xl_args { bool on; unsigned long long epoch_in; int set; int trace_part = 0;
+                 const aacg_dev_tns* tns = nullptr; const double* tns_m = nullptr; };   /* tns, tns_m: a stages plan's records and matrices, the launch's own */   /* trace_part: which quarter of the profiling buffer this launch stamps */
 /* a shaped plan's launch (aacg_plan_shape.h): the run and link tables of the set shaped last and their count — the host has no copy
  * to count — and the plan's capacity in links, which is what a set of in-launch cells holds */
 struct shaped_run { const aacg_run* runs; const aacg_rv_link* links; size_t n_runs, cell_links; };
@@ -489,6 +489,7 @@ int launch_run(aacg_engine* e, const aacg_route& R, const aacg_dev_unit* d_units
         if (R.run_key & AACG_RK_EX) {                    /* optional stages inside the run kernel */
             P.tns = h.any_tns ? b.tns() : nullptr; P.pns = e->d_pns;
             if (h.any_tns) aacg_set_tns_m(&P, b.tns_m);
+            if (h.stages_plan && xl.tns) { P.tns = xl.tns; aacg_set_tns_m(&P, xl.tns_m); }      /* the batch's, not the plan's */
         }
         if (epoch_out) *epoch_out = V.epoch;
         P.ablate = e->d_trace ? e->ablate : (e->ablate & ~16);                                       /* profiling builds only (0 in the library that ships) */
@@ -633,6 +634,7 @@ int aacg_debug_route(int input_kind, int output_kind, int debug_route, int plan_
     aacg_plan_host h;
     h.any_tns = (plan_flags & AACG_ROUTE_PLAN_TNS) != 0;
     h.any_pns = (plan_flags & AACG_ROUTE_PLAN_PNS) != 0;
+    h.stages_plan = (plan_flags & AACG_ROUTE_PLAN_STAGES) != 0;
     h.needs_scratch = (plan_flags & AACG_ROUTE_PLAN_FULL_LATER_RUNS) != 0;
     h.long_chains = (plan_flags & (AACG_ROUTE_PLAN_LONG_CHAINS | AACG_ROUTE_PLAN_FULL_LATER_RUNS)) != 0;
     h.wide_frames = (plan_flags & AACG_ROUTE_PLAN_WIDE_FRAMES) != 0;
@@ -925,8 +927,42 @@ static int plan_host(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_uni
     return AACG_OK;
 }
 
+/* what an engine must be for plans whose launches bring the optional stages' records (aacg_decode_pipelined_stages); 0 or the text */
+static const char* stages_refusal(const aacg_engine* e)
+{
+    if (e->cfg.input_kind != AACG_INPUT_QUANT_I16) return "an AACG_INPUT_QUANT_I16 engine (the device parser's spectra)";
+    if (e->cfg.tns_mode != AACG_TNS_SPEC && e->cfg.pns_mode != AACG_PNS_SPEC) return "an engine with AACG_TNS_SPEC and / or AACG_PNS_SPEC (there is no stage to run)";
+    if (e->cfg.output_kind != AACG_OUTPUT_F32) return "float32 PCM (int16 PCM takes the staged spectral launch, which needs a spectrum buffer per plan and does not overlap)";
+    if (e->cfg.cce_mode == AACG_CCE_SPEC) return "no AACG_CCE_SPEC (coupling records are prepared on the host, per batch)";
+    return nullptr;
+}
+
+static int plan_create(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units, const aacg_tns_info* tns, uint32_t n_tns,
+                       const aacg_cce_info* cce, uint32_t n_cce, bool stages, aacg_plan** out);
+
 int aacg_plan_create_ex(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units,
                         const aacg_tns_info* tns, uint32_t n_tns, const aacg_cce_info* cce, uint32_t n_cce, aacg_plan** out)
+{
+    return plan_create(e, units, n_units, tns, n_tns, cce, n_cce, false, out);
+}
+
+/* A kept plan for aacg_decode_pipelined_stages: `units` carry the structure only (aacg_plan_refresh_from_parse_ex brings the
+ * rest, batch by batch), the launches bring the TNS records. */
+int aacg_plan_create_stages(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units, aacg_plan** out)
+{
+    if (!e || !units || !n_units || !out) return AACG_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (const char* why = stages_refusal(e)) { e->err = std::string("aacg_plan_create_stages needs ") + why; return AACG_ERR_UNSUPPORTED; }
+    for (uint32_t i = 0; i < n_units; i++) {
+        bool plain = !(units[i].flags & (AACG_UNIT_HAS_PNS | AACG_UNIT_CCE));
+        for (int c = 0; c < 2; c++) plain = plain && !(units[i].ch[c].flags & AACG_CHAN_TNS_PRESENT);
+        if (!plain) { e->err = "aacg_plan_create_stages: the units carry the batch's structure only — no TNS side info, noise bands or coupling element (the refresh brings what the frames hold)"; return AACG_ERR_INVALID_ARG; }
+    }
+    return plan_create(e, units, n_units, nullptr, 0, nullptr, 0, true, out);
+}
+
+static int plan_create(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units, const aacg_tns_info* tns, uint32_t n_tns,
+                       const aacg_cce_info* cce, uint32_t n_cce, bool stages, aacg_plan** out)
 {
     if (!e || !units || !n_units || !out) return AACG_ERR_INVALID_ARG;
     *out = nullptr;
@@ -936,6 +972,7 @@ int aacg_plan_create_ex(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_
     p->n_units = n_units;
     const int rc = plan_host(e, units, n_units, tns, n_tns, cce, n_cce, &p->h);
     if (rc) { delete p; return rc; }
+    p->h.stages_plan = stages;                             /* before the route is asked for: it decides which tables go to the device */
     bool ok = hip_ok(e, hipSetDevice(e->cfg.device_ordinal), "hipSetDevice") &&
               hip_ok(e, hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming), "hipEventCreate") &&
               hip_ok(e, hipEventCreateWithFlags(&p->last_use, hipEventDisableTiming), "hipEventCreate");
@@ -956,14 +993,30 @@ int aacg_plan_create_ex(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_
 }
 
 /* ---- plans shaped on the device (aacg_plan_shape.h) -------------------------------------------------------------------- */
+static int plan_create_shaped(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, bool stages, aacg_plan** out);
+
 int aacg_plan_create_shaped(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, aacg_plan** out)
+{
+    return plan_create_shaped(e, max_streams, max_frames, max_elems, n_sets, false, out);
+}
+
+/* The shaped plan for aacg_decode_pipelined_stages: its launches bring the TNS records, the refresh the noise-band units. */
+int aacg_plan_create_shaped_stages(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, aacg_plan** out)
+{
+    return plan_create_shaped(e, max_streams, max_frames, max_elems, n_sets, true, out);
+}
+
+static int plan_create_shaped(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, bool stages, aacg_plan** out)
 {
     if (!e || !out || !max_streams || !max_frames || !max_elems || max_elems > 8 || n_sets < 1 || n_sets > 8 ||
         (uint64_t)max_streams * (uint64_t)max_frames > (1u << 22))
         return AACG_ERR_INVALID_ARG;
     *out = nullptr;
-    if (e->cfg.input_kind != AACG_INPUT_QUANT_I16 || e->cfg.tns_mode == AACG_TNS_SPEC || e->cfg.pns_mode == AACG_PNS_SPEC || e->cfg.cce_mode == AACG_CCE_SPEC) {
-        e->err = "aacg_plan_create_shaped: an AACG_INPUT_QUANT_I16 engine without optional stages (TNS / PNS / coupling records are prepared on the host, per batch)";
+    if (stages) {
+        if (const char* why = stages_refusal(e)) { e->err = std::string("aacg_plan_create_shaped_stages needs ") + why; return AACG_ERR_UNSUPPORTED; }
+    } else if (e->cfg.input_kind != AACG_INPUT_QUANT_I16 || e->cfg.tns_mode == AACG_TNS_SPEC || e->cfg.pns_mode == AACG_PNS_SPEC || e->cfg.cce_mode == AACG_CCE_SPEC) {
+        e->err = "aacg_plan_create_shaped: an AACG_INPUT_QUANT_I16 engine without optional stages (coupling records are prepared on the host, per batch; "
+                 "TNS records and noise bands reach a plan made by aacg_plan_create_shaped_stages)";
         return AACG_ERR_UNSUPPORTED;
     }
     if ((int)max_streams > e->cfg.max_streams) { e->err = "aacg_plan_create_shaped: more streams than the engine has slots"; return AACG_ERR_CAPACITY; }
@@ -971,6 +1024,7 @@ int aacg_plan_create_shaped(aacg_engine* e, uint32_t max_streams, uint32_t max_f
     if (p) p->sh = new (std::nothrow) aacg_plan::shaped_t();
     if (!p || !p->sh) { delete p; return AACG_ERR_OUT_OF_MEMORY; }
     p->e = e;
+    p->h.stages_plan = stages;
     aacg_plan::shaped_t& sh = *p->sh;
     sh.lim = aacg_shape_capacity(max_streams, max_frames, max_elems, (uint32_t)e->cfg.max_channels);
     sh.set_units.assign(n_sets, 0);
@@ -1146,6 +1200,7 @@ int aacg_decode_device(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const
 {
     if (!e || !p || p->e != e || !d_coeffs || !d_pcm) return AACG_ERR_INVALID_ARG;
     if (p->sh) return shaped_refused(e, "aacg_decode_device", "the serial route walks the cut with recomputed tails (aacg_decode_pipelined launches such a plan)");
+    if (p->h.stages_plan) { e->err = "aacg_decode_device: the plan was made for aacg_decode_pipelined_stages (its launches bring the TNS records)"; return AACG_ERR_UNSUPPORTED; }
     const bool quant = e->cfg.input_kind == AACG_INPUT_QUANT_I16;
     if (quant && !d_meta) { e->err = "QUANT_I16 engine needs band meta"; return AACG_ERR_INVALID_ARG; }
     /* relaunched back to back (nothing else advanced any stream since): the per-chain check is known to pass */
@@ -1246,6 +1301,9 @@ static int pipe_setup(aacg_engine* e)
     return AACG_OK;
 }
 
+static int decode_pipelined(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const aacg_band_meta* d_meta, void* d_pcm, void* stop_mark,
+                            const aacg_dev_tns* d_tns, const double* d_tns_m);
+
 int aacg_decode_pipelined(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const aacg_band_meta* d_meta, void* d_pcm)
 {
     return aacg_decode_pipelined_timed(e, p, d_coeffs, d_meta, d_pcm, nullptr);
@@ -1253,6 +1311,28 @@ int aacg_decode_pipelined(aacg_engine* e, aacg_plan* p, const void* d_coeffs, co
 
 /* the same with a timing mark (aacg_timer_create) bound to the launch's completion: measurement only (aacgpu_tools.h) */
 int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const aacg_band_meta* d_meta, void* d_pcm, void* stop_mark)
+{
+    if (e && p && p->e == e && p->h.stages_plan) { e->err = "aacg_decode_pipelined: the plan was made for aacg_decode_pipelined_stages (its launches bring the TNS records)"; return AACG_ERR_UNSUPPORTED; }
+    return decode_pipelined(e, p, d_coeffs, d_meta, d_pcm, stop_mark, nullptr, nullptr);
+}
+
+/* The next launch of a plan made for it (aacg_plan_create_stages, aacg_plan_create_shaped_stages),
+ * with the batch's TNS records — aacg_tns_records_from_parse's buffer of n_tns_records records, their matrices behind them — as
+ * a launch input like the spectra and the band words.  Everything else is aacg_decode_pipelined's. */
+int aacg_decode_pipelined_stages(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const aacg_band_meta* d_meta, const void* d_tns_records,
+                                 uint32_t n_tns_records, void* d_pcm)
+{
+    if (!e || !p || p->e != e) return AACG_ERR_INVALID_ARG;
+    if (!p->h.stages_plan) { e->err = "aacg_decode_pipelined_stages: not a plan made for it (aacg_plan_create_stages, aacg_plan_create_shaped_stages)"; return AACG_ERR_INVALID_ARG; }
+    const bool tns = e->cfg.tns_mode == AACG_TNS_SPEC;
+    if (tns && (!d_tns_records || !n_tns_records)) { e->err = "aacg_decode_pipelined_stages: an AACG_TNS_SPEC engine's launch needs the batch's TNS records"; return AACG_ERR_INVALID_ARG; }
+    if (tns && ((uintptr_t)d_tns_records & 255u)) { e->err = "aacg_decode_pipelined_stages: d_tns_records must be 256-byte aligned"; return AACG_ERR_INVALID_ARG; }
+    const aacg_dev_tns* recs = tns ? (const aacg_dev_tns*)d_tns_records : nullptr;      /* (without AACG_TNS_SPEC no unit keeps its TNS flag: nothing would read them) */
+    return decode_pipelined(e, p, d_coeffs, d_meta, d_pcm, nullptr, recs, tns ? (const double*)((const char*)d_tns_records + aacg_tns_record_bytes(n_tns_records)) : nullptr);
+}
+
+static int decode_pipelined(aacg_engine* e, aacg_plan* p, const void* d_coeffs, const aacg_band_meta* d_meta, void* d_pcm, void* stop_mark,
+                            const aacg_dev_tns* d_tns, const double* d_tns_m)
 {
     if (!e || !p || p->e != e || !d_coeffs || !d_pcm) return AACG_ERR_INVALID_ARG;
     const bool quant = e->cfg.input_kind == AACG_INPUT_QUANT_I16;
@@ -1315,7 +1395,7 @@ int aacg_decode_pipelined_timed(aacg_engine* e, aacg_plan* p, const void* d_coef
         HIP_TRY(e, hipEventRecord(pp.fork, s), AACG_ERR_NO_DEVICE);
         for (hipStream_t ps : pp.stream) if (ps != s) HIP_TRY(e, hipStreamWaitEvent(ps, pp.fork, 0), AACG_ERR_NO_DEVICE);
     }
-    const xl_args xl = {R.overlappable, continues ? pp.epoch : 0ull, ord.stream, (int)(pp.n & 3u)};
+    const xl_args xl = {R.overlappable, continues ? pp.epoch : 0ull, ord.stream, (int)(pp.n & 3u), d_tns, d_tns_m};
     unsigned long long epoch = 0;
     /* the host will wait for this one: its event rides on the dispatch itself where the route is a single launch
      * (no marker packet between this launch and the next of its stream), else it is recorded behind the route's last launch */
@@ -1411,10 +1491,14 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
 {
     if (!e || !p || p->e != e || !d_parsed_units || !d_results || !max_units || !d_refused || set >= p->unit_sets) return AACG_ERR_INVALID_ARG;
     if (e->cfg.input_kind != AACG_INPUT_QUANT_I16) { e->err = "aacg_plan_refresh_from_parse needs a QUANT_I16 engine"; return AACG_ERR_INVALID_ARG; }
-    if (p->h.any_tns || p->h.any_pns || e->cfg.tns_mode == AACG_TNS_SPEC) {
-        e->err = "aacg_plan_refresh_from_parse: TNS records / noise tables are prepared on the host, such plans are rebuilt per batch";
+    if (!p->h.stages_plan && (p->h.any_tns || p->h.any_pns || e->cfg.tns_mode == AACG_TNS_SPEC)) {
+        e->err = "aacg_plan_refresh_from_parse: this plan's TNS records / noise tables were prepared on the host, such plans are rebuilt per batch "
+                 "(aacg_plan_create_stages / aacg_plan_create_shaped_stages make plans whose launches take them from the device)";
         return AACG_ERR_UNSUPPORTED;
     }
+    /* a plan made for aacg_decode_pipelined_stages decodes what its engine's modes decode: TNS side info stays with the unit where
+     * the launch brings records, a unit with noise bands is taken where the engine has the noise tables */
+    const int keep_tns = p->h.stages_plan && e->cfg.tns_mode == AACG_TNS_SPEC, refuse_pns = !(p->h.stages_plan && e->cfg.pns_mode == AACG_PNS_SPEC);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
     note_stream(e, s);
     HIP_TRY(e, hipStreamWaitEvent(s, p->uploaded, 0), AACG_ERR_NO_DEVICE);
@@ -1422,25 +1506,53 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
         /* a shaped set: the records aacg_plan_shape_launch has just written on this stream, as many as the shape has; a set of
          * its own like the sets of a kept plan (nothing in flight reads it: the caller's word) */
         if (!p->sh->ready || set != p->cur_set || !d_map) { e->err = "aacg_plan_refresh_from_parse_ex: a shaped plan refreshes the set shaped last (aacg_plan_shape_launch), through its map"; return AACG_ERR_INVALID_ARG; }
-        aacg_refresh_launch(p->b.units() + (size_t)set * p->unit_stride(), d_parsed_units, d_results, d_map, p->sh->set_units[set], max_units, 1, d_refused, s);
+        aacg_refresh_launch(p->b.units() + (size_t)set * p->unit_stride(), d_parsed_units, d_results, d_map, p->sh->set_units[set], max_units, refuse_pns, keep_tns, d_refused, s);
         HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
         return AACG_OK;
     }
     if (p->unit_sets > 1) {
         /* a set of its own: nothing in flight reads it (the caller's word), so neither the pipeline is joined nor the plan's
          * sequence of overlapped launches ended; the next launch reads this set */
-        aacg_refresh_launch(p->b.units() + (size_t)set * p->n_units, d_parsed_units, d_results, d_map, p->n_units, max_units, 1, d_refused, s);
+        aacg_refresh_launch(p->b.units() + (size_t)set * p->n_units, d_parsed_units, d_results, d_map, p->n_units, max_units, refuse_pns, keep_tns, d_refused, s);
         HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
         p->cur_set = set;
         return AACG_OK;
     }
     if (p->last_pipelined) { int jrc = pipe_join(e, s); if (jrc) return jrc; }
     if (const int frc = plan_follow(e, p, s)) return frc;                      /* the records' readers on the plan's previous stream first */
-    aacg_refresh_launch(p->b.units(), d_parsed_units, d_results, d_map, p->n_units, max_units, 1, d_refused, s);
+    aacg_refresh_launch(p->b.units(), d_parsed_units, d_results, d_map, p->n_units, max_units, refuse_pns, keep_tns, d_refused, s);
     HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
     p->last_stream = s;
     p->used = true;
     p->last_pipelined = false;
+    return AACG_OK;
+}
+
+/* A batch's TNS records and their transition matrices made where the parser left its outputs (aacg_tns_prep.h): what
+ * aacg_tns_prepare makes of the same aacg_tns_info on the host, byte for byte, and behind it the kernel every upload of host-made
+ * records is followed by. */
+size_t aacg_tns_records_bytes(uint32_t n_records) { return aacg_tns_buffer_bytes(n_records); }
+
+int aacg_tns_records_from_parse(aacg_engine* e, const aacg_unit_desc* d_parsed_units, const aacg_parse_result* d_results, const aacg_tns_info* d_tns_info,
+                                uint32_t n_frames, uint32_t max_units, uint32_t parse_channels, void* d_records, void* hip_stream)
+{
+    if (!e || !d_parsed_units || !d_results || !d_tns_info || !d_records || !max_units || !parse_channels) return AACG_ERR_INVALID_ARG;
+    if (!n_frames) return AACG_OK;
+    if ((uint64_t)n_frames * parse_channels > 0x7fffffffull / sizeof(aacg_dev_tns)) { e->err = "aacg_tns_records_from_parse: more records than a launch indexes"; return AACG_ERR_CAPACITY; }
+    if ((uintptr_t)d_records & 255u) { e->err = "aacg_tns_records_from_parse: d_records must be 256-byte aligned"; return AACG_ERR_INVALID_ARG; }
+    aacg_tnsprep_args A;
+    std::memset(&A, 0, sizeof A);
+    if (aacg_tns_bands_make(e->cfg.sample_index, &A.bands)) return AACG_ERR_INVALID_ARG;
+    HIP_TRY(e, hipSetDevice(e->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    note_stream(e, s);
+    const uint32_t n = n_frames * parse_channels;
+    A.units = d_parsed_units; A.results = d_results; A.info = d_tns_info; A.recs = (aacg_dev_tns*)d_records;
+    A.n_frames = n_frames; A.max_units = max_units; A.parse_channels = parse_channels;
+    aacg_tns_records_launch(A, s);
+    HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    aacg_tns_matrices_launch(A.recs, (double*)((char*)d_records + aacg_tns_record_bytes(n)), n, s);
+    HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
     return AACG_OK;
 }
 

@@ -26,7 +26,7 @@ static __device__ bool unit_matches(const aacg_unit_desc& have, const aacg_unit_
 
 extern "C" __global__ __launch_bounds__(256)
 void aacg_units_refresh(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg_parse_result* results, const aacg_refresh_map* map,
-                        uint32_t n_units, uint32_t max_units, int refuse_pns, uint32_t* refused)
+                        uint32_t n_units, uint32_t max_units, int refuse_pns, int keep_tns, uint32_t* refused)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_units) return;
@@ -47,13 +47,15 @@ void aacg_units_refresh(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg
     }
     /* A refused frame's record (and the slots e >= n_units) is unspecified: nothing is taken from it.  Its unit keeps
      * the offsets the planner validated — a silent unit still loads its blocks (quant_load reads unconditionally). */
-    u.d.tns_offset = 0;
+    u.d.tns_offset = 0;                                  /* (keep_tns: an accepted frame's comes from the parser, below) */
     u.gmap[0] = u.gmap[1] = 0;
     if (ok) {
         u.d.flags = p.flags;
         for (int c = 0; c < 2; c++) {
             u.d.ch[c] = p.ch[c];
-            u.d.ch[c].flags &= (uint8_t)~AACG_CHAN_TNS_PRESENT;                  /* no TNS records on this path */
+            /* no TNS records on this path — unless the plan's launches bring them (keep_tns: aacg_decode_pipelined_stages on an
+             * AACG_TNS_SPEC engine): then the flag stays, and the records are indexed as the parser indexed its side info */
+            if (!keep_tns) u.d.ch[c].flags &= (uint8_t)~AACG_CHAN_TNS_PRESENT;
             if (c < p.n_ch && p.ch[c].window_sequence == AACG_EIGHT_SHORT_SEQUENCE) {
                 uint32_t gmap = 0;
                 int w = 0;
@@ -62,6 +64,7 @@ void aacg_units_refresh(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg
                 u.gmap[c] = gmap;
             }
         }
+        if (keep_tns) u.d.tns_offset = p.tns_offset;
     } else {
         u.d.flags = 0;
         for (int c = 0; c < 2; c++) {
@@ -75,7 +78,7 @@ void aacg_units_refresh(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg
 }
 
 void aacg_refresh_launch(aacg_dev_unit* units, const aacg_unit_desc* parsed, aacg_parse_result* results, const aacg_refresh_map* map, uint32_t n_units,
-                         uint32_t max_units, int refuse_pns, uint32_t* refused, hipStream_t s)
+                         uint32_t max_units, int refuse_pns, int keep_tns, uint32_t* refused, hipStream_t s)
 {
-    hipLaunchKernelGGL(aacg_units_refresh, dim3((n_units + 255u) / 256u), dim3(256), 0, s, units, parsed, results, map, n_units, max_units, refuse_pns, refused);
+    hipLaunchKernelGGL(aacg_units_refresh, dim3((n_units + 255u) / 256u), dim3(256), 0, s, units, parsed, results, map, n_units, max_units, refuse_pns, keep_tns, refused);
 }

@@ -35,6 +35,11 @@ struct aacg_plan_host {
     std::vector<aacg_dev_tns>  tns;     /* device form of the TNS side info (AACG_TNS_SPEC), same indexing as the input */
     bool     any_tns = false;         /* some channel has AACG_CHAN_TNS_PRESENT and TNS records were given */
     bool     any_pns = false;         /* some unit carries AACG_UNIT_HAS_PNS */
+    /* set at creation, never by a batch: a plan whose launches run the optional stages on records that arrive WITH the launch
+     * (aacg_decode_pipelined_stages: unit records refreshed from the device parser, TNS records made on the device).  Its route is
+     * the run kernel with the stages inside on the rendezvous cut whatever a batch holds — a filter, a noise band or neither — so
+     * that the route, the pipeline's stream count and the sequence rule never depend on a batch's content (aacg_pick_route) */
+    bool     stages_plan = false;
     uint32_t short_units = 0;         /* units with an EIGHT_SHORT_SEQUENCE channel, as planned (or last refreshed from the host) */
     bool     needs_scratch = false;   /* some later run holds 16 frames: its first wave parks the predecessor's tails */
     bool     wide_frames = false;     /* at least half of the units belong to frames of more than two channels: the multichannel kernel variants (aacg_engine_nt.hip) */

@@ -1371,7 +1371,7 @@ DP_DEVICE void tns_run(float* blk, int inc, int chunks, int n_valid, const float
  * slots per pass when every wave derived it for itself, so it is made ONCE per plan by a kernel of its own
  * (aacg_tns_matrices, aacg_engine_spectral.hip: one lane per row, this very function) and read back by the row lanes —
  * 96 bytes per lane, requested before the block's zero-state pass and in the registers after it. */
-#define AACG_TNS_M_DOUBLES (3 * AACG_TNS_MAX_ORDER * AACG_TNS_MAX_ORDER)      /* per channel record: [filter slot 0..2][row][column] */
+/* (AACG_TNS_M_DOUBLES per channel record, aacg_device.h: [filter slot 0..2][row][column]) */
 /* where they ride in the kernel arguments of the launches that run filters (aacg_set_tns_m, aacg_device.h) */
 DP_DEVICE const double* aacg_tns_m(const aacg_kparams& P) { return (const double*)(const void*)P.scratch; }
 DP_DEVICE void tns_matrix_row(const float (&lpc)[AACG_TNS_MAX_ORDER], int r, double (&row)[AACG_TNS_MAX_ORDER])

@@ -33,6 +33,11 @@
  * shape not seen before costs the submit path no plan build, no allocation, no upload of O(units) bytes and no eviction.  The two
  * modes part in aacg_pipeline_submit_ragged where the plan is chosen and where the map / shaping kernel is launched, nowhere else.
  *
+ * The spec-correct stages (aacg_pipeline_config.stages): the engine is created with AACG_TNS_SPEC / AACG_PNS_SPEC, the parser writes
+ * TNS side info into a buffer of the lane's, aacg_tns_records_from_parse makes the batch's TNS records and their matrices behind the
+ * parse on the lane's stream, and the plans are plans for aacg_decode_pipelined_stages, which takes those records as a launch input
+ * (aacg_plan_create_stages in plan mode 0, aacg_plan_create_shaped_stages in mode 1).  With stages = 0 no call differs from before.
+ *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
  * (and aacg_pipe_map.h / aacg_plan_shape.h for the tables it fills).
  */
@@ -114,6 +119,9 @@ struct aacg_pipeline {
         hipEvent_t done = nullptr;
         void *d_bytes = nullptr, *d_frames = nullptr, *d_units = nullptr, *d_q = nullptr, *d_meta = nullptr, *d_res = nullptr, *d_pcm = nullptr, *d_refused = nullptr;
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
+        /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
+         * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
+        void *d_tns_info = nullptr, *d_tns = nullptr;
         void *h_in = nullptr, *h_pcm = nullptr, *h_res = nullptr;
         size_t bytes_cap = 0, h_in_cap = 0;
         /* the batch in flight */
@@ -197,7 +205,7 @@ int plan_for(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of,
     aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, S, p->C, p->Cp, p->U, &u, nullptr, nullptr);
     if (u.empty()) { *out = nullptr; return AACG_OK; }     /* no stream of the batch has a layout yet: nothing to transform, every frame is refused */
     aacg_plan* plan = nullptr;
-    int rc = aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
+    int rc = p->cfg.stages ? aacg_plan_create_stages(p->engine, u.data(), (uint32_t)u.size(), &plan) : aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
     if (rc == AACG_OK && (rc = aacg_plan_set_unit_sets(p->engine, plan, (uint32_t)p->n_lanes))) { aacg_plan_destroy(plan); plan = nullptr; }
     if (rc) { p->err = std::string("aacg_plan_create: ") + aacg_last_error(p->engine); return rc; }
     p->plan_builds++;
@@ -328,7 +336,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (W.st) (void)hipStreamDestroy(W.st);
     }
     for (auto& L : p->lane) {
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_map}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
         for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.parser) aacg_parser_destroy(L.parser);
@@ -345,8 +353,14 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     *out = nullptr;
     if (cfg->abi_version != AACG_ABI_VERSION || cfg->max_streams < 1 || cfg->max_frames < 1 || cfg->channels < 1 || cfg->channels > AACG_MAX_CHANNELS ||
         (cfg->output_kind != AACG_OUTPUT_F32 && cfg->output_kind != AACG_OUTPUT_I16) || (uint64_t)cfg->max_streams * (uint64_t)cfg->max_frames > (1u << 22) ||
-        cfg->lanes < 0 || cfg->lanes > AACG_PIPELINE_MAX_LANES || cfg->plan_mode < 0 || cfg->plan_mode > 1)
+        cfg->lanes < 0 || cfg->lanes > AACG_PIPELINE_MAX_LANES || cfg->plan_mode < 0 || cfg->plan_mode > 1 ||
+        (cfg->stages & ~(AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS)) || cfg->reserved[0])
         return AACG_ERR_INVALID_ARG;
+    if (cfg->stages && cfg->output_kind == AACG_OUTPUT_I16) {
+        std::fprintf(stderr, "aacgpu: aacg_pipeline_create: stages (AACG_TNS_SPEC / AACG_PNS_SPEC) need AACG_OUTPUT_F32 — with int16 PCM the stages are a spectral launch of "
+                             "their own, which needs a spectrum buffer per plan and does not overlap\n");
+        return AACG_ERR_UNSUPPORTED;
+    }
     aacg_pipeline* p = new (std::nothrow) aacg_pipeline();
     if (!p) return AACG_ERR_OUT_OF_MEMORY;
     p->cfg = *cfg;
@@ -365,13 +379,15 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     std::memset(&ec, 0, sizeof ec);
     ec.abi_version = AACG_ABI_VERSION; ec.device_ordinal = cfg->device_ordinal; ec.sample_index = cfg->sample_index;
     ec.max_streams = cfg->max_streams; ec.max_channels = cfg->channels; ec.input_kind = AACG_INPUT_QUANT_I16;
-    ec.tns_mode = AACG_TNS_REFERENCE; ec.pns_mode = AACG_PNS_REFERENCE; ec.output_kind = cfg->output_kind; ec.cce_mode = AACG_CCE_REFERENCE;
+    ec.tns_mode = (cfg->stages & AACG_PIPELINE_STAGE_TNS) ? AACG_TNS_SPEC : AACG_TNS_REFERENCE;
+    ec.pns_mode = (cfg->stages & AACG_PIPELINE_STAGE_PNS) ? AACG_PNS_SPEC : AACG_PNS_REFERENCE;
+    ec.output_kind = cfg->output_kind; ec.cce_mode = AACG_CCE_REFERENCE;
     int rc = aacg_create(&ec, &p->engine);
     if (rc == AACG_OK) rc = aacg_parser_create(cfg->device_ordinal, cfg->sample_index, entries, counts, &p->parser);
     /* device plans: the one plan, made here — a failure (the in-launch cells of long chains are the large part) is the caller's to
      * see, there is no falling back to kept plans */
     if (rc == AACG_OK && cfg->plan_mode == 1 &&
-        (rc = aacg_plan_create_shaped(p->engine, (uint32_t)cfg->max_streams, (uint32_t)cfg->max_frames, p->U, (uint32_t)p->n_lanes, &p->shaped)))
+        (rc = (cfg->stages ? aacg_plan_create_shaped_stages : aacg_plan_create_shaped)(p->engine, (uint32_t)cfg->max_streams, (uint32_t)cfg->max_frames, p->U, (uint32_t)p->n_lanes, &p->shaped)))
         std::fprintf(stderr, "aacgpu: %s\n", aacg_last_error(p->engine));
     if (rc) { aacg_pipeline_destroy(p); return rc; }
     const size_t n = (size_t)cfg->max_streams * (size_t)cfg->max_frames, C = p->C, Cp = p->Cp, U = p->U;
@@ -399,6 +415,9 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
                ok(p, hipMalloc(&L.d_res, p->res_cap16 + 16), "hipMalloc") &&      /* the refusal count lies behind the results: one copy brings both down */
                ok(p, hipMemsetAsync(L.d_res, 0, p->res_cap16 + 16, L.st), "hipMemset") &&
                ok(p, hipMalloc(&L.d_pcm, n * C * 1024 * pcm_elem(p)), "hipMalloc") &&
+               (!(cfg->stages & AACG_PIPELINE_STAGE_TNS) ||
+                (ok(p, hipMalloc(&L.d_tns_info, n * Cp * sizeof(aacg_tns_info)), "hipMalloc") &&
+                 ok(p, hipMalloc(&L.d_tns, aacg_tns_records_bytes((uint32_t)(n * Cp))), "hipMalloc"))) &&
                ok(p, hipHostMalloc(&L.h_res, p->res_cap16 + 16, hipHostMallocDefault), "hipHostMalloc") &&
                aacg_wait_stream(L.st, p->wait) == hipSuccess;
         if (good) L.d_refused = (char*)L.d_res + p->res_cap16;
@@ -527,8 +546,14 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     /* the spectra of a refused frame and the positions outside the coded bands are never read by the transform (a refused frame
      * becomes a silent unit), so the parser need not clear 8 KB per frame first */
     rc = aacg_parse_device(L.parser, L.d_bytes, (const aacg_parse_frame*)L.d_frames, n, U, Cp, (uint32_t)p->cfg.parse_options | AACG_PARSE_SKIP_ZERO_FILL,
-                           (aacg_unit_desc*)L.d_units, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, nullptr, (aacg_parse_result*)L.d_res, st);
+                           (aacg_unit_desc*)L.d_units, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, (aacg_tns_info*)L.d_tns_info, (aacg_parse_result*)L.d_res, st);
     if (rc) { p->err = std::string("aacg_parse_device: ") + aacg_parser_last_error(L.parser); return rc; }
+    /* AACG_PIPELINE_STAGE_TNS: the batch's TNS records and their matrices, made where the side info lies, behind the parse on the
+     * lane's stream; the launch that read this lane's buffer last was its previous batch's, whose PCM has come down since */
+    if (kp && L.d_tns && (rc = aacg_tns_records_from_parse(p->engine, (const aacg_unit_desc*)L.d_units, (const aacg_parse_result*)L.d_res, (const aacg_tns_info*)L.d_tns_info,
+                                                           n, U, Cp, L.d_tns, st))) {
+        p->err = std::string("aacg_tns_records_from_parse: ") + aacg_last_error(p->engine); return rc;
+    }
     if (kp && device_plans) {                            /* the shaping kernel INSTEAD of aacg_pipe_map: the map, and the set's unit, run and link records */
         if ((rc = aacg_plan_shape_launch(p->engine, p->shaped, (const aacg_shape_stream*)((char*)L.d_bytes + padded + table16), U, (aacg_refresh_map*)L.d_map, st))) {
             p->err = std::string("aacg_plan_shape_launch: ") + aacg_last_error(p->engine); return rc;
@@ -548,7 +573,8 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
         if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, st);
-        if (rc == AACG_OK) rc = aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_pcm);
+        if (rc == AACG_OK) rc = p->cfg.stages ? aacg_decode_pipelined_stages(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? n * Cp : 0u, L.d_pcm)
+                                              : aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_pcm);
         if (rc == AACG_OK) p->launches++;
         if (rc != AACG_ERR_STALE_PLAN || attempt || device_plans) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
         /* another shape's plan has advanced these streams since this one was used: plans are made from the engine's current state */

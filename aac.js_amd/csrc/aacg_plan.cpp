@@ -10,6 +10,7 @@
  * before it from that frame's spectrum (no inter-workgroup communication).
  */
 #include "aacg_host.h"
+#include "aacg_tns_bands.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -52,18 +53,16 @@ int fail(std::string* err, int code, const char* fmt, long a = 0, long b = 0, lo
 
 }  // namespace
 
-/* TNS_MAX_BANDS_1024 / _128 (tns.js:65-66; ISO/IEC 14496-3 Table 4.138) by sampleIndex */
-static const uint8_t kTnsMaxBandsLong[13]  = {31, 31, 34, 40, 42, 51, 46, 46, 42, 42, 42, 39, 39};
-static const uint8_t kTnsMaxBandsShort[13] = {9, 9, 10, 14, 14, 14, 14, 14, 14, 14, 14, 14, 14};
-
 int aacg_tns_prepare(int sample_index, const aacg_chan_info* info, const aacg_tns_info* in, aacg_dev_tns* out)
 {
     std::memset(out, 0, sizeof *out);
     const bool is_short = info->window_sequence == AACG_EIGHT_SHORT_SEQUENCE;
-    int swb[64];
-    const int swb_count = aacg_swb_offsets(sample_index, is_short ? 0 : 1, swb);
+    aacg_tns_bands bands;                                            /* the limits the device's maker of these records takes too */
+    if (aacg_tns_bands_make(sample_index, &bands)) return AACG_ERR_INVALID_ARG;
+    const uint16_t* swb = is_short ? bands.swb_short : bands.swb_long;
+    const int swb_count = (int)(is_short ? bands.n_short : bands.n_long);
     /* tns.js:106 intends min(maxBands, maxSFB); the short-window table is the documented deviation of SPEC mode */
-    const int max_bands = is_short ? kTnsMaxBandsShort[sample_index] : kTnsMaxBandsLong[sample_index];
+    const int max_bands = (int)(is_short ? bands.tns_short : bands.tns_long);
     const int mmm = std::min<int>(max_bands, info->max_sfb);
     const int n_win = is_short ? 8 : 1;
     for (int w = 0; w < n_win; w++) {

@@ -14,7 +14,7 @@ aacg_route aacg_pick_route(int input_kind, int output_kind, int debug_route, boo
     r.has_side = false; r.side_key = 0; r.side_first = false; r.couple_pcm = false; r.overlappable = false;
     const bool i16 = output_kind == AACG_OUTPUT_I16;
     bool quant = input_kind == AACG_INPUT_QUANT_I16;
-    const bool stages = h.any_tns || (quant && h.any_pns);
+    const bool stages = h.stages_plan || h.any_tns || (quant && h.any_pns);
     const unsigned nt = (h.wide_frames && !tracing) ? AACG_RK_NT : 0u;     /* batches of multichannel frames: non-temporal loads of the spectra */
     /* plain batches — no optional stage, no coupling element: with a chain longer than a run, or launched through the
      * pipeline, they take the rendezvous cut of their chains (AACG_DEBUG_ROUTE_RECOMPUTE: long chains the old way; serial launches only) */
@@ -28,7 +28,8 @@ aacg_route aacg_pick_route(int input_kind, int output_kind, int debug_route, boo
     }
     /* the optional stages inside the run kernel, same cut: one launch where a chain longer than a run took a staged route, and
      * launches through the pipeline overlap */
-    if (stages && !i16 && !h.any_cce && !h.runs_rv.empty() && (pipelined || (h.long_chains && !(debug_route & AACG_DEBUG_ROUTE_RECOMPUTE)))) {
+    /* (a plan made for aacg_decode_pipelined_stages knows no other route: aacg_host.h, stages_plan) */
+    if (stages && !i16 && !h.any_cce && !h.runs_rv.empty() && (h.stages_plan || pipelined || (h.long_chains && !(debug_route & AACG_DEBUG_ROUTE_RECOMPUTE)))) {
         r.has_run = true;
         r.run_key = AACG_RK_EX | AACG_RK_RV | (quant ? AACG_RK_QUANT : 0u);
         r.rv = true;

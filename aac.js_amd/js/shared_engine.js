@@ -22,9 +22,10 @@
  * transform kernel, PCM down) and slices what comes back.  JavaScript touches no coefficient and no unit record; what
  * readChunk() returns are views of the batch's PCM array.  For ADTS byte streams of any channel configuration 1..8 (one
  * pipeline per sample rate and channel count; a stream's element layout — SCE + CPE + CPE + LFE, say — is learnt on the device
- * from its first frame, coupling elements are parsed and dropped), as the reference executes them (TNS identity, no PNS /
- * coupling modes).  MP4 samples ('mp4a': packets without ADTS headers, several to a buffer, whose boundaries only a parse
- * finds) and decoders with spec modes take the parsing route above on the same SharedEngine — unless
+ * from its first frame, coupling elements are parsed and dropped), as the reference executes them (TNS identity, no PNS) or, on a
+ * SharedEngine made with { tnsMode, pnsMode }, with the spec-correct TNS filters and noise bands (aacg_pipeline_config.stages: the
+ * TNS records are made on the device; float32 PCM).  MP4 samples ('mp4a': packets without ADTS headers, several to a buffer, whose
+ * boundaries only a parse finds) and decoders with cceMode or carryWindowShape take the parsing route above on the same SharedEngine — unless
  * { residentPackets: true }: then an 'mp4a' decoder takes the resident route too.  A single-sample packet is a frame; the blocks
  * of a multi-sample packet are found on the device (aacg_pipeline_walk_submit: one GPU lane walks one packet), a flush ahead of
  * the flush that decodes them, and then travel like ADTS frames.
@@ -101,7 +102,11 @@ SharedEngine.prototype.attach = function (dec) {
 SharedEngine.prototype.takesResident = function (dec) {
     const cfg = dec.config, id = dec.format ? dec.format.formatID : undefined;
     const adts = id === undefined || id === 'aac ', mp4a = this.residentPackets && id === 'mp4a';
-    return this.resident && (adts || mp4a) && cfg.profile === 2 && cfg.chanConfig >= 1 && cfg.chanConfig <= 8 && !dec.tnsMode && !dec.pnsMode && !dec.cceMode && !dec.carryWindowShape;
+    /* the spec-correct stages ride the resident route when the engine was made with them: the decoder's modes must be the engine's
+     * (as on the parsing route), and the stages' launches write float32 PCM */
+    const o = this.opts, stages = (o.tnsMode | 0) || (o.pnsMode | 0);
+    const modes = (dec.tnsMode | 0) === (o.tnsMode | 0) && (dec.pnsMode | 0) === (o.pnsMode | 0) && !(stages && (o.outputKind | 0) === host.OUTPUT_I16);
+    return this.resident && (adts || mp4a) && cfg.profile === 2 && cfg.chanConfig >= 1 && cfg.chanConfig <= 8 && modes && !dec.cceMode && !dec.carryWindowShape;
 };
 
 /* resident route: one pipeline (engine + parser on the device) per (sample rate, channel count) */
@@ -114,7 +119,8 @@ SharedEngine.prototype.attachResident = function (dec) {
         const pipeline = addon.pipelineCreate({ deviceOrdinal: this.opts.deviceOrdinal | 0, sampleIndex: cfg.sampleIndex, maxStreams: this.maxStreams,
                                                 channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
                                                 parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0),
-                                                planMode: this.devicePlans ? 1 : 0 }, rec.entries, rec.counts);
+                                                planMode: this.devicePlans ? 1 : 0,
+                                                stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) }, rec.entries, rec.counts);
         g = { resident: true, addon: addon, pipeline: pipeline, channels: cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }

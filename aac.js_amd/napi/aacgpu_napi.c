@@ -511,8 +511,8 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     free(b);
 }
 
-/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode}, entries, counts) -> external
- * (planMode 1: device plans, aacg_pipeline_config.plan_mode) */
+/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages}, entries, counts) -> external
+ * (planMode 1: device plans, aacg_pipeline_config.plan_mode; stages: AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS, aacg_pipeline_config.stages) */
 static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
 {
     size_t argc = 3; napi_value argv[3], out;
@@ -537,6 +537,7 @@ static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
     cfg.parse_options = get_i32(env, argv[0], "parseOptions", AACG_PARSE_REFERENCE_QUIRKS);
     cfg.lanes = get_i32(env, argv[0], "lanes", 0);
     cfg.plan_mode = get_i32(env, argv[0], "planMode", 0);
+    cfg.stages = get_i32(env, argv[0], "stages", 0);
     aacg_pipeline* p = NULL;
     int rc = L.pipeline_create(&cfg, (const aacg_code_entry*)de, (const uint32_t*)dc, &p);
     if (rc) {

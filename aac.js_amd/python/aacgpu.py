@@ -32,9 +32,9 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_create", "aacg_pipeline_destroy", "aacg_pipeline_last_error", "aacg_pipeline_reset_stream", "aacg_pipeline_decode",
                "aacg_pipeline_submit", "aacg_pipeline_collect", "aacg_pipeline_set_wait_limit_ms", "aacg_pipeline_stream_layout",
                "aacg_set_wait_limit_ms", "aacg_parser_set_wait_limit_ms", "aacg_pipeline_info",
-               "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_parse_walk", "aacg_parse_walk_device",
+               "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_tns_records_bytes", "aacg_tns_records_from_parse", "aacg_plan_create_stages", "aacg_decode_pipelined_stages", "aacg_parse_walk", "aacg_parse_walk_device",
                "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged",
-               "aacg_plan_create_shaped", "aacg_plan_shape_table", "aacg_plan_shape_launch"]
+               "aacg_plan_create_shaped", "aacg_plan_create_shaped_stages", "aacg_plan_shape_table", "aacg_plan_shape_launch"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -45,6 +45,7 @@ WAIT_SPIN, WAIT_YIELD, WAIT_SLEEP, WAIT_BLOCK = 0, 1, 2, 3
 DEBUG_ROUTE_UNFUSED_COUPLING, DEBUG_ROUTE_RECOMPUTE = 1, 8
 ROUTE_PLAN_TNS, ROUTE_PLAN_PNS, ROUTE_PLAN_LONG_CHAINS, ROUTE_PLAN_FULL_LATER_RUNS = 1, 2, 4, 8
 ROUTE_PLAN_WIDE_FRAMES, ROUTE_PLAN_CCE_INDEPENDENT, ROUTE_PLAN_CCE_DEPENDENT, ROUTE_PLAN_NO_RUNS = 0x10, 0x20, 0x40, 0x80
+ROUTE_PLAN_STAGES = 0x100
 # switches of a run kernel (aacg_run_kernels.h), as aacg_debug_run_kernel returns them
 RK_QUANT, RK_I16, RK_DD, RK_EX, RK_CPL, RK_RV, RK_NT = 1, 2, 4, 8, 16, 32, 64
 
@@ -63,6 +64,11 @@ TNS_DTYPE = np.dtype([
     ("filt", [("length", "u1"), ("order", "u1"), ("direction", "u1"), ("reserved", "u1"), ("coef", "<f4", (12,))], (8,)),
 ])
 assert TNS_DTYPE.itemsize == 424
+# aacg_dev_tns: the device form of one channel's TNS side info (aacg_tns_records_from_parse; behind a buffer's records, 256-byte
+# aligned, lie TNS_M_DOUBLES doubles of transition matrices per record)
+DEV_TNS_DTYPE = np.dtype([("start", "<i4", (8,)), ("size", "<i4", (8,)), ("inc", "<i4", (8,)), ("order", "<i4", (8,)), ("lpc", "<f4", (8, 12))])
+assert DEV_TNS_DTYPE.itemsize == 512
+TNS_M_DOUBLES = 3 * 12 * 12
 # aacg_cce_info: one per coupling channel element (CCE_SPEC engines; units flagged UNIT_CCE, reserved1 = its index)
 CCE_DTYPE = np.dtype([("coupling_point", "u1"), ("n_targets", "u1"), ("reserved", "u1", (2,)),
                       ("target", [("channel", "u1"), ("gain_list", "u1")], (16,)), ("gain", "<f4", (16, 120))])
@@ -70,6 +76,7 @@ assert CCE_DTYPE.itemsize == 7716
 CCE_REFERENCE, CCE_SPEC = 0, 1
 CCE_BEFORE_TNS, CCE_AFTER_TNS, CCE_AFTER_IMDCT = 0, 1, 2
 TNS_REFERENCE, TNS_SPEC = 0, 1
+PIPELINE_STAGE_TNS, PIPELINE_STAGE_PNS = 1, 2        # aacg_pipeline_config.stages
 PNS_REFERENCE, PNS_SPEC = 0, 1
 UNIT_COMMON_WINDOW, UNIT_MASK_PRESENT, UNIT_HAS_PNS, UNIT_CCE = 1, 2, 4, 8
 CHAN_TNS_PRESENT = 0x01
@@ -84,7 +91,7 @@ class Config(C.Structure):
 class PipelineConfig(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("device_ordinal", C.c_int32), ("sample_index", C.c_int32), ("max_streams", C.c_int32),
                 ("channels", C.c_int32), ("max_frames", C.c_int32), ("output_kind", C.c_int32), ("parse_options", C.c_int32),
-                ("lanes", C.c_int32), ("plan_mode", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("lanes", C.c_int32), ("plan_mode", C.c_int32), ("stages", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 # aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
@@ -218,6 +225,11 @@ def load_library(path=LIB_PATH):
     L.aacg_debug_in_flight.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.aacg_plan_set_unit_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.aacg_plan_refresh_from_parse_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.aacg_plan_create_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.aacg_decode_pipelined_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.aacg_tns_records_bytes.restype = C.c_size_t
+    L.aacg_tns_records_bytes.argtypes = [C.c_uint32]
+    L.aacg_tns_records_from_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.aacg_pipeline_create.argtypes = [C.POINTER(PipelineConfig), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.aacg_pipeline_destroy.argtypes = [C.c_void_p]
     L.aacg_pipeline_destroy.restype = None
@@ -234,6 +246,7 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_plan_builds.restype = C.c_uint64
     L.aacg_pipeline_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.aacg_plan_create_shaped.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.aacg_plan_create_shaped_stages.argtypes = L.aacg_plan_create_shaped.argtypes
     L.aacg_plan_shape_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     L.aacg_plan_shape_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.aacg_pipeline_set_wait_limit_ms.argtypes = [C.c_void_p, C.c_uint32]
@@ -431,13 +444,13 @@ class Pipeline:
     (aacg_pipeline_config.plan_mode 1) instead of a kept plan per batch shape: for feeds whose batches seldom repeat a shape."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
-                 parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False):
+                 parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
         entries, counts = np.ascontiguousarray(entries), np.ascontiguousarray(counts, np.uint32)
         cfg = PipelineConfig(self.lib.aacg_abi_version(), device, sample_index, max_streams, channels, max_frames, output_kind, parse_options, lanes,
-                             1 if device_plans else 0)
+                             1 if device_plans else 0, (PIPELINE_STAGE_TNS if tns_spec else 0) | (PIPELINE_STAGE_PNS if pns_spec else 0))
         h = C.c_void_p()
         rc = self.lib.aacg_pipeline_create(C.byref(cfg), entries.ctypes.data, counts.ctypes.data, C.byref(h))
         if rc != 0:
@@ -692,10 +705,12 @@ class Engine:
         self._check(self.lib.aacg_plan_create(self.handle, units.ctypes.data, len(units), C.byref(h)))
         return Plan(self, h, len(units))
 
-    def plan_shaped(self, max_streams, max_frames, max_elems=1, n_sets=1):
-        """aacg_plan_create_shaped: a plan with a capacity instead of a shape, shaped on the device batch by batch."""
+    def plan_shaped(self, max_streams, max_frames, max_elems=1, n_sets=1, stages=False):
+        """aacg_plan_create_shaped: a plan with a capacity instead of a shape, shaped on the device batch by batch
+        (stages: aacg_plan_create_shaped_stages, the one for decode_pipelined_stages on a SPEC engine)."""
         h = C.c_void_p()
-        self._check(self.lib.aacg_plan_create_shaped(self.handle, max_streams, max_frames, max_elems, n_sets, C.byref(h)))
+        make = self.lib.aacg_plan_create_shaped_stages if stages else self.lib.aacg_plan_create_shaped
+        self._check(make(self.handle, max_streams, max_frames, max_elems, n_sets, C.byref(h)))
         return Plan(self, h, 0)
 
     def plan_shape_table(self, plan, set_index, table, parse_channels):
@@ -704,6 +719,26 @@ class Engine:
         n = C.c_uint32()
         self._check(self.lib.aacg_plan_shape_table(self.handle, plan.handle, set_index, table.ctypes.data, len(table), parse_channels, C.byref(n)))
         return int(n.value)
+
+    def plan_stages(self, units):
+        """aacg_plan_create_stages: a kept plan whose launches bring the optional stages' records (decode_pipelined_stages)"""
+        units = np.ascontiguousarray(units)
+        assert units.dtype == UNIT_DTYPE
+        h = C.c_void_p()
+        self._check(self.lib.aacg_plan_create_stages(self.handle, units.ctypes.data, len(units), C.byref(h)))
+        return Plan(self, h, len(units))
+
+    def decode_pipelined_stages(self, plan, d_coeffs, d_meta, d_tns_records, n_tns_records, d_pcm):
+        self._check(self.lib.aacg_decode_pipelined_stages(self.handle, plan.handle, d_coeffs, d_meta, d_tns_records, n_tns_records, d_pcm))
+
+    def tns_records_bytes(self, n_records):
+        return int(self.lib.aacg_tns_records_bytes(n_records))
+
+    def tns_records_from_parse(self, d_parsed_units, d_results, d_tns_info, n_frames, max_units, parse_channels, d_records, stream=0):
+        """aacg_tns_records_from_parse: the batch's TNS records (DEV_TNS_DTYPE) and their matrices from aacg_parse_device's outputs,
+        on the device; d_* raw device addresses, d_records of tns_records_bytes(n_frames * parse_channels) bytes."""
+        self._check(self.lib.aacg_tns_records_from_parse(self.handle, d_parsed_units, d_results, d_tns_info, n_frames, max_units, parse_channels,
+                                                         d_records, stream))
 
     def decode_device(self, plan, d_coeffs, d_meta, d_pcm, stream=0):
         """d_* are raw device addresses (e.g. torch.Tensor.data_ptr()); stream a hipStream_t handle or 0."""

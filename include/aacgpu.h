@@ -547,7 +547,8 @@ int aacg_parse_walk_device(aacg_parser* p, const void* d_bytes, const aacg_parse
  * with max_units per frame), the rest stays.  A frame the parser refused, an element that is not the one the plan
  * expects (other channels, other blocks), or a unit with noise bands (their stage is chosen when a plan is built) becomes a silent unit and is counted in *d_refused (device
  * counter, caller zeroes it).  Asynchronous on hip_stream; follow with aacg_decode_device on the same stream.
- * QUANT_I16 engines with AACG_TNS_REFERENCE only (TNS records are prepared on the host).                      */
+ * QUANT_I16 engines; with AACG_TNS_SPEC / AACG_PNS_SPEC for plans made for aacg_decode_pipelined_stages only (any other plan's
+ * TNS records and noise-band route were prepared on the host, when it was built).                              */
 int aacg_plan_refresh_from_parse(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* d_parsed_units,
                                  const aacg_parse_result* d_results, uint32_t max_units, uint32_t* d_refused,
                                  void* hip_stream);
@@ -572,6 +573,40 @@ int aacg_plan_set_unit_sets(aacg_engine* e, aacg_plan* p, uint32_t n_sets);     
 int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* d_parsed_units,
                                     aacg_parse_result* d_results, uint32_t max_units, const aacg_refresh_map* d_map,
                                     uint32_t set, uint32_t* d_refused, void* hip_stream);
+
+/* ---- TNS records made on the device (AACG_TNS_SPEC) ---------------------------------------------------------------------------
+ * What the host planner makes of an aacg_tns_info before a launch can run its filters — per filter the sample range, the
+ * direction and the direct-form coefficients (tns.js:111-152) — made where aacg_parse_device left its outputs instead: one small
+ * launch on hip_stream and, behind it, the records' transition matrices.  The bytes are those of the host-made records.
+ *   d_parsed_units, d_results, d_tns_info: aacg_parse_device's outputs of n_frames frames (max_units elements and parse_channels
+ *     channel blocks per frame; d_tns_info must have been requested from the parser);
+ *   d_records: aacg_tns_records_bytes(n_frames * parse_channels) bytes of device memory, 256-byte aligned.  Record
+ *     tns_offset + c of a parsed unit is its channel c's, as in a host-made array; the record of a block no accepted frame's unit
+ *     owns, or whose channel has no AACG_CHAN_TNS_PRESENT, is empty (order 0 in every slot).  Every record is written.
+ * A frame the parser refused is not read.  TNS orders above AACG_TNS_MAX_ORDER never arrive (AACG_PARSE_TNS_ORDER refuses the
+ * frame when TNS records are requested); a filter count or order beyond the syntax leaves its slots empty. */
+size_t aacg_tns_records_bytes(uint32_t n_records);
+int aacg_tns_records_from_parse(aacg_engine* e, const aacg_unit_desc* d_parsed_units, const aacg_parse_result* d_results,
+                                const aacg_tns_info* d_tns_info, uint32_t n_frames, uint32_t max_units, uint32_t parse_channels,
+                                void* d_records, void* hip_stream);
+/* The optional stages between parser and transform without the host: on an engine with AACG_TNS_SPEC and / or AACG_PNS_SPEC
+ * (AACG_INPUT_QUANT_I16, float32 PCM, no coupling) a plan made FOR THIS ROUTE holds structure only, and what a batch's frames
+ * hold arrives with the launch — unit records through aacg_plan_refresh_from_parse_ex (TNS flags and tns_offset as parsed on
+ * AACG_TNS_SPEC engines, units with noise bands taken on AACG_PNS_SPEC engines), TNS records through d_tns_records.
+ *   aacg_plan_create_stages: a kept plan from units that carry the structure (as for aacg_plan_refresh_from_parse; no TNS flag,
+ *     no noise-band flag).
+ *   aacg_plan_create_shaped_stages: aacg_plan_create_shaped (below) for this route — the same capacity, sets and shaping calls.
+ *     aacg_plan_create_shaped itself refuses an engine with optional stages, as it always did.
+ *   aacg_decode_pipelined_stages: aacg_decode_pipelined with the batch's TNS records (aacg_tns_records_from_parse's buffer of
+ *     n_tns_records records; NULL / 0 on an engine without AACG_TNS_SPEC).  The caller orders the launch behind the work that
+ *     made them (aacg_pipeline_fork) and keeps them until the launch is complete.
+ * Such a plan always launches aacg_imdct_run_quant_ex_rv on two pipeline streams (aacg_plan_kernels), whether or not a batch
+ * holds a filter or a noise band: route, stream count and the rule which launches continue their predecessor do not depend on
+ * a batch's content.  aacg_decode_device / aacg_decode_pipelined refuse it (AACG_ERR_UNSUPPORTED). */
+int aacg_plan_create_stages(aacg_engine* e, const aacg_unit_desc* units, uint32_t n_units, aacg_plan** out);
+int aacg_plan_create_shaped_stages(aacg_engine* e, uint32_t max_streams, uint32_t max_frames, uint32_t max_elems, uint32_t n_sets, aacg_plan** out);
+int aacg_decode_pipelined_stages(aacg_engine* e, aacg_plan* plan, const void* d_coeffs, const aacg_band_meta* d_meta,
+                                 const void* d_tns_records, uint32_t n_tns_records, void* d_pcm);
 
 /* ---- a plan with a capacity instead of a shape: shaped on the device, batch by batch --------------------------------------
  * On the resident route a plan is a pure function of the batch's shape — the stream slots in order, each one's frame count
@@ -642,7 +677,8 @@ int aacg_plan_refresh_units(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* 
  * elements of a frame in order, channels dealt out in element order, elements beyond `channels` dropped (decoder.js:233-247) —
  * is learnt from the first frame it submits after aacg_pipeline_reset_stream, and a later frame with other elements is
  * refused as a whole (AACG_PARSE_LAYOUT).  Coupling channel elements are parsed and dropped, as the reference executes them.
- * A pipeline owns an engine (AACG_INPUT_QUANT_I16, AACG_TNS_REFERENCE) and a parser; it is not re-entrant. */
+ * A pipeline owns an engine (AACG_INPUT_QUANT_I16; AACG_TNS_REFERENCE / AACG_PNS_REFERENCE unless aacg_pipeline_config.stages says
+ * otherwise) and a parser; it is not re-entrant. */
 typedef struct aacg_pipeline aacg_pipeline;
 typedef struct aacg_pipeline_config {
     int32_t abi_version;       /* AACG_ABI_VERSION                                                          */
@@ -660,8 +696,20 @@ typedef struct aacg_pipeline_config {
                                   one round: mode 0 is what existing callers get and what the tests compare mode 1's bits
                                   against; once mode 1 is measured the switch and mode 0's path (plan_for, its LRU, the
                                   stale-plan retry) go.  (reserved[0] until now: zero selects today's path)                */
-    int32_t reserved[2];       /* zero                                                                      */
+    int32_t stages;            /* AACG_PIPELINE_STAGE_*: the spec-correct optional stages on this route.  Bit 0: AACG_TNS_SPEC —
+                                  the parser writes TNS side info, aacg_tns_records_from_parse makes the records on the lane's
+                                  stream behind the parse, the transform runs the filters.  Bit 1: AACG_PNS_SPEC — a frame with
+                                  noise bands is decoded instead of refused.  With either the engine is created in those modes
+                                  and every launch goes through aacg_decode_pipelined_stages (aacg_imdct_run_quant_ex_rv), in
+                                  both plan modes.  Needs AACG_OUTPUT_F32 (AACG_ERR_UNSUPPORTED with AACG_OUTPUT_I16: that route is
+                                  the staged spectral launch, which needs a spectrum buffer per plan and does not overlap).
+                                  Unchanged: TNS orders 13..20 refuse the frame (AACG_PARSE_TNS_ORDER), coupling elements are
+                                  parsed and dropped, window_shape_prev is 0.  (reserved[0] until now: zero selects today's
+                                  path, call for call)                                                                     */
+    int32_t reserved[1];       /* zero                                                                      */
 } aacg_pipeline_config;
+#define AACG_PIPELINE_STAGE_TNS 1
+#define AACG_PIPELINE_STAGE_PNS 2
 int  aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry* entries, const uint32_t counts[12], aacg_pipeline** out);
 void aacg_pipeline_destroy(aacg_pipeline* p);
 const char* aacg_pipeline_last_error(const aacg_pipeline* p);

@@ -85,6 +85,7 @@ int aacg_debug_set_route(aacg_engine* e, int flags);
 #define AACG_ROUTE_PLAN_CCE_INDEPENDENT  0x020   /* independently switched coupling elements */
 #define AACG_ROUTE_PLAN_CCE_DEPENDENT    0x040   /* coupling in the spectral domain */
 #define AACG_ROUTE_PLAN_NO_RUNS          0x080   /* no element with a filterbank pass of its own in the main runs */
+#define AACG_ROUTE_PLAN_STAGES           0x100   /* a plan made for aacg_decode_pipelined_stages (aacg_plan_create_stages): the flag set at creation */
 int aacg_debug_route(int input_kind, int output_kind, int debug_route, int plan_flags, int pipelined, char* dst, size_t n);
 /* The registered run kernels: the index-th symbol into dst, returns its switches (the key launch_run looks it up by), < 0 past the end. */
 int aacg_debug_run_kernel(int index, char* dst, size_t n);

@@ -5,8 +5,10 @@
  * the other 0.5 ms goes" — run it under `rocprofv3 --kernel-trace --memory-copy-trace --stats` for the per-stage durations.
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
- *                                         [--device-plans] [--new-shapes [--seed N]]
+ *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *
+ * --tns-spec / --pns-spec: aacg_pipeline_config.stages (the spec-correct TNS filters / noise bands; the TNS records are made on the
+ * device, every launch is aacg_imdct_run_quant_ex_rv).  --pulses: AACG_PARSE_APPLY_PULSES (streams with pulse data).
  * --device-plans: aacg_pipeline_config.plan_mode 1 (one plan shaped on the device per batch instead of a kept plan per shape).
  * --new-shapes: every batch a NEW seeded shape — each stream brings 1..F frames (aacg_pipeline_submit_ragged) — which is what a
  * jittered feed gives the route; the line then also says how long the host spent inside the submit call alone, per batch.
@@ -35,7 +37,7 @@ int main(int argc, char** argv)
     if (argc < 2) { std::fprintf(stderr, "usage: resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]\n"); return 2; }
     uint32_t S = 256, F = 16;
     int batches = 200, lanes = 3;
-    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false;
+    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false;
     uint64_t seed = 1;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
@@ -49,6 +51,9 @@ int main(int argc, char** argv)
         else if (a == "--pageable") pageable = true;
         else if (a == "--device-plans") device_plans = true;
         else if (a == "--new-shapes") new_shapes = true;
+        else if (a == "--tns-spec") tns_spec = true;
+        else if (a == "--pns-spec") pns_spec = true;
+        else if (a == "--pulses") pulses = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -82,8 +87,9 @@ int main(int argc, char** argv)
     aacg_pipeline_config cfg;
     std::memset(&cfg, 0, sizeof cfg);
     cfg.abi_version = AACG_ABI_VERSION; cfg.sample_index = (int32_t)sample_index; cfg.max_streams = (int32_t)S; cfg.channels = (int32_t)channels; cfg.max_frames = (int32_t)F;
-    cfg.output_kind = i16 ? AACG_OUTPUT_I16 : AACG_OUTPUT_F32; cfg.parse_options = AACG_PARSE_REFERENCE_QUIRKS; cfg.lanes = sync ? 1 : lanes;
+    cfg.output_kind = i16 ? AACG_OUTPUT_I16 : AACG_OUTPUT_F32; cfg.parse_options = AACG_PARSE_REFERENCE_QUIRKS | (pulses ? AACG_PARSE_APPLY_PULSES : 0); cfg.lanes = sync ? 1 : lanes;
     cfg.plan_mode = device_plans ? 1 : 0;
+    cfg.stages = (tns_spec ? AACG_PIPELINE_STAGE_TNS : 0) | (pns_spec ? AACG_PIPELINE_STAGE_PNS : 0);
     aacg_pipeline* p = nullptr;
     int rc = aacg_pipeline_create(&cfg, entries.data(), counts, &p);
     if (rc) { std::fprintf(stderr, "aacg_pipeline_create: %d\n", rc); return 2; }
@@ -141,11 +147,11 @@ int main(int argc, char** argv)
     else { const int16_t* w = (const int16_t*)out[0]; for (size_t i = 0; i < pcm_bytes / 2; i += 97) nonzero = nonzero || w[i] != 0; }
     std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", "
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
-                "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
+                "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
                 pageable ? "pageable" : "page-locked", bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
-                (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
+                (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
     return (finite && nonzero && !bad) ? 0 : 1;

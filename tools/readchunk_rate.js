@@ -10,6 +10,8 @@
  *   - GpuAACDecoder with the JavaScript front end (parse on the CPU, transform on the GPU),
  *   - GpuAACDecoder with the device front end (parse and transform on the GPU),
  *   - the reference's own AACDecoder.readChunk() when the reference checkout is present (build container only; CPU).
+ *                                                            --tns-spec / --pns-spec: decoders and SharedEngine in the spec-correct
+ *                                                            modes (with --resident: the stages on the resident route)
  *   node tools/readchunk_rate.js --mp4a [--samples-per-packet 16] [--streams 256] [repeats]
  *                                                            the same streams as MP4 chunks (ADTS headers cut off, N samples per
  *                                                            feedPacket buffer) on a SharedEngine: the parsing route, and the
@@ -91,6 +93,9 @@ function ours(gpuParse) {
 /* N concurrent streams: the same bytes into N decoders, read round robin as N players would; `shared`: one SharedEngine
  * (one batch per flush for all of them) or an engine per decoder (one batch per decoder: what N independent plugin instances
  * do).  Engine time = wall time inside engine.decodeBatch (upload, kernels, download), on this one JavaScript thread. */
+/* --tns-spec / --pns-spec: decoders and SharedEngine in the spec-correct modes (resident: aacg_pipeline_config.stages) */
+const specTns = process.argv.indexOf('--tns-spec') >= 0 ? 1 : 0, specPns = process.argv.indexOf('--pns-spec') >= 0 ? 1 : 0;
+
 /* yieldEvery > 0 (manyAsync): the same drain, but back to the event loop after every yieldEvery round-robin passes — what an
  * event-driven host (Aurora decodes from timers and 'data' events) does anyway, and what lets the garbage collector's finalizers
  * return a flush's page-locked PCM buffer to the addon's pool instead of a fresh 33 MB being page-locked per flush */
@@ -104,7 +109,7 @@ function many(shared, lookahead, pcmRing, overlap, yieldEvery, done) {
             return eng;
         };
         const sh = shared ? new host.SharedEngine({ maxStreams: nStreams, maxChannels: Math.max(2, nChannels), resident: resident, lookahead: lookahead, pcmRing: pcmRing | 0, overlap: !!overlap,
-                                                 devicePlans: argv0.indexOf('--device-plans') >= 0 }) : null;
+                                                 devicePlans: argv0.indexOf('--device-plans') >= 0, tnsMode: specTns, pnsMode: specPns, applyPulses: specTns || specPns ? true : undefined }) : null;
         const finish = function (t0, n, sum) {
             if (resident) { engineNs = sh.stats.engineNs; batches = sh.stats.batches; }       // wall time inside the one native call per flush
             const s = Number(process.hrtime.bigint() - t0) / 1e9, es = Number(engineNs) / 1e9;
@@ -113,7 +118,7 @@ function many(shared, lookahead, pcmRing, overlap, yieldEvery, done) {
         };
         const decs = [];
         for (let i = 0; i < nStreams; i++) {
-            const dec = new host.GpuAACDecoder({ frontend: resident ? null : new host.FrontEnd(), lookahead: lookahead, shared: sh });
+            const dec = new host.GpuAACDecoder({ frontend: resident ? null : new host.FrontEnd(), lookahead: lookahead, shared: sh, tnsMode: specTns, pnsMode: specPns });
             dec.init();
             const demux = new host.adts.AdtsDemuxer(function (event, payload) {
                 if (event === 'format') Object.assign(dec.format, payload);
