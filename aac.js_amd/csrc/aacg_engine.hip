@@ -26,6 +26,7 @@
 #include "aacg_host.h"
 #include "aacg_routes.h"
 #include "aacg_plan_shape.h"
+#include "aacg_shape_carry.h"
 #include "aacg_tns_prep.h"
 #include "aacg_wait.h"
 
@@ -39,6 +40,8 @@ void aacg_refresh_launch(aacg_dev_unit* units, const aacg_unit_desc* parsed, aac
                          uint32_t max_units, int refuse_pns, int keep_tns, uint32_t* refused, hipStream_t s);
 /* aacg_engine_shape.hip: a shaped plan's set of tables from the batch's per-stream table (aacg_plan_shape.h) */
 void aacg_shape_launch(const aacg_shape_args& A, hipStream_t s);
+/* aacg_engine_carry.hip: window_shape_prev of a set's refreshed records, from frame to frame and batch to batch (aacg_shape_carry.h) */
+void aacg_carry_launch(const aacg_carry_args& A, hipStream_t s);
 /* aacg_engine_spectral.hip: the optional stages (AACG_PNS_SPEC noise bands, AACG_TNS_SPEC filters) -> f32 spectra */
 int aacg_spectral_ex_set_lds_limits(void);
 void aacg_spectral_ex_launch(bool quant, int n_units, hipStream_t s, const aacg_kparams& P);
@@ -106,6 +109,12 @@ struct aacg_engine {
     float* d_overlap = nullptr;             /* [max_streams][max_channels][AACG_OV_BUFFERS][1024] */
     std::vector<uint8_t> parity;            /* live buffer (0..AACG_OV_BUFFERS-1) per (stream, channel) */
     uint64_t epoch = 0;                     /* bumped whenever `parity` changes: lets a relaunched plan skip its check */
+    /* the other half of a stream's filterbank state: the window shape of each channel's last frame (aacg_shape_carry.h) */
+    uint32_t* d_wshape = nullptr;           /* [max_streams][max_channels] entries (before | after << 1 | serial << 2) */
+    hipEvent_t carried = nullptr;           /* behind the most recent carry launch: the next one's stream waits for it */
+    bool carried_any = false;
+    uint32_t carry_serial = 0;              /* of the most recent carry launch */
+    bool carry_open = false;                /* no launch has taken that carry's records yet: a carry now repeats its batch (same serial) */
     aacg_tables h_tab;
     aacg_host_windows h_win;
     /* pipelined launches (aacg_decode_pipelined): AACG_PIPE_STREAMS internal streams taken in turn, so that a launch starts on the
@@ -200,6 +209,8 @@ struct aacg_plan {
         uint64_t epoch = ~0ull;                     /* the engine's epoch the rotation words were taken at */
     };
     shaped_t* sh = nullptr;
+    int carry_ok = -1;                      /* aacg_plan_carry_window_shape: can the listing be carried through (aacg_carry_listing_ok)?  -1: not looked at yet */
+    std::string carry_why;
     size_t unit_stride() const { return sh ? sh->lim.max_units : n_units; }
     const aacg_dev_unit* units_now() const { return b.units() + (size_t)cur_set * unit_stride(); }
     ~aacg_plan() { delete sh; }
@@ -711,6 +722,9 @@ int aacg_create(const aacg_config* cfg, aacg_engine** out)
         !hip_ok(e, hipMalloc((void**)&e->d_overlap, ov_bytes), "hipMalloc overlap") ||
         !hip_ok(e, hipMemcpy(e->d_tab, &e->h_tab, sizeof(aacg_tables), hipMemcpyHostToDevice), "upload tables") ||
         !hip_ok(e, hipMemset(e->d_overlap, 0, ov_bytes), "zero overlap") ||
+        !hip_ok(e, hipMalloc((void**)&e->d_wshape, (size_t)cfg->max_streams * (size_t)cfg->max_channels * sizeof(uint32_t)), "hipMalloc window shapes") ||
+        !hip_ok(e, hipMemset(e->d_wshape, 0, (size_t)cfg->max_streams * (size_t)cfg->max_channels * sizeof(uint32_t)), "zero window shapes") ||
+        !hip_ok(e, hipEventCreateWithFlags(&e->carried, hipEventDisableTiming), "hipEventCreate (carry)") ||
         /* pipelined launches: the cross-launch cells (state words count only with an epoch in them: they start from zero) and the pool of windowed first halves */
         !hip_ok(e, hipMalloc((void**)&e->d_xl_cells, n_cells * sizeof(aacg_xl_cell)), "hipMalloc cells") ||
         !hip_ok(e, hipMemset(e->d_xl_cells, 0, n_cells * sizeof(aacg_xl_cell)), "zero cells") ||
@@ -807,6 +821,8 @@ void aacg_destroy(aacg_engine* e)
     if (e->pipe.fork) (void)hipEventDestroy(e->pipe.fork);
     for (hipStream_t st : e->pipe.stream) if (st) (void)hipStreamDestroy(st);
     if (e->d_overlap) (void)hipFree(e->d_overlap);
+    if (e->d_wshape) (void)hipFree(e->d_wshape);
+    if (e->carried) (void)hipEventDestroy(e->carried);
     for (auto& sl : e->slot) {
         for (void* p : sl.b.p) if (p) (void)hipFree(p);
         for (void* p : {sl.d_coeffs, sl.d_meta, sl.d_pcm}) if (p) (void)hipFree(p);
@@ -849,6 +865,8 @@ int aacg_reset_stream(aacg_engine* e, uint32_t stream)
     if (rc) return rc;
     for (int c = 0; c < e->cfg.max_channels; c++)
         HIP_TRY(e, hipMemsetAsync(ov_ptr(e, stream, (uint32_t)c), 0, 4096, e->stream), AACG_ERR_NO_DEVICE);
+    /* ... and the shape its first frame's first half is windowed with: sine (ov_check has waited for every carry in flight) */
+    HIP_TRY(e, hipMemsetAsync(e->d_wshape + (size_t)stream * (size_t)e->cfg.max_channels, 0, (size_t)e->cfg.max_channels * sizeof(uint32_t), e->stream), AACG_ERR_NO_DEVICE);
     return wait_stream(e, e->stream, "aacg_reset_stream");      /* complete before any later launch, whatever stream it takes */
 }
 
@@ -874,6 +892,30 @@ int aacg_set_overlap(aacg_engine* e, uint32_t stream, uint32_t channel, const fl
     for (int i = 0; i < 1024; i++) e->h_ov[i] = src[i] * AACG_PCM_SCALE;
     HIP_TRY(e, hipMemcpyAsync(ov_ptr(e, stream, channel), e->h_ov, 4096, hipMemcpyHostToDevice, e->stream), AACG_ERR_NO_DEVICE);
     return wait_stream(e, e->stream, "aacg_set_overlap");
+}
+
+/* the window shape of the channel's last frame (aacg_shape_carry.h): the other half of what a checkpoint of a stream holds */
+int aacg_get_window_shape(aacg_engine* e, uint32_t stream, uint32_t channel, uint8_t* shape)
+{
+    int rc = ov_check(e, stream, channel);
+    if (rc) return rc;
+    if (!shape) return AACG_ERR_INVALID_ARG;
+    uint32_t* h = (uint32_t*)e->h_ov;
+    HIP_TRY(e, hipMemcpyAsync(h, e->d_wshape + (size_t)stream * (size_t)e->cfg.max_channels + channel, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream), AACG_ERR_NO_DEVICE);
+    if ((rc = wait_stream(e, e->stream, "aacg_get_window_shape"))) return rc;
+    *shape = (uint8_t)aacg_carry_now(*h);
+    return AACG_OK;
+}
+
+int aacg_set_window_shape(aacg_engine* e, uint32_t stream, uint32_t channel, uint8_t shape)
+{
+    int rc = ov_check(e, stream, channel);
+    if (rc) return rc;
+    if (shape > 1) { e->err = "aacg_set_window_shape: 0 (sine) or 1 (KBD)"; return AACG_ERR_INVALID_ARG; }
+    uint32_t* h = (uint32_t*)e->h_ov;
+    *h = aacg_carry_word(shape, shape, 0);                /* serial 0: no launch carries it, every batch starts from `after` */
+    HIP_TRY(e, hipMemcpyAsync(e->d_wshape + (size_t)stream * (size_t)e->cfg.max_channels + channel, h, sizeof(uint32_t), hipMemcpyHostToDevice, e->stream), AACG_ERR_NO_DEVICE);
+    return wait_stream(e, e->stream, "aacg_set_window_shape");
 }
 
 int aacg_get_table(aacg_engine* e, int which, float* dst, size_t n)
@@ -1171,6 +1213,7 @@ static void plan_advance(aacg_engine* e, aacg_plan* p)
 {
     p->launches++;
     p->seen_epoch = parity_advance(e, p->h);
+    e->carry_open = false;                  /* the records a carry prepared have been launched: the next carry is the next batch's */
 }
 
 /* the device buffers a route needs are the ones the plan was made with (aacg_debug_set_route may have changed since) */
@@ -1553,6 +1596,44 @@ int aacg_tns_records_from_parse(aacg_engine* e, const aacg_unit_desc* d_parsed_u
     HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
     aacg_tns_matrices_launch(A.recs, (double*)((char*)d_records + aacg_tns_record_bytes(n)), n, s);
     HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    return AACG_OK;
+}
+
+/* window_shape_prev of the set's records, behind their refresh on the same stream (aacg_shape_carry.h) */
+int aacg_plan_carry_window_shape(aacg_engine* e, aacg_plan* p, const aacg_refresh_map* d_map, uint32_t set, void* hip_stream)
+{
+    if (!e || !p || p->e != e || !d_map || set >= p->unit_sets) return AACG_ERR_INVALID_ARG;
+    if (e->cfg.input_kind != AACG_INPUT_QUANT_I16) { e->err = "aacg_plan_carry_window_shape needs a QUANT_I16 engine"; return AACG_ERR_INVALID_ARG; }
+    uint32_t n_units = p->n_units;
+    if (p->sh) {
+        /* (a shaped set lists a stream's frames one behind the other, a frame's units next to each other: aacg_plan_shape.h) */
+        if (set != p->cur_set) { e->err = "aacg_plan_carry_window_shape: a shaped plan carries through the set shaped and refreshed last"; return AACG_ERR_INVALID_ARG; }
+        n_units = p->sh->set_units[set];
+    } else {
+        if (p->carry_ok < 0) {
+            std::vector<aacg_unit_desc> d(p->h.units.size());
+            for (size_t i = 0; i < d.size(); i++) d[i] = p->h.units[i].d;
+            std::string why;
+            p->carry_ok = aacg_carry_listing_ok(d.data(), d.size(), &why) ? 1 : 0;
+            if (!p->carry_ok) p->carry_why = why;
+        }
+        if (!p->carry_ok) { e->err = "aacg_plan_carry_window_shape: " + p->carry_why; return AACG_ERR_UNSUPPORTED; }
+    }
+    if (!n_units) return AACG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    note_stream(e, s);
+    /* behind the carry before it, whatever stream that took: it reads the state that one left (the wait stands behind this
+     * stream's own parse and refresh) */
+    if (e->carried_any) HIP_TRY(e, hipStreamWaitEvent(s, e->carried, 0), AACG_ERR_NO_DEVICE);
+    if (!e->carry_open) { e->carry_serial = e->carry_serial >= AACG_CARRY_SERIAL_MAX ? 1u : e->carry_serial + 1u; e->carry_open = true; }
+    aacg_carry_args A;
+    A.units = p->b.units() + (size_t)set * p->unit_stride(); A.map = d_map; A.W = e->d_wshape; A.n_units = n_units;
+    A.n_slots = (uint32_t)e->cfg.max_streams; A.C = (uint32_t)e->cfg.max_channels; A.serial = e->carry_serial;
+    aacg_carry_launch(A, s);
+    HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    HIP_TRY(e, hipEventRecord(e->carried, s), AACG_ERR_NO_DEVICE);
+    e->carried_any = true;
     return AACG_OK;
 }
 

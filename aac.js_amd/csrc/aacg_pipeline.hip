@@ -38,6 +38,10 @@
  * parse on the lane's stream, and the plans are plans for aacg_decode_pipelined_stages, which takes those records as a launch input
  * (aacg_plan_create_stages in plan mode 0, aacg_plan_create_shaped_stages in mode 1).  With stages = 0 no call differs from before.
  *
+ * Carried window shapes (AACG_PIPELINE_STAGE_WINDOW_SHAPE, the third bit of stages, independent of the two above): one launch of
+ * aacg_plan_carry_window_shape behind every refresh, inside the stale-plan retry and in both plan modes, sets window_shape_prev of
+ * the batch's unit records from the frame before and, across batches, from the engine's per-channel state (aacg_shape_carry.h).
+ *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
  * (and aacg_pipe_map.h / aacg_plan_shape.h for the tables it fills).
  */
@@ -55,6 +59,9 @@
 #include "aacg_wait.h"
 
 #define AACG_PIPELINE_MAX_LANES 8
+/* the bits of aacg_pipeline_config.stages that select the SPEC engine modes and the plans and launches that go with them
+ * (AACG_PIPELINE_STAGE_WINDOW_SHAPE selects neither: one carry launch behind the refresh, whatever the plan) */
+#define AACG_PIPELINE_SPEC_STAGES (AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS)
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -95,6 +102,8 @@ struct aacg_pipeline {
     uint32_t C = 2;                     /* channels of a frame's PCM (chanConfig) */
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
+    bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
+    bool carry_shape = false;           /* cfg.stages has AACG_PIPELINE_STAGE_WINDOW_SHAPE: aacg_plan_carry_window_shape behind every refresh */
     /* a stream's element layout (aacg_pipe_map.h): channels of every SCE / LFE / CPE of a frame in order; kept = how many of them fit into C channels */
     typedef aacg_pipe_layout layout_t;
     std::vector<layout_t> layout;       /* per slot; n = 0: not learnt yet */
@@ -205,7 +214,7 @@ int plan_for(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of,
     aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, S, p->C, p->Cp, p->U, &u, nullptr, nullptr);
     if (u.empty()) { *out = nullptr; return AACG_OK; }     /* no stream of the batch has a layout yet: nothing to transform, every frame is refused */
     aacg_plan* plan = nullptr;
-    int rc = p->cfg.stages ? aacg_plan_create_stages(p->engine, u.data(), (uint32_t)u.size(), &plan) : aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
+    int rc = p->spec_stages ? aacg_plan_create_stages(p->engine, u.data(), (uint32_t)u.size(), &plan) : aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
     if (rc == AACG_OK && (rc = aacg_plan_set_unit_sets(p->engine, plan, (uint32_t)p->n_lanes))) { aacg_plan_destroy(plan); plan = nullptr; }
     if (rc) { p->err = std::string("aacg_plan_create: ") + aacg_last_error(p->engine); return rc; }
     p->plan_builds++;
@@ -354,9 +363,9 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     if (cfg->abi_version != AACG_ABI_VERSION || cfg->max_streams < 1 || cfg->max_frames < 1 || cfg->channels < 1 || cfg->channels > AACG_MAX_CHANNELS ||
         (cfg->output_kind != AACG_OUTPUT_F32 && cfg->output_kind != AACG_OUTPUT_I16) || (uint64_t)cfg->max_streams * (uint64_t)cfg->max_frames > (1u << 22) ||
         cfg->lanes < 0 || cfg->lanes > AACG_PIPELINE_MAX_LANES || cfg->plan_mode < 0 || cfg->plan_mode > 1 ||
-        (cfg->stages & ~(AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS)) || cfg->reserved[0])
+        (cfg->stages & ~(AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS | AACG_PIPELINE_STAGE_WINDOW_SHAPE)) || cfg->reserved[0])
         return AACG_ERR_INVALID_ARG;
-    if (cfg->stages && cfg->output_kind == AACG_OUTPUT_I16) {
+    if ((cfg->stages & AACG_PIPELINE_SPEC_STAGES) && cfg->output_kind == AACG_OUTPUT_I16) {
         std::fprintf(stderr, "aacgpu: aacg_pipeline_create: stages (AACG_TNS_SPEC / AACG_PNS_SPEC) need AACG_OUTPUT_F32 — with int16 PCM the stages are a spectral launch of "
                              "their own, which needs a spectrum buffer per plan and does not overlap\n");
         return AACG_ERR_UNSUPPORTED;
@@ -364,6 +373,8 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     aacg_pipeline* p = new (std::nothrow) aacg_pipeline();
     if (!p) return AACG_ERR_OUT_OF_MEMORY;
     p->cfg = *cfg;
+    p->spec_stages = (cfg->stages & AACG_PIPELINE_SPEC_STAGES) != 0;
+    p->carry_shape = (cfg->stages & AACG_PIPELINE_STAGE_WINDOW_SHAPE) != 0;
     p->n_lanes = cfg->lanes ? cfg->lanes : 5;      /* four of the lowest priority and one of the level above: int16 PCM 0.37 -> 0.33 ms per batch, the link's rate; six and more share queues again */
     p->C = (uint32_t)cfg->channels;
     p->learn = p->C > 2;
@@ -387,7 +398,7 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
     /* device plans: the one plan, made here — a failure (the in-launch cells of long chains are the large part) is the caller's to
      * see, there is no falling back to kept plans */
     if (rc == AACG_OK && cfg->plan_mode == 1 &&
-        (rc = (cfg->stages ? aacg_plan_create_shaped_stages : aacg_plan_create_shaped)(p->engine, (uint32_t)cfg->max_streams, (uint32_t)cfg->max_frames, p->U, (uint32_t)p->n_lanes, &p->shaped)))
+        (rc = (p->spec_stages ? aacg_plan_create_shaped_stages : aacg_plan_create_shaped)(p->engine, (uint32_t)cfg->max_streams, (uint32_t)cfg->max_frames, p->U, (uint32_t)p->n_lanes, &p->shaped)))
         std::fprintf(stderr, "aacgpu: %s\n", aacg_last_error(p->engine));
     if (rc) { aacg_pipeline_destroy(p); return rc; }
     const size_t n = (size_t)cfg->max_streams * (size_t)cfg->max_frames, C = p->C, Cp = p->Cp, U = p->U;
@@ -570,10 +581,13 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
         if (attempt) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* the stale plan's refresh has counted this batch's refusals already */
         rc = aacg_plan_refresh_from_parse_ex(p->engine, kp->plan, (const aacg_unit_desc*)L.d_units, (aacg_parse_result*)L.d_res, U,
                                              (const aacg_refresh_map*)L.d_map, set, (uint32_t*)L.d_refused, st);
+        /* AACG_PIPELINE_STAGE_WINDOW_SHAPE: the refreshed shapes are final — each frame's first half takes the shape of the frame
+         * before, a stream's first frame the one its previous batch left (a second attempt starts from where the first started) */
+        if (rc == AACG_OK && p->carry_shape) rc = aacg_plan_carry_window_shape(p->engine, kp->plan, (const aacg_refresh_map*)L.d_map, set, st);
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
         if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, st);
-        if (rc == AACG_OK) rc = p->cfg.stages ? aacg_decode_pipelined_stages(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? n * Cp : 0u, L.d_pcm)
+        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? n * Cp : 0u, L.d_pcm)
                                               : aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_pcm);
         if (rc == AACG_OK) p->launches++;
         if (rc != AACG_ERR_STALE_PLAN || attempt || device_plans) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
@@ -717,6 +731,20 @@ int aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     int rc = aacg_pipeline_submit_ragged(p, bytes, n_bytes, frames, slots, n_streams, frames_of, pcm_out, results, n_refused, &t);
     if (rc) return rc;
     return aacg_pipeline_collect(p, t);
+}
+
+int aacg_pipeline_stream_window_shape(aacg_pipeline* p, uint32_t slot, uint8_t shapes[8])
+{
+    if (!p || !shapes || (int)slot >= p->cfg.max_streams) return AACG_ERR_INVALID_ARG;
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    /* what is in flight for the slot is finished first (aacg_get_window_shape waits for the engine's launches and the lanes' streams) */
+    for (int k = 0; k < p->n_lanes; k++) { int rc = finish_lane(p, p->lane[k]); if (rc) return rc; }
+    std::memset(shapes, 0, 8);
+    for (uint32_t c = 0; c < p->C; c++) {
+        int rc = aacg_get_window_shape(p->engine, slot, c, &shapes[c]);
+        if (rc) { p->err = aacg_last_error(p->engine); return rc; }
+    }
+    return AACG_OK;
 }
 
 uint64_t aacg_pipeline_plan_builds(const aacg_pipeline* p) { return p ? p->plan_builds : 0; }

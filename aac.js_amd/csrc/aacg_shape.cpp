@@ -7,6 +7,7 @@
  * aacg_plan_build, which is the reference for every figure here.
  */
 #include "aacg_plan_shape.h"
+#include "aacg_shape_carry.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -118,6 +119,35 @@ bool aacg_shape_same(const aacg_shape_stream* a, size_t na, const aacg_shape_str
         aacg_shape_stream x = a[s], y = b[s];
         x.rot = y.rot = 0;                                 /* the rotation moves on with every launch */
         if (std::memcmp(&x, &y, sizeof x) != 0) return false;
+    }
+    return true;
+}
+
+/* aacg_shape_carry.h: the listing the carry kernel finds a unit's predecessor in */
+bool aacg_carry_listing_ok(const aacg_unit_desc* units, size_t n_units, std::string* why)
+{
+    std::vector<uint32_t> closed;                          /* streams whose stretch has ended */
+    size_t i = 0;
+    while (i < n_units) {
+        const uint32_t stream = units[i].stream;
+        if (std::find(closed.begin(), closed.end(), stream) != closed.end())
+            return fail(why, 0, "the plan lists stream %ld in more than one stretch (unit %ld): a stream's frames must be consecutive", (long)stream, (long)i) != 0;
+        /* the first frame's elements */
+        size_t k = 0;
+        while (i + k < n_units && units[i + k].stream == stream && units[i + k].pcm_offset == units[i].pcm_offset) k++;
+        if (k > 8) return fail(why, 0, "a frame of stream %ld lists %ld units: at most 8", (long)stream, (long)k) != 0;
+        size_t j = i + k;
+        while (j < n_units && units[j].stream == stream) {    /* every further frame: the same elements in the same order */
+            for (size_t e = 0; e < k; e++)
+                if (j + e >= n_units || units[j + e].stream != stream || units[j + e].pcm_offset != units[j].pcm_offset ||
+                    units[j + e].channel != units[i + e].channel || units[j + e].n_ch != units[i + e].n_ch)
+                    return fail(why, 0, "the frames of stream %ld do not list the same elements next to each other (unit %ld)", (long)stream, (long)(j + e)) != 0;
+            if (j + k < n_units && units[j + k].stream == stream && units[j + k].pcm_offset == units[j].pcm_offset)
+                return fail(why, 0, "a frame of stream %ld lists more units than the stream's first (unit %ld)", (long)stream, (long)(j + k)) != 0;
+            j += k;
+        }
+        closed.push_back(stream);
+        i = j;
     }
     return true;
 }

@@ -25,7 +25,9 @@
  * from its first frame, coupling elements are parsed and dropped), as the reference executes them (TNS identity, no PNS) or, on a
  * SharedEngine made with { tnsMode, pnsMode }, with the spec-correct TNS filters and noise bands (aacg_pipeline_config.stages: the
  * TNS records are made on the device; float32 PCM).  MP4 samples ('mp4a': packets without ADTS headers, several to a buffer, whose
- * boundaries only a parse finds) and decoders with cceMode or carryWindowShape take the parsing route above on the same SharedEngine — unless
+ * boundaries only a parse finds) and decoders with cceMode take the parsing route above on the same SharedEngine, and so does a
+ * decoder whose carryWindowShape is not the SharedEngine's ({ resident: true, carryWindowShape: true }: each channel's window shape is
+ * carried from frame to frame on the device, aacg_pipeline_config.stages bit 2; with int16 PCM too) — unless
  * { residentPackets: true }: then an 'mp4a' decoder takes the resident route too.  A single-sample packet is a frame; the blocks
  * of a multi-sample packet are found on the device (aacg_pipeline_walk_submit: one GPU lane walks one packet), a flush ahead of
  * the flush that decodes them, and then travel like ADTS frames.
@@ -106,7 +108,10 @@ SharedEngine.prototype.takesResident = function (dec) {
      * (as on the parsing route), and the stages' launches write float32 PCM */
     const o = this.opts, stages = (o.tnsMode | 0) || (o.pnsMode | 0);
     const modes = (dec.tnsMode | 0) === (o.tnsMode | 0) && (dec.pnsMode | 0) === (o.pnsMode | 0) && !(stages && (o.outputKind | 0) === host.OUTPUT_I16);
-    return this.resident && (adts || mp4a) && cfg.profile === 2 && cfg.chanConfig >= 1 && cfg.chanConfig <= 8 && modes && !dec.cceMode && !dec.carryWindowShape;
+    /* ... and so does the carried window shape ({ carryWindowShape: true }: the pipelines carry it on the device): a decoder that
+     * wants it on an engine made without it, or the other way round, takes the parsing route */
+    const shape = !!dec.carryWindowShape === !!o.carryWindowShape;
+    return this.resident && (adts || mp4a) && cfg.profile === 2 && cfg.chanConfig >= 1 && cfg.chanConfig <= 8 && modes && !dec.cceMode && shape;
 };
 
 /* resident route: one pipeline (engine + parser on the device) per (sample rate, channel count) */
@@ -120,7 +125,8 @@ SharedEngine.prototype.attachResident = function (dec) {
                                                 channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
                                                 parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0),
                                                 planMode: this.devicePlans ? 1 : 0,
-                                                stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) }, rec.entries, rec.counts);
+                                                stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) | (this.opts.carryWindowShape ? 4 : 0) },
+                                              rec.entries, rec.counts);
         g = { resident: true, addon: addon, pipeline: pipeline, channels: cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }

@@ -47,6 +47,7 @@ static struct {
     void (*pipeline_destroy)(aacg_pipeline*);
     const char* (*pipeline_last_error)(const aacg_pipeline*);
     int  (*pipeline_reset_stream)(aacg_pipeline*, uint32_t);
+    int  (*pipeline_stream_window_shape)(aacg_pipeline*, uint32_t, uint8_t*);
     int  (*pipeline_decode)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, uint32_t,
                             void*, aacg_parse_result*, uint32_t*);
     int  (*pipeline_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, const uint32_t*, uint32_t, uint32_t,
@@ -94,6 +95,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(parser_create, "aacg_parser_create"); SYM(parser_destroy, "aacg_parser_destroy"); SYM(parser_last_error, "aacg_parser_last_error");
     SYM(parse_status_string, "aacg_parse_status_string"); SYM(parse_batch, "aacg_parse_batch");
     SYM(pipeline_create, "aacg_pipeline_create"); SYM(pipeline_destroy, "aacg_pipeline_destroy"); SYM(pipeline_last_error, "aacg_pipeline_last_error");
+    SYM(pipeline_stream_window_shape, "aacg_pipeline_stream_window_shape");
     SYM(pipeline_reset_stream, "aacg_pipeline_reset_stream"); SYM(pipeline_decode, "aacg_pipeline_decode");
     SYM(pipeline_submit, "aacg_pipeline_submit"); SYM(pipeline_collect, "aacg_pipeline_collect");
     SYM(pipeline_decode_ragged, "aacg_pipeline_decode_ragged"); SYM(pipeline_submit_ragged, "aacg_pipeline_submit_ragged");
@@ -512,7 +514,8 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
 }
 
 /* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages}, entries, counts) -> external
- * (planMode 1: device plans, aacg_pipeline_config.plan_mode; stages: AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS, aacg_pipeline_config.stages) */
+ * (planMode 1: device plans, aacg_pipeline_config.plan_mode; stages: AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS | AACG_PIPELINE_STAGE_WINDOW_SHAPE,
+ * aacg_pipeline_config.stages — bit 2 carries each channel's window shape from frame to frame on the device) */
 static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
 {
     size_t argc = 3; napi_value argv[3], out;
@@ -949,6 +952,26 @@ static napi_value js_pipeline_reset_stream(napi_env env, napi_callback_info info
     return NULL;
 }
 
+/* pipelineStreamWindowShape(pipeline, slot) -> Uint8Array(8): the window shape (0 sine, 1 KBD) each channel of the slot carries into
+ * its next frame (aacg_pipeline_stream_window_shape; finishes the batches in flight first) */
+static napi_value js_pipeline_stream_window_shape(napi_env env, napi_callback_info info)
+{
+    size_t argc = 2; napi_value argv[2], ab, out; uint32_t slot = 0; void* data = NULL;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_box* pb = box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle");
+    if (!pb) return NULL;
+    napi_get_value_uint32(env, argv[1], &slot);
+    uint8_t shapes[8] = {0};
+    pthread_mutex_lock(&pb->lock);
+    int rc = L.pipeline_stream_window_shape((aacg_pipeline*)pb->ptr, slot, shapes);
+    pthread_mutex_unlock(&pb->lock);
+    if (rc) { napi_throw_error(env, NULL, "aacgpu: aacg_pipeline_stream_window_shape failed"); return NULL; }
+    CHECK(env, napi_create_arraybuffer(env, 8, &data, &ab));
+    memcpy(data, shapes, 8);
+    CHECK(env, napi_create_typedarray(env, napi_uint8_array, 8, ab, 0, &out));
+    return out;
+}
+
 /* pipelinePlanBuilds(pipeline) -> how many plans the pipeline has built (one per batch shape it had not kept; aacgpu_tools.h) */
 static napi_value js_pipeline_plan_builds(napi_env env, napi_callback_info info)
 {
@@ -1014,6 +1037,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelineSubmit", NULL, js_pipeline_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineCollect", NULL, js_pipeline_collect, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineResetStream", NULL, js_pipeline_reset_stream, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelineStreamWindowShape", NULL, js_pipeline_stream_window_shape, NULL, NULL, NULL, napi_default, NULL},
         {"pipelinePlanBuilds", NULL, js_pipeline_plan_builds, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineLaunchCounts", NULL, js_pipeline_launch_counts, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},

@@ -34,7 +34,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_set_wait_limit_ms", "aacg_parser_set_wait_limit_ms", "aacg_pipeline_info",
                "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_tns_records_bytes", "aacg_tns_records_from_parse", "aacg_plan_create_stages", "aacg_decode_pipelined_stages", "aacg_parse_walk", "aacg_parse_walk_device",
                "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged",
-               "aacg_plan_create_shaped", "aacg_plan_create_shaped_stages", "aacg_plan_shape_table", "aacg_plan_shape_launch"]
+               "aacg_plan_create_shaped", "aacg_plan_create_shaped_stages", "aacg_plan_shape_table", "aacg_plan_shape_launch",
+               "aacg_get_window_shape", "aacg_set_window_shape", "aacg_plan_carry_window_shape", "aacg_pipeline_stream_window_shape"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -77,6 +78,7 @@ CCE_REFERENCE, CCE_SPEC = 0, 1
 CCE_BEFORE_TNS, CCE_AFTER_TNS, CCE_AFTER_IMDCT = 0, 1, 2
 TNS_REFERENCE, TNS_SPEC = 0, 1
 PIPELINE_STAGE_TNS, PIPELINE_STAGE_PNS = 1, 2        # aacg_pipeline_config.stages
+PIPELINE_STAGE_WINDOW_SHAPE = 4                      # ... each channel's window shape carried from frame to frame (aacg_plan_carry_window_shape)
 PNS_REFERENCE, PNS_SPEC = 0, 1
 UNIT_COMMON_WINDOW, UNIT_MASK_PRESENT, UNIT_HAS_PNS, UNIT_CCE = 1, 2, 4, 8
 CHAN_TNS_PRESENT = 0x01
@@ -175,6 +177,10 @@ def load_library(path=LIB_PATH):
     L.aacg_reset_stream.argtypes = [C.c_void_p, C.c_uint32]
     L.aacg_get_overlap.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.aacg_set_overlap.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.aacg_get_window_shape.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]
+    L.aacg_set_window_shape.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8]
+    L.aacg_plan_carry_window_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.aacg_pipeline_stream_window_shape.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.aacg_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
     L.aacg_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
@@ -444,13 +450,15 @@ class Pipeline:
     (aacg_pipeline_config.plan_mode 1) instead of a kept plan per batch shape: for feeds whose batches seldom repeat a shape."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
-                 parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False):
+                 parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
+                 carry_window_shape=False):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
         entries, counts = np.ascontiguousarray(entries), np.ascontiguousarray(counts, np.uint32)
         cfg = PipelineConfig(self.lib.aacg_abi_version(), device, sample_index, max_streams, channels, max_frames, output_kind, parse_options, lanes,
-                             1 if device_plans else 0, (PIPELINE_STAGE_TNS if tns_spec else 0) | (PIPELINE_STAGE_PNS if pns_spec else 0))
+                             1 if device_plans else 0, (PIPELINE_STAGE_TNS if tns_spec else 0) | (PIPELINE_STAGE_PNS if pns_spec else 0) |
+                             (PIPELINE_STAGE_WINDOW_SHAPE if carry_window_shape else 0))
         h = C.c_void_p()
         rc = self.lib.aacg_pipeline_create(C.byref(cfg), entries.ctypes.data, counts.ctypes.data, C.byref(h))
         if rc != 0:
@@ -500,6 +508,13 @@ class Pipeline:
         if n < 0:
             raise AacgError(n, "aacg_pipeline_stream_layout")
         return [int(c) for c in ch[:n]], int(kept.value)
+
+    def stream_window_shape(self, slot):
+        """The window shape (0 sine, 1 KBD) each of the slot's channels carries into its next frame (carry_window_shape pipelines;
+        zeros otherwise).  Finishes the batches in flight first."""
+        sh = np.zeros(8, np.uint8)
+        self._check(self.lib.aacg_pipeline_stream_window_shape(self.handle, slot, sh.ctypes.data))
+        return [int(v) for v in sh[:self.channels]]
 
     def plan_builds(self):
         """how many plans the pipeline has built (one per batch shape it had not kept)"""
@@ -821,6 +836,20 @@ class Engine:
         a = np.ascontiguousarray(values, np.float32)
         assert a.size == 1024
         self._check(self.lib.aacg_set_overlap(self.handle, stream, channel, a.ctypes.data))
+
+    def get_window_shape(self, stream, channel):
+        """The window shape (0 sine, 1 KBD) of the channel's last frame, as carry_window_shape left it: the other half of the state."""
+        v = C.c_uint8()
+        self._check(self.lib.aacg_get_window_shape(self.handle, stream, channel, C.byref(v)))
+        return int(v.value)
+
+    def set_window_shape(self, stream, channel, shape):
+        self._check(self.lib.aacg_set_window_shape(self.handle, stream, channel, int(shape)))
+
+    def carry_window_shape(self, plan, d_map, set=0, stream=0):
+        """aacg_plan_carry_window_shape: behind plan_refresh_from_parse_ex on the same stream, window_shape_prev of the set's records
+        from the frame before, a stream's first frame from the engine's state.  d_map: the refresh's map (a device address)."""
+        self._check(self.lib.aacg_plan_carry_window_shape(self.handle, plan.handle, d_map, set, stream))
 
     def reset_stream(self, stream):
         self._check(self.lib.aacg_reset_stream(self.handle, stream))

@@ -267,6 +267,11 @@ int  aacg_set_wait_limit_ms(aacg_engine* e, uint32_t ms);
 int aacg_reset_stream(aacg_engine* e, uint32_t stream);                       /* zero = new FilterBank */
 int aacg_get_overlap(aacg_engine* e, uint32_t stream, uint32_t channel, float* dst1024);
 int aacg_set_overlap(aacg_engine* e, uint32_t stream, uint32_t channel, const float* src1024);
+/* The other half of a stream's filterbank state: the window shape (0 sine, 1 KBD) of the channel's last frame, which the first
+ * half of its next frame is windowed with.  The engine keeps it where aacg_plan_carry_window_shape carries it (0 at create and
+ * after aacg_reset_stream); a checkpoint of a stream holds both halves.  Bounded waits, as aacg_get / aacg_set_overlap. */
+int aacg_get_window_shape(aacg_engine* e, uint32_t stream, uint32_t channel, uint8_t* shape);
+int aacg_set_window_shape(aacg_engine* e, uint32_t stream, uint32_t channel, uint8_t shape);
 
 /* ---- the hot path, host buffers ---------------------------------------------------- */
 /* Synchronous equivalent of  process(elements) + interleave  for a whole batch:
@@ -573,6 +578,25 @@ int aacg_plan_set_unit_sets(aacg_engine* e, aacg_plan* p, uint32_t n_sets);     
 int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* d_parsed_units,
                                     aacg_parse_result* d_results, uint32_t max_units, const aacg_refresh_map* d_map,
                                     uint32_t set, uint32_t* d_refused, void* hip_stream);
+/* window_shape_prev carried on the device.  The parser writes window_shape_prev = 0 (a fresh ICSInfo per frame, decoder.js:145,153)
+ * and the refresh copies it; a standard decoder windows a frame's first half with the PREVIOUS frame's shape.  This call, behind
+ * aacg_plan_refresh_from_parse_ex on the same hip_stream and in front of the launch, sets it in the records of `set` (the same
+ * caller's word about `set` as the refresh): for each stream of the plan, its frames in order, each unit's channel k (output
+ * channel c = channel + k) takes the window_shape of the frame before as refreshed — 0 behind a frame the refresh made silent —
+ * and the stream's first frame takes the engine's state of (stream, c), which the stream's last frame then replaces
+ * (aacg_get / aacg_set_window_shape; 0 at create and after aacg_reset_stream).  Channels without a unit in the plan keep their state;
+ * no other byte of a record changes.  One small launch (aacg_units_carry_shape); consecutive calls are ordered on the device
+ * whatever their streams, and a call repeated before any launch has taken the records — the refresh of a plan that turned out
+ * stale, done again, on the same plan or on the one made in its place — starts from the state its first attempt started from.
+ * That is the engine's only notion of "the same batch": EVERY carry between two launches of the engine repeats the one before it.
+ * So the records a carry prepared are launched (aacg_decode_pipelined, aacg_decode_pipelined_stages, aacg_decode_device) before the
+ * next batch is carried, on whatever plan: two different batches carried back to back with no launch in between would both start
+ * from the state in front of the first.
+ *   d_map: the map the set was refreshed through (required: it says how many units a frame has).
+ * Kept plans (with or without unit sets), shaped plans and plans for aacg_decode_pipelined_stages; QUANT_I16 engines.  A plan that
+ * does not list each stream's frames one behind the other with the same elements next to each other in every frame is refused:
+ * AACG_ERR_UNSUPPORTED, the reason in aacg_last_error. */
+int aacg_plan_carry_window_shape(aacg_engine* e, aacg_plan* p, const aacg_refresh_map* d_map, uint32_t set, void* hip_stream);
 
 /* ---- TNS records made on the device (AACG_TNS_SPEC) ---------------------------------------------------------------------------
  * What the host planner makes of an aacg_tns_info before a launch can run its filters — per filter the sample range, the
@@ -704,16 +728,22 @@ typedef struct aacg_pipeline_config {
                                   both plan modes.  Needs AACG_OUTPUT_F32 (AACG_ERR_UNSUPPORTED with AACG_OUTPUT_I16: that route is
                                   the staged spectral launch, which needs a spectrum buffer per plan and does not overlap).
                                   Unchanged: TNS orders 13..20 refuse the frame (AACG_PARSE_TNS_ORDER), coupling elements are
-                                  parsed and dropped, window_shape_prev is 0.  (reserved[0] until now: zero selects today's
+                                  parsed and dropped.  Bit 2: AACG_PIPELINE_STAGE_WINDOW_SHAPE — each channel's window shape is
+                                  carried from frame to frame and batch to batch (aacg_plan_carry_window_shape, one small launch
+                                  per batch behind the refresh): a frame's first half is windowed with the previous frame's
+                                  shape, as a standard decoder does, where the reference always takes sine.  Independent of
+                                  bits 0 and 1: it selects no engine mode and no other kernel, and it goes with AACG_OUTPUT_I16.
+                                  With the bit clear window_shape_prev is 0.  (reserved[0] until now: zero selects today's
                                   path, call for call)                                                                     */
     int32_t reserved[1];       /* zero                                                                      */
 } aacg_pipeline_config;
 #define AACG_PIPELINE_STAGE_TNS 1
 #define AACG_PIPELINE_STAGE_PNS 2
+#define AACG_PIPELINE_STAGE_WINDOW_SHAPE 4
 int  aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry* entries, const uint32_t counts[12], aacg_pipeline** out);
 void aacg_pipeline_destroy(aacg_pipeline* p);
 const char* aacg_pipeline_last_error(const aacg_pipeline* p);
-int  aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot);                 /* new FilterBank for that slot */
+int  aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot);                 /* new FilterBank for that slot (and sine for its carried window shapes) */
 /* One batch, synchronous: n_streams streams (slots[s]: the stream slot that owns stream s's overlap state; each slot at most
  * once per batch: AACG_ERR_INVALID_ARG otherwise), the next
  * frames_per_stream frames of each; frames[s * frames_per_stream + f] = frame f of stream s in `bytes` (an ADTS frame,
@@ -767,6 +797,10 @@ int  aacg_pipeline_walk_collect(aacg_pipeline* p, uint64_t ticket);
 /* The element layout learnt for a stream slot: returns the number of SCE / CPE / LFE elements of its frames (0: not learnt
  * yet), their channel counts in element_channels[0..7] and how many of them (the first ones) fit `channels` in *kept. */
 int  aacg_pipeline_stream_layout(aacg_pipeline* p, uint32_t slot, uint8_t element_channels[8], uint32_t* kept);
+/* The window shape each output channel of a stream slot carries into its next frame (AACG_PIPELINE_STAGE_WINDOW_SHAPE; all 0
+ * without it): shapes[c] for c < channels, 0 behind them.  Finishes the batches in flight first (bounded, as
+ * aacg_pipeline_reset_stream). */
+int  aacg_pipeline_stream_window_shape(aacg_pipeline* p, uint32_t slot, uint8_t shapes[8]);
 
 #ifdef __cplusplus
 }

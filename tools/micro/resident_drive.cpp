@@ -6,9 +6,12 @@
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
+ *                                         [--carry-shape]
  *
  * --tns-spec / --pns-spec: aacg_pipeline_config.stages (the spec-correct TNS filters / noise bands; the TNS records are made on the
  * device, every launch is aacg_imdct_run_quant_ex_rv).  --pulses: AACG_PARSE_APPLY_PULSES (streams with pulse data).
+ * --carry-shape: AACG_PIPELINE_STAGE_WINDOW_SHAPE (each channel's window shape carried on the device: one more small launch per
+ * batch behind the refresh; goes with --i16 and with either plan mode).
  * --device-plans: aacg_pipeline_config.plan_mode 1 (one plan shaped on the device per batch instead of a kept plan per shape).
  * --new-shapes: every batch a NEW seeded shape — each stream brings 1..F frames (aacg_pipeline_submit_ragged) — which is what a
  * jittered feed gives the route; the line then also says how long the host spent inside the submit call alone, per batch.
@@ -37,7 +40,7 @@ int main(int argc, char** argv)
     if (argc < 2) { std::fprintf(stderr, "usage: resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]\n"); return 2; }
     uint32_t S = 256, F = 16;
     int batches = 200, lanes = 3;
-    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false;
+    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false;
     uint64_t seed = 1;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
@@ -54,6 +57,7 @@ int main(int argc, char** argv)
         else if (a == "--tns-spec") tns_spec = true;
         else if (a == "--pns-spec") pns_spec = true;
         else if (a == "--pulses") pulses = true;
+        else if (a == "--carry-shape") carry_shape = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -89,7 +93,7 @@ int main(int argc, char** argv)
     cfg.abi_version = AACG_ABI_VERSION; cfg.sample_index = (int32_t)sample_index; cfg.max_streams = (int32_t)S; cfg.channels = (int32_t)channels; cfg.max_frames = (int32_t)F;
     cfg.output_kind = i16 ? AACG_OUTPUT_I16 : AACG_OUTPUT_F32; cfg.parse_options = AACG_PARSE_REFERENCE_QUIRKS | (pulses ? AACG_PARSE_APPLY_PULSES : 0); cfg.lanes = sync ? 1 : lanes;
     cfg.plan_mode = device_plans ? 1 : 0;
-    cfg.stages = (tns_spec ? AACG_PIPELINE_STAGE_TNS : 0) | (pns_spec ? AACG_PIPELINE_STAGE_PNS : 0);
+    cfg.stages = (tns_spec ? AACG_PIPELINE_STAGE_TNS : 0) | (pns_spec ? AACG_PIPELINE_STAGE_PNS : 0) | (carry_shape ? AACG_PIPELINE_STAGE_WINDOW_SHAPE : 0);
     aacg_pipeline* p = nullptr;
     int rc = aacg_pipeline_create(&cfg, entries.data(), counts, &p);
     if (rc) { std::fprintf(stderr, "aacg_pipeline_create: %d\n", rc); return 2; }
