@@ -9,7 +9,7 @@
  * finds its parsed record — is rewritten for every batch into the lane's own buffer on the lane's stream, so that a new shape
  * costs no device allocation and no synchronous copy on the submit path.
  *
- * Written against devport.h like aacg_parse.h, and executed lane by lane on the CPU by tests/emu_map.
+ * Written against devport.h like aacg_parse.h, and executed lane by lane on the CPU by tests/emu/map_emu.cpp.
  */
 #ifndef AACG_PIPE_MAP_H
 #define AACG_PIPE_MAP_H

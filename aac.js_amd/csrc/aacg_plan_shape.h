@@ -13,7 +13,7 @@
  * run and first link in that order into the table (aacg_shape_plan, aacg_shape.cpp: prefix sums over the streams sorted by slot),
  * so the kernel sorts nothing.
  *
- * Written against devport.h like aacg_parse.h and aacg_pipe_map.h, and executed lane by lane on the CPU by tests/emu_shape.
+ * Written against devport.h like aacg_parse.h and aacg_pipe_map.h, and executed lane by lane on the CPU by tests/emu/shape_emu.cpp.
  */
 #ifndef AACG_PLAN_SHAPE_H
 #define AACG_PLAN_SHAPE_H
@@ -146,7 +146,7 @@ inline uint32_t shape_table(const aacg_pipe_layout* lay, const uint32_t* slots, 
 #include <string>
 #include "aacg_host.h"
 
-/* ---- the host's part (aacg_shape.cpp, plain C++: the engine calls it, tests/emu_shape links it) ------------------------------- */
+/* ---- the host's part (aacg_shape.cpp, plain C++: the engine calls it, tests/emu/shape_emu.cpp links it) ------------------------------- */
 /* what a shaped plan's buffers hold at most */
 struct aacg_shape_limits {
     uint32_t max_streams;      /* streams of a batch                                                                     */

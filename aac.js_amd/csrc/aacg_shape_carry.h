@@ -33,7 +33,7 @@
  *     refresh, so that the parses of consecutive batches still run side by side (the transforms of consecutive batches are ordered
  *     through the cross-launch cells anyway).
  *
- * Written against devport.h like aacg_pipe_map.h and aacg_plan_shape.h, and executed lane by lane on the CPU by tests/emu_carry.
+ * Written against devport.h like aacg_pipe_map.h and aacg_plan_shape.h, and executed lane by lane on the CPU by tests/emu/carry_emu.cpp.
  */
 #ifndef AACG_SHAPE_CARRY_H
 #define AACG_SHAPE_CARRY_H

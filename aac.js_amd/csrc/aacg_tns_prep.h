@@ -10,7 +10,7 @@
  * accepted frame's unit owns the block and its channel has AACG_CHAN_TNS_PRESENT.  A refused frame's parser records are never read.
  * Global memory only, no LDS; the recursion is unrolled over the orders so that the coefficients stay in registers.
  *
- * Written against devport.h like aacg_plan_shape.h, and executed lane by lane on the CPU by tests/emu_tnsprep.
+ * Written against devport.h like aacg_plan_shape.h, and executed lane by lane on the CPU by tests/emu/tnsprep_emu.cpp.
  */
 #ifndef AACG_TNS_PREP_H
 #define AACG_TNS_PREP_H

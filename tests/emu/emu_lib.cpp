@@ -24,6 +24,7 @@
 #include "../../aac.js_amd/csrc/aacg_parse.h"
 #include "../../aac.js_amd/csrc/aacg_host.h"
 #include "../../aac.js_amd/csrc/aacg_routes.h"
+#include "emu_launch.h"
 
 thread_local emu_lane_ctx g_emu;
 int g_emu_fault_kind = EMU_FAULT_NONE, g_emu_fault_lo = 0, g_emu_fault_hi = 0, g_emu_fault_wave = -1;
@@ -447,42 +448,14 @@ void emu_sched_note(int kind, const void* addr)
 
 namespace {
 
-/* one workgroup of a launch, its lanes as threads */
+/* one workgroup of a launch, its lanes as threads (emu_launch.h): no schedule controller, so lane_body without lane_main's turn-taking */
 void run_block(const aacg_kparams& P, int kind, unsigned key, int block, int waves, size_t lds_bytes, int n_units = 0, const aacg_parse_params* PP = nullptr,
                const aacg_couple_params* Q = nullptr, const aacg_rv_args* V = nullptr)
 {
-    const int threads = waves * 64;
-    std::vector<emu_wave> wv((size_t)waves);
-    std::vector<launch_arg> args((size_t)threads);
-    std::vector<pthread_t> tid((size_t)threads);
-    unsigned char* lds = (unsigned char*)aligned_alloc(512, (lds_bytes + 511) & ~(size_t)511);
-    pthread_attr_t attr;
-    pthread_attr_init(&attr);
-    pthread_attr_setstacksize(&attr, 256 * 1024);
-    emu_block blk;
-    blk.lds = lds;
-    blk.lds_bytes = lds_bytes;
-    blk.block_id = block;
-    blk.threads = threads; blk.sync_arrived = 0; blk.sync_gen = 0; blk.flags_off = -1;
-    std::memset(lds, 0xff, lds_bytes);             /* NaN pattern: reads of unwritten LDS show up */
-    pthread_barrier_init(&blk.bar, nullptr, (unsigned)threads);
-    for (int w = 0; w < waves; w++) { pthread_barrier_init(&wv[(size_t)w].bar, nullptr, 64); wv[(size_t)w].sw = nullptr; }
-    for (int t = 0; t < threads; t++) {
-        args[(size_t)t].ctx = emu_lane_ctx{t & 63, t >> 6, &wv[(size_t)(t >> 6)], &blk};
-        args[(size_t)t].P = &P;
-        args[(size_t)t].kind = kind;
-        args[(size_t)t].key = key;
-        args[(size_t)t].n_units = n_units;
-        args[(size_t)t].PP = PP;
-        args[(size_t)t].Q = Q;
-        args[(size_t)t].V = V;
-        pthread_create(&tid[(size_t)t], &attr, lane_main, &args[(size_t)t]);
-    }
-    for (int t = 0; t < threads; t++) pthread_join(tid[(size_t)t], nullptr);
-    for (int w = 0; w < waves; w++) pthread_barrier_destroy(&wv[(size_t)w].bar);
-    pthread_barrier_destroy(&blk.bar);
-    pthread_attr_destroy(&attr);
-    free(lds);
+    launch_arg a{};
+    a.P = &P; a.kind = kind; a.key = key; a.n_units = n_units; a.PP = PP; a.Q = Q; a.V = V;
+    auto body = [&] { lane_body(&a); };
+    emu_launch_block(block, waves * 64, lds_bytes, body);
 }
 
 /* a whole grid, workgroup after workgroup */

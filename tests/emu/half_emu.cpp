@@ -11,7 +11,7 @@
  */
 #define AACG_PROFILE
 #define AACG_EMU_SCHEDULER              /* devport_emu.h: emu_lib.cpp, included below, has the schedule controller */
-#include "../aac.js_amd/csrc/aacg_kernels.h"
+#include "../../aac.js_amd/csrc/aacg_kernels.h"
 
 namespace half_emu {
 
@@ -33,6 +33,6 @@ void run_body(const aacg_kparams& P, const aacg_rv_args* V = nullptr)
 }  // namespace half_emu
 
 #define imdct_run_body half_emu::run_body
-#include "emu/emu_lib.cpp"
+#include "emu_lib.cpp"
 
 extern "C" void emu_half_set_ablate(int bits) { half_emu::g_ablate = bits; }

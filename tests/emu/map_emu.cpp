@@ -8,46 +8,9 @@
 #include <vector>
 
 #include "../../aac.js_amd/csrc/aacg_pipe_map.h"
+#include "emu_launch.h"
 
 thread_local emu_lane_ctx g_emu;
-
-namespace {
-
-struct lane_arg { emu_lane_ctx ctx; const aacg_pipe_stream* tab; uint32_t n_streams, U, blocks; aacg_refresh_map* map; };
-
-void* lane_main(void* p)
-{
-    lane_arg* a = (lane_arg*)p;
-    g_emu = a->ctx;
-    aacg_pipe::map_body(a->tab, a->n_streams, a->U, a->map, a->blocks);
-    return nullptr;
-}
-
-/* one workgroup of AACG_PIPE_MAP_THREADS lanes (one wave), as hipLaunchKernelGGL(aacg_pipe_map, blocks, 64) runs it */
-void run_block(const aacg_pipe_stream* tab, uint32_t n_streams, uint32_t U, aacg_refresh_map* map, uint32_t blocks, int block)
-{
-    const int threads = AACG_PIPE_MAP_THREADS, waves = threads / 64;
-    std::vector<emu_wave> wv((size_t)waves);
-    std::vector<lane_arg> args((size_t)threads);
-    std::vector<pthread_t> tid((size_t)threads);
-    emu_block blk;
-    blk.lds = nullptr; blk.lds_bytes = 0; blk.block_id = block;
-    pthread_barrier_init(&blk.bar, nullptr, (unsigned)threads);
-    for (int w = 0; w < waves; w++) pthread_barrier_init(&wv[(size_t)w].bar, nullptr, 64);
-    pthread_attr_t attr;
-    pthread_attr_init(&attr);
-    pthread_attr_setstacksize(&attr, 64 * 1024);
-    for (int t = 0; t < threads; t++) {
-        args[(size_t)t] = lane_arg{emu_lane_ctx{t & 63, t >> 6, &wv[(size_t)(t >> 6)], &blk}, tab, n_streams, U, blocks, map};
-        pthread_create(&tid[(size_t)t], &attr, lane_main, &args[(size_t)t]);
-    }
-    for (int t = 0; t < threads; t++) pthread_join(tid[(size_t)t], nullptr);
-    for (int w = 0; w < waves; w++) pthread_barrier_destroy(&wv[(size_t)w].bar);
-    pthread_barrier_destroy(&blk.bar);
-    pthread_attr_destroy(&attr);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -67,7 +30,8 @@ int emu_pipe_map(const uint8_t* n, const uint8_t* kept, const uint8_t* nch, cons
     if (n_units > max_units || u.size() != n_units || m.size() != n_units) return -1;
     std::memcpy(host_map, m.data(), m.size() * sizeof(aacg_refresh_map));
     if (units) std::memcpy(units, u.data(), u.size() * sizeof(aacg_unit_desc));
-    for (uint32_t b = 0; b < blocks; b++) run_block(table, n_streams, U, dev_map, blocks, (int)b);
+    /* workgroups of AACG_PIPE_MAP_THREADS lanes (one wave), as hipLaunchKernelGGL(aacg_pipe_map, blocks, 64) runs them */
+    emu_launch((int)blocks, AACG_PIPE_MAP_THREADS, 0, EMU_BLOCKS_FORWARD, [&] { aacg_pipe::map_body(table, n_streams, U, dev_map, blocks); });
     return (int)n_units;
 }
 

@@ -10,44 +10,11 @@
 #include <vector>
 
 #include "../../aac.js_amd/csrc/aacg_plan_shape.h"
+#include "emu_launch.h"
 
 thread_local emu_lane_ctx g_emu;
 
 namespace {
-
-struct lane_arg { emu_lane_ctx ctx; const aacg_shape_args* A; uint32_t blocks; };
-
-void* lane_main(void* p)
-{
-    lane_arg* a = (lane_arg*)p;
-    g_emu = a->ctx;
-    aacg_pipe::shape_body(*a->A, a->blocks);
-    return nullptr;
-}
-
-/* one workgroup of AACG_SHAPE_THREADS lanes (one wave), as hipLaunchKernelGGL(aacg_plan_shape, blocks, 64) runs it */
-void run_block(const aacg_shape_args& A, uint32_t blocks, int block)
-{
-    const int threads = AACG_SHAPE_THREADS, waves = threads / 64;
-    std::vector<emu_wave> wv((size_t)waves);
-    std::vector<lane_arg> args((size_t)threads);
-    std::vector<pthread_t> tid((size_t)threads);
-    emu_block blk;
-    blk.lds = nullptr; blk.lds_bytes = 0; blk.block_id = block;
-    pthread_barrier_init(&blk.bar, nullptr, (unsigned)threads);
-    for (int w = 0; w < waves; w++) pthread_barrier_init(&wv[(size_t)w].bar, nullptr, 64);
-    pthread_attr_t attr;
-    pthread_attr_init(&attr);
-    pthread_attr_setstacksize(&attr, 64 * 1024);
-    for (int t = 0; t < threads; t++) {
-        args[(size_t)t] = lane_arg{emu_lane_ctx{t & 63, t >> 6, &wv[(size_t)(t >> 6)], &blk}, &A, blocks};
-        pthread_create(&tid[(size_t)t], &attr, lane_main, &args[(size_t)t]);
-    }
-    for (int t = 0; t < threads; t++) pthread_join(tid[(size_t)t], nullptr);
-    for (int w = 0; w < waves; w++) pthread_barrier_destroy(&wv[(size_t)w].bar);
-    pthread_barrier_destroy(&blk.bar);
-    pthread_attr_destroy(&attr);
-}
 
 std::string g_err;
 
@@ -120,7 +87,8 @@ int emu_plan_shape(const uint8_t* n, const uint8_t* kept, const uint8_t* nch, co
     std::memset(&A, 0, sizeof A);
     A.tab = table; A.n_streams = n_streams; A.U = U; A.C = C; A.Cp = Cp; A.n_runs = info.n_runs; A.unit0_coef = info.unit0_coef; A.unit0_nch = info.unit0_nch;
     A.map = dev_map; A.units = dev_units; A.runs = dev_runs; A.links = dev_links;
-    for (uint32_t b = 0; b < blocks; b++) run_block(A, blocks, (int)b);
+    /* workgroups of AACG_SHAPE_THREADS lanes (one wave), as hipLaunchKernelGGL(aacg_plan_shape, blocks, 64) runs them */
+    emu_launch((int)blocks, AACG_SHAPE_THREADS, 0, EMU_BLOCKS_FORWARD, [&] { aacg_pipe::shape_body(A, blocks); });
     return 0;
 }
 

@@ -2,7 +2,8 @@
  * tnsprep_emu.cpp — the TNS records kernel's source (aac.js_amd/csrc/aacg_tns_prep.h: tns_records_body) and the matrices kernel
  * behind it (aacg_kernels.h: tns_matrices_body) run lane by lane on the CPU (tests/emu/devport_emu.h), next to what the host
  * makes of the same parser outputs (aacg_tns_prepare, aacg_plan.cpp; tns_matrix_row), for tests/test_tns_records_emu.py, which
- * compiles it into a library of its own.  Neither body has a point where lanes meet, so the lanes run one after the other.
+ * compiles it into a library of its own.  Neither body has a point where lanes meet, so the lanes run one after the other, on
+ * purpose: no thread per lane, and so not through emu_launch.h like the other drivers here.
  * TESTS ONLY.
  */
 #include <cstdlib>

@@ -10,51 +10,15 @@
 #include <string>
 #include <vector>
 
-#include "../aac.js_amd/csrc/aacg_parse.h"
-#include "../aac.js_amd/csrc/aacg_host.h"
+#include "../../aac.js_amd/csrc/aacg_parse.h"
+#include "../../aac.js_amd/csrc/aacg_host.h"
+#include "emu_launch.h"
 
 thread_local emu_lane_ctx g_emu;
 
 namespace {
 
 std::string g_err;
-
-struct lane_arg { emu_lane_ctx ctx; const aacg_walk_params* W; };
-
-void* lane_main(void* p)
-{
-    lane_arg* a = (lane_arg*)p;
-    g_emu = a->ctx;
-    aacg_parse::walk_body(*a->W);
-    return nullptr;
-}
-
-void run_block(const aacg_walk_params& W, int block, size_t lds_bytes)
-{
-    const int threads = (int)W.P.wg_threads, waves = threads / 64;
-    std::vector<emu_wave> wv((size_t)waves);
-    std::vector<lane_arg> args((size_t)threads);
-    std::vector<pthread_t> tid((size_t)threads);
-    unsigned char* lds = (unsigned char*)aligned_alloc(512, (lds_bytes + 511) & ~(size_t)511);
-    std::memset(lds, 0xff, lds_bytes);                 /* poisoned: reads of unwritten LDS show up */
-    emu_block blk;
-    blk.lds = lds; blk.lds_bytes = lds_bytes; blk.block_id = block;
-    pthread_barrier_init(&blk.bar, nullptr, (unsigned)threads);
-    for (int w = 0; w < waves; w++) pthread_barrier_init(&wv[(size_t)w].bar, nullptr, 64);
-    pthread_attr_t attr;
-    pthread_attr_init(&attr);
-    pthread_attr_setstacksize(&attr, 256 * 1024);
-    for (int t = 0; t < threads; t++) {
-        args[(size_t)t].ctx = emu_lane_ctx{t & 63, t >> 6, &wv[(size_t)(t >> 6)], &blk};
-        args[(size_t)t].W = &W;
-        pthread_create(&tid[(size_t)t], &attr, lane_main, &args[(size_t)t]);
-    }
-    for (int t = 0; t < threads; t++) pthread_join(tid[(size_t)t], nullptr);
-    for (int w = 0; w < waves; w++) pthread_barrier_destroy(&wv[(size_t)w].bar);
-    pthread_barrier_destroy(&blk.bar);
-    pthread_attr_destroy(&attr);
-    free(lds);
-}
 
 }  // namespace
 
@@ -86,7 +50,7 @@ int emu_walk(int sample_index, const aacg_code_entry* entries, const uint32_t* c
     for (uint32_t pos = 0; pos < n_spans; pos++) order[pos] = sorted[pos];
     W.P.order = n_spans > 64 ? order.data() : nullptr;
     const size_t lds_bytes = AACG_PARSE_LDS_FIXED(tab.lut_words, 64);
-    for (uint32_t b = 0; b < n_wg; b++) run_block(W, (int)b, lds_bytes);
+    emu_launch((int)n_wg, (int)W.P.wg_threads, lds_bytes, EMU_BLOCKS_FORWARD, [&] { aacg_parse::walk_body(W); });
     return AACG_OK;
 }
 

@@ -31,12 +31,26 @@ class EmuDeadlock(RuntimeError):
     """A decode in schedule-controlled mode in which no wave could run any more: the text names who waited for what."""
 
 
+def _build_locked(cmd, **kw):
+    import fcntl
+    with open(os.path.join(HERE, "emu", ".build.lock"), "w") as lock:      # one build at a time (pytest-xdist workers)
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        subprocess.run(cmd, check=True, **kw)
+
+
+def build_driver(name, sources, out_dir):
+    """A driver under tests/emu/ and the host sources it links (paths from the repository's root) compiled as tests/emu/Makefile
+    compiles the emulator, into out_dir/lib<name>.so; returns the loaded library.  The caller sets its argtypes."""
+    so = os.path.join(str(out_dir), "lib%s.so" % name)
+    _build_locked(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I", os.path.join(HERE, "emu"),
+                   "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-Wl,--no-undefined", "-o", so]
+                  + [os.path.join(os.path.dirname(HERE), s) for s in sources])
+    return C.CDLL(so)
+
+
 class Emu:
     def __init__(self, target="libaacg_emu.so"):
-        import fcntl
-        with open(os.path.join(HERE, "emu", ".build.lock"), "w") as lock:      # one make at a time (pytest-xdist workers)
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", os.path.join(HERE, "emu"), target], check=True, stdout=subprocess.DEVNULL)
+        _build_locked(["make", "-C", os.path.join(HERE, "emu"), target], stdout=subprocess.DEVNULL)
         self.lib = L = C.CDLL(os.path.join(HERE, "emu", target))
         L.emu_last_error.restype = C.c_char_p
         L.emu_decode.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -12,51 +12,9 @@ import numpy as np
 import pytest
 
 import aacgpu
-from test_ragged_pipeline_gpu import CASES, CORPUS, NODE, ROOT, adts_frame_table, check_corpus_pcm, close_to, load, packed
-
-ERR_INVALID_ARG, ERR_CAPACITY, ERR_UNSUPPORTED = -1, -4, -5          # AACG_ERR_* (include/aacgpu.h)
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32 if a.dtype.itemsize == 4 else np.uint16),
-                                                                         b.view(np.uint32 if b.dtype.itemsize == 4 else np.uint16))
-
-
-def ragged_script(tables, max_frames, rng):
-    """the batches of tests/test_ragged_pipeline_gpu.py's ragged_run, drawn once so that both plan modes decode the same ones:
-    random counts (1..max_frames, at most what is left), streams that are done drop out -> [(live slots, counts, first frames)]"""
-    S = len(tables)
-    at = [0] * S
-    out = []
-    while any(at[s] < len(tables[s]) for s in range(S)):
-        live = [s for s in range(S) if at[s] < len(tables[s])]
-        counts = [int(rng.integers(1, min(max_frames, len(tables[s]) - at[s]) + 1)) for s in live]
-        out.append((live, counts, [at[s] for s in live]))
-        for s, c in zip(live, counts):
-            at[s] += c
-    return out
-
-
-def run_script(members, script, C_, si, max_frames, device_plans, **kw):
-    """-> (per-stream PCM, per-stream statuses, refusals in all, plan builds, launch counts)"""
-    S = len(members)
-    data = np.concatenate([m[0] for m in members])
-    bases = np.cumsum([0] + [len(m[0]) for m in members])[:-1]
-    tables = [m[1] for m in members]
-    p = aacgpu.Pipeline(channels=C_, max_streams=S, max_frames=max_frames, sample_index=si, device_plans=device_plans, **kw)
-    got, status, refusals = [[] for _ in range(S)], [[] for _ in range(S)], 0
-    per = 1024 * C_
-    for live, counts, at in script:
-        fr = packed([tables[s] for s in live], [bases[s] for s in live], at, counts)
-        pcm, res, refused = p.decode(data, fr, np.array(live, np.uint32), np.array(counts, np.uint32))
-        refusals += refused
-        first = np.concatenate([[0], np.cumsum(counts)])
-        for k, s in enumerate(live):
-            got[s].append(pcm[first[k] * per:first[k + 1] * per])
-            status[s].append(res["status"][first[k]:first[k + 1]].copy())
-    builds, counts_ = p.plan_builds(), p.launch_counts()
-    p.close()
-    return [np.concatenate(g) for g in got], [np.concatenate(x) for x in status], refusals, builds, counts_
+from resident_kit import CASES, CORPUS, ERR_CAPACITY, ERR_INVALID_ARG, ERR_UNSUPPORTED, NODE, ROOT, adts_frame_table, check_corpus_pcm, close_to, load, packed
+from resident_kit import ragged_script, run_script, same_bits, steady
+from resident_kit import corpus_streams          # noqa: F401  (fixture)
 
 
 def both_modes(members, C_, si, max_frames, rng, **kw):
@@ -81,14 +39,6 @@ def test_same_bits_as_kept_plans_on_the_committed_streams():
             assert same_bits(shaped[0][s], kept[0][s]), (case["name"], s)
             close_to(shaped[0][s], refpcm)
             close_to(kept[0][s], refpcm)
-
-
-@pytest.fixture(scope="module")
-def corpus_streams(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("corpus"))
-    r = subprocess.run([NODE or "node", os.path.join(ROOT, "tests", "js", "corpus_cases.js"), d], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return {e["name"]: np.fromfile(os.path.join(d, e["name"] + ".aac"), np.uint8) for e in CORPUS}
 
 
 @pytest.mark.gpu
@@ -221,40 +171,24 @@ def test_long_chains():
         close_to(out[True][0][first[k] * 2048:(first[k] + m) * 2048], refpcm[:m * 2048])
 
 
-def steady(mode, odd_at=None, B=32):
-    data, table, _ = load(CASES[0])
-    S = 16
-    p = aacgpu.Pipeline(channels=2, max_streams=S, max_frames=2, lanes=5, device_plans=mode)
-    pcm = []
-    pending = []
-    for b in range(B):
-        k = S - 3 if b == odd_at else S                       # the odd one: three streams fewer
-        fr = packed([table] * k, [0] * k, [(2 * b) % 16] * k, [2] * k)
-        pending.append(p.submit(data, fr, np.arange(k), np.full(k, 2, np.uint32), pcm=p.pinned(k * 2 * 2048, np.float32)))
-        if len(pending) == 5:
-            pcm.append(p.collect(pending.pop(0))[0].copy())
-    pcm += [p.collect(t)[0].copy() for t in pending]
-    counts = p.launch_counts()
-    p.close()
-    assert counts["launches"] == B
-    return counts["chained"], pcm
-
-
 @pytest.mark.gpu
 def test_the_steady_feed_still_overlaps():
     """the same shape 32 times, submitted ahead on five lanes: as many launches continue their predecessor with device plans as with
     kept plans (the parent's path is the yardstick), and one batch of another shape in the middle costs exactly two continuations —
     its own and its successor's"""
-    kept, pcm0 = steady(False)
-    shaped, pcm1 = steady(True)
+    data, table, _ = load(CASES[0])
+    feed = lambda mode, odd_at=None: steady(data, table, 16, 32, 16, mode, odd_at)
+    (kept, pcm0), (shaped, pcm1) = feed(False), feed(True)
+    kept, shaped = kept["chained"], shaped["chained"]
     print("continued launches of 32: kept plans %d, device plans %d" % (kept, shaped))
     assert shaped == kept and shaped > 0
     for a, b in zip(pcm0, pcm1):
         assert same_bits(a, b)
-    odd, pcm2 = steady(True, odd_at=16)
+    odd, pcm2 = feed(True, odd_at=16)
+    odd = odd["chained"]
     print("... with another shape at batch 16: %d" % odd)
     assert odd == shaped - 2
-    odd0, pcm3 = steady(False, odd_at=16)
+    odd0, pcm3 = feed(False, odd_at=16)
     for a, b in zip(pcm2, pcm3):
         assert same_bits(a, b)
 

@@ -1,5 +1,5 @@
 """The eight-wave run body (imdct_run_body<..., NW = AACG_HALF_WAVES>, behind aacg_imdct_run_quant_rv): a run of 16 frames on 8 waves,
-wave w taking frame w and then frame w + 8, seven LDS slots for sixteen frames.  In the lane emulator (tests/half_emu.cpp: the
+wave w taking frame w and then frame w + 8, seven LDS slots for sixteen frames.  In the lane emulator (tests/emu/half_emu.cpp: the
 unchanged emulator with its f32-PCM rendezvous kernels on that body) it must give the same BITS — PCM and overlap state — as the
 16-wave body: chains of 1 to 48 frames, every window sequence (mixed batches), both seams, both workgroup orders of the rendezvous,
 and overlapped launches meeting in cross-launch cells in several orders.  Lanes run as threads, so the waves interleave as the OS
@@ -22,19 +22,14 @@ import emu_lib  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = "libaacg_emu_half.so"
-SRC = ["../half_emu.cpp", "../../aac.js_amd/csrc/aacg_tables.cpp", "../../aac.js_amd/csrc/aacg_plan.cpp",
-       "../../aac.js_amd/csrc/aacg_routes.cpp", "../../aac.js_amd/csrc/aacg_parse_host.cpp"]
+SRC = ["tests/emu/half_emu.cpp", "aac.js_amd/csrc/aacg_tables.cpp", "aac.js_amd/csrc/aacg_plan.cpp",
+       "aac.js_amd/csrc/aacg_routes.cpp", "aac.js_amd/csrc/aacg_parse_host.cpp"]
 
 
 @pytest.fixture(scope="module")
 def emus():
-    import fcntl
-    emu_dir = os.path.join(HERE, "emu")
-    with open(os.path.join(emu_dir, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I.", "-pthread", "-Wall",
-                        "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-o", LIB] + SRC, cwd=emu_dir, check=True)
-    return emu_lib.Emu(), emu_lib.Emu(LIB)      # (make finds the half library up to date: it has no rule for it)
+    emu_lib.build_driver("aacg_emu_half", SRC, os.path.join(HERE, "emu"))
+    return emu_lib.Emu(), emu_lib.Emu(LIB)      # (make finds the half library up to date)
 
 
 CHILD_LIMIT_S = 600

@@ -53,13 +53,17 @@ def make_var(name):
     return shlex.split(r.stdout)
 
 
-def resource_report(tu):
+def report_text(tu):
     flags = make_var("CXXFLAGS") + make_var("FLAGS_" + tu[:-len(".hip")])
     r = subprocess.run([HIPCC, "--offload-arch=gfx950"] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", tu, "-o", "/dev/null"],
                        cwd=CSRC, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    return r.stderr
+
+
+def resource_report(tu):
     out, name = {}, None
-    for line in r.stderr.splitlines():
+    for line in report_text(tu).splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             name = m.group(1)
@@ -104,3 +108,41 @@ def test_hot_kernels_keep_their_register_and_lds_budget(reports, tu):
         assert int(rep["Occupancy [waves/SIMD]"]) >= min_occ, (kernel, rep)
         assert int(rep["LDS Size [bytes/block]"]) <= max_lds, (kernel, rep)
         assert rep["Dynamic Stack"] == "False", (kernel, rep)
+
+
+def test_the_makefile_gate_bites():
+    """The Makefile's resource gate (GATED, resource_gate.awk), run as its recipe runs it on hipcc's report of the carry unit:
+    the report as it is passes; with scratch, without the kernel's entry, or over a VGPR / LDS budget it fails and says why."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    row = [g.split(":") for g in make_var("GATED") if g.startswith("aacg_engine_carry:")]
+    assert row == [["aacg_engine_carry", "aacg_units_carry_shape", "-", "-"]], row
+    unit, kernel, max_vgprs, max_lds = row[0]
+    text = report_text(unit + ".hip")
+
+    def gate(report, vgprs=max_vgprs, lds=max_lds):
+        r = subprocess.run(["awk", "-v", "unit=" + unit, "-v", "kernel=" + kernel, "-v", "max_vgprs=%s" % vgprs, "-v", "max_lds=%s" % lds,
+                            "-f", os.path.join(CSRC, "resource_gate.awk")], input=report, capture_output=True, text=True, timeout=60)
+        return r.returncode, r.stdout
+
+    rc, out = gate(text)
+    assert rc == 0 and out.startswith(unit + ": ") and "fails" not in out, (rc, out)
+    spoiled, n = re.subn(r"(ScratchSize \[bytes/lane\]: )0 ", r"\g<1>16 ", text)
+    assert n == 1
+    rc, out = gate(spoiled)
+    assert rc != 0 and "scratch=16" in out, (rc, out)
+    renamed, n = re.subn(r"(Function Name: )" + kernel + " ", r"\1somebody_else ", text)
+    assert n == 1
+    rc, out = gate(renamed)
+    assert rc != 0 and "no resource report" in out, (rc, out)
+    # the headline kernel's two extra budgets, on this report: one below what the kernel uses
+    vgprs = int(re.search(r" VGPRs: (\d+) ", text).group(1))
+    rc, out = gate(text, vgprs=vgprs - 1)
+    assert rc != 0 and "VGPRs=%d" % vgprs in out and "LDS" not in out.splitlines()[-1], (rc, out)
+    rc, out = gate(text, vgprs=vgprs)
+    assert rc == 0, (rc, out)
+    lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+) ", text).group(1))
+    rc, out = gate(text, lds=lds - 1)
+    assert rc != 0 and "LDS=%d" % lds in out and "VGPRs=" not in out.splitlines()[-1], (rc, out)
+    rc, out = gate(text, lds=lds)
+    assert rc == 0, (rc, out)

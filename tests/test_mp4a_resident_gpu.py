@@ -4,13 +4,12 @@ option routes an 'mp4a' decoder there, and only the option does.  GPU: the commi
 streams give as ADTS on the resident route, bit for bit, with ADTS streams on the same engine, overlap on and off, a PCM ring and
 packets longer than the look-ahead; errors come where the parsing route raises them."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
+from resident_kit import NODE, ROOT
+
 SCRIPT = os.path.join(ROOT, "tests", "js", "test_mp4a_resident.js")
 needs_node = pytest.mark.skipif(NODE is None or not os.path.exists("/usr/include/node/node_api.h"),
                                 reason="node / node_api.h not present on this machine")

@@ -99,7 +99,7 @@ def test_uncovered_channels_are_zero_on_the_device(oracle, layout, C, path):
 def test_resident_pipeline_clears_the_channels_a_stereo_stream_leaves():
     """ADVICE (round 6) item 1: a stereo stream through a channels = 6 pipeline, on the lane whose last batch was 5.1 PCM: channels
     0-1 are the reference's, channels 2-5 exactly zero (the plan of a layout with holes clears the lane's PCM buffer)"""
-    from test_pipeline_gpu import CASES, load
+    from resident_kit import CASES, load
     case = {c["name"]: c for c in CASES}
     d51, t51, _ = load(case["surround48"])
     d2, t2, ref2 = load(case["stereo48"])

@@ -14,7 +14,6 @@ code it is given.
 """
 import json
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -22,9 +21,8 @@ import pytest
 
 import aacgpu
 import emu_lib
+from resident_kit import NODE, ROOT, STREAMS, adts_frame_table
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODE = shutil.which("node")
 pytestmark = pytest.mark.skipif(NODE is None, reason="node not present")
 
 
@@ -125,20 +123,6 @@ def test_kernel_source_under_address_sanitizer(standard):
                             str(case["maxChannels"]), str(case["options"]), "1" if case["wantTns"] else "0"],
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "asan_parse" in r.stdout, r.stdout + r.stderr[-2000:]
-
-
-def adts_frame_table(data):
-    """(offset, length) of every ADTS frame: 13-bit frame_length at bit 30 of the header."""
-    out, off = [], 0
-    while off + 7 <= len(data):
-        assert data[off] == 0xFF and (data[off + 1] & 0xF0) == 0xF0
-        length = ((int(data[off + 3]) & 3) << 11) | (int(data[off + 4]) << 3) | (int(data[off + 5]) >> 5)
-        out.append((off, length))
-        off += length
-    return np.array(out, aacgpu.PARSE_FRAME_DTYPE)
-
-
-STREAMS = os.path.join(ROOT, "tests", "golden", "streams")
 
 
 def reference_stream(case):

@@ -1,17 +1,15 @@
 """The resident batch's refresh map built on the device (aacg_pipe_map, aac.js_amd/csrc/aacg_pipe_map.h: map_body) against the map the
 host planner lists for the same batch (aacg_pipe::plan_list), byte for byte: the kernel's source run lane by lane on CPU threads
-(tests/emu_map/map_emu.cpp with tests/emu/devport_emu.h).  Ragged batches (each stream its own frame count, packed stream after
+(tests/emu/map_emu.cpp with tests/emu/devport_emu.h).  Ragged batches (each stream its own frame count, packed stream after
 stream), 1 / 2 / 6 / 8-channel layouts, layouts whose last elements are dropped (kept < n), streams without a layout yet."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import aacgpu
+import emu_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAP_DTYPE = np.dtype([("parsed_index", "<u4"), ("frame_units", "<u4")])          # aacg_refresh_map
 STREAM_DTYPE = np.dtype([("frame_first", "<u4"), ("frames", "<u4"), ("unit_first", "<u4"), ("frame_units", "<u4")])    # aacg_pipe_stream
 MAX_CHANNELS = 8
@@ -19,12 +17,7 @@ MAX_CHANNELS = 8
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("map_emu")), "libmap_emu.so")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I", os.path.join(ROOT, "tests", "emu"),
-           "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-Wl,--no-undefined", "-o", so,
-           os.path.join(ROOT, "tests", "emu_map", "map_emu.cpp")]
-    subprocess.run(cmd, check=True)
-    L = C.CDLL(so)
+    L = emu_lib.build_driver("map_emu", ["tests/emu/map_emu.cpp"], tmp_path_factory.mktemp("map_emu"))
     L.emu_pipe_map.argtypes = [C.c_void_p] * 5 + [C.c_uint32] * 6 + [C.c_void_p] * 4
     return L
 

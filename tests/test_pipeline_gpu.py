@@ -7,43 +7,15 @@ PCM down — reproduces them within 1e-5 RMS / 5e-6 of the signal from the same 
 5.1 (SCE + CPE + CPE + LFE: the layout is learnt from the stream's first frame) and a stream with coupling elements (parsed and
 dropped, as the reference executes them).  Internal consistency that must hold bit for bit: batches in flight on three lanes
 against the same batches one at a time on one lane."""
-import json
-import os
 import time
 
 import numpy as np
 import pytest
 
 import aacgpu
+from resident_kit import CASES, close_to, load
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STREAMS = os.path.join(ROOT, "tests", "golden", "streams")
-CASES = json.load(open(os.path.join(STREAMS, "manifest.json")))
-
-
-def adts_frame_table(data):
-    out, off = [], 0
-    while off + 7 <= len(data):
-        assert data[off] == 0xFF and (data[off + 1] & 0xF0) == 0xF0
-        length = ((int(data[off + 3]) & 3) << 11) | (int(data[off + 4]) << 3) | (int(data[off + 5]) >> 5)
-        out.append((off, length))
-        off += length
-    return np.array(out, aacgpu.PARSE_FRAME_DTYPE)
-
-
-def load(case):
-    data = np.fromfile(os.path.join(STREAMS, case["name"] + ".aac"), np.uint8)
-    table = adts_frame_table(data)
-    assert len(table) == case["frames"]
-    return data, table, np.fromfile(os.path.join(STREAMS, case["name"] + ".refpcm"), np.float32)
-
-
-def close_to(pcm, ref):
-    assert np.isfinite(pcm).all()
-    d = pcm.astype(np.float64) - ref
-    err, sig = float(np.sqrt(np.mean(d * d))), float(np.sqrt(np.mean(ref.astype(np.float64) ** 2)))
-    assert sig > 1e-3 and err < 1e-5 and err <= 5e-6 * sig, (err, sig)
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c["name"])

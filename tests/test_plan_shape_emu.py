@@ -1,18 +1,16 @@
 """A resident batch's plan shaped on the device (aacg_plan_shape, aac.js_amd/csrc/aacg_plan_shape.h: shape_body) against what the host
 planner makes of the same batch and the same rotation state (aacg_pipe::plan_list's units through aacg_plan_build), byte for byte:
 unit records, the rendezvous cut of the run table in its XCD-aware block order, its link records, the refresh map, the counts.  The
-kernel's source runs lane by lane on CPU threads (tests/emu_shape/shape_emu.cpp with tests/emu/devport_emu.h) into poisoned buffers;
+kernel's source runs lane by lane on CPU threads (tests/emu/shape_emu.cpp with tests/emu/devport_emu.h) into poisoned buffers;
 nothing may be written past the counts.  And the engine's own part without a device (aacg_shape.cpp): the per-shape figures against
 aacg_plan_build's, the capacity check, and the rule which consecutive launches of a shaped plan may meet in the cross-launch cells."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "aac.js_amd", "csrc")
+import emu_lib
+
 MAX_CHANNELS = 8
 OV_BUFFERS = 16
 POISON = 0xA5
@@ -27,13 +25,8 @@ RUN_DTYPE = np.dtype([("pred_unit", "<i4"), ("n_units", "<i4"), ("is_last", "<i4
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("shape_emu")), "libshape_emu.so")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I", os.path.join(ROOT, "tests", "emu"),
-           "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-Wl,--no-undefined", "-o", so,
-           os.path.join(ROOT, "tests", "emu_shape", "shape_emu.cpp"), os.path.join(CSRC, "aacg_shape.cpp"), os.path.join(CSRC, "aacg_plan.cpp"),
-           os.path.join(CSRC, "aacg_tables.cpp")]
-    subprocess.run(cmd, check=True)
-    L = C.CDLL(so)
+    L = emu_lib.build_driver("shape_emu", ["tests/emu/shape_emu.cpp", "aac.js_amd/csrc/aacg_shape.cpp", "aac.js_amd/csrc/aacg_plan.cpp",
+                                           "aac.js_amd/csrc/aacg_tables.cpp"], tmp_path_factory.mktemp("shape_emu"))
     L.emu_plan_shape.argtypes = [C.c_void_p] * 5 + [C.c_uint32] * 5 + [C.c_void_p, C.c_uint32] + [C.c_uint32] * 3 + [C.c_void_p] * 13
     L.emu_shape_capacity.argtypes = [C.c_uint32] * 4 + [C.c_void_p]
     L.emu_shape_same.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]

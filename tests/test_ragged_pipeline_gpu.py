@@ -6,66 +6,15 @@ ragged batches with seeded random per-stream counts, gives the reference's PCM (
 test_corpus.py) and the same bits as the same frames decoded stream by stream through the rectangular aacg_pipeline_decode: no
 arithmetic crosses streams.  Then batches in flight on five lanes, refusals at packed indices, a stream without a layout, a
 narrower layout after a wider one on the same lane, and the calls that are refused before anything is enqueued."""
-import base64
-import json
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import aacgpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STREAMS = os.path.join(ROOT, "tests", "golden", "streams")
-CASES = json.load(open(os.path.join(STREAMS, "manifest.json")))
-CORPUS = json.load(open(os.path.join(ROOT, "tests", "golden", "corpus.json")))["streams"]
-NODE = shutil.which("node")
-ERR_INVALID_ARG, ERR_CAPACITY = -1, -4          # AACG_ERR_* (include/aacgpu.h)
-
-
-def adts_frame_table(data):
-    out, off = [], 0
-    while off + 7 <= len(data):
-        assert data[off] == 0xFF and (data[off + 1] & 0xF0) == 0xF0
-        length = ((int(data[off + 3]) & 3) << 11) | (int(data[off + 4]) << 3) | (int(data[off + 5]) >> 5)
-        out.append((off, length))
-        off += length
-    return np.array(out, aacgpu.PARSE_FRAME_DTYPE)
-
-
-def load(case):
-    data = np.fromfile(os.path.join(STREAMS, case["name"] + ".aac"), np.uint8)
-    table = adts_frame_table(data)
-    assert len(table) == case["frames"]
-    return data, table, np.fromfile(os.path.join(STREAMS, case["name"] + ".refpcm"), np.float32)
-
-
-def close_to(pcm, ref):
-    assert np.isfinite(pcm).all()
-    d = pcm.astype(np.float64) - ref
-    err, sig = float(np.sqrt(np.mean(d * d))), float(np.sqrt(np.mean(ref.astype(np.float64) ** 2)))
-    assert sig > 1e-3 and err < 1e-5 and err <= 5e-6 * sig, (err, sig)
-
-
-def check_corpus_pcm(e, pcm):
-    p = e["pcm"]
-    assert pcm.size == p["n"] and np.isfinite(pcm).all(), e["name"]
-    probes = np.frombuffer(base64.b64decode(p["probes"]), np.float32)
-    idx = [((k * 7919 + 13) * 104729) % p["n"] for k in range(64)]
-    rms = (p["sumsq"] / p["n"]) ** 0.5
-    assert np.abs(pcm[idx].astype(np.float64) - probes).max() <= 1e-5 * max(1.0, 4.0 * rms), (e["name"], float(np.abs(pcm[idx] - probes).max()), rms)
-    x = pcm.astype(np.float64)
-    assert abs(float(x.sum()) - p["sum"]) <= 2e-6 * p["n"] ** 0.5 * max(rms, 1e-3) + 1e-9 * p["n"], (e["name"], float(x.sum()), p["sum"])
-    assert abs(float((x * x).sum()) - p["sumsq"]) <= 2e-5 * p["sumsq"] + 1e-12, (e["name"], float((x * x).sum()), p["sumsq"])
-
-
-def packed(tables, bases, at, counts):
-    """the batch's frame table: stream s's frames at[s] .. at[s] + counts[s] - 1, packed stream after stream"""
-    out = np.concatenate([tables[s][at[s]:at[s] + counts[s]] for s in range(len(counts))]).copy()
-    out["byte_offset"] += np.repeat(np.asarray(bases, np.uint32), counts)
-    return out
+from resident_kit import CASES, CORPUS, ERR_CAPACITY, ERR_INVALID_ARG, NODE, ROOT, adts_frame_table, check_corpus_pcm, close_to, load, packed
+from resident_kit import corpus_streams          # noqa: F401  (fixture)
 
 
 def ragged_run(members, C, si, max_frames, rng):
@@ -109,14 +58,6 @@ def test_ragged_batches_decode_the_committed_streams():
         for s in range(4):
             close_to(got[s], refpcm)
             assert np.array_equal(got[s].view(np.uint32), alone[s].view(np.uint32)), (case["name"], s)
-
-
-@pytest.fixture(scope="module")
-def corpus_streams(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("corpus"))
-    r = subprocess.run([NODE or "node", os.path.join(ROOT, "tests", "js", "corpus_cases.js"), d], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return {e["name"]: np.fromfile(os.path.join(d, e["name"] + ".aac"), np.uint8) for e in CORPUS}
 
 
 @pytest.mark.gpu

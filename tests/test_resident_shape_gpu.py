@@ -9,7 +9,6 @@ Engine.plan -> decode_pipelined, bit for bit; the oracle on the same units bound
 Streams: tests/js/shape_cases.js (plain frames: no TNS, no noise bands, no pulses) and tests/js/stage_cases.js (all three, for the
 carried shape together with the spec-correct stages).  The conditions they were chosen for are asserted here from the parser's
 records; no frame is left out of any comparison."""
-import json
 import os
 import subprocess
 
@@ -17,114 +16,12 @@ import numpy as np
 import pytest
 
 import aacgpu
-from test_device_plans_gpu import ragged_script, same_bits
-from test_ragged_pipeline_gpu import NODE, ROOT, adts_frame_table, packed
-from test_resident_stages_gpu import EX_RV, OPTIONS, close_to, members_of, parse_dims, rect_script, silent
-from test_resident_stages_gpu import streams as stage_streams          # noqa: F401  (fixture: tests/js/stage_cases.js)
+from resident_kit import ERR_INVALID_ARG, ERR_UNSUPPORTED, EX_RV, GROUPS, NODE, OPTIONS, PLAIN, ROOT, HostRoute, close_to, members_of, packed
+from resident_kit import ragged_script, rect_script, same_bits, steady
+from resident_kit import oracle, stage_streams          # noqa: F401  (fixtures: the oracle; tests/js/stage_cases.js)
+from resident_kit import shape_streams as streams          # noqa: F401  (fixture: tests/js/shape_cases.js)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(NODE is None, reason="node not present")]
-PLAIN = aacgpu.PARSE_REFERENCE_QUIRKS
-ERR_INVALID_ARG, ERR_UNSUPPORTED = -1, -5
-
-
-@pytest.fixture(scope="module")
-def streams(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("shape_cases"))
-    r = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "shape_cases.js"), d], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    out = {}
-    for c in json.load(open(os.path.join(d, "manifest.json"))):
-        data = np.fromfile(os.path.join(d, c["name"] + ".aac"), np.uint8)
-        table = adts_frame_table(data)
-        assert len(table) == c["frames"] == c["parsed"] == 12 and c["pnsUnits"] == 0 and c["bothWays"] and c["kbdAtBoundary"], c
-        out[c["name"]] = (c, data, table)
-    return out
-
-
-@pytest.fixture(scope="module")
-def oracle():
-    import orc
-    return orc.load()
-
-
-class HostRoute:
-    """the yardstick: host parse -> window_shape_prev by the rule (carry) or 0 -> a plan per batch -> decode_pipelined; the oracle"""
-
-    def __init__(self, S, C_, si, oracle=None, carry=True, spec=False, options=PLAIN):
-        import torch
-        self.torch, self.S, self.C, self.si, self.carry, self.spec, self.options = torch, S, C_, si, carry, spec, options
-        self.U, self.Cp = parse_dims(C_)
-        self.parser = aacgpu.Parser(sample_index=si)
-        modes = dict(tns_mode=aacgpu.TNS_SPEC, pns_mode=aacgpu.PNS_SPEC) if spec else {}
-        self.eng = aacgpu.Engine(aacgpu.INPUT_QUANT_I16, max_streams=S, max_channels=C_, sample_index=si, **modes)
-        self.oracle, self.ov = oracle, np.zeros((S, C_, 1024), np.float32)
-        self.W = np.zeros((S, C_), np.uint8)                  # the rule's state
-        self.shapes = [[] for _ in range(S)]                  # per stream: per frame, (shape of every channel, shape_prev it was given)
-        self.routes, self.refused, self.pns_units = set(), 0, 0
-
-    def reset(self, s):
-        self.eng.reset_stream(s)
-        self.W[s] = 0
-        self.ov[s] = 0
-
-    def decode(self, data, fr, live, counts):
-        """-> (PCM of the batch, packed stream after stream like the pipeline's; the oracle's or None)"""
-        torch = self.torch
-        out = self.parser.parse_batch(data, fr, self.U, self.Cp, self.options, self.spec)
-        n, per = len(fr), 1024 * self.C
-        units = []
-        first = np.concatenate([[0], np.cumsum(counts)])
-        for k, s in enumerate(live):
-            for i in range(first[k], first[k + 1]):
-                shape, prev = np.zeros(self.C, np.uint8), self.W[s].copy()
-                if int(out["results"]["status"][i]) or (self.C <= 2 and int(out["results"]["n_units"][i]) != 1):
-                    # a refused frame (a parse error, or not the one element the plan lists): what the refresh makes of it — a silent
-                    # unit on the planner's record (one element: C <= 2)
-                    assert self.C <= 2
-                    u = np.zeros((), aacgpu.UNIT_DTYPE)
-                    u["n_ch"], u["coef_offset"], u["meta_offset"] = self.C, i * self.Cp, i * self.Cp
-                    silent(u)
-                    u["stream"], u["n_out_ch"], u["pcm_offset"] = s, self.C, i * per
-                    frame_units = [u]
-                    self.refused += 1
-                else:
-                    frame_units, chan = [], 0
-                    for e in range(int(out["results"]["n_units"][i])):
-                        u = out["units"][i * self.U + e].copy()
-                        if chan + int(u["n_ch"]) > self.C:
-                            break                               # decoder.js:233: elements beyond chanConfig channels are dropped
-                        u["stream"], u["n_out_ch"], u["pcm_offset"] = s, self.C, i * per
-                        self.pns_units += bool(int(u["flags"]) & aacgpu.UNIT_HAS_PNS)
-                        for c in range(int(u["n_ch"])):
-                            shape[chan + c] = u["ch"]["window_shape"][c]
-                        chan += int(u["n_ch"])
-                        frame_units.append(u)
-                for u in frame_units:
-                    for c in range(int(u["n_ch"])):
-                        u["ch"]["window_shape_prev"][c] = prev[int(u["channel"]) + c] if self.carry else 0
-                units += frame_units
-                self.shapes[s].append((shape, prev))
-                self.W[s] = shape                               # (every channel of these streams has a unit in every frame)
-        units = np.array(units, aacgpu.UNIT_DTYPE)
-        tns = out["tns"] if self.spec else None
-        plan = self.eng.plan(units, tns=tns) if self.spec else self.eng.plan(units)
-        self.routes.add(self.eng.plan_kernels(plan, pipelined=True))
-        d_q, d_meta = torch.from_numpy(out["q"]).cuda(), torch.from_numpy(out["meta"].view(np.int16)).cuda()
-        d_pcm = torch.zeros(n * per, dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        self.eng.decode_pipelined(plan, d_q.data_ptr(), d_meta.data_ptr(), d_pcm.data_ptr())
-        self.eng.synchronize()
-        pcm = d_pcm.cpu().numpy()
-        plan.destroy()
-        ref = None
-        if self.oracle is not None:
-            kw = dict(tns=tns, pns=True) if self.spec else {}
-            ref = self.oracle.decode_batch(units, out["q"], out["meta"], n * per, self.ov, sample_index=self.si, **kw)
-        return pcm, ref
-
-    def close(self):
-        self.eng.close()
-        self.parser.close()
 
 
 def host_run(mem, script, C_, si, oracle=None, **kw):
@@ -137,7 +34,7 @@ def host_run(mem, script, C_, si, oracle=None, **kw):
     per = 1024 * C_
     for live, counts, at in script:
         fr = packed([mem[s][1] for s in live], [bases[s] for s in live], at, counts)
-        pcm, r = host.decode(data, fr, live, counts)
+        pcm, r, _ = host.decode(data, fr, live, counts)
         first = np.concatenate([[0], np.cumsum(counts)])
         for k, s in enumerate(live):
             want[s].append(pcm[first[k] * per:first[k + 1] * per])
@@ -197,9 +94,6 @@ def not_carried(frame, other, kbd, what):
         assert not same_bits(frame, other), what + ": KBD carried into it, and yet the samples of a pipeline that always takes sine"
     else:
         assert float(np.abs(frame.astype(np.float64) - other).max()) <= 1e-5, what + ": no KBD carried into it"
-
-
-GROUPS = [("mono48", 1, 3), ("stereo48+split48", 2, 3), ("five1_48", 6, 3), ("mono16", 1, 8), ("stereo16+split16", 2, 8), ("five1_16", 6, 8)]
 
 
 @pytest.mark.parametrize("names,C_,si", GROUPS, ids=[g[0] for g in GROUPS])
@@ -309,32 +203,15 @@ def test_plan_modes_ragged_counts_and_five_lanes_in_flight(streams):
         assert e.value.code == ERR_UNSUPPORTED
 
 
-def steady(streams, device_plans, **kw):
-    """the same shape 24 times (six stereo streams x 2 frames, the streams fed round and round), submitted ahead on five lanes"""
-    c, data, table = streams["stereo48"]
-    S, B = 6, 24
-    p = aacgpu.Pipeline(channels=2, max_streams=S, max_frames=2, lanes=5, device_plans=device_plans, **kw)
-    pcm, pending = [], []
-    for b in range(B):
-        fr = packed([table] * S, [0] * S, [(2 * b) % 12] * S, [2] * S)
-        pending.append(p.submit(data, fr, np.arange(S), np.full(S, 2, np.uint32), pcm=p.pinned(S * 2 * 2048, np.float32)))
-        if len(pending) == 5:
-            pcm.append(p.collect(pending.pop(0))[0].copy())
-    pcm += [p.collect(t)[0].copy() for t in pending]
-    counts = p.launch_counts()
-    p.close()
-    return counts, pcm
-
-
 def test_the_steady_feed_still_continues_its_predecessor(streams):
     """consecutive batches of one shape still meet in the cross-launch cells with the carry launch between refresh and transform: as
     many launches, and as many of them continued, as with the bit clear; the bits of one batch at a time"""
+    c, data, table = streams["stereo48"]
     for mode in (False, True):
-        on, pcm = steady(streams, mode, carry_window_shape=True)
-        off, _ = steady(streams, mode)
+        on, pcm = steady(data, table, 6, 24, 12, mode, carry_window_shape=True)
+        off, _ = steady(data, table, 6, 24, 12, mode)
         print("device plans %s: %s with the carried shape, %s without" % (mode, on, off))
         assert on["launches"] == off["launches"] == 24 and on["chained"] == off["chained"] > 0 and on["shaped"] == off["shaped"]
-    c, data, table = streams["stereo48"]
     one = aacgpu.Pipeline(channels=2, max_streams=6, max_frames=2, lanes=1, carry_window_shape=True)
     for b in range(24):
         fr = packed([table] * 6, [0] * 6, [(2 * b) % 12] * 6, [2] * 6)
@@ -372,7 +249,7 @@ def test_state_reset_absent_streams_and_a_truncated_frame(streams, oracle, mode)
             assert any(before), "slot 3 carried KBD into the reset"
         fr = packed([mem[s][1] for s in live], [bases[s] for s in live], at, counts)
         pcm, res, refused = p.decode(all_data, fr, np.array(live, np.uint32), np.array(counts, np.uint32))
-        w, r = host.decode(all_data, fr, live, counts)
+        w, r, _ = host.decode(all_data, fr, live, counts)
         refusals += refused
         if b == 1:
             assert refused == 1 and np.count_nonzero(res["status"]) == 1 and res["status"][4 + 2] != 0, "the truncated frame, counted once"

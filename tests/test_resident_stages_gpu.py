@@ -9,7 +9,6 @@ ragged counts, five lanes in flight, the steady feed's overlap, `stages = 0` as 
 
 Streams: tests/js/stage_cases.js (TNS filters, noise bands and pulse data throughout; seeds fixed there).  The conditions they were
 chosen for are asserted here from what the device returns."""
-import json
 import os
 import subprocess
 
@@ -17,117 +16,15 @@ import numpy as np
 import pytest
 
 import aacgpu
-from test_device_plans_gpu import ragged_script, run_script, same_bits
-from test_ragged_pipeline_gpu import NODE, ROOT, adts_frame_table, packed
-from test_tns_records_emu import lib as emu_tns          # noqa: F401  (fixture: aacg_tns_prepare on the host, built with g++)
-from test_tns_records_emu import layout as records_layout
+from resident_kit import ERR_INVALID_ARG, ERR_UNSUPPORTED, EX_RV, GROUPS, NODE, OPTIONS, PARSE_TNS_ORDER, ROOT, HostRoute, close_to, members_of, packed
+from resident_kit import ragged_script, records_layout, rect_script, run_script, same_bits, silent, steady
+from resident_kit import emu_tns, oracle          # noqa: F401  (fixtures: aacg_tns_prepare on the host, built with g++; the oracle)
+from resident_kit import stage_streams as streams          # noqa: F401  (fixture: tests/js/stage_cases.js)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(NODE is None, reason="node not present")]
-OPTIONS = aacgpu.PARSE_APPLY_PULSES | aacgpu.PARSE_REFERENCE_QUIRKS
 SPEC = dict(tns_spec=True, pns_spec=True, parse_options=OPTIONS)
-EX_RV = "aacg_imdct_run_quant_ex_rv"
-ERR_INVALID_ARG, ERR_UNSUPPORTED = -1, -5
-PARSE_TNS_ORDER, PARSE_LAYOUT = 8, 16
-
-
-@pytest.fixture(scope="module")
-def streams(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("stage_cases"))
-    r = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "stage_cases.js"), d], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    out = {}
-    for c in json.load(open(os.path.join(d, "manifest.json"))):
-        data = np.fromfile(os.path.join(d, c["name"] + ".aac"), np.uint8)
-        table = adts_frame_table(data)
-        assert len(table) == c["frames"] == c["parsed"] == 12, "the JavaScript front end parses every frame of the chosen seeds"
-        out[c["name"]] = (c, data, table)
-    return out
-
-
-def parse_dims(C_):
-    """what the pipeline allows the parser per frame: (elements, channel blocks)"""
-    return (8, 8) if C_ > 2 else (1, C_)
-
-
-@pytest.fixture(scope="module")
-def oracle():
-    import orc
-    return orc.load()
-
-
-class HostRoute:
-    """the yardstick: host parse with TNS records -> a plan per batch with host-made records -> decode_pipelined; and the oracle"""
-
-    def __init__(self, S, C_, si, oracle=None):
-        import torch
-        self.torch, self.S, self.C, self.si = torch, S, C_, si
-        self.U, self.Cp = parse_dims(C_)
-        self.parser = aacgpu.Parser(sample_index=si)
-        self.eng = aacgpu.Engine(aacgpu.INPUT_QUANT_I16, max_streams=S, max_channels=C_, sample_index=si, tns_mode=aacgpu.TNS_SPEC, pns_mode=aacgpu.PNS_SPEC)
-        self.oracle, self.ov = oracle, np.zeros((S, C_, 1024), np.float32)
-        self.tns_channels = self.channel_frames = self.units = self.pns_units = 0
-        self.routes = set()
-
-    def decode(self, data, fr, live, counts):
-        """-> (PCM of the batch, packed stream after stream like the pipeline's; the oracle's or None)"""
-        torch = self.torch
-        out = self.parser.parse_batch(data, fr, self.U, self.Cp, OPTIONS, True)
-        assert not out["results"]["status"].any(), "every frame parses"
-        n, per = len(fr), 1024 * self.C
-        units = []
-        first = np.concatenate([[0], np.cumsum(counts)])
-        for k, s in enumerate(live):
-            for i in range(first[k], first[k + 1]):
-                chan = 0
-                for e in range(int(out["results"]["n_units"][i])):
-                    u = out["units"][i * self.U + e].copy()
-                    if chan + int(u["n_ch"]) > self.C:
-                        break                                   # decoder.js:233: elements beyond chanConfig channels are dropped
-                    chan += int(u["n_ch"])
-                    u["stream"], u["n_out_ch"], u["pcm_offset"] = s, self.C, i * per
-                    units.append(u)
-                    self.units += 1
-                    self.pns_units += bool(int(u["flags"]) & aacgpu.UNIT_HAS_PNS)
-                    self.channel_frames += int(u["n_ch"])
-        units = np.array(units, aacgpu.UNIT_DTYPE)
-        plan = self.eng.plan(units, tns=out["tns"])
-        self.routes.add(self.eng.plan_kernels(plan, pipelined=True))
-        d_q, d_meta = torch.from_numpy(out["q"]).cuda(), torch.from_numpy(out["meta"].view(np.int16)).cuda()
-        d_pcm = torch.zeros(n * per, dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        self.eng.decode_pipelined(plan, d_q.data_ptr(), d_meta.data_ptr(), d_pcm.data_ptr())
-        self.eng.synchronize()
-        pcm = d_pcm.cpu().numpy()
-        plan.destroy()
-        ref = None
-        if self.oracle is not None:
-            ref = self.oracle.decode_batch(units, out["q"], out["meta"], n * per, self.ov, sample_index=self.si, tns=out["tns"], pns=True)
-        return pcm, ref, out
-
-    def close(self):
-        self.eng.close()
-        self.parser.close()
-
-
-def members_of(streams, names, copies):
-    """[(bytes, table)] for the pipeline: `copies` slots per named stream, each at a starting frame of its own where noted"""
-    return [(streams[n][1], streams[n][2]) for n in names for _ in range(copies)]
-
-
-def rect_script(S, F, n_frames):
-    return [(list(range(S)), [F] * S, [a] * S) for a in range(0, n_frames, F)]
-
-
-def close_to(pcm, ref):
-    """the project's tolerances: RMS error <= 1e-5 absolute and <= 5e-6 of the signal RMS, on a signal that is one"""
-    assert np.isfinite(pcm).all() and np.isfinite(ref).all()
-    d = pcm.astype(np.float64) - ref
-    err, sig = float(np.sqrt(np.mean(d * d))), float(np.sqrt(np.mean(ref.astype(np.float64) ** 2)))
-    print("rms error %.3e, signal rms %.3e" % (err, sig))
-    assert sig > 1e-3 and err <= 1e-5 and err <= 5e-6 * sig, (err, sig)
-
-
-GROUPS = [("mono48", 1, 3), ("stereo48+split48", 2, 3), ("five1_48", 6, 3), ("mono16", 1, 8), ("stereo16+split16", 2, 8), ("five1_16", 6, 8)]
+# the yardstick of these tests: the host-planned SPEC path on host-made records, window_shape_prev 0, every frame parses
+HOST = dict(carry=False, spec=True, options=OPTIONS, every_frame_parses=True)
 
 
 @pytest.mark.parametrize("names,C_,si", GROUPS, ids=[g[0] for g in GROUPS])
@@ -144,7 +41,7 @@ def test_device_records_equal_host_records_bit_for_bit_and_the_oracle(streams, o
     script = rect_script(S, 4, 12)
     got = run_script(mem, script, C_, si, 4, False, **SPEC)
     assert got[2] == 0 and not any(x.any() for x in got[1]), "every frame parses on the device"
-    host = HostRoute(S, C_, si, oracle)
+    host = HostRoute(S, C_, si, oracle, **HOST)
     data = np.concatenate([m[0] for m in mem])
     bases = np.cumsum([0] + [len(m[0]) for m in mem])[:-1]
     want, ref = [[] for _ in range(S)], [[] for _ in range(S)]
@@ -157,7 +54,7 @@ def test_device_records_equal_host_records_bit_for_bit_and_the_oracle(streams, o
             want[s].append(pcm[k * 4 * per:(k + 1) * 4 * per])
             ref[s].append(r[k * 4 * per:(k + 1) * 4 * per])
         # the kernel on the GPU against the host function, on this batch's parser outputs
-        n, (U, Cp) = len(fr), parse_dims(C_)
+        n, U, Cp = len(fr), host.U, host.Cp
         m_off, total = records_layout(emu_tns, n * Cp)
         assert total == host.eng.tns_records_bytes(n * Cp)
         hbuf = np.zeros(total, np.uint8)
@@ -261,34 +158,16 @@ def test_both_plan_modes_ragged_counts_and_five_lanes_in_flight(streams):
         assert same_bits(np.concatenate(flight[s]), shaped[0][s]), s
 
 
-def steady(streams, device_plans, **kw):
-    """the same shape 24 times (six stereo streams x 2 frames, the streams fed round and round), submitted ahead on five lanes"""
-    c, data, table = streams["stereo48"]
-    S, B = 6, 24
-    p = aacgpu.Pipeline(channels=2, max_streams=S, max_frames=2, lanes=5, device_plans=device_plans, **kw)
-    pcm, pending = [], []
-    for b in range(B):
-        fr = packed([table] * S, [0] * S, [(2 * b) % 12] * S, [2] * S)
-        pending.append(p.submit(data, fr, np.arange(S), np.full(S, 2, np.uint32), pcm=p.pinned(S * 2 * 2048, np.float32)))
-        if len(pending) == 5:
-            pcm.append(p.collect(pending.pop(0))[0].copy())
-    pcm += [p.collect(t)[0].copy() for t in pending]
-    counts = p.launch_counts()
-    p.close()
-    assert counts["launches"] == B
-    return counts["chained"], pcm
-
-
 def test_the_steady_feed_still_continues_launches_through_the_cells(streams):
     """consecutive batches of one shape are consecutive launches of one plan and meet in the cross-launch cells, with the stages
     as without them; the chained launches' bits are those of one batch at a time"""
-    kept, pcm0 = steady(streams, False, **SPEC)
-    shaped, pcm1 = steady(streams, True, **SPEC)
+    c, data, table = streams["stereo48"]
+    (kept, pcm0), (shaped, pcm1) = steady(data, table, 6, 24, 12, False, **SPEC), steady(data, table, 6, 24, 12, True, **SPEC)
+    kept, shaped = kept["chained"], shaped["chained"]
     print("continued launches of 24: kept plans %d, device plans %d" % (kept, shaped))
     assert kept > 0 and shaped > 0
     for a, b in zip(pcm0, pcm1):
         assert same_bits(a, b)
-    c, data, table = streams["stereo48"]
     one = aacgpu.Pipeline(channels=2, max_streams=6, max_frames=2, lanes=1, **SPEC)
     for b in range(24):
         fr = packed([table] * 6, [0] * 6, [(2 * b) % 12] * 6, [2] * 6)
@@ -306,21 +185,13 @@ def test_a_chain_across_three_runs(streams, oracle):
     for mode in (False, True):
         got = run_script(mem, script, 2, 3, 40, mode, **SPEC)
         assert got[2] == 0
-        host = HostRoute(2, 2, 3, oracle)
+        host = HostRoute(2, 2, 3, oracle, **HOST)
         fr = packed([m[1] for m in mem], [0, 0], [0, 0], [40, 40])
         pcm, ref, out = host.decode(data, fr, [0, 1], [40, 40])
         assert host.routes == {EX_RV}
         assert same_bits(np.concatenate(got[0]), pcm)
         close_to(np.concatenate(got[0]), ref)
         host.close()
-
-
-def silent(units):
-    """what the refresh makes of a refused frame's unit: ONLY_LONG, sine, nothing coded; the planner's part stays"""
-    units["flags"] = 0
-    units["tns_offset"] = 0
-    units["ch"] = np.zeros((), aacgpu.UNIT_DTYPE["ch"].base)
-    units["ch"]["group_count"], units["ch"]["group_len"][..., 0] = 1, 1
 
 
 @pytest.mark.parametrize("name,si", [("mono48", 3), ("mono16", 8)])

@@ -37,7 +37,7 @@ import aacgpu_workload as W  # noqa: E402
 import emu_lib  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-HALF = "libaacg_emu_half.so"    # tests/half_emu.cpp: the rendezvous kernels of f32 PCM on the eight-wave body (tests/emu/Makefile)
+HALF = "libaacg_emu_half.so"    # tests/emu/half_emu.cpp: the rendezvous kernels of f32 PCM on the eight-wave body (tests/emu/Makefile)
 WIDE = ("cpe", "cpe", "cpe", "sce")
 SEEDS = 16
 RK_QUANT, RK_RV = 1, 32         # AACG_RK_* (aacg_routes.h)

@@ -1,33 +1,26 @@
 """Each channel's window shape carried from frame to frame on the device (aacg_units_carry_shape, aac.js_amd/csrc/aacg_shape_carry.h:
 carry_body) against a plain walk of the rule, byte for byte on the whole unit array: the kernel's source run lane by lane on CPU
-threads (tests/emu_carry/carry_emu.cpp with tests/emu/devport_emu.h).
+threads (tests/emu/carry_emu.cpp with tests/emu/devport_emu.h).
 
 The rule: the engine holds W[slot][c]; for each stream of a batch, its frames in order, each unit's channel k (output channel
 c = channel + k) gets window_shape_prev = the stream's first frame ? W[slot][c] : window_shape of the frame before, and after the
 batch W[slot][c] is the last frame's window_shape.  A silent frame's shape is 0; channels without a unit keep their W; nothing else
 in a record changes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import aacgpu
+import emu_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV_UNIT_DTYPE = np.dtype([("d", aacgpu.UNIT_DTYPE), ("gmap", "<u4", (2,)), ("cpl_first", "<u4"), ("cpl_n", "<u4")])      # aacg_dev_unit
 MAP_DTYPE = np.dtype([("parsed_index", "<u4"), ("frame_units", "<u4")])                                                 # aacg_refresh_map
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("carry_emu")), "libcarry_emu.so")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I", os.path.join(ROOT, "tests", "emu"),
-           "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-Wl,--no-undefined", "-o", so,
-           os.path.join(ROOT, "tests", "emu_carry", "carry_emu.cpp")]
-    subprocess.run(cmd, check=True)
-    L = C.CDLL(so)
+    L = emu_lib.build_driver("carry_emu", ["tests/emu/carry_emu.cpp"], tmp_path_factory.mktemp("carry_emu"))
     L.emu_carry.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.emu_carry.restype = None
     L.emu_carry_entry.argtypes = [C.c_uint32] * 3

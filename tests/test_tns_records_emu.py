@@ -1,26 +1,24 @@
 """A batch's TNS records made on the device (aacg_tns_records, aac.js_amd/csrc/aacg_tns_prep.h: tns_records_body, and the matrices
 kernel behind it) against what the host makes of the same parser outputs (aacg_tns_prepare, aac.js_amd/csrc/aacg_plan.cpp; the
-matrices from tns_matrix_row), BYTE FOR BYTE.  The kernels' source runs lane by lane on the CPU (tests/emu_tnsprep/tnsprep_emu.cpp
+matrices from tns_matrix_row), BYTE FOR BYTE.  The kernels' source runs lane by lane on the CPU (tests/emu/tnsprep_emu.cpp
 with tests/emu/devport_emu.h) into a poisoned buffer laid out as aacg_tns_records_bytes lays it out; nothing may be left of the
 poison inside it and nothing may be written outside it.
 
 The inputs come from a seeded generator, for every sample index that has band tables (0..11: the TNS limits know a thirteenth, the
 engine and aacg_swb_offsets refuse it), and the test asserts of the inputs themselves that they hold what it means to check."""
-import ctypes as C
 import json
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import aacgpu
+from resident_kit import NODE, ROOT
+from resident_kit import emu_tns as lib          # noqa: F401  (fixture: tests/emu/tnsprep_emu.cpp, built with g++)
+from resident_kit import records_layout as layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "aac.js_amd", "csrc")
-NODE = shutil.which("node")
 POISON = 0xA5
 GUARD = 4096                       # poisoned bytes in front of and behind the buffer
 SHORT = 2                          # AACG_EIGHT_SHORT_SEQUENCE
@@ -44,32 +42,6 @@ def coef_tables():
                 vals.append(np.float32(-math.sin(s / (((half - 0.5) if s >= 0 else (half + 0.5)) / (math.pi / 2.0)))))
             out.append(vals)
     return out
-
-
-@pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("tnsprep_emu")), "libtnsprep_emu.so")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I", os.path.join(ROOT, "tests", "emu"),
-           "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-Wl,--no-undefined", "-o", so,
-           os.path.join(ROOT, "tests", "emu_tnsprep", "tnsprep_emu.cpp"), os.path.join(CSRC, "aacg_plan.cpp"), os.path.join(CSRC, "aacg_tables.cpp")]
-    subprocess.run(cmd, check=True)
-    L = C.CDLL(so)
-    L.emu_tnsprep_layout.restype = C.c_uint64
-    L.emu_tnsprep_layout.argtypes = [C.c_uint32, C.c_void_p]
-    L.emu_tns_records.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_uint32] * 4 + [C.c_void_p]
-    L.emu_tns_host.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p]
-    sizes = np.zeros(6, np.uint32)
-    L.emu_tnsprep_sizes(sizes.ctypes.data_as(C.c_void_p))
-    assert list(sizes[:5]) == [aacgpu.DEV_TNS_DTYPE.itemsize, aacgpu.TNS_DTYPE.itemsize, aacgpu.UNIT_DTYPE.itemsize, aacgpu.PARSE_RESULT_DTYPE.itemsize,
-                               aacgpu.TNS_M_DOUBLES]
-    return L
-
-
-def layout(lib, n):
-    total = C.c_uint64()
-    m_off = int(lib.emu_tnsprep_layout(n, C.byref(total)))
-    assert m_off % 256 == 0 and m_off >= n * 512 and int(total.value) == m_off + n * aacgpu.TNS_M_DOUBLES * 8
-    return m_off, int(total.value)
 
 
 def run(lib, si, units, results, info, max_units, Cp, blocks=None):

@@ -1,5 +1,5 @@
 """Shared by the span-walk tests (test_parse_walk_emu.py, test_parse_walk_gpu.py): the walk kernel's source built for the lane
-emulator (tests/walk_emu.cpp), the front-end corpus as MP4 samples (bare raw_data_blocks: the ADTS headers cut off, as
+emulator (tests/emu/walk_emu.cpp), the front-end corpus as MP4 samples (bare raw_data_blocks: the ADTS headers cut off, as
 test_corpus.py and tests/js/test_aurora.js build them) and spans over those samples."""
 import ctypes as C
 import os
@@ -8,20 +8,15 @@ import subprocess
 import numpy as np
 
 import aacgpu
+import emu_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPAN_SIZES = (1, 3, 7, 16, 40)          # blocks per span, cycled
 
 
 def build_emu(out_dir):
-    """tests/walk_emu.cpp + the host's table builders, as tests/emu/Makefile builds the emulator, into out_dir."""
-    so = os.path.join(str(out_dir), "libwalk_emu.so")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-DAACG_EMU_BUILD", "-I", os.path.join(ROOT, "tests", "emu"),
-           "-pthread", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-Wl,--no-undefined", "-o", so,
-           os.path.join(ROOT, "tests", "walk_emu.cpp"), os.path.join(ROOT, "aac.js_amd", "csrc", "aacg_parse_host.cpp"),
-           os.path.join(ROOT, "aac.js_amd", "csrc", "aacg_tables.cpp")]
-    subprocess.run(cmd, check=True)
-    lib = C.CDLL(so)
+    """tests/emu/walk_emu.cpp + the host's table builders, as tests/emu/Makefile builds the emulator, into out_dir."""
+    lib = emu_lib.build_driver("walk_emu", ["tests/emu/walk_emu.cpp", "aac.js_amd/csrc/aacg_parse_host.cpp", "aac.js_amd/csrc/aacg_tables.cpp"], out_dir)
     lib.emu_walk_last_error.restype = C.c_char_p
     lib.emu_walk.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                              C.c_void_p, C.c_void_p]
