@@ -42,8 +42,16 @@
  * aacg_plan_carry_window_shape behind every refresh, inside the stale-plan retry and in both plan modes, sets window_shape_prev of
  * the batch's unit records from the frame before and, across batches, from the engine's per-channel state (aacg_shape_carry.h).
  *
+ * PCM left on the device (aacg_pipeline_submit_device): the same batch with a caller's device memory for the PCM.  AACG_PCM_PACKED: the
+ * caller's pointer takes the place of the lane's d_pcm in the transform's launch (and in the clear for unlearnt streams) — the
+ * cross-launch hand-over finds a successor's PCM through the pointer its cell carries, so a caller's buffer needs nothing new there.
+ * AACG_PCM_PLANAR: the transform writes the lane's d_pcm and aacg_pcm_planar_* (aacg_pcm_planar.h, aacg_engine_planar.hip) writes the
+ * caller's tensor from it and from the per-stream table the batch brought up, behind aacg_pipeline_join where a host batch's copy
+ * down sits.  Neither has a copy down of PCM nor touches h_pcm; the results' copy and the lane's `done` event are as ever, and
+ * aacg_pipeline_wait_device puts a consumer's stream behind that event.  The two submissions share one body (submit_batch).
+ *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
- * (and aacg_pipe_map.h / aacg_plan_shape.h for the tables it fills).
+ * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h for the tables it fills and the side launch it makes).
  */
 #include <hip/hip_runtime.h>
 
@@ -55,6 +63,7 @@
 
 #include "../../include/aacgpu.h"
 #include "../../include/aacgpu_tools.h"
+#include "aacg_pcm_planar.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
@@ -62,6 +71,9 @@
 /* the bits of aacg_pipeline_config.stages that select the SPEC engine modes and the plans and launches that go with them
  * (AACG_PIPELINE_STAGE_WINDOW_SHAPE selects neither: one carry launch behind the refresh, whatever the plan) */
 #define AACG_PIPELINE_SPEC_STAGES (AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS)
+
+/* aacg_engine_planar.hip: a batch's packed PCM into a caller's planar tensor (aacg_pcm_planar.h); false: not a launch it serves */
+bool aacg_planar_launch(const aacg_planar_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -137,6 +149,7 @@ struct aacg_pipeline {
         bool busy = false, count_stale = false;
         uint64_t ticket = 0;
         void* user_pcm = nullptr; bool direct = false; size_t pcm_bytes = 0;
+        bool device_out = false;          /* aacg_pipeline_submit_device: the PCM stays on the device, nothing of it is the host's to copy */
         aacg_parse_result* user_results = nullptr; uint32_t* user_refused = nullptr; uint32_t n = 0;
         std::vector<uint32_t> first, frames_of;   /* the batch's streams: first packed frame, frame count */
         std::vector<uint32_t> unlearnt;   /* streams of the batch (by position) whose layout was not known: nothing of them was decoded */
@@ -259,7 +272,7 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
     const hipError_t st = aacg_wait_event(L.done, p->wait);
     if (st == hipErrorNotReady) return timed_out(p, "aacg_pipeline_collect");
     P_TRY(p, st, AACG_ERR_NO_DEVICE);
-    if (!L.direct) std::memcpy(L.user_pcm, L.h_pcm, L.pcm_bytes);
+    if (!L.device_out && !L.direct) std::memcpy(L.user_pcm, L.h_pcm, L.pcm_bytes);
     /* a stream whose first frame did not parse has no layout yet: every frame of it in this batch came out silent and says so */
     aacg_parse_result* res = (aacg_parse_result*)L.h_res;
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
@@ -311,6 +324,30 @@ int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const 
             for (uint32_t s : p->plans[i].slots) has = has || s == slots[who[k]];
             if (has) drop_plan(p, i);
         }
+    }
+    return AACG_OK;
+}
+
+/* aacg_pipeline_submit_device's own refusals, for a batch of n frames in n_streams streams whose largest count is `longest`: all on
+ * the host, before anything is enqueued */
+int check_device_out(aacg_pipeline* p, const aacg_pcm_device_out* out, uint32_t n, uint32_t n_streams, uint32_t longest)
+{
+    if (!out || !out->d_pcm) { p->err = "aacg_pipeline_submit_device: no device memory for the PCM (out or out->d_pcm is null)"; return AACG_ERR_INVALID_ARG; }
+    if ((uintptr_t)out->d_pcm & 15u) { p->err = "aacg_pipeline_submit_device: d_pcm is not 16-byte aligned"; return AACG_ERR_INVALID_ARG; }
+    if (out->layout != AACG_PCM_PACKED && out->layout != AACG_PCM_PLANAR) { p->err = "aacg_pipeline_submit_device: unknown layout (AACG_PCM_PACKED or AACG_PCM_PLANAR)"; return AACG_ERR_INVALID_ARG; }
+    if (out->layout == AACG_PCM_PACKED && out->stride_frames) { p->err = "aacg_pipeline_submit_device: AACG_PCM_PACKED takes stride_frames 0"; return AACG_ERR_INVALID_ARG; }
+    if (out->layout == AACG_PCM_PLANAR && out->stride_frames < longest) { p->err = "aacg_pipeline_submit_device: stride_frames is below the batch's largest frame count"; return AACG_ERR_INVALID_ARG; }
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, out->d_pcm) != hipSuccess) { (void)hipGetLastError(); p->err = "aacg_pipeline_submit_device: d_pcm is not memory the HIP runtime knows (pageable host memory?)"; return AACG_ERR_INVALID_ARG; }
+    if (a.type != hipMemoryTypeDevice || a.device != p->cfg.device_ordinal) {
+        p->err = a.type == hipMemoryTypeDevice ? "aacg_pipeline_submit_device: d_pcm is another device's memory" : "aacg_pipeline_submit_device: d_pcm is not device memory (host memory, page-locked or not)";
+        return AACG_ERR_INVALID_ARG;
+    }
+    const uint64_t elems = out->layout == AACG_PCM_PLANAR ? (uint64_t)n_streams * p->C * out->stride_frames * 1024u : (uint64_t)n * 1024u * p->C;
+    const uint64_t need = elems * pcm_elem(p);
+    if ((uint64_t)out->d_pcm_bytes < need) { p->err = "aacg_pipeline_submit_device: d_pcm_bytes is smaller than the batch needs (" + std::to_string(need) + " bytes)"; return AACG_ERR_CAPACITY; }
+    if (out->layout == AACG_PCM_PLANAR && !aacg_planar_items(n_streams, out->stride_frames, (uint32_t)pcm_elem(p))) {
+        p->err = "aacg_pipeline_submit_device: n_streams x stride_frames is more than one aacg_pcm_planar launch addresses"; return AACG_ERR_CAPACITY;
     }
     return AACG_OK;
 }
@@ -468,17 +505,20 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     return AACG_OK;
 }
 
-int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
-                                const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
-                                void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
+/* One batch onto the next lane: aacg_pipeline_submit_ragged (pcm_out: host memory, dev null) and aacg_pipeline_submit_device (dev:
+ * the caller's device memory, pcm_out null) are this, and differ where the PCM goes and nowhere else. */
+static int submit_batch(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                        const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                        void* pcm_out, const aacg_pcm_device_out* dev, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
 {
-    if (!p || !bytes || !frames || !slots || !frames_of || !pcm_out || !n_streams || !ticket) return AACG_ERR_INVALID_ARG;
     if ((int)n_streams > p->cfg.max_streams) { p->err = "batch larger than the pipeline was created for"; return AACG_ERR_CAPACITY; }
     uint64_t total = 0;
+    uint32_t longest = 0;
     for (uint32_t s = 0; s < n_streams; s++) {
         if (!frames_of[s]) { p->err = "a stream of the batch brings no frame (frames_of[s] == 0)"; return AACG_ERR_INVALID_ARG; }
         if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "a stream brings more frames than max_frames"; return AACG_ERR_CAPACITY; }
         total += frames_of[s];
+        if (frames_of[s] > longest) longest = frames_of[s];
     }
     if (total > (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames) { p->err = "the batch's frames exceed max_streams x max_frames"; return AACG_ERR_CAPACITY; }
     const uint32_t n = (uint32_t)total, C = p->C, Cp = p->Cp, U = p->U;
@@ -490,10 +530,15 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     for (uint32_t i = 0; i < n; i++)
         if ((size_t)frames[i].byte_offset + frames[i].byte_length > n_bytes) { p->err = "a frame points outside the byte buffer"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    int rc = AACG_OK;
+    if (!pcm_out && (rc = check_device_out(p, dev, n, n_streams, longest))) return rc;
+    const bool planar = dev && dev->layout == AACG_PCM_PLANAR;
     aacg_pipeline::lane_t& L = p->lane[p->submitted % (uint64_t)p->n_lanes];
     const uint32_t set = (uint32_t)(p->submitted % (uint64_t)p->n_lanes);
-    int rc = finish_lane(p, L);                          /* the batch `lanes` submissions ago, if nobody has collected it */
+    rc = finish_lane(p, L);                              /* the batch `lanes` submissions ago, if nobody has collected it */
     if (rc) return rc;
+    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed — the caller's in its place */
+    void* const d_pcm = dev && !planar ? dev->d_pcm : L.d_pcm;
     if (p->learn && (rc = learn_layouts(p, bytes, n_bytes, frames, slots, n_streams, frames_of))) return rc;
     /* the batch's layouts as its plan lists them (a stream without one has no unit in the plan) */
     p->batch_layout.resize(n_streams);
@@ -541,7 +586,7 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     const size_t pcm_bytes = (size_t)n * C * 1024u * pcm_elem(p);
     /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
      * lane's own page-locked staging and one host copy at collect */
-    const bool direct = is_pinned(pcm_out);
+    const bool direct = dev || is_pinned(pcm_out);       /* (PCM left on the device: no staging either) */
     if (!direct && !L.h_pcm)
         P_TRY(p, hipHostMalloc(&L.h_pcm, (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * C * 1024u * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
     hipStream_t st = L.st;
@@ -550,7 +595,7 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     L.frames_of.assign(frames_of, frames_of + n_streams);
     L.first.resize(n_streams);
     for (uint32_t s = 0, i = 0; s < n_streams; i += frames_of[s], s++) L.first[s] = i;
-    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(L.d_pcm, 0, pcm_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
+    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(d_pcm, 0, pcm_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
     pipe_copy(L.h_in, L.d_bytes, up, st);                 /* aacg_pipe_copy: not the SDMA engines, where it would queue behind other lanes' PCM */
     if (L.count_stale) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* a submission that failed half-way left its count behind */
     L.count_stale = true;
@@ -587,8 +632,8 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
         if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, st);
-        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? n * Cp : 0u, L.d_pcm)
-                                              : aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_pcm);
+        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? n * Cp : 0u, d_pcm)
+                                              : aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, d_pcm);
         if (rc == AACG_OK) p->launches++;
         if (rc != AACG_ERR_STALE_PLAN || attempt || device_plans) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
         /* another shape's plan has advanced these streams since this one was used: plans are made from the engine's current state */
@@ -597,7 +642,15 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     }
     if (rc == AACG_OK && kp) rc = aacg_pipeline_join(p->engine, st);
     if (rc) { p->err = std::string("transform: ") + aacg_last_error(p->engine); return rc; }
-    {
+    if (planar) {
+        /* the caller's tensor from the lane's packed PCM and the per-stream table that came up with the bytes (either plan mode's
+         * record begins with frame_first and frames), padding included: where the copy down sits for a host batch */
+        aacg_planar_args A;
+        A.src = L.d_pcm; A.dst = dev->d_pcm; A.tab = (const char*)L.d_bytes + padded + table16;
+        A.tab_stride = (uint32_t)(device_plans ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
+        A.n_streams = n_streams; A.stride_frames = dev->stride_frames; A.channels = C; A.elem = (uint32_t)pcm_elem(p);
+        if (!aacg_planar_launch(A, st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+    } else if (!dev) {
         char* dst = (char*)(direct ? pcm_out : L.h_pcm);
         P_TRY(p, hipMemcpyAsync(dst, L.d_pcm, pcm_bytes, hipMemcpyDeviceToHost, st), AACG_ERR_NO_DEVICE);      /* one SDMA copy per batch (see aacg_pipe_copy) */
     }
@@ -607,9 +660,40 @@ int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
     pipe_copy(L.d_res, L.h_res, p->res_cap16 + 16, st, true);           /* ... and the count is cleared for the lane's next batch (set to zero at create) */
     P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
     P_TRY(p, hipEventRecord(L.done, st), AACG_ERR_NO_DEVICE);
-    L.busy = true; L.ticket = ++p->submitted; L.user_pcm = pcm_out; L.direct = direct; L.pcm_bytes = pcm_bytes;
+    L.busy = true; L.ticket = ++p->submitted; L.user_pcm = pcm_out; L.direct = direct; L.pcm_bytes = pcm_bytes; L.device_out = dev != nullptr;
     L.user_results = results; L.user_refused = n_refused; L.n = n;
     *ticket = L.ticket;
+    return AACG_OK;
+}
+
+int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
+{
+    if (!p || !bytes || !frames || !slots || !frames_of || !pcm_out || !n_streams || !ticket) return AACG_ERR_INVALID_ARG;
+    return submit_batch(p, bytes, n_bytes, frames, slots, n_streams, frames_of, pcm_out, nullptr, results, n_refused, ticket);
+}
+
+int aacg_pipeline_submit_device(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                const aacg_pcm_device_out* out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
+{
+    if (!p || !bytes || !frames || !slots || !frames_of || !n_streams || !ticket) return AACG_ERR_INVALID_ARG;
+    if (!out || !out->d_pcm) { p->err = "aacg_pipeline_submit_device: no device memory for the PCM (out or out->d_pcm is null)"; return AACG_ERR_INVALID_ARG; }
+    return submit_batch(p, bytes, n_bytes, frames, slots, n_streams, frames_of, nullptr, out, results, n_refused, ticket);
+}
+
+int aacg_pipeline_wait_device(aacg_pipeline* p, uint64_t ticket, void* hip_stream)
+{
+    if (!p || !ticket || ticket > p->submitted) { if (p) p->err = "aacg_pipeline_wait_device: no such ticket"; return AACG_ERR_INVALID_ARG; }
+    aacg_pipeline::lane_t& L = p->lane[(ticket - 1) % (uint64_t)p->n_lanes];
+    if (L.ticket != ticket || !L.busy) return AACG_OK;       /* collected, or a later batch has taken the lane and finished this one first */
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const hipError_t st = hipEventQuery(L.done);
+    if (st == hipSuccess) return AACG_OK;                   /* complete: nothing to wait for */
+    if (st != hipErrorNotReady) P_TRY(p, st, AACG_ERR_NO_DEVICE);
+    (void)hipGetLastError();
+    P_TRY(p, hipStreamWaitEvent((hipStream_t)hip_stream, L.done, 0), AACG_ERR_NO_DEVICE);
     return AACG_OK;
 }
 

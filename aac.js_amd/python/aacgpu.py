@@ -35,7 +35,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_plan_set_unit_sets", "aacg_plan_refresh_from_parse_ex", "aacg_tns_records_bytes", "aacg_tns_records_from_parse", "aacg_plan_create_stages", "aacg_decode_pipelined_stages", "aacg_parse_walk", "aacg_parse_walk_device",
                "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged",
                "aacg_plan_create_shaped", "aacg_plan_create_shaped_stages", "aacg_plan_shape_table", "aacg_plan_shape_launch",
-               "aacg_get_window_shape", "aacg_set_window_shape", "aacg_plan_carry_window_shape", "aacg_pipeline_stream_window_shape"]
+               "aacg_get_window_shape", "aacg_set_window_shape", "aacg_plan_carry_window_shape", "aacg_pipeline_stream_window_shape",
+               "aacg_pipeline_submit_device", "aacg_pipeline_wait_device"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -94,6 +95,15 @@ class PipelineConfig(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("device_ordinal", C.c_int32), ("sample_index", C.c_int32), ("max_streams", C.c_int32),
                 ("channels", C.c_int32), ("max_frames", C.c_int32), ("output_kind", C.c_int32), ("parse_options", C.c_int32),
                 ("lanes", C.c_int32), ("plan_mode", C.c_int32), ("stages", C.c_int32), ("reserved", C.c_int32 * 1)]
+
+
+# aacg_pcm_device_out: where aacg_pipeline_submit_device leaves a batch's PCM on the device
+PCM_PACKED, PCM_PLANAR = 0, 1                        # AACG_PCM_*: [frame][1024][channels] as the host call's / [stream][channel][stride_frames * 1024]
+AACG_PCM_PACKED, AACG_PCM_PLANAR = PCM_PACKED, PCM_PLANAR
+
+
+class PcmDeviceOut(C.Structure):
+    _fields_ = [("d_pcm", C.c_void_p), ("d_pcm_bytes", C.c_size_t), ("layout", C.c_int32), ("stride_frames", C.c_uint32)]
 
 
 # aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
@@ -248,6 +258,9 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_decode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.aacg_pipeline_submit_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_uint64)]
+    L.aacg_pipeline_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(PcmDeviceOut), C.c_void_p,
+                                              C.c_void_p, C.POINTER(C.c_uint64)]
+    L.aacg_pipeline_wait_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     L.aacg_pipeline_plan_builds.argtypes = [C.c_void_p]
     L.aacg_pipeline_plan_builds.restype = C.c_uint64
     L.aacg_pipeline_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -464,7 +477,7 @@ class Pipeline:
         if rc != 0:
             raise AacgError(rc, "aacg_pipeline_create failed (no GPU?%s)" % (" or no room for the device plan's buffers: see stderr" if device_plans else ""))
         self.device_plans = bool(device_plans)
-        self.handle, self.channels, self.i16 = h, channels, output_kind == OUTPUT_I16
+        self.handle, self.channels, self.i16, self.device = h, channels, output_kind == OUTPUT_I16, device
         self._keep = {}
 
     def close(self):
@@ -570,9 +583,79 @@ class Pipeline:
         return t.value
 
     def collect(self, ticket):
+        """(pcm, results, n_refused) of a submitted batch; for a submit_device ticket pcm is the `out` that was given"""
         self._check(self.lib.aacg_pipeline_collect(self.handle, ticket))
         pcm, res, refused = self._keep.pop(ticket)
         return pcm, res, int(refused.value)
+
+    @staticmethod
+    def _device_memory(out):
+        """(address, bytes) of `out`: anything with data_ptr() and nbytes or numel() * element_size() (a torch tensor), or the pair"""
+        if hasattr(out, "data_ptr"):
+            addr = out.data_ptr()
+            nbytes = out.nbytes if hasattr(out, "nbytes") else out.numel() * out.element_size()
+        else:
+            try:
+                addr, nbytes = out
+            except (TypeError, ValueError):
+                raise TypeError("submit_device: out is neither a tensor (data_ptr(), nbytes) nor an (address, nbytes) pair")
+        if not isinstance(addr, int) or isinstance(addr, bool) or addr <= 0 or int(nbytes) < 0:
+            raise ValueError("submit_device: out has no device address")
+        return addr, int(nbytes)
+
+    def submit_device(self, data, frames, slots, frames_per_stream, out, planar=False, stride_frames=None, layout=None):
+        """Asynchronous, the PCM left on the device (aacg_pipeline_submit_device): returns a ticket; collect(ticket) ->
+        (out, results, n_refused).  out: device memory of the pipeline's device, 16-byte aligned — a torch tensor, or an
+        (address, nbytes) pair.  Packed (the default): [frame][1024][channels] as submit's PCM.  planar: [stream][channel]
+        [stride_frames * 1024], zeros behind a stream's samples; stride_frames defaults to the largest count.  frames_per_stream:
+        a scalar or per-stream counts, as for submit.  The batch writes out on a stream of the pipeline's, ordered behind nothing of
+        the caller's: work already queued that reads or writes out's memory (torch's allocator hands a block freed on a stream out
+        again while that stream's kernels on it are still queued) must have completed when this is called — synchronise that stream
+        first, as decode_tensor does.  From then on out must stay untouched until collect, or until the stream given to wait_device
+        has passed the wait.  layout: an AACG_PCM_* code given as such, in the place of planar."""
+        addr, nbytes = self._device_memory(out)             # (before the library is called: an `out` without an address never reaches it)
+        data = np.ascontiguousarray(data, np.uint8)
+        frames = np.ascontiguousarray(frames)
+        slots = np.ascontiguousarray(slots, np.uint32)
+        counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
+        assert len(counts) == len(slots) and frames.dtype == PARSE_FRAME_DTYPE and len(frames) == int(counts.sum())
+        if planar and stride_frames is None:
+            stride_frames = int(counts.max()) if len(counts) else 0
+        desc = PcmDeviceOut(addr, nbytes, (PCM_PLANAR if planar else PCM_PACKED) if layout is None else int(layout), int(stride_frames or 0))
+        res, refused, t = np.zeros(len(frames), PARSE_RESULT_DTYPE), C.c_uint32(0), C.c_uint64()
+        self._check(self.lib.aacg_pipeline_submit_device(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
+                                                         counts.ctypes.data, C.byref(desc), res.ctypes.data, C.byref(refused), C.byref(t)))
+        self._keep[t.value] = (out, res, refused)
+        return t.value
+
+    def wait_device(self, ticket, stream=None):
+        """Puts a HIP stream behind the ticket's batch without the host waiting (aacg_pipeline_wait_device): what is queued on it
+        afterwards sees the batch's PCM.  stream: a hipStream_t as an integer, or anything with .cuda_stream (a torch stream);
+        None: torch's current stream on the pipeline's device when torch is imported, else the null stream."""
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream(self.device).cuda_stream if torch is not None and torch.cuda.is_available() else 0
+        stream = getattr(stream, "cuda_stream", stream)
+        self._check(self.lib.aacg_pipeline_wait_device(self.handle, ticket, C.c_void_p(int(stream) or None)))
+
+    def decode_tensor(self, data, frames, slots, frames_per_stream, planar=True):
+        """One batch into a new torch tensor on the pipeline's device -> (tensor, lengths, results, n_refused).  planar:
+        (B, C, max count * 1024) with lengths[s] = count * 1024 samples of stream s and zeros behind them; packed: (n, 1024, C),
+        the n frames stream after stream.  The tensor is torch's current stream's: that stream is synchronised before the batch is
+        submitted, because the allocator may hand out a block whose previous user's kernels are still queued there and the lane's
+        stream would write under them (or a late fill land in the PCM); afterwards the stream is put behind the batch, so work queued
+        on it sees the PCM, and the host has waited for the results only."""
+        import torch
+        slots = np.ascontiguousarray(slots, np.uint32)
+        counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
+        shape = (len(slots), self.channels, int(counts.max()) * 1024) if planar else (int(counts.sum()), 1024, self.channels)
+        out = torch.empty(shape, dtype=torch.int16 if self.i16 else torch.float32, device="cuda:%d" % self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # nothing of the block's previous life is still queued when the lane writes it
+        t = self.submit_device(data, frames, slots, counts, out, planar=bool(planar))
+        self.wait_device(t)
+        out, res, refused = self.collect(t)
+        return out, counts.astype(np.int64) * 1024, res, refused
 
 
 class Plan:

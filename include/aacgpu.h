@@ -783,6 +783,42 @@ int  aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t 
 int  aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
                                  const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
                                  void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket);
+/* PCM left on the device: aacg_pipeline_submit_ragged in every respect — bytes, frames, slots, counts, results, the refusal count,
+ * tickets, lanes, both plan modes, every `stages` bit, both output kinds (the element is float, or int16 for AACG_OUTPUT_I16
+ * pipelines) — except where the PCM goes: into device memory of the caller's, for a consumer that computes on the card it decodes
+ * on.  Nothing of the PCM crosses the link and no host PCM staging is allocated or touched for such a batch; results and the
+ * refusal count still come down, and aacg_pipeline_collect serves these tickets too: the PCM is complete in d_pcm when it returns.
+ *   AACG_PCM_PACKED: d_pcm is what the transform is launched with, in the place of the lane's own buffer — no extra pass, no extra
+ *     traffic.  The batch needs n x 1024 x channels elements, n the sum of the counts.
+ *   AACG_PCM_PLANAR: the transform writes the lane's buffer as ever and one more launch on the lane's stream (aacg_pcm_planar_*)
+ *     writes the caller's tensor, padding included: every element of the n_streams x channels x stride_frames x 1024 block, once.
+ * The batch writes d_pcm on a stream of the pipeline's own, ordered behind nothing of the caller's: whatever the caller has queued
+ * that reads or writes d_pcm — a consumer of the memory's previous contents, a fill, a stream-ordered allocator that has just handed
+ * the block out again — must have COMPLETED when this call is made (synchronise that stream, or an event of it, first).  From
+ * then on d_pcm must stay valid, and unwritten by the caller, until aacg_pipeline_collect(ticket) has returned or the stream given
+ * to aacg_pipeline_wait_device has passed the wait (a batch's predecessor may write the batch's first frames before the batch's
+ * own launch starts).  Bytes of d_pcm behind what the batch needs are never written.
+ * Refused before anything is enqueued, with no ticket taken and the reason in aacg_pipeline_last_error — AACG_ERR_INVALID_ARG: a null
+ * `out` or d_pcm; a d_pcm that is not 16-byte aligned; a d_pcm that is not device memory of the pipeline's device (pageable or
+ * page-locked host memory, another device's memory); a layout that is not one of the two; AACG_PCM_PLANAR with stride_frames below the
+ * largest count; AACG_PCM_PACKED with stride_frames != 0.  AACG_ERR_CAPACITY: d_pcm_bytes smaller than the batch needs.  And whatever aacg_pipeline_submit_ragged refuses. */
+#define AACG_PCM_PACKED 0   /* the host call's layout: [first_s + f][1024][channels], streams packed one behind the other */
+#define AACG_PCM_PLANAR 1   /* [stream s][channel c][stride_frames * 1024]: stream s's frames_of[s] * 1024 samples of channel c,
+                               then zeros up to the row's end — a (B, C, T) tensor with its padding written */
+typedef struct aacg_pcm_device_out {
+    void*    d_pcm;          /* device memory on the pipeline's device, 16-byte aligned */
+    size_t   d_pcm_bytes;    /* what the caller owns there: the call refuses a batch that does not fit */
+    int32_t  layout;         /* AACG_PCM_* */
+    uint32_t stride_frames;  /* PLANAR: frames per row, >= every frames_of[s]; PACKED: 0 */
+} aacg_pcm_device_out;
+int  aacg_pipeline_submit_device(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
+                                 const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
+                                 const aacg_pcm_device_out* out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket);
+/* Puts hip_stream (a hipStream_t of the pipeline's device; NULL: the null stream) behind the ticket's batch: hipStreamWaitEvent on
+ * the lane's completion event, the host does not wait — a consumer queues its own kernels on the PCM while further batches are
+ * submitted.  A ticket that is already complete or collected: AACG_OK with nothing enqueued; a ticket never given out:
+ * AACG_ERR_INVALID_ARG.  The results and the refusal count are the host's only after aacg_pipeline_collect. */
+int  aacg_pipeline_wait_device(aacg_pipeline* p, uint64_t ticket, void* hip_stream);
 int  aacg_pipeline_set_wait_limit_ms(aacg_pipeline* p, uint32_t ms);
 /* Span walks on the pipeline's device (aacg_parse_walk's semantics and outputs, the pipeline's parse_options): where the blocks of
  * MP4 sample runs lie, ahead of the batches that decode them.  aacg_pipeline_walk_submit stages the bytes (they may be reused when

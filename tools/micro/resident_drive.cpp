@@ -6,7 +6,14 @@
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
- *                                         [--carry-shape]
+ *                                         [--carry-shape] [--device-pcm [--planar]]
+ *
+ * --device-pcm: the PCM left on the device (aacg_pipeline_submit_device, AACG_PCM_PACKED: the transform writes the caller's buffer);
+ * with --planar AACG_PCM_PLANAR, stride_frames = F (one more launch per batch, aacg_pcm_planar).  One device buffer per lane; nothing
+ * of the PCM is read back inside the timed region (one buffer comes down after it, for output_ok).  Combines with --i16, --lanes,
+ * --sync, --device-plans and --new-shapes.  The line then also carries what a device-to-device copy of the batch's PCM bytes takes
+ * on this box in this run (aacg_calib_copy, 20 launches between two events): what aacg_pcm_planar's time in a kernel trace is read
+ * against.
  *
  * --tns-spec / --pns-spec: aacg_pipeline_config.stages (the spec-correct TNS filters / noise bands; the TNS records are made on the
  * device, every launch is aacg_imdct_run_quant_ex_rv).  --pulses: AACG_PARSE_APPLY_PULSES (streams with pulse data).
@@ -30,6 +37,8 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../../include/aacgpu.h"
 #include "../../include/aacgpu_tools.h"
 
@@ -40,7 +49,7 @@ int main(int argc, char** argv)
     if (argc < 2) { std::fprintf(stderr, "usage: resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]\n"); return 2; }
     uint32_t S = 256, F = 16;
     int batches = 200, lanes = 3;
-    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false;
+    bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
@@ -58,9 +67,12 @@ int main(int argc, char** argv)
         else if (a == "--pns-spec") pns_spec = true;
         else if (a == "--pulses") pulses = true;
         else if (a == "--carry-shape") carry_shape = true;
+        else if (a == "--device-pcm") device_pcm = true;
+        else if (a == "--planar") planar = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
+    if (planar && !device_pcm) { std::fprintf(stderr, "--planar goes with --device-pcm\n"); return 2; }
     std::vector<uint8_t> file;
     if (FILE* f = std::fopen(argv[1], "rb")) { uint8_t buf[65536]; size_t k; while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + k); std::fclose(f); }
     std::vector<aacg_parse_frame> src;
@@ -101,11 +113,16 @@ int main(int argc, char** argv)
     const int n_out = 4;
     void* out[n_out];
     for (auto& o : out) { o = pageable ? std::malloc(pcm_bytes) : aacg_host_alloc(pcm_bytes); if (!o) { std::fprintf(stderr, "allocation failed\n"); return 2; } std::memset(o, 0, pcm_bytes); }
+    /* --device-pcm: a device buffer per lane (a batch in flight keeps its own until it is collected); planar rows of F frames */
+    const int n_dev = device_pcm ? (sync ? 1 : lanes) : 0;
+    std::vector<void*> dev((size_t)n_dev, nullptr);
+    for (auto& d : dev) if (hipMalloc(&d, pcm_bytes) != hipSuccess || hipMemset(d, 0, pcm_bytes) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); return 2; }
+    if (n_dev && hipDeviceSynchronize() != hipSuccess) { std::fprintf(stderr, "hipDeviceSynchronize failed\n"); return 2; }
     std::vector<aacg_parse_result> results((size_t)S * F * n_out);
     uint32_t refused[n_out] = {};
     auto fail = [&](const char* what, int code) { std::fprintf(stderr, "%s: %d %s\n", what, code, aacg_pipeline_last_error(p)); std::exit(2); };
     /* --new-shapes: the batch's counts (1..F per stream, a new draw per batch) and its frame table, packed stream after stream */
-    std::vector<uint32_t> counts_of(S);
+    std::vector<uint32_t> counts_of(S), rect_counts;
     std::vector<aacg_parse_frame> ragged((size_t)S * F);
     uint64_t lcg = seed * 0x9E3779B97F4A7C15ull + 1;
     double submit_s = 0;
@@ -116,6 +133,8 @@ int main(int argc, char** argv)
         for (int b = 0; b < n + depth; b++) {
             if (b < n) {
                 const int k = b % n_out;
+                aacg_pcm_device_out where;
+                if (device_pcm) { where.d_pcm = dev[(size_t)(b % n_dev)]; where.d_pcm_bytes = pcm_bytes; where.layout = planar ? AACG_PCM_PLANAR : AACG_PCM_PACKED; where.stride_frames = planar ? F : 0u; }
                 if (new_shapes) {
                     size_t at = 0;
                     for (uint32_t s = 0; s < S; s++) {
@@ -125,10 +144,19 @@ int main(int argc, char** argv)
                         at += counts_of[s];
                     }
                     const double t0 = now_s();
-                    if (sync) { if ((rc = aacg_pipeline_decode_ragged(p, bytes.data(), bytes.size(), ragged.data(), slots.data(), S, counts_of.data(), out[k], &results[(size_t)k * S * F], &refused[k]))) fail("aacg_pipeline_decode_ragged", rc); }
+                    if (device_pcm) {
+                        if ((rc = aacg_pipeline_submit_device(p, bytes.data(), bytes.size(), ragged.data(), slots.data(), S, counts_of.data(), &where, &results[(size_t)k * S * F], &refused[k], &t[(size_t)b]))) fail("aacg_pipeline_submit_device", rc);
+                        if (sync && (rc = aacg_pipeline_collect(p, t[(size_t)b]))) fail("aacg_pipeline_collect", rc);
+                    }
+                    else if (sync) { if ((rc = aacg_pipeline_decode_ragged(p, bytes.data(), bytes.size(), ragged.data(), slots.data(), S, counts_of.data(), out[k], &results[(size_t)k * S * F], &refused[k]))) fail("aacg_pipeline_decode_ragged", rc); }
                     else if ((rc = aacg_pipeline_submit_ragged(p, bytes.data(), bytes.size(), ragged.data(), slots.data(), S, counts_of.data(), out[k], &results[(size_t)k * S * F], &refused[k], &t[(size_t)b]))) fail("aacg_pipeline_submit_ragged", rc);
                     submit_s += now_s() - t0;
                     fed += at;
+                }
+                else if (device_pcm) {
+                    rect_counts.assign(S, F);
+                    if ((rc = aacg_pipeline_submit_device(p, bytes.data(), bytes.size(), frames.data(), slots.data(), S, rect_counts.data(), &where, &results[(size_t)k * S * F], &refused[k], &t[(size_t)b]))) fail("aacg_pipeline_submit_device", rc);
+                    if (sync && (rc = aacg_pipeline_collect(p, t[(size_t)b]))) fail("aacg_pipeline_collect", rc);
                 }
                 else if (sync) { if ((rc = aacg_pipeline_decode(p, bytes.data(), bytes.size(), frames.data(), slots.data(), S, F, out[k], &results[(size_t)k * S * F], &refused[k]))) fail("aacg_pipeline_decode", rc); }
                 else if ((rc = aacg_pipeline_submit(p, bytes.data(), bytes.size(), frames.data(), slots.data(), S, F, out[k], &results[(size_t)k * S * F], &refused[k], &t[(size_t)b]))) fail("aacg_pipeline_submit", rc);
@@ -144,19 +172,40 @@ int main(int argc, char** argv)
     uint64_t shaped = 0, chained = 0, launches = 0;
     (void)aacg_pipeline_launch_counts(p, &shaped, &chained, &launches);
     std::sort(ms.begin(), ms.end());
+    /* --device-pcm: what a device-to-device copy of a batch's PCM bytes takes here and now, and — outside the timed region — the last
+     * warm buffer down for the output check (planar rows are as long as the packed frames of a stream when every stream brings F) */
+    double copy_us = 0;
+    if (device_pcm) {
+        void* spare = nullptr;
+        hipEvent_t e0, e1;
+        float span = 0;
+        if (hipMalloc(&spare, pcm_bytes) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); return 2; }
+        (void)aacg_calib_copy(spare, dev[0], pcm_bytes, nullptr);
+        (void)hipEventRecord(e0, nullptr);
+        for (int i = 0; i < 20; i++) (void)aacg_calib_copy(spare, dev[0], pcm_bytes, nullptr);
+        (void)hipEventRecord(e1, nullptr);
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&span, e0, e1) != hipSuccess) { std::fprintf(stderr, "the calibration copy failed\n"); return 2; }
+        copy_us = span * 1e3 / 20.0;
+        if (hipMemcpy(out[0], dev[0], pcm_bytes, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 2; }
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(spare);
+    }
     bool finite = true, nonzero = false;
     uint32_t bad = 0;
     for (int k = 0; k < n_out; k++) bad += refused[k];
     if (!i16) { const float* w = (const float*)out[0]; for (size_t i = 0; i < pcm_bytes / 4; i += 97) { finite = finite && std::isfinite(w[i]); nonzero = nonzero || w[i] != 0.0f; } }
     else { const int16_t* w = (const int16_t*)out[0]; for (size_t i = 0; i < pcm_bytes / 2; i += 97) nonzero = nonzero || w[i] != 0; }
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", "
+    char copy_key[64] = "";                                 /* only where it was measured: the host-PCM modes' lines are as they were */
+    if (device_pcm) std::snprintf(copy_key, sizeof copy_key, "\"d2d_copy_of_pcm_us\": %.2f, ", copy_us);
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
-                sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                pageable ? "pageable" : "page-locked", bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
+                           : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
+    for (void* d : dev) (void)hipFree(d);
     return (finite && nonzero && !bad) ? 0 : 1;
 }
