@@ -123,6 +123,9 @@ void aacg_parse_prepare(const aacg_clear_regions C, const aacg_parse_frame* fram
     }
 }
 
+/* the device buffers, grown on demand: the host round trips' (aacg_parse_batch's seven, aacg_parse_walk's four) and the lane order */
+enum { B_BYTES, B_FRAMES, B_UNITS, B_Q, B_META, B_TNS, B_RESULTS, W_BYTES, W_SPANS, W_BLOCKS, W_RESULTS, ORDER, N_BUF };
+
 struct aacg_parser {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -130,13 +133,10 @@ struct aacg_parser {
     size_t lds_bytes = 0;
     uint32_t lut_words = 0;
     int n_cus = 256;
-    /* device staging of aacg_parse_batch, grown on demand */
-    uint32_t* d_order = nullptr;      /* lane order + the bucket counters behind it */
-    size_t order_cap = 0;
-    hipEvent_t order_free = nullptr;  /* recorded behind every launch: the scratch above may be rewritten after it */
+    void* d_buf[N_BUF] = {};          /* (ORDER: the lane order + the bucket counters behind it) */
+    size_t cap[N_BUF] = {};
+    hipEvent_t order_free = nullptr;  /* recorded behind every launch: the lane-order scratch may be rewritten after it */
     hipStream_t last_stream = nullptr;
-    void* d_buf[11] = {};             /* 0..6 aacg_parse_batch's, 7..10 aacg_parse_walk's (bytes, spans, blocks, results) */
-    size_t cap[11] = {};
     aacg_wait_policy wait;            /* aacg_parse_batch's host waits are bounded (aacg_wait.h): AACG_ERR_TIMEOUT */
     std::string err;
 };
@@ -157,6 +157,60 @@ int grow(aacg_parser* p, int i, size_t bytes)
     return AACG_OK;
 }
 
+/* The lane order and the clearing in front of a parse or walk kernel on stream s: P.order is set (sorted: the parser's scratch,
+ * grown here; otherwise null: table order), the regions that have an address are zeroed.  One launch (aacg_parse_prepare) when
+ * every region is a multiple of 16 bytes at a multiple of 16 and there are at most AACG_PARSE_PREPARE_MAX frames, else memsets and
+ * the three sorting kernels.  grid x P.wg_threads are the lanes of the kernel that follows. */
+struct region { void* at; size_t bytes; };
+int order_and_clear(aacg_parser* p, aacg_parse_params& P, bool sorted, unsigned grid, const region* regions, int n_regions, hipStream_t s)
+{
+    const size_t lanes = (size_t)grid * P.wg_threads;
+    int rc = sorted ? grow(p, ORDER, (lanes + AACG_PARSE_BUCKETS) * sizeof(uint32_t)) : AACG_OK;
+    if (rc) return rc;
+    /* The lane-order scratch belongs to the parser, not to the launch: a launch on another stream first waits for the
+     * previous launch's kernels (same stream: ordered anyway).  Two streams may therefore alternate on one parser. */
+    if (p->last_stream && p->last_stream != s) HIPCHECK(hipStreamWaitEvent(s, p->order_free, 0));
+    uint32_t* const order = sorted ? (uint32_t*)p->d_buf[ORDER] : nullptr;
+    P.order = order;
+    bool fused = P.n_frames <= AACG_PARSE_PREPARE_MAX;
+    aacg_clear_regions C = {};
+    size_t total16 = 0;
+    for (int i = 0; i < n_regions; i++) {
+        const region& r = regions[i];
+        if (!r.at) continue;
+        if (((uintptr_t)r.at | r.bytes) & 15u) fused = false;
+        C.at[i] = r.at; C.n16[i] = r.bytes / 16u; total16 += r.bytes / 16u;
+    }
+    if (fused) {                                         /* one launch in front of the kernel (aacg_parse_prepare) */
+        /* clearing blocks: four 16-byte stores per thread, 512 at the most, and 0 when there is nothing to clear (the walk): its
+         * prepare launch is the sorting block alone, and with nothing to sort either there is no launch */
+        const size_t clearing = (total16 + 4095u) / 4096u;
+        const unsigned blocks = (unsigned)(clearing > 512u ? 512u : clearing) + (sorted ? 1u : 0u);
+        if (blocks) hipLaunchKernelGGL(aacg_parse_prepare, dim3(blocks), dim3(1024), 0, s, C, P.frames, P.n_frames, order, (uint32_t)lanes, grid, P.wg_threads / 64u);
+        return AACG_OK;
+    }
+    for (int i = 0; i < n_regions; i++) if (regions[i].at) HIPCHECK(hipMemsetAsync(regions[i].at, 0, regions[i].bytes, s));
+    if (sorted) {
+        uint32_t* hist = order + lanes;
+        const unsigned blocks = (P.n_frames + 255u) / 256u;
+        HIPCHECK(hipMemsetAsync(order, 0xff, lanes * sizeof(uint32_t), s));
+        HIPCHECK(hipMemsetAsync(hist, 0, AACG_PARSE_BUCKETS * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(aacg_parse_order_count, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist);
+        hipLaunchKernelGGL(aacg_parse_order_scan, dim3(1), dim3(AACG_PARSE_BUCKETS), 0, s, hist);
+        hipLaunchKernelGGL(aacg_parse_order_fill, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist, order, grid, P.wg_threads / 64u);
+    }
+    return AACG_OK;
+}
+
+/* behind the kernel that reads the lane order: the scratch may be rewritten after order_free */
+int launched(aacg_parser* p, hipStream_t s)
+{
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(p->order_free, s));
+    p->last_stream = s;
+    return AACG_OK;
+}
+
 int launch(aacg_parser* p, aacg_parse_params& P, hipStream_t s)
 {
     /* up to one small workgroup per CU: stage the frames in LDS; beyond that the rate matters more than the time per
@@ -170,93 +224,32 @@ int launch(aacg_parser* p, aacg_parse_params& P, hipStream_t s)
     /* Frames of similar length into the same wave, and long and short waves onto every CU alike (AACG_PARSE_SORT=0: table
      * order).  Measured with frame lengths spread 44..1186 bytes: 16 k frames 1.40 -> 0.89 ms, 64 k 1.36 -> 0.94. */
     static const bool sort_enabled = [] { const char* v = std::getenv("AACG_PARSE_SORT"); return !(v && v[0] == '0'); }();
-    const bool sorted = sort_enabled && P.n_frames > 64u;
-    const size_t lanes = (size_t)grid * P.wg_threads;
-    if (sorted) {
-        const size_t need = lanes + AACG_PARSE_BUCKETS;
-        if (need > p->order_cap) {
-            if (p->d_order) (void)hipFree(p->d_order);
-            p->d_order = nullptr; p->order_cap = 0;
-            if (hipMalloc((void**)&p->d_order, need * sizeof(uint32_t)) != hipSuccess) return fail(p, AACG_ERR_OUT_OF_MEMORY, "hipMalloc failed");
-            p->order_cap = need;
-        }
-    }
     /* what the parser promises zeroed: the spectra (positions outside the coded bands), the band words (only the coded ones are
      * written), TNS records, and the unit records of refused frames and of element slots beyond a frame's count (never stale memory) */
-    struct region { void* at; size_t bytes; };
     const region regions[4] = {
         { (P.options & AACG_PARSE_SKIP_ZERO_FILL) ? nullptr : (void*)P.q, (size_t)P.n_frames * P.max_channels * 1024u * sizeof(int16_t) },
         { (void*)P.meta, (size_t)P.n_frames * P.max_channels * sizeof(aacg_band_meta) },
         { (void*)P.tns, (size_t)P.n_frames * P.max_channels * sizeof(aacg_tns_info) },
         { (void*)P.units, (size_t)P.n_frames * P.max_units * sizeof(aacg_unit_desc) } };
-    /* The lane-order scratch belongs to the parser, not to the launch: a launch on another stream first waits for the
-     * previous launch's kernels (same stream: ordered anyway).  Two streams may therefore alternate on one parser. */
-    if (p->last_stream && p->last_stream != s) HIPCHECK(hipStreamWaitEvent(s, p->order_free, 0));
-    P.order = sorted ? p->d_order : nullptr;
-    bool fused = P.n_frames <= AACG_PARSE_PREPARE_MAX;
-    for (const region& r : regions) if (r.at && (((uintptr_t)r.at | r.bytes) & 15u)) fused = false;
-    if (fused) {                                         /* one launch in front of the parse kernel (aacg_parse_prepare) */
-        aacg_clear_regions C;
-        size_t total16 = 0;
-        for (int i = 0; i < 4; i++) { C.at[i] = regions[i].at; C.n16[i] = regions[i].at ? regions[i].bytes / 16u : 0u; total16 += (size_t)C.n16[i]; }
-        unsigned blocks = (unsigned)((total16 + 4095u) / 4096u);                    /* four 16-byte stores per thread */
-        blocks = (blocks < 1u ? 1u : blocks > 512u ? 512u : blocks) + (sorted ? 1u : 0u);
-        hipLaunchKernelGGL(aacg_parse_prepare, dim3(blocks), dim3(1024), 0, s, C, P.frames, P.n_frames, sorted ? p->d_order : nullptr, (uint32_t)lanes, grid, P.wg_threads / 64u);
-    } else {
-        for (const region& r : regions) if (r.at) HIPCHECK(hipMemsetAsync(r.at, 0, r.bytes, s));
-        if (sorted) {
-            uint32_t* hist = p->d_order + lanes;
-            const unsigned blocks = (P.n_frames + 255u) / 256u;
-            HIPCHECK(hipMemsetAsync(p->d_order, 0xff, lanes * sizeof(uint32_t), s));
-            HIPCHECK(hipMemsetAsync(hist, 0, AACG_PARSE_BUCKETS * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(aacg_parse_order_count, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist);
-            hipLaunchKernelGGL(aacg_parse_order_scan, dim3(1), dim3(AACG_PARSE_BUCKETS), 0, s, hist);
-            hipLaunchKernelGGL(aacg_parse_order_fill, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist, p->d_order, grid, P.wg_threads / 64u);
-        }
-    }
+    int rc = order_and_clear(p, P, sort_enabled && P.n_frames > 64u, grid, regions, 4, s);
+    if (rc) return rc;
     hipLaunchKernelGGL(aacg_parse_frames, dim3(grid), dim3(P.wg_threads), p->lds_bytes, s, P);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(p->order_free, s));
-    p->last_stream = s;
-    return AACG_OK;
+    return launched(p, s);
 }
 
 /* The walk: spans sorted by length, longest first (aacg_parse_prepare with nothing to clear, or the three sorting kernels for
- * very many spans), then one lane per span.  Spans of 8 KiB and more share the longest bucket. */
+ * very many spans), then one lane per span.  Spans of 8 KiB and more share the longest bucket.  AACG_PARSE_SORT is the frame
+ * parse's switch, not the walk's. */
 int walk_launch(aacg_parser* p, aacg_walk_params& W, hipStream_t s)
 {
     aacg_parse_params& P = W.P;
     P.wg_threads = AACG_WALK_WG;
     P.arena_bytes = 0;
     const unsigned grid = (P.n_frames + AACG_WALK_WG - 1) / AACG_WALK_WG;
-    const size_t lanes = (size_t)grid * AACG_WALK_WG;
-    const bool sorted = P.n_frames > 64u;
-    if (sorted && lanes + AACG_PARSE_BUCKETS > p->order_cap) {
-        if (p->d_order) (void)hipFree(p->d_order);
-        p->d_order = nullptr; p->order_cap = 0;
-        if (hipMalloc((void**)&p->d_order, (lanes + AACG_PARSE_BUCKETS) * sizeof(uint32_t)) != hipSuccess) return fail(p, AACG_ERR_OUT_OF_MEMORY, "hipMalloc failed");
-        p->order_cap = lanes + AACG_PARSE_BUCKETS;
-    }
-    if (p->last_stream && p->last_stream != s) HIPCHECK(hipStreamWaitEvent(s, p->order_free, 0));
-    P.order = sorted ? p->d_order : nullptr;
-    if (sorted && P.n_frames <= AACG_PARSE_PREPARE_MAX) {
-        aacg_clear_regions C;
-        for (int i = 0; i < 4; i++) { C.at[i] = nullptr; C.n16[i] = 0; }
-        hipLaunchKernelGGL(aacg_parse_prepare, dim3(1), dim3(1024), 0, s, C, P.frames, P.n_frames, p->d_order, (uint32_t)lanes, grid, 1u);
-    } else if (sorted) {
-        uint32_t* hist = p->d_order + lanes;
-        const unsigned blocks = (P.n_frames + 255u) / 256u;
-        HIPCHECK(hipMemsetAsync(p->d_order, 0xff, lanes * sizeof(uint32_t), s));
-        HIPCHECK(hipMemsetAsync(hist, 0, AACG_PARSE_BUCKETS * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(aacg_parse_order_count, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist);
-        hipLaunchKernelGGL(aacg_parse_order_scan, dim3(1), dim3(AACG_PARSE_BUCKETS), 0, s, hist);
-        hipLaunchKernelGGL(aacg_parse_order_fill, dim3(blocks), dim3(256), 0, s, P.frames, P.n_frames, hist, p->d_order, grid, 1u);
-    }
+    int rc = order_and_clear(p, P, P.n_frames > 64u, grid, nullptr, 0, s);
+    if (rc) return rc;
     hipLaunchKernelGGL(aacg_parse_walk_spans, dim3(grid), dim3(AACG_WALK_WG), AACG_PARSE_LDS_FIXED(p->lut_words, AACG_WALK_WG), s, W);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(p->order_free, s));
-    p->last_stream = s;
-    return AACG_OK;
+    return launched(p, s);
 }
 
 void walk_params(aacg_parser* p, aacg_walk_params& W, const void* d_bytes, const aacg_parse_frame* d_spans, uint32_t n_spans,
@@ -266,6 +259,35 @@ void walk_params(aacg_parser* p, aacg_walk_params& W, const void* d_bytes, const
     W.P.bytes = (const uint32_t*)d_bytes; W.P.frames = d_spans; W.P.tab = p->d_tab; W.P.n_frames = n_spans;
     W.P.options = options & ~AACG_PARSE_SKIP_ZERO_FILL;
     W.blocks = d_frames; W.results = d_results; W.max_frames = max_frames;
+}
+
+/* The host round trips (aacg_parse_batch, aacg_parse_walk) on the parser's own stream.  Up: the bytes with AACG_PARSE_PAD_BYTES
+ * readable zeros behind them, and the frame or span table. */
+size_t padded_bytes(size_t n_bytes) { return (n_bytes + 15u) / 16u * 16u + AACG_PARSE_PAD_BYTES; }
+int upload(aacg_parser* p, int b_bytes, const uint8_t* bytes, size_t n_bytes, int b_table, const aacg_parse_frame* table, uint32_t n)
+{
+    hipStream_t s = p->stream;
+    const size_t padded = padded_bytes(n_bytes);
+    const size_t tail = padded < AACG_PARSE_PAD_BYTES + 16u ? padded : AACG_PARSE_PAD_BYTES + 16u;      /* zeros behind the last byte */
+    HIPCHECK(hipMemsetAsync((char*)p->d_buf[b_bytes] + padded - tail, 0, tail, s));
+    HIPCHECK(hipMemcpyAsync(p->d_buf[b_bytes], bytes, n_bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(p->d_buf[b_table], table, n * sizeof(aacg_parse_frame), hipMemcpyHostToDevice, s));
+    return AACG_OK;
+}
+/* the bounded wait for the parser's stream: AACG_ERR_TIMEOUT says what did not complete */
+int wait_for(aacg_parser* p, const char* entry, const char* what)
+{
+    const hipError_t st = aacg_wait_stream(p->stream, p->wait);
+    if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, std::string(entry) + ": the " + what + " did not complete within the wait limit");
+    HIPCHECK(st);
+    return AACG_OK;
+}
+/* Down, behind the bounded wait for the kernel: the copies into the caller's (pageable) memory wait inside the runtime, and a
+ * device that has just answered will carry them out.  Buffer first + i goes to to[i]; null: not an output, or one not asked for. */
+int download(aacg_parser* p, const char* entry, int first, void* const* to, const size_t* sizes, int n)
+{
+    for (int i = 0; i < n; i++) if (to[i]) HIPCHECK(hipMemcpyAsync(to[i], p->d_buf[first + i], sizes[i], hipMemcpyDeviceToHost, p->stream));
+    return wait_for(p, entry, "copies back");
 }
 
 }  // namespace
@@ -328,8 +350,7 @@ void aacg_parser_destroy(aacg_parser* p)
     }
     (void)hipGetLastError();
     if (p->order_free) (void)hipEventDestroy(p->order_free);
-    if (p->d_order) (void)hipFree(p->d_order);
-    for (int i = 0; i < 11; i++) if (p->d_buf[i]) (void)hipFree(p->d_buf[i]);
+    for (int i = 0; i < N_BUF; i++) if (p->d_buf[i]) (void)hipFree(p->d_buf[i]);
     if (p->d_tab) (void)hipFree(p->d_tab);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
@@ -362,37 +383,23 @@ int aacg_parse_batch(aacg_parser* p, const uint8_t* bytes, size_t n_bytes, const
     for (uint32_t f = 0; f < n_frames; f++)
         if ((size_t)frames[f].byte_offset + frames[f].byte_length > n_bytes) return fail(p, AACG_ERR_INVALID_ARG, "frame " + std::to_string(f) + " lies outside the byte buffer");
     HIPCHECK(hipSetDevice(p->device));
-    const size_t padded = (n_bytes + 15u) / 16u * 16u + AACG_PARSE_PAD_BYTES, blocks = (size_t)n_frames * max_channels;
-    const size_t sizes[7] = { padded, n_frames * sizeof(aacg_parse_frame), (size_t)n_frames * max_units * sizeof(aacg_unit_desc),
+    const size_t blocks = (size_t)n_frames * max_channels;
+    const size_t sizes[7] = { padded_bytes(n_bytes), n_frames * sizeof(aacg_parse_frame), (size_t)n_frames * max_units * sizeof(aacg_unit_desc),
                               blocks * 1024u * sizeof(int16_t), blocks * sizeof(aacg_band_meta), tns ? blocks * sizeof(aacg_tns_info) : 0,
                               n_frames * sizeof(aacg_parse_result) };
-    for (int i = 0; i < 7; i++) { int rc = sizes[i] ? grow(p, i, sizes[i]) : AACG_OK; if (rc) return rc; }
-    hipStream_t s = p->stream;
-    const size_t tail = padded < AACG_PARSE_PAD_BYTES + 16u ? padded : AACG_PARSE_PAD_BYTES + 16u;      /* zeros behind the last byte */
-    HIPCHECK(hipMemsetAsync((char*)p->d_buf[0] + padded - tail, 0, tail, s));
-    HIPCHECK(hipMemcpyAsync(p->d_buf[0], bytes, n_bytes, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(p->d_buf[1], frames, sizes[1], hipMemcpyHostToDevice, s));
+    int rc = AACG_OK;
+    for (int i = 0; i < 7; i++) if (sizes[i] && (rc = grow(p, B_BYTES + i, sizes[i]))) return rc;
+    if ((rc = upload(p, B_BYTES, bytes, n_bytes, B_FRAMES, frames, n_frames))) return rc;
     aacg_parse_params P;
-    P.bytes = (const uint32_t*)p->d_buf[0]; P.frames = (const aacg_parse_frame*)p->d_buf[1]; P.tab = p->d_tab;
-    P.units = (aacg_unit_desc*)p->d_buf[2]; P.q = (int16_t*)p->d_buf[3]; P.meta = (aacg_band_meta*)p->d_buf[4];
-    P.tns = tns ? (aacg_tns_info*)p->d_buf[5] : nullptr; P.results = (aacg_parse_result*)p->d_buf[6];
+    P.bytes = (const uint32_t*)p->d_buf[B_BYTES]; P.frames = (const aacg_parse_frame*)p->d_buf[B_FRAMES]; P.tab = p->d_tab;
+    P.units = (aacg_unit_desc*)p->d_buf[B_UNITS]; P.q = (int16_t*)p->d_buf[B_Q]; P.meta = (aacg_band_meta*)p->d_buf[B_META];
+    P.tns = tns ? (aacg_tns_info*)p->d_buf[B_TNS] : nullptr; P.results = (aacg_parse_result*)p->d_buf[B_RESULTS];
     P.n_frames = n_frames; P.max_units = max_units; P.max_channels = max_channels; P.options = options & ~AACG_PARSE_SKIP_ZERO_FILL;
-    int rc = launch(p, P, s);
+    if ((rc = launch(p, P, p->stream))) return rc;
+    void* const to[7] = { nullptr, nullptr, units, q, meta, tns, results };
+    if ((rc = wait_for(p, "aacg_parse_batch", "parse kernel")) == AACG_ERR_TIMEOUT) p->err += " (" + std::to_string(n_frames) + " frames, workgroups of " + std::to_string(P.wg_threads) + ")";
     if (rc) return rc;
-    /* the kernel first, bounded: the copies into the caller's (pageable) memory below wait inside the runtime, and a device that
-     * has just answered will carry them out */
-    { const hipError_t st = aacg_wait_stream(s, p->wait);
-      if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_batch: the parse kernel did not complete within the wait limit (" + std::to_string(n_frames) + " frames, workgroups of " + std::to_string(P.wg_threads) + ")");
-      HIPCHECK(st); }
-    HIPCHECK(hipMemcpyAsync(units, p->d_buf[2], sizes[2], hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipMemcpyAsync(q, p->d_buf[3], sizes[3], hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipMemcpyAsync(meta, p->d_buf[4], sizes[4], hipMemcpyDeviceToHost, s));
-    if (tns) HIPCHECK(hipMemcpyAsync(tns, p->d_buf[5], sizes[5], hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipMemcpyAsync(results, p->d_buf[6], sizes[6], hipMemcpyDeviceToHost, s));
-    { const hipError_t st = aacg_wait_stream(s, p->wait);
-      if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_batch: the copies back did not complete within the wait limit");
-      HIPCHECK(st); }
-    return AACG_OK;
+    return download(p, "aacg_parse_batch", B_BYTES, to, sizes, 7);
 }
 
 int aacg_parse_walk_device(aacg_parser* p, const void* d_bytes, const aacg_parse_frame* d_spans, uint32_t n_spans,
@@ -419,29 +426,19 @@ int aacg_parse_walk(aacg_parser* p, const uint8_t* bytes, size_t n_bytes, const 
     for (uint32_t f = 0; f < n_spans; f++)
         if ((size_t)spans[f].byte_offset + spans[f].byte_length > n_bytes) return fail(p, AACG_ERR_INVALID_ARG, "span " + std::to_string(f) + " lies outside the byte buffer");
     HIPCHECK(hipSetDevice(p->device));
-    const size_t padded = (n_bytes + 15u) / 16u * 16u + AACG_PARSE_PAD_BYTES;
-    const size_t sizes[4] = { padded, n_spans * sizeof(aacg_parse_frame), (size_t)n_spans * max_frames * sizeof(aacg_parse_frame),
+    const size_t sizes[4] = { padded_bytes(n_bytes), n_spans * sizeof(aacg_parse_frame), (size_t)n_spans * max_frames * sizeof(aacg_parse_frame),
                               n_spans * sizeof(aacg_walk_result) };
-    for (int i = 0; i < 4; i++) { int rc = grow(p, 7 + i, sizes[i]); if (rc) return rc; }
-    hipStream_t s = p->stream;
-    const size_t tail = padded < AACG_PARSE_PAD_BYTES + 16u ? padded : AACG_PARSE_PAD_BYTES + 16u;      /* zeros behind the last byte */
-    HIPCHECK(hipMemsetAsync((char*)p->d_buf[7] + padded - tail, 0, tail, s));
-    HIPCHECK(hipMemcpyAsync(p->d_buf[7], bytes, n_bytes, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(p->d_buf[8], spans, sizes[1], hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(p->d_buf[9], 0, sizes[2], s));        /* the slots beyond a span's count read as zero */
+    int rc = AACG_OK;
+    for (int i = 0; i < 4; i++) if ((rc = grow(p, W_BYTES + i, sizes[i]))) return rc;
+    if ((rc = upload(p, W_BYTES, bytes, n_bytes, W_SPANS, spans, n_spans))) return rc;
+    HIPCHECK(hipMemsetAsync(p->d_buf[W_BLOCKS], 0, sizes[2], p->stream));        /* the slots beyond a span's count read as zero */
     aacg_walk_params W;
-    walk_params(p, W, p->d_buf[7], (const aacg_parse_frame*)p->d_buf[8], n_spans, max_frames, options, (aacg_parse_frame*)p->d_buf[9], (aacg_walk_result*)p->d_buf[10]);
-    int rc = walk_launch(p, W, s);
+    walk_params(p, W, p->d_buf[W_BYTES], (const aacg_parse_frame*)p->d_buf[W_SPANS], n_spans, max_frames, options, (aacg_parse_frame*)p->d_buf[W_BLOCKS], (aacg_walk_result*)p->d_buf[W_RESULTS]);
+    if ((rc = walk_launch(p, W, p->stream))) return rc;
+    void* const to[4] = { nullptr, nullptr, frames, results };
+    if ((rc = wait_for(p, "aacg_parse_walk", "walk kernel")) == AACG_ERR_TIMEOUT) p->err += " (" + std::to_string(n_spans) + " spans)";
     if (rc) return rc;
-    { const hipError_t st = aacg_wait_stream(s, p->wait);
-      if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_walk: the walk kernel did not complete within the wait limit (" + std::to_string(n_spans) + " spans)");
-      HIPCHECK(st); }
-    HIPCHECK(hipMemcpyAsync(frames, p->d_buf[9], sizes[2], hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipMemcpyAsync(results, p->d_buf[10], sizes[3], hipMemcpyDeviceToHost, s));
-    { const hipError_t st = aacg_wait_stream(s, p->wait);
-      if (st == hipErrorNotReady) return fail(p, AACG_ERR_TIMEOUT, "aacg_parse_walk: the copies back did not complete within the wait limit");
-      HIPCHECK(st); }
-    return AACG_OK;
+    return download(p, "aacg_parse_walk", W_BYTES, to, sizes, 4);
 }
 
 int aacg_parser_set_wait_limit_ms(aacg_parser* p, uint32_t ms)

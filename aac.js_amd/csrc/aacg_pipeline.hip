@@ -31,7 +31,7 @@
  * (aacg_plan_create_shaped) and every batch shapes that plan's set of its lane on the device — aacg_plan_shape_table completes the
  * per-stream table in the staging, aacg_plan_shape_launch runs the shaping kernel in the place of aacg_pipe_map — so a batch of a
  * shape not seen before costs the submit path no plan build, no allocation, no upload of O(units) bytes and no eviction.  The two
- * modes part in aacg_pipeline_submit_ragged where the plan is chosen and where the map / shaping kernel is launched, nowhere else.
+ * modes part in submit_batch's choose_plan, where the plan is chosen, and enqueue_front, where the map / shaping kernel is launched.
  *
  * The spec-correct stages (aacg_pipeline_config.stages): the engine is created with AACG_TNS_SPEC / AACG_PNS_SPEC, the parser writes
  * TNS side info into a buffer of the lane's, aacg_tns_records_from_parse makes the batch's TNS records and their matrices behind the
@@ -120,52 +120,44 @@ struct aacg_pipeline {
     typedef aacg_pipe_layout layout_t;
     std::vector<layout_t> layout;       /* per slot; n = 0: not learnt yet */
     /* kept plans, by batch shape: (the stream slots in order, each one's frame count); the layouts are the slots' */
-    struct kept { std::vector<uint32_t> frames; std::vector<uint32_t> slots; aacg_plan* plan; uint32_t n_units; uint64_t used; };
+    struct kept { std::vector<uint32_t> frames; std::vector<uint32_t> slots; aacg_plan* plan; uint64_t used; };
     std::vector<kept> plans;
     uint64_t tick = 0, plan_builds = 0;
     /* plan_mode 1 (aacg_pipeline_config): ONE plan with the pipeline's capacity, a set per lane, shaped on the device batch by batch
      * (aacg_plan_create_shaped) — `plans`, plan_for and the stale-plan retry are not on that path */
     aacg_plan* shaped = nullptr;
-    kept shaped_kept;                   /* what the submit path takes from a kept plan: the plan and the batch's unit count */
     uint64_t shaped_batches = 0, launches = 0;
     std::vector<layout_t> batch_layout; /* the submitting batch's streams' layouts, as its plan lists them */
     std::vector<uint32_t> rect_counts;  /* aacg_pipeline_submit's counts: every stream frames_per_stream */
-    struct lane_t {
+    /* what a lane and a walk slot share: a parser and a stream of its own, and what says whether something is in flight on them */
+    struct slot_t { aacg_parser* parser = nullptr; hipStream_t st = nullptr; hipEvent_t done = nullptr; bool busy = false; uint64_t ticket = 0; };
+    struct lane_t : slot_t {
         /* A parser of its own per lane: a parser's launches are ordered one behind the other (they share its lane-order scratch),
          * and a batch's parse is the longest single step of the route — one GPU lane walks one frame's bits, so 4096 frames keep a
          * quarter of the chip busy for as long as the longest frame takes (0.5-0.8 ms; profiles/r06_resident_budget.txt).  With a
          * parser per lane the parses of consecutive batches run side by side. */
-        aacg_parser* parser = nullptr;
-        hipStream_t st = nullptr;
-        hipEvent_t done = nullptr;
         void *d_bytes = nullptr, *d_frames = nullptr, *d_units = nullptr, *d_q = nullptr, *d_meta = nullptr, *d_res = nullptr, *d_pcm = nullptr, *d_refused = nullptr;
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
          * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
         void *d_tns_info = nullptr, *d_tns = nullptr;
         void *h_in = nullptr, *h_pcm = nullptr, *h_res = nullptr;
-        size_t bytes_cap = 0, h_in_cap = 0;
+        size_t bytes_cap = 0;             /* of h_in and of d_bytes: they grow together (grow_pair) */
         /* the batch in flight */
-        bool busy = false, count_stale = false;
-        uint64_t ticket = 0;
+        bool count_stale = false;
         void* user_pcm = nullptr; bool direct = false; size_t pcm_bytes = 0;
         bool device_out = false;          /* aacg_pipeline_submit_device: the PCM stays on the device, nothing of it is the host's to copy */
         aacg_parse_result* user_results = nullptr; uint32_t* user_refused = nullptr; uint32_t n = 0;
-        std::vector<uint32_t> first, frames_of;   /* the batch's streams: first packed frame, frame count */
-        std::vector<uint32_t> unlearnt;   /* streams of the batch (by position) whose layout was not known: nothing of them was decoded */
+        struct span_t { uint32_t first, frames; };
+        std::vector<span_t> unlearnt;     /* the packed frames of the batch's streams whose layout was not known: nothing of them was decoded */
     } lane[AACG_PIPELINE_MAX_LANES];
     uint64_t submitted = 0;
     /* span walks (aacg_pipeline_walk_submit): two slots, made at the first walk — a stream more at set-up would shift the
      * runtime's stream -> hardware queue assignment under the lanes' streams.  Bytes up and results down by aacg_pipe_copy through
      * page-locked staging, as a batch's; buffers grow, never shrink. */
-    struct walk_t {
-        aacg_parser* parser = nullptr;
-        hipStream_t st = nullptr;
-        hipEvent_t done = nullptr;
+    struct walk_t : slot_t {
         void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
         size_t in_cap = 0, out_cap = 0;
-        bool busy = false;
-        uint64_t ticket = 0;
         aacg_parse_frame* user_frames = nullptr; aacg_walk_result* user_results = nullptr;
         size_t frames_bytes = 0, results_bytes = 0, results_at = 0;
     } walk[2];
@@ -184,9 +176,18 @@ bool ok(aacg_pipeline* p, hipError_t rc, const char* what)
     p->err = std::string(what) + ": " + hipGetErrorString(rc);
     return false;
 }
+int engine_fail(aacg_pipeline* p, const char* what, int rc) { p->err = std::string(what) + aacg_last_error(p->engine); return rc; }
 #define P_TRY(p, call, code) do { if (!ok((p), (call), #call)) return (code); } while (0)
 
 size_t pcm_elem(const aacg_pipeline* p) { return p->cfg.output_kind == AACG_OUTPUT_I16 ? 2 : 4; }
+
+/* a slot's layout as plans and callers see it: the learnt one (n = 0: none yet), or, C <= 2, one element of C channels */
+aacg_pipeline::layout_t layout_of(const aacg_pipeline* p, uint32_t slot)
+{
+    aacg_pipeline::layout_t lay = p->layout[slot];
+    if (!p->learn) { lay.n = lay.kept = 1; lay.nch[0] = (uint8_t)p->C; }
+    return lay;
+}
 
 /* true if the runtime knows this host pointer as page-locked (aacg_host_alloc / hipHostMalloc / hipHostRegister) */
 bool is_pinned(const void* ptr)
@@ -205,41 +206,45 @@ void pipe_copy(const void* src, void* dst, size_t bytes, hipStream_t s, bool cle
     hipLaunchKernelGGL(aacg_pipe_copy, dim3(blocks), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, n16, clear_last ? 1 : 0);
 }
 
-void drop_plan(aacg_pipeline* p, size_t i)
+/* page-locked and device buffers of at least `need` bytes (grown by half again: a steady state allocates nothing) */
+int grow_pair(aacg_pipeline* p, void** h, void** d, size_t* cap, size_t need)
 {
-    aacg_plan_destroy(p->plans[i].plan);                 /* waits (bounded) for the launches that read it */
-    p->plans.erase(p->plans.begin() + (long)i);
-}
-void drop_plans(aacg_pipeline* p) { while (!p->plans.empty()) drop_plan(p, p->plans.size() - 1); }
-
-/* The plan for a batch of this shape: stream s brings frames_of[s] frames, parsed frames first_s .. first_s + frames_of[s] - 1
- * (aacg_pipe::plan_list: the units the plan lists; the map they are refreshed through is the lane's, aacg_pipe_map).  The
- * batch's layouts are in p->batch_layout. */
-int plan_for(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t S, aacg_pipeline::kept** out)
-{
-    for (auto& k : p->plans)
-        if (k.slots.size() == S && std::memcmp(k.slots.data(), slots, S * sizeof(uint32_t)) == 0 &&
-            std::memcmp(k.frames.data(), frames_of, S * sizeof(uint32_t)) == 0) { k.used = ++p->tick; *out = &k; return AACG_OK; }
-    std::vector<aacg_unit_desc> u;
-    uint32_t total = 0;
-    for (uint32_t s = 0; s < S; s++) total += frames_of[s];
-    u.reserve((size_t)total * (p->learn ? 4 : 1));
-    aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, S, p->C, p->Cp, p->U, &u, nullptr, nullptr);
-    if (u.empty()) { *out = nullptr; return AACG_OK; }     /* no stream of the batch has a layout yet: nothing to transform, every frame is refused */
-    aacg_plan* plan = nullptr;
-    int rc = p->spec_stages ? aacg_plan_create_stages(p->engine, u.data(), (uint32_t)u.size(), &plan) : aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
-    if (rc == AACG_OK && (rc = aacg_plan_set_unit_sets(p->engine, plan, (uint32_t)p->n_lanes))) { aacg_plan_destroy(plan); plan = nullptr; }
-    if (rc) { p->err = std::string("aacg_plan_create: ") + aacg_last_error(p->engine); return rc; }
-    p->plan_builds++;
-    if (p->plans.size() >= 8) {                          /* the least recently used shape makes room */
-        size_t lru = 0;
-        for (size_t i = 1; i < p->plans.size(); i++) if (p->plans[i].used < p->plans[lru].used) lru = i;
-        drop_plan(p, lru);
-    }
-    p->plans.push_back({std::vector<uint32_t>(frames_of, frames_of + S), std::vector<uint32_t>(slots, slots + S), plan, (uint32_t)u.size(), ++p->tick});
-    *out = &p->plans.back();
+    if (need <= *cap) return AACG_OK;
+    if (*h) (void)hipHostFree(*h);
+    if (*d) (void)hipFree(*d);
+    *h = *d = nullptr; *cap = 0;
+    const size_t want = need * 3 / 2 + 4096;
+    P_TRY(p, hipHostMalloc(h, want, hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
+    P_TRY(p, hipMalloc(d, want), AACG_ERR_OUT_OF_MEMORY);
+    *cap = want;
     return AACG_OK;
 }
+
+/* A staging block, made and filled: the bytes (16-byte aligned, AACG_PARSE_PAD readable bytes behind them), the table of frames or
+ * spans, and at extra_at (16-byte aligned again) room for what else goes up with them: a batch's per-stream table.  Page-locked
+ * and device copy have one layout and one size, `up`. */
+struct staging_t { size_t padded, extra_at, up; };
+int stage(aacg_pipeline* p, void** h, void** d, size_t* cap, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* rows, uint32_t n_rows, size_t extra, staging_t& G)
+{
+    const size_t table = (size_t)n_rows * sizeof(aacg_parse_frame);
+    G.padded = ((n_bytes + 15) & ~(size_t)15) + 64; G.extra_at = G.padded + ((table + 15) & ~(size_t)15); G.up = G.extra_at + extra;
+    int rc = grow_pair(p, h, d, cap, G.up);
+    if (rc) return rc;
+    std::memcpy(*h, bytes, n_bytes);
+    std::memset((char*)*h + n_bytes, 0, G.padded - n_bytes);
+    std::memcpy((char*)*h + G.padded, rows, table);
+    return AACG_OK;
+}
+
+/* One batch on its way through submit_batch: what the caller gave, then what each step leaves for the steps behind it */
+struct batch_t {
+    const uint8_t* bytes; size_t n_bytes; const aacg_parse_frame* frames; const uint32_t* slots; uint32_t n_streams; const uint32_t* frames_of;
+    void* pcm_out; const aacg_pcm_device_out* dev; aacg_parse_result* results; uint32_t* n_refused;
+    uint32_t n, longest;                         /* check_batch: the batch's frames, the largest count of a stream */
+    uint32_t set;                                /* the lane's index: the set of a plan's unit records that is this lane's */
+    staging_t G; bool planar, direct; void* d_pcm; size_t pcm_bytes;      /* stage_batch (the per-stream table lies at G.extra_at) */
+    aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
+};
 
 std::string lanes_text(aacg_pipeline* p)
 {
@@ -265,27 +270,104 @@ int timed_out(aacg_pipeline* p, const char* what)
     return AACG_ERR_TIMEOUT;
 }
 
+/* the bounded wait for what is in flight in a lane or a walk slot */
+int wait_done(aacg_pipeline* p, aacg_pipeline::slot_t& S, const char* what)
+{
+    const hipError_t st = aacg_wait_event(S.done, p->wait);
+    if (st == hipErrorNotReady) return timed_out(p, what);
+    P_TRY(p, st, AACG_ERR_NO_DEVICE);
+    return AACG_OK;
+}
+
 /* the lane's batch is complete: what it staged goes to the caller */
 int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
 {
     if (!L.busy) return AACG_OK;
-    const hipError_t st = aacg_wait_event(L.done, p->wait);
-    if (st == hipErrorNotReady) return timed_out(p, "aacg_pipeline_collect");
-    P_TRY(p, st, AACG_ERR_NO_DEVICE);
+    int rc = wait_done(p, L, "aacg_pipeline_collect");
+    if (rc) return rc;
     if (!L.device_out && !L.direct) std::memcpy(L.user_pcm, L.h_pcm, L.pcm_bytes);
     /* a stream whose first frame did not parse has no layout yet: every frame of it in this batch came out silent and says so */
     aacg_parse_result* res = (aacg_parse_result*)L.h_res;
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
-    for (uint32_t s : L.unlearnt)
-        for (uint32_t f = 0; f < L.frames_of[s]; f++) { aacg_parse_result& r = res[(size_t)L.first[s] + f]; if (r.status == AACG_PARSE_OK) r.status = AACG_PARSE_LAYOUT; (*refused)++; }
+    for (const auto& u : L.unlearnt)
+        for (uint32_t f = 0; f < u.frames; f++) { aacg_parse_result& r = res[(size_t)u.first + f]; if (r.status == AACG_PARSE_OK) r.status = AACG_PARSE_LAYOUT; (*refused)++; }
     if (L.user_results) std::memcpy(L.user_results, res, (size_t)L.n * sizeof(aacg_parse_result));
     if (L.user_refused) std::memcpy(L.user_refused, refused, 4);
     L.busy = false;
     return AACG_OK;
 }
 
+/* the walk in a slot is complete: its results go to the caller */
+int finish_walk(aacg_pipeline* p, aacg_pipeline::walk_t& W)
+{
+    if (!W.busy) return AACG_OK;
+    int rc = wait_done(p, W, "aacg_pipeline_walk_collect");
+    if (rc) return rc;
+    std::memcpy(W.user_frames, W.h_out, W.frames_bytes);
+    std::memcpy(W.user_results, (char*)W.h_out + W.results_at, W.results_bytes);
+    W.busy = false;
+    return AACG_OK;
+}
+
+/* ---- Plan mode 0, all of it: the kept plans by batch shape and their LRU, the plans a relearnt slot invalidates, the new plan for
+ * a launch that found its own stale.  With plan mode 1 `plans` stays empty and choose_plan / enqueue_transform call none of this. ---- */
+void drop_plan(aacg_pipeline* p, size_t i)
+{
+    aacg_plan_destroy(p->plans[i].plan);                 /* waits (bounded) for the launches that read it */
+    p->plans.erase(p->plans.begin() + (long)i);
+}
+void drop_plans(aacg_pipeline* p) { while (!p->plans.empty()) drop_plan(p, p->plans.size() - 1); }
+/* the plans that list this slot: made for a layout the slot no longer has, or while it had none (they list nothing of it) */
+void drop_plans_with(aacg_pipeline* p, uint32_t slot)
+{
+    for (size_t i = p->plans.size(); i-- > 0;) {
+        bool has = false;
+        for (uint32_t s : p->plans[i].slots) has = has || s == slot;
+        if (has) drop_plan(p, i);
+    }
+}
+
+/* The plan for a batch of this shape: stream s brings frames_of[s] frames, parsed frames first_s .. first_s + frames_of[s] - 1
+ * (aacg_pipe::plan_list: the units the plan lists; the map they are refreshed through is the lane's, aacg_pipe_map).  The
+ * batch's layouts are in p->batch_layout. */
+int plan_for(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t S, aacg_plan** out)
+{
+    for (auto& k : p->plans)
+        if (k.slots.size() == S && std::memcmp(k.slots.data(), slots, S * sizeof(uint32_t)) == 0 &&
+            std::memcmp(k.frames.data(), frames_of, S * sizeof(uint32_t)) == 0) { k.used = ++p->tick; *out = k.plan; return AACG_OK; }
+    std::vector<aacg_unit_desc> u;
+    uint32_t total = 0;
+    for (uint32_t s = 0; s < S; s++) total += frames_of[s];
+    u.reserve((size_t)total * (p->learn ? 4 : 1));
+    aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, S, p->C, p->Cp, p->U, &u, nullptr, nullptr);
+    if (u.empty()) { *out = nullptr; return AACG_OK; }     /* no stream of the batch has a layout yet: nothing to transform, every frame is refused */
+    aacg_plan* plan = nullptr;
+    int rc = p->spec_stages ? aacg_plan_create_stages(p->engine, u.data(), (uint32_t)u.size(), &plan) : aacg_plan_create(p->engine, u.data(), (uint32_t)u.size(), &plan);
+    if (rc == AACG_OK && (rc = aacg_plan_set_unit_sets(p->engine, plan, (uint32_t)p->n_lanes))) { aacg_plan_destroy(plan); plan = nullptr; }
+    if (rc) return engine_fail(p, "aacg_plan_create: ", rc);
+    p->plan_builds++;
+    if (p->plans.size() >= 8) {                          /* the least recently used shape makes room */
+        size_t lru = 0;
+        for (size_t i = 1; i < p->plans.size(); i++) if (p->plans[i].used < p->plans[lru].used) lru = i;
+        drop_plan(p, lru);
+    }
+    p->plans.push_back({std::vector<uint32_t>(frames_of, frames_of + S), std::vector<uint32_t>(slots, slots + S), plan, ++p->tick});
+    *out = plan;
+    return AACG_OK;
+}
+
+/* another shape's plan has advanced these streams since this one was used: plans are made from the engine's current state */
+int replan_stale(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
+{
+    drop_plans(p);
+    int rc = plan_for(p, B.slots, B.frames_of, B.n_streams, &B.plan);
+    if (rc == AACG_OK && B.plan) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, L.st), AACG_ERR_NO_DEVICE);      /* the stale plan's refresh has counted this batch's refusals already */
+    return rc;
+}
+/* ---- end of plan mode 0 ---- */
+
 /* the element layouts of streams that are new: their first frames through one small synchronous parse (host pointers) */
-int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames, const uint32_t* slots, uint32_t S, const uint32_t* frames_of)
+int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, const aacg_parse_frame* frames, const uint32_t* slots, uint32_t S, const uint32_t* frames_of)
 {
     std::vector<uint32_t> who, first;
     for (uint32_t s = 0, i = 0; s < S; i += frames_of[s], s++) if (!p->layout[slots[s]].n) { who.push_back(s); first.push_back(i); }
@@ -299,7 +381,6 @@ int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const 
         buf.insert(buf.end(), bytes + f.byte_offset, bytes + f.byte_offset + f.byte_length);
         buf.resize((buf.size() + 15) & ~(size_t)15);
     }
-    (void)n_bytes;
     const uint32_t n = (uint32_t)who.size(), U = p->U, Cp = p->Cp;
     std::vector<aacg_unit_desc> units((size_t)n * U);
     std::vector<int16_t> q((size_t)n * Cp * 1024);
@@ -318,12 +399,7 @@ int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const 
             chan += lay.nch[e];
         }
         p->layout[slots[who[k]]] = lay;
-        /* plans made while this slot's layout was unknown list nothing of it */
-        for (size_t i = p->plans.size(); i-- > 0;) {
-            bool has = false;
-            for (uint32_t s : p->plans[i].slots) has = has || s == slots[who[k]];
-            if (has) drop_plan(p, i);
-        }
+        drop_plans_with(p, slots[who[k]]);                  /* plans made while this slot's layout was unknown list nothing of it */
     }
     return AACG_OK;
 }
@@ -493,185 +569,188 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
      * engine's launches; the PCM on its way down and the caller's buffers are the lanes') */
     for (int k = 0; k < p->n_lanes; k++) { int rc = finish_lane(p, p->lane[k]); if (rc) return rc; }
     int rc = aacg_reset_stream(p->engine, slot);
-    if (rc) { p->err = aacg_last_error(p->engine); return rc; }
+    if (rc) return engine_fail(p, "", rc);
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
-        for (size_t i = p->plans.size(); i-- > 0;) {
-            bool has = false;
-            for (uint32_t s : p->plans[i].slots) has = has || s == slot;
-            if (has) drop_plan(p, i);
-        }
+        drop_plans_with(p, slot);
     }
+    return AACG_OK;
+}
+
+namespace {
+
+/* Step 1, the host refusals: nothing is enqueued and no lane touched before they pass */
+int check_batch(aacg_pipeline* p, batch_t& B)
+{
+    if ((int)B.n_streams > p->cfg.max_streams) { p->err = "batch larger than the pipeline was created for"; return AACG_ERR_CAPACITY; }
+    uint64_t total = 0;
+    B.longest = 0;
+    for (uint32_t s = 0; s < B.n_streams; s++) {
+        if (!B.frames_of[s]) { p->err = "a stream of the batch brings no frame (frames_of[s] == 0)"; return AACG_ERR_INVALID_ARG; }
+        if ((int64_t)B.frames_of[s] > p->cfg.max_frames) { p->err = "a stream brings more frames than max_frames"; return AACG_ERR_CAPACITY; }
+        total += B.frames_of[s];
+        if (B.frames_of[s] > B.longest) B.longest = B.frames_of[s];
+    }
+    if (total > (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames) { p->err = "the batch's frames exceed max_streams x max_frames"; return AACG_ERR_CAPACITY; }
+    B.n = (uint32_t)total;
+    for (uint32_t s = 0; s < B.n_streams; s++) if ((int)B.slots[s] >= p->cfg.max_streams) { p->err = "stream slot out of range"; return AACG_ERR_CAPACITY; }
+    {   /* a slot is one stream's overlap state: a batch brings each at most once (its frames are consecutive ones of that stream) */
+        std::vector<bool> seen((size_t)p->cfg.max_streams, false);
+        for (uint32_t s = 0; s < B.n_streams; s++) { if (seen[B.slots[s]]) { p->err = "a stream slot is listed twice in one batch"; return AACG_ERR_INVALID_ARG; } seen[B.slots[s]] = true; }
+    }
+    for (uint32_t i = 0; i < B.n; i++)
+        if ((size_t)B.frames[i].byte_offset + B.frames[i].byte_length > B.n_bytes) { p->err = "a frame points outside the byte buffer"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    return B.pcm_out ? AACG_OK : check_device_out(p, B.dev, B.n, B.n_streams, B.longest);
+}
+
+/* Step 3, staging: the bytes, the frame table and room for the per-stream table that aacg_pipe_map expands into the refresh map
+ * (plan mode 1: that the shaping kernel reads) in one block, the tables behind the bytes on the device too; and where the PCM goes */
+int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
+{
+    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n,
+                   (size_t)B.n_streams * (p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)), B.G);
+    if (rc) return rc;
+    L.d_frames = (char*)L.d_bytes + B.G.padded;
+    B.planar = B.dev && B.dev->layout == AACG_PCM_PLANAR;
+    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed — the caller's in its place */
+    B.d_pcm = B.dev && !B.planar ? B.dev->d_pcm : L.d_pcm;
+    B.pcm_bytes = (size_t)B.n * p->C * 1024u * pcm_elem(p);
+    /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
+     * lane's own page-locked staging and one host copy at collect */
+    B.direct = B.dev || is_pinned(B.pcm_out);            /* (PCM left on the device: no staging either) */
+    if (!B.direct && !L.h_pcm)
+        P_TRY(p, hipHostMalloc(&L.h_pcm, (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * p->C * 1024u * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
+    return AACG_OK;
+}
+
+/* Step 4, the plan is chosen and the per-stream table filled in: the first of the two places where the plan modes part */
+int choose_plan(aacg_pipeline* p, const aacg_pipeline::lane_t& L, batch_t& B)
+{
+    void* const tab = (char*)L.h_in + B.G.extra_at;
+    if (!p->shaped) {
+        aacg_pipe::plan_list(p->batch_layout.data(), B.slots, B.frames_of, B.n_streams, p->C, p->Cp, p->U, nullptr, nullptr, (aacg_pipe_stream*)tab);
+        return plan_for(p, B.slots, B.frames_of, B.n_streams, &B.plan);
+    }
+    /* the plan is chosen: the one there is, its set of this lane shaped from the batch's table — which the engine checks against
+     * the plan's capacity and completes (each stream's first run and link, the overlap rotation) before anything is enqueued */
+    uint32_t n_units = 0;
+    aacg_pipe::shape_table(p->batch_layout.data(), B.slots, B.frames_of, B.n_streams, (aacg_shape_stream*)tab);
+    int rc = aacg_plan_shape_table(p->engine, p->shaped, B.set, (aacg_shape_stream*)tab, B.n_streams, p->Cp, &n_units);
+    B.plan = n_units ? p->shaped : nullptr;              /* (no stream of the batch has a layout yet: nothing to transform, as with kept plans) */
+    return rc ? engine_fail(p, "aacg_plan_shape_table: ", rc) : AACG_OK;
+}
+
+/* Step 5, the front of the lane's stream: the clear for unlearnt streams, the staging's copy up, the stale count, the parse, the TNS
+ * records, and the map or — the second place where the plan modes part — the shaping launch */
+int enqueue_front(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B)
+{
+    hipStream_t st = L.st;
+    const uint32_t Cp = p->Cp, U = p->U;
+    L.unlearnt.clear();
+    if (p->learn) for (uint32_t s = 0, i = 0; s < B.n_streams; i += B.frames_of[s], s++) if (!p->layout[B.slots[s]].kept) L.unlearnt.push_back({i, B.frames_of[s]});
+    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(B.d_pcm, 0, B.pcm_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
+    pipe_copy(L.h_in, L.d_bytes, B.G.up, st);             /* aacg_pipe_copy: not the SDMA engines, where it would queue behind other lanes' PCM */
+    if (L.count_stale) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* a submission that failed half-way left its count behind */
+    L.count_stale = true;
+    /* the spectra of a refused frame and the positions outside the coded bands are never read by the transform (a refused frame
+     * becomes a silent unit), so the parser need not clear 8 KB per frame first */
+    int rc = aacg_parse_device(L.parser, L.d_bytes, (const aacg_parse_frame*)L.d_frames, B.n, U, Cp, (uint32_t)p->cfg.parse_options | AACG_PARSE_SKIP_ZERO_FILL,
+                               (aacg_unit_desc*)L.d_units, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, (aacg_tns_info*)L.d_tns_info, (aacg_parse_result*)L.d_res, st);
+    if (rc) { p->err = std::string("aacg_parse_device: ") + aacg_parser_last_error(L.parser); return rc; }
+    if (!B.plan) return AACG_OK;
+    /* AACG_PIPELINE_STAGE_TNS: the batch's TNS records and their matrices, made where the side info lies, behind the parse on the
+     * lane's stream; the launch that read this lane's buffer last was its previous batch's, whose PCM has come down since */
+    if (L.d_tns && (rc = aacg_tns_records_from_parse(p->engine, (const aacg_unit_desc*)L.d_units, (const aacg_parse_result*)L.d_res, (const aacg_tns_info*)L.d_tns_info,
+                                                     B.n, U, Cp, L.d_tns, st))) return engine_fail(p, "aacg_tns_records_from_parse: ", rc);
+    const void* const d_tab = (const char*)L.d_bytes + B.G.extra_at;
+    if (p->shaped) {                                     /* the shaping kernel INSTEAD of aacg_pipe_map: the map, and the set's unit, run and link records */
+        if ((rc = aacg_plan_shape_launch(p->engine, p->shaped, (const aacg_shape_stream*)d_tab, U, (aacg_refresh_map*)L.d_map, st))) return engine_fail(p, "aacg_plan_shape_launch: ", rc);
+        p->shaped_batches++;
+    } else {                                             /* the map the refresh reads: behind the staging's copy, on the lane's stream */
+        const uint32_t blocks = B.n_streams < 256 ? B.n_streams : 256;
+        hipLaunchKernelGGL(aacg_pipe_map, dim3(blocks), dim3(AACG_PIPE_MAP_THREADS), 0, st, (const aacg_pipe_stream*)d_tab, B.n_streams, U, (aacg_refresh_map*)L.d_map);
+    }
+    return AACG_OK;
+}
+
+/* Step 6, the transform and the join behind it; a batch without a plan has neither */
+int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
+{
+    int rc = AACG_OK;
+    for (int attempt = 0; B.plan; attempt++) {
+        /* this lane's set of the plan's unit records: the launch that read it last was this lane's previous batch, whose PCM has
+         * come down on this stream since */
+        rc = aacg_plan_refresh_from_parse_ex(p->engine, B.plan, (const aacg_unit_desc*)L.d_units, (aacg_parse_result*)L.d_res, p->U,
+                                             (const aacg_refresh_map*)L.d_map, B.set, (uint32_t*)L.d_refused, L.st);
+        /* AACG_PIPELINE_STAGE_WINDOW_SHAPE: the refreshed shapes are final — each frame's first half takes the shape of the frame
+         * before, a stream's first frame the one its previous batch left (a second attempt starts from where the first started) */
+        if (rc == AACG_OK && p->carry_shape) rc = aacg_plan_carry_window_shape(p->engine, B.plan, (const aacg_refresh_map*)L.d_map, B.set, L.st);
+        /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
+         * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
+        if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, L.st);
+        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, B.plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? B.n * p->Cp : 0u, B.d_pcm)
+                                              : aacg_decode_pipelined(p->engine, B.plan, L.d_q, (const aacg_band_meta*)L.d_meta, B.d_pcm);
+        if (rc == AACG_OK) p->launches++;
+        if (rc != AACG_ERR_STALE_PLAN || attempt || p->shaped) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
+        if ((rc = replan_stale(p, L, B))) return rc;        /* plan mode 0: once more, with a plan made now */
+    }
+    if (rc == AACG_OK && B.plan) rc = aacg_pipeline_join(p->engine, L.st);
+    return rc ? engine_fail(p, "transform: ", rc) : AACG_OK;
+}
+
+/* Step 7, the way out: the PCM (planar launch, copy down, or nothing), the results' copy, the lane's event, what finish_lane needs */
+int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, uint64_t* ticket)
+{
+    if (B.planar) {
+        /* the caller's tensor from the lane's packed PCM and the per-stream table that came up with the bytes (either plan mode's
+         * record begins with frame_first and frames), padding included: where the copy down sits for a host batch */
+        aacg_planar_args A;
+        A.src = L.d_pcm; A.dst = B.dev->d_pcm; A.tab = (const char*)L.d_bytes + B.G.extra_at;
+        A.tab_stride = (uint32_t)(p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
+        A.n_streams = B.n_streams; A.stride_frames = B.dev->stride_frames; A.channels = p->C; A.elem = (uint32_t)pcm_elem(p);
+        if (!aacg_planar_launch(A, L.st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+    } else if (!B.dev) {
+        char* dst = (char*)(B.direct ? B.pcm_out : L.h_pcm);
+        P_TRY(p, hipMemcpyAsync(dst, L.d_pcm, B.pcm_bytes, hipMemcpyDeviceToHost, L.st), AACG_ERR_NO_DEVICE);      /* one SDMA copy per batch (see aacg_pipe_copy) */
+    }
+    /* the results and, behind where the largest batch's would end, the refusal count: one small launch (a launch that writes to
+     * host memory costs 50 us of the lane's time whatever it carries) */
+    L.count_stale = false;
+    pipe_copy(L.d_res, L.h_res, p->res_cap16 + 16, L.st, true);         /* ... and the count is cleared for the lane's next batch (set to zero at create) */
+    P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    P_TRY(p, hipEventRecord(L.done, L.st), AACG_ERR_NO_DEVICE);
+    L.busy = true; L.ticket = ++p->submitted; L.user_pcm = B.pcm_out; L.direct = B.direct; L.pcm_bytes = B.pcm_bytes; L.device_out = B.dev != nullptr;
+    L.user_results = B.results; L.user_refused = B.n_refused; L.n = B.n;
+    *ticket = L.ticket;
     return AACG_OK;
 }
 
 /* One batch onto the next lane: aacg_pipeline_submit_ragged (pcm_out: host memory, dev null) and aacg_pipeline_submit_device (dev:
  * the caller's device memory, pcm_out null) are this, and differ where the PCM goes and nowhere else. */
-static int submit_batch(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
-                        const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
-                        void* pcm_out, const aacg_pcm_device_out* dev, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
+int submit_batch(aacg_pipeline* p, batch_t B, uint64_t* ticket)
 {
-    if ((int)n_streams > p->cfg.max_streams) { p->err = "batch larger than the pipeline was created for"; return AACG_ERR_CAPACITY; }
-    uint64_t total = 0;
-    uint32_t longest = 0;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        if (!frames_of[s]) { p->err = "a stream of the batch brings no frame (frames_of[s] == 0)"; return AACG_ERR_INVALID_ARG; }
-        if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "a stream brings more frames than max_frames"; return AACG_ERR_CAPACITY; }
-        total += frames_of[s];
-        if (frames_of[s] > longest) longest = frames_of[s];
-    }
-    if (total > (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames) { p->err = "the batch's frames exceed max_streams x max_frames"; return AACG_ERR_CAPACITY; }
-    const uint32_t n = (uint32_t)total, C = p->C, Cp = p->Cp, U = p->U;
-    for (uint32_t s = 0; s < n_streams; s++) if ((int)slots[s] >= p->cfg.max_streams) { p->err = "stream slot out of range"; return AACG_ERR_CAPACITY; }
-    {   /* a slot is one stream's overlap state: a batch brings each at most once (its frames are consecutive ones of that stream) */
-        std::vector<bool> seen((size_t)p->cfg.max_streams, false);
-        for (uint32_t s = 0; s < n_streams; s++) { if (seen[slots[s]]) { p->err = "a stream slot is listed twice in one batch"; return AACG_ERR_INVALID_ARG; } seen[slots[s]] = true; }
-    }
-    for (uint32_t i = 0; i < n; i++)
-        if ((size_t)frames[i].byte_offset + frames[i].byte_length > n_bytes) { p->err = "a frame points outside the byte buffer"; return AACG_ERR_INVALID_ARG; }
-    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
-    int rc = AACG_OK;
-    if (!pcm_out && (rc = check_device_out(p, dev, n, n_streams, longest))) return rc;
-    const bool planar = dev && dev->layout == AACG_PCM_PLANAR;
-    aacg_pipeline::lane_t& L = p->lane[p->submitted % (uint64_t)p->n_lanes];
-    const uint32_t set = (uint32_t)(p->submitted % (uint64_t)p->n_lanes);
-    rc = finish_lane(p, L);                              /* the batch `lanes` submissions ago, if nobody has collected it */
+    int rc = check_batch(p, B);
     if (rc) return rc;
-    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed — the caller's in its place */
-    void* const d_pcm = dev && !planar ? dev->d_pcm : L.d_pcm;
-    if (p->learn && (rc = learn_layouts(p, bytes, n_bytes, frames, slots, n_streams, frames_of))) return rc;
+    B.set = (uint32_t)(p->submitted % (uint64_t)p->n_lanes);
+    aacg_pipeline::lane_t& L = p->lane[B.set];
+    if ((rc = finish_lane(p, L))) return rc;             /* step 2: the batch `lanes` submissions ago, if nobody has collected it */
+    if (p->learn && (rc = learn_layouts(p, B.bytes, B.frames, B.slots, B.n_streams, B.frames_of))) return rc;
     /* the batch's layouts as its plan lists them (a stream without one has no unit in the plan) */
-    p->batch_layout.resize(n_streams);
-    for (uint32_t s = 0; s < n_streams; s++) {
-        aacg_pipeline::layout_t lay = p->layout[slots[s]];
-        if (!p->learn) { lay.n = lay.kept = 1; lay.nch[0] = (uint8_t)C; }
-        p->batch_layout[s] = lay;
-    }
-    /* staging: the bytes (16-byte aligned, AACG_PARSE_PAD readable bytes behind them), the frame table and the per-stream table
-     * that aacg_pipe_map expands into the refresh map, in one page-locked block */
-    const size_t padded = ((n_bytes + 15) & ~(size_t)15) + 64, table = (size_t)n * sizeof(aacg_parse_frame), table16 = (table + 15) & ~(size_t)15;
-    const bool device_plans = p->shaped != nullptr;
-    const size_t up = padded + table16 + (size_t)n_streams * (device_plans ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
-    if (up > L.h_in_cap) {
-        if (L.h_in) (void)hipHostFree(L.h_in);
-        L.h_in = nullptr; L.h_in_cap = 0;
-        const size_t want = up * 3 / 2 + 4096;
-        P_TRY(p, hipHostMalloc(&L.h_in, want, hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
-        L.h_in_cap = want;
-    }
-    if (up > L.bytes_cap) {                              /* bytes and frame table travel as one block: the table lies behind the bytes on the device too */
-        if (L.d_bytes) (void)hipFree(L.d_bytes);
-        L.d_bytes = nullptr; L.bytes_cap = 0;
-        const size_t want = up * 3 / 2 + 4096;
-        P_TRY(p, hipMalloc(&L.d_bytes, want), AACG_ERR_OUT_OF_MEMORY);
-        L.bytes_cap = want;
-    }
-    L.d_frames = (char*)L.d_bytes + padded;
-    std::memcpy(L.h_in, bytes, n_bytes);
-    std::memset((char*)L.h_in + n_bytes, 0, padded - n_bytes);
-    std::memcpy((char*)L.h_in + padded, frames, table);
-    aacg_pipeline::kept* kp = nullptr;
-    if (device_plans) {
-        /* the plan is chosen: the one there is, its set of this lane shaped from the batch's table — which the engine checks against
-         * the plan's capacity and completes (each stream's first run and link, the overlap rotation) before anything is enqueued */
-        aacg_shape_stream* tab = (aacg_shape_stream*)((char*)L.h_in + padded + table16);
-        aacg_pipe::shape_table(p->batch_layout.data(), slots, frames_of, n_streams, tab);
-        if ((rc = aacg_plan_shape_table(p->engine, p->shaped, set, tab, n_streams, Cp, &p->shaped_kept.n_units))) { p->err = std::string("aacg_plan_shape_table: ") + aacg_last_error(p->engine); return rc; }
-        p->shaped_kept.plan = p->shaped;
-        if (p->shaped_kept.n_units) kp = &p->shaped_kept;      /* (no stream of the batch has a layout yet: nothing to transform, as with kept plans) */
-    } else {
-        aacg_pipe::plan_list(p->batch_layout.data(), slots, frames_of, n_streams, C, Cp, U, nullptr, nullptr, (aacg_pipe_stream*)((char*)L.h_in + padded + table16));
-        if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
-    }
-    const size_t pcm_bytes = (size_t)n * C * 1024u * pcm_elem(p);
-    /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
-     * lane's own page-locked staging and one host copy at collect */
-    const bool direct = dev || is_pinned(pcm_out);       /* (PCM left on the device: no staging either) */
-    if (!direct && !L.h_pcm)
-        P_TRY(p, hipHostMalloc(&L.h_pcm, (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * C * 1024u * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
-    hipStream_t st = L.st;
-    L.unlearnt.clear();
-    if (p->learn) for (uint32_t s = 0; s < n_streams; s++) if (!p->layout[slots[s]].kept) L.unlearnt.push_back(s);
-    L.frames_of.assign(frames_of, frames_of + n_streams);
-    L.first.resize(n_streams);
-    for (uint32_t s = 0, i = 0; s < n_streams; i += frames_of[s], s++) L.first[s] = i;
-    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(d_pcm, 0, pcm_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
-    pipe_copy(L.h_in, L.d_bytes, up, st);                 /* aacg_pipe_copy: not the SDMA engines, where it would queue behind other lanes' PCM */
-    if (L.count_stale) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* a submission that failed half-way left its count behind */
-    L.count_stale = true;
-    /* the spectra of a refused frame and the positions outside the coded bands are never read by the transform (a refused frame
-     * becomes a silent unit), so the parser need not clear 8 KB per frame first */
-    rc = aacg_parse_device(L.parser, L.d_bytes, (const aacg_parse_frame*)L.d_frames, n, U, Cp, (uint32_t)p->cfg.parse_options | AACG_PARSE_SKIP_ZERO_FILL,
-                           (aacg_unit_desc*)L.d_units, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, (aacg_tns_info*)L.d_tns_info, (aacg_parse_result*)L.d_res, st);
-    if (rc) { p->err = std::string("aacg_parse_device: ") + aacg_parser_last_error(L.parser); return rc; }
-    /* AACG_PIPELINE_STAGE_TNS: the batch's TNS records and their matrices, made where the side info lies, behind the parse on the
-     * lane's stream; the launch that read this lane's buffer last was its previous batch's, whose PCM has come down since */
-    if (kp && L.d_tns && (rc = aacg_tns_records_from_parse(p->engine, (const aacg_unit_desc*)L.d_units, (const aacg_parse_result*)L.d_res, (const aacg_tns_info*)L.d_tns_info,
-                                                           n, U, Cp, L.d_tns, st))) {
-        p->err = std::string("aacg_tns_records_from_parse: ") + aacg_last_error(p->engine); return rc;
-    }
-    if (kp && device_plans) {                            /* the shaping kernel INSTEAD of aacg_pipe_map: the map, and the set's unit, run and link records */
-        if ((rc = aacg_plan_shape_launch(p->engine, p->shaped, (const aacg_shape_stream*)((char*)L.d_bytes + padded + table16), U, (aacg_refresh_map*)L.d_map, st))) {
-            p->err = std::string("aacg_plan_shape_launch: ") + aacg_last_error(p->engine); return rc;
-        }
-        p->shaped_batches++;
-    } else if (kp) {                                     /* the map the refresh reads: behind the staging's copy, on the lane's stream */
-        const uint32_t blocks = n_streams < 256 ? n_streams : 256;
-        hipLaunchKernelGGL(aacg_pipe_map, dim3(blocks), dim3(AACG_PIPE_MAP_THREADS), 0, st, (const aacg_pipe_stream*)((char*)L.d_bytes + padded + table16),
-                           n_streams, U, (aacg_refresh_map*)L.d_map);
-    }
-    for (int attempt = 0; kp; attempt++) {
-        /* this lane's set of the plan's unit records: the launch that read it last was this lane's previous batch, whose PCM has
-         * come down on this stream since */
-        if (attempt) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* the stale plan's refresh has counted this batch's refusals already */
-        rc = aacg_plan_refresh_from_parse_ex(p->engine, kp->plan, (const aacg_unit_desc*)L.d_units, (aacg_parse_result*)L.d_res, U,
-                                             (const aacg_refresh_map*)L.d_map, set, (uint32_t*)L.d_refused, st);
-        /* AACG_PIPELINE_STAGE_WINDOW_SHAPE: the refreshed shapes are final — each frame's first half takes the shape of the frame
-         * before, a stream's first frame the one its previous batch left (a second attempt starts from where the first started) */
-        if (rc == AACG_OK && p->carry_shape) rc = aacg_plan_carry_window_shape(p->engine, kp->plan, (const aacg_refresh_map*)L.d_map, set, st);
-        /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
-         * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
-        if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, st);
-        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? n * Cp : 0u, d_pcm)
-                                              : aacg_decode_pipelined(p->engine, kp->plan, L.d_q, (const aacg_band_meta*)L.d_meta, d_pcm);
-        if (rc == AACG_OK) p->launches++;
-        if (rc != AACG_ERR_STALE_PLAN || attempt || device_plans) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
-        /* another shape's plan has advanced these streams since this one was used: plans are made from the engine's current state */
-        drop_plans(p);
-        if ((rc = plan_for(p, slots, frames_of, n_streams, &kp))) return rc;
-    }
-    if (rc == AACG_OK && kp) rc = aacg_pipeline_join(p->engine, st);
-    if (rc) { p->err = std::string("transform: ") + aacg_last_error(p->engine); return rc; }
-    if (planar) {
-        /* the caller's tensor from the lane's packed PCM and the per-stream table that came up with the bytes (either plan mode's
-         * record begins with frame_first and frames), padding included: where the copy down sits for a host batch */
-        aacg_planar_args A;
-        A.src = L.d_pcm; A.dst = dev->d_pcm; A.tab = (const char*)L.d_bytes + padded + table16;
-        A.tab_stride = (uint32_t)(device_plans ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
-        A.n_streams = n_streams; A.stride_frames = dev->stride_frames; A.channels = C; A.elem = (uint32_t)pcm_elem(p);
-        if (!aacg_planar_launch(A, st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-    } else if (!dev) {
-        char* dst = (char*)(direct ? pcm_out : L.h_pcm);
-        P_TRY(p, hipMemcpyAsync(dst, L.d_pcm, pcm_bytes, hipMemcpyDeviceToHost, st), AACG_ERR_NO_DEVICE);      /* one SDMA copy per batch (see aacg_pipe_copy) */
-    }
-    /* the results and, behind where the largest batch's would end, the refusal count: one small launch (a launch that writes to
-     * host memory costs 50 us of the lane's time whatever it carries) */
-    L.count_stale = false;
-    pipe_copy(L.d_res, L.h_res, p->res_cap16 + 16, st, true);           /* ... and the count is cleared for the lane's next batch (set to zero at create) */
-    P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
-    P_TRY(p, hipEventRecord(L.done, st), AACG_ERR_NO_DEVICE);
-    L.busy = true; L.ticket = ++p->submitted; L.user_pcm = pcm_out; L.direct = direct; L.pcm_bytes = pcm_bytes; L.device_out = dev != nullptr;
-    L.user_results = results; L.user_refused = n_refused; L.n = n;
-    *ticket = L.ticket;
-    return AACG_OK;
+    p->batch_layout.resize(B.n_streams);
+    for (uint32_t s = 0; s < B.n_streams; s++) p->batch_layout[s] = layout_of(p, B.slots[s]);
+    if ((rc = stage_batch(p, L, B)) || (rc = choose_plan(p, L, B)) || (rc = enqueue_front(p, L, B)) || (rc = enqueue_transform(p, L, B))) return rc;
+    return enqueue_out(p, L, B, ticket);
 }
+
+}  // namespace
 
 int aacg_pipeline_submit_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
                                 const uint32_t* slots, uint32_t n_streams, const uint32_t* frames_of,
                                 void* pcm_out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
 {
     if (!p || !bytes || !frames || !slots || !frames_of || !pcm_out || !n_streams || !ticket) return AACG_ERR_INVALID_ARG;
-    return submit_batch(p, bytes, n_bytes, frames, slots, n_streams, frames_of, pcm_out, nullptr, results, n_refused, ticket);
+    return submit_batch(p, {bytes, n_bytes, frames, slots, n_streams, frames_of, pcm_out, nullptr, results, n_refused}, ticket);
 }
 
 int aacg_pipeline_submit_device(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
@@ -679,8 +758,7 @@ int aacg_pipeline_submit_device(aacg_pipeline* p, const uint8_t* bytes, size_t n
                                 const aacg_pcm_device_out* out, aacg_parse_result* results, uint32_t* n_refused, uint64_t* ticket)
 {
     if (!p || !bytes || !frames || !slots || !frames_of || !n_streams || !ticket) return AACG_ERR_INVALID_ARG;
-    if (!out || !out->d_pcm) { p->err = "aacg_pipeline_submit_device: no device memory for the PCM (out or out->d_pcm is null)"; return AACG_ERR_INVALID_ARG; }
-    return submit_batch(p, bytes, n_bytes, frames, slots, n_streams, frames_of, nullptr, out, results, n_refused, ticket);
+    return submit_batch(p, {bytes, n_bytes, frames, slots, n_streams, frames_of, nullptr, out, results, n_refused}, ticket);      /* (check_device_out refuses a null `out`) */
 }
 
 int aacg_pipeline_wait_device(aacg_pipeline* p, uint64_t ticket, void* hip_stream)
@@ -716,37 +794,6 @@ int aacg_pipeline_collect(aacg_pipeline* p, uint64_t ticket)
     return finish_lane(p, L);
 }
 
-namespace {
-
-/* the walk in a slot is complete: its results go to the caller */
-int finish_walk(aacg_pipeline* p, aacg_pipeline::walk_t& W)
-{
-    if (!W.busy) return AACG_OK;
-    const hipError_t st = aacg_wait_event(W.done, p->wait);
-    if (st == hipErrorNotReady) return timed_out(p, "aacg_pipeline_walk_collect");
-    P_TRY(p, st, AACG_ERR_NO_DEVICE);
-    std::memcpy(W.user_frames, W.h_out, W.frames_bytes);
-    std::memcpy(W.user_results, (char*)W.h_out + W.results_at, W.results_bytes);
-    W.busy = false;
-    return AACG_OK;
-}
-
-/* page-locked and device buffers of at least `need` bytes (grown by half again: a steady state allocates nothing) */
-int grow_pair(aacg_pipeline* p, void** h, void** d, size_t* cap, size_t need)
-{
-    if (need <= *cap) return AACG_OK;
-    if (*h) (void)hipHostFree(*h);
-    if (*d) (void)hipFree(*d);
-    *h = *d = nullptr; *cap = 0;
-    const size_t want = need * 3 / 2 + 4096;
-    P_TRY(p, hipHostMalloc(h, want, hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
-    P_TRY(p, hipMalloc(d, want), AACG_ERR_OUT_OF_MEMORY);
-    *cap = want;
-    return AACG_OK;
-}
-
-}  // namespace
-
 int aacg_pipeline_walk_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* spans, uint32_t n_spans,
                               uint32_t max_frames, aacg_parse_frame* frames, aacg_walk_result* results, uint64_t* ticket)
 {
@@ -768,15 +815,12 @@ int aacg_pipeline_walk_submit(aacg_pipeline* p, const uint8_t* bytes, size_t n_b
         P_TRY(p, hipEventCreateWithFlags(&W.done, hipEventDisableTiming), AACG_ERR_NO_DEVICE);
     }
     /* up: the bytes (16-byte aligned, zeros behind them) and the spans; down: the block table, then the per-span results */
-    const size_t padded = ((n_bytes + 15) & ~(size_t)15) + 64, table = ((size_t)n_spans * sizeof(aacg_parse_frame) + 15) & ~(size_t)15;
+    staging_t G;
     const size_t fr = (size_t)n_spans * max_frames * sizeof(aacg_parse_frame), fr16 = (fr + 15) & ~(size_t)15, rs = (size_t)n_spans * sizeof(aacg_walk_result);
-    if ((rc = grow_pair(p, &W.h_in, &W.d_in, &W.in_cap, padded + table))) return rc;
+    if ((rc = stage(p, &W.h_in, &W.d_in, &W.in_cap, bytes, n_bytes, spans, n_spans, 0, G))) return rc;
     if ((rc = grow_pair(p, &W.h_out, &W.d_out, &W.out_cap, fr16 + rs))) return rc;
-    std::memcpy(W.h_in, bytes, n_bytes);
-    std::memset((char*)W.h_in + n_bytes, 0, padded - n_bytes);
-    std::memcpy((char*)W.h_in + padded, spans, (size_t)n_spans * sizeof(aacg_parse_frame));
-    pipe_copy(W.h_in, W.d_in, padded + table, W.st);
-    rc = aacg_parse_walk_device(W.parser, W.d_in, (const aacg_parse_frame*)((char*)W.d_in + padded), n_spans, max_frames, (uint32_t)p->cfg.parse_options,
+    pipe_copy(W.h_in, W.d_in, G.up, W.st);
+    rc = aacg_parse_walk_device(W.parser, W.d_in, (const aacg_parse_frame*)((char*)W.d_in + G.padded), n_spans, max_frames, (uint32_t)p->cfg.parse_options,
                                 (aacg_parse_frame*)W.d_out, (aacg_walk_result*)((char*)W.d_out + fr16), W.st);
     if (rc) { p->err = std::string("aacg_parse_walk_device: ") + aacg_parser_last_error(W.parser); return rc; }
     pipe_copy(W.d_out, W.h_out, fr16 + ((rs + 15) & ~(size_t)15), W.st);
@@ -803,8 +847,7 @@ int aacg_pipeline_decode(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes,
 {
     uint64_t t = 0;
     int rc = aacg_pipeline_submit(p, bytes, n_bytes, frames, slots, n_streams, frames_per_stream, pcm_out, results, n_refused, &t);
-    if (rc) return rc;
-    return aacg_pipeline_collect(p, t);
+    return rc ? rc : aacg_pipeline_collect(p, t);
 }
 
 int aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n_bytes, const aacg_parse_frame* frames,
@@ -813,8 +856,7 @@ int aacg_pipeline_decode_ragged(aacg_pipeline* p, const uint8_t* bytes, size_t n
 {
     uint64_t t = 0;
     int rc = aacg_pipeline_submit_ragged(p, bytes, n_bytes, frames, slots, n_streams, frames_of, pcm_out, results, n_refused, &t);
-    if (rc) return rc;
-    return aacg_pipeline_collect(p, t);
+    return rc ? rc : aacg_pipeline_collect(p, t);
 }
 
 int aacg_pipeline_stream_window_shape(aacg_pipeline* p, uint32_t slot, uint8_t shapes[8])
@@ -826,7 +868,7 @@ int aacg_pipeline_stream_window_shape(aacg_pipeline* p, uint32_t slot, uint8_t s
     std::memset(shapes, 0, 8);
     for (uint32_t c = 0; c < p->C; c++) {
         int rc = aacg_get_window_shape(p->engine, slot, c, &shapes[c]);
-        if (rc) { p->err = aacg_last_error(p->engine); return rc; }
+        if (rc) return engine_fail(p, "", rc);
     }
     return AACG_OK;
 }
@@ -845,8 +887,7 @@ int aacg_pipeline_launch_counts(const aacg_pipeline* p, uint64_t* shaped, uint64
 int aacg_pipeline_stream_layout(aacg_pipeline* p, uint32_t slot, uint8_t element_channels[8], uint32_t* kept)
 {
     if (!p || (int)slot >= p->cfg.max_streams) return AACG_ERR_INVALID_ARG;
-    aacg_pipeline::layout_t lay = p->layout[slot];
-    if (!p->learn) { lay.n = lay.kept = 1; lay.nch[0] = (uint8_t)p->C; }
+    const aacg_pipeline::layout_t lay = layout_of(p, slot);
     if (element_channels) std::memcpy(element_channels, lay.nch, 8);
     if (kept) *kept = lay.kept;
     return (int)lay.n;
