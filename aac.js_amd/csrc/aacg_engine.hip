@@ -1642,6 +1642,13 @@ int aacg_plan_refresh_units(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* 
 {
     if (!e || !p || p->e != e || !units) return AACG_ERR_INVALID_ARG;
     if (p->sh) return shaped_refused(e, "aacg_plan_refresh_units", "there are no host unit records to rewrite (aacg_plan_refresh_from_parse_ex refreshes a shaped set)");
+    if (p->unit_sets > 1) {
+        /* the copy below rewrites set 0 in stream order behind the plan's launches; with more sets the launches read cur_set, which
+         * a device refresh chose, and nothing orders a copy against the launches that still read a set */
+        e->err = "aacg_plan_refresh_units: the plan has more than one set of unit records (aacg_plan_set_unit_sets) and its launches read the set refreshed "
+                 "last on the device; the host's records would go to set 0 (aacg_plan_refresh_from_parse_ex refreshes a set)";
+        return AACG_ERR_UNSUPPORTED;
+    }
     int rc = aacg_plan_refresh_host(&p->h, units, n_units, e->cfg.sample_index, e->cfg.tns_mode == AACG_TNS_SPEC, &e->err);
     if (rc) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;

@@ -259,6 +259,8 @@ DP_DEVICE float dp_g_load_f1(const float* p)
 DP_DEVICE void dp_g_store_u64(dp_u64* p, dp_u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DP_DEVICE unsigned dp_g_load_u32(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DP_DEVICE void dp_g_store_u32(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+/* a counter in global memory that lanes of any workgroup bump (the refresh's refusal count): atomicAdd as it is, the old value */
+DP_DEVICE unsigned dp_g_atomic_add_u32(unsigned* p, unsigned v) { return atomicAdd(p, v); }
 DP_DEVICE void dp_vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 /* lane 0's value in every lane (a 64-bit scalar) */
 DP_DEVICE dp_u64 dp_first_u64(dp_u64 v)

@@ -685,7 +685,10 @@ int aacg_plan_shape_launch(aacg_engine* e, aacg_plan* p, const aacg_shape_stream
  * offsets — replace the plan's (validated like aacg_plan_create validates them, then one asynchronous copy on hip_stream;
  * follow with aacg_decode_device on the same stream).  AACG_ERR_LAYOUT_CHANGE if the structure differs (nothing is
  * changed then: build a new plan); plans with TNS records, noise bands or coupling elements are built per batch
- * (AACG_ERR_UNSUPPORTED).  Replaces decoder.js:138-198's per-frame `new ICStream` bookkeeping for a whole batch. */
+ * (AACG_ERR_UNSUPPORTED).  Replaces decoder.js:138-198's per-frame `new ICStream` bookkeeping for a whole batch.
+ * A plan with ONE set of unit records only: after aacg_plan_set_unit_sets(n > 1) the plan's launches read the set a device
+ * refresh chose, the host's records have no set to go to, and the call is refused (AACG_ERR_UNSUPPORTED, the reason in
+ * aacg_last_error; nothing is changed). */
 int aacg_plan_refresh_units(aacg_engine* e, aacg_plan* p, const aacg_unit_desc* units, uint32_t n_units, void* hip_stream);
 
 /* ---- bytes in, PCM out: front end and transform resident, ONE call per batch, several batches in flight ---------------

@@ -205,6 +205,7 @@ DP_DEVICE float dp_g_load_f1(const float* p) { emu_sp(EMU_SP_G_LOAD, p); return 
 DP_DEVICE void dp_g_store_u64(dp_u64* p, dp_u64 v) { emu_sp(EMU_SP_G_STORE, p); __atomic_store_n(p, v, __ATOMIC_RELAXED); }
 DP_DEVICE unsigned dp_g_load_u32(const unsigned* p) { emu_sp(EMU_SP_G_LOAD, p); return __atomic_load_n(p, __ATOMIC_RELAXED); }
 DP_DEVICE void dp_g_store_u32(unsigned* p, unsigned v) { emu_sp(EMU_SP_G_STORE, p); __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+DP_DEVICE unsigned dp_g_atomic_add_u32(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }      /* a global counter (devport.h) */
 DP_DEVICE unsigned dp_cu_id() { return 0; }
 /* scalar loads in a spelled-out batch (devport.h): here plain reads */
 struct dp_su4 { unsigned v[4]; unsigned operator[](int i) const { return v[i]; } unsigned& operator[](int i) { return v[i]; } };
