@@ -50,11 +50,19 @@
  * down sits.  Neither has a copy down of PCM nor touches h_pcm; the results' copy and the lane's `done` event are as ever, and
  * aacg_pipeline_wait_device puts a consumer's stream behind that event.  The two submissions share one body (submit_batch).
  *
+ * A mix matrix (aacg_pipeline_set_mix): O = 1 or 2 channels leave in the place of C.  The transform then ALWAYS writes the lane's d_pcm,
+ * and one launch of aacg_pcm_mix_* (aacg_pcm_mix.h, aacg_engine_mix.hip) behind aacg_pipeline_join writes the mix: into the caller's
+ * d_pcm for an AACG_PCM_PACKED batch, else into the lane's second buffer d_mix, which the copy down or the planar launch (with O for
+ * its channels) then reads.  A batch has two sizes from there on: the transform's, n x C (the clear for unlearnt streams acts on it),
+ * and what leaves, n x O (pcm_bytes, h_pcm, finish_lane's copy, check_device_out's need).  Without a matrix the two are one and no call
+ * or launch differs.
+ *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
- * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h for the tables it fills and the side launch it makes).
+ * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h for the tables it fills and the side launches it makes).
  */
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -63,6 +71,7 @@
 
 #include "../../include/aacgpu.h"
 #include "../../include/aacgpu_tools.h"
+#include "aacg_pcm_mix.h"
 #include "aacg_pcm_planar.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
@@ -74,6 +83,8 @@
 
 /* aacg_engine_planar.hip: a batch's packed PCM into a caller's planar tensor (aacg_pcm_planar.h); false: not a launch it serves */
 bool aacg_planar_launch(const aacg_planar_args& A, hipStream_t s);
+/* aacg_engine_mix.hip: a batch's packed PCM mixed to one or two channels (aacg_pcm_mix.h); false: not a launch it serves */
+bool aacg_mix_launch(const aacg_mix_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -112,6 +123,8 @@ struct aacg_pipeline {
     aacg_parser* parser = nullptr;      /* layouts of new streams (synchronous, host pointers) */
     int n_lanes = 5;
     uint32_t C = 2;                     /* channels of a frame's PCM (chanConfig) */
+    uint32_t O = 0;                     /* aacg_pipeline_set_mix: channels that leave (1 or 2); 0: no mix, C leave */
+    float mix[AACG_MIX_MAX_OUT * AACG_MIX_MAX_IN] = {};      /* M[o][c] at mix[o * C + c] */
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -137,6 +150,7 @@ struct aacg_pipeline {
          * quarter of the chip busy for as long as the longest frame takes (0.5-0.8 ms; profiles/r06_resident_budget.txt).  With a
          * parser per lane the parses of consecutive batches run side by side. */
         void *d_bytes = nullptr, *d_frames = nullptr, *d_units = nullptr, *d_q = nullptr, *d_meta = nullptr, *d_res = nullptr, *d_pcm = nullptr, *d_refused = nullptr;
+        void* d_mix = nullptr;            /* aacg_pipeline_set_mix: the mixed PCM of a host or planar batch, max_streams x max_frames x 1024 x O elements */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
          * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
@@ -180,6 +194,8 @@ int engine_fail(aacg_pipeline* p, const char* what, int rc) { p->err = std::stri
 #define P_TRY(p, call, code) do { if (!ok((p), (call), #call)) return (code); } while (0)
 
 size_t pcm_elem(const aacg_pipeline* p) { return p->cfg.output_kind == AACG_OUTPUT_I16 ? 2 : 4; }
+/* the channels of the PCM that leaves: the mix's rows, or the transform's channels */
+uint32_t out_channels(const aacg_pipeline* p) { return p->O ? p->O : p->C; }
 
 /* a slot's layout as plans and callers see it: the learnt one (n = 0: none yet), or, C <= 2, one element of C channels */
 aacg_pipeline::layout_t layout_of(const aacg_pipeline* p, uint32_t slot)
@@ -242,7 +258,8 @@ struct batch_t {
     void* pcm_out; const aacg_pcm_device_out* dev; aacg_parse_result* results; uint32_t* n_refused;
     uint32_t n, longest;                         /* check_batch: the batch's frames, the largest count of a stream */
     uint32_t set;                                /* the lane's index: the set of a plan's unit records that is this lane's */
-    staging_t G; bool planar, direct; void* d_pcm; size_t pcm_bytes;      /* stage_batch (the per-stream table lies at G.extra_at) */
+    staging_t G; bool planar, direct; void* d_pcm;                        /* stage_batch (the per-stream table lies at G.extra_at) */
+    size_t xform_bytes, pcm_bytes;               /* what the transform writes at d_pcm, n x C, and what leaves, n x O (one size without a mix) */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
@@ -419,7 +436,7 @@ int check_device_out(aacg_pipeline* p, const aacg_pcm_device_out* out, uint32_t 
         p->err = a.type == hipMemoryTypeDevice ? "aacg_pipeline_submit_device: d_pcm is another device's memory" : "aacg_pipeline_submit_device: d_pcm is not device memory (host memory, page-locked or not)";
         return AACG_ERR_INVALID_ARG;
     }
-    const uint64_t elems = out->layout == AACG_PCM_PLANAR ? (uint64_t)n_streams * p->C * out->stride_frames * 1024u : (uint64_t)n * 1024u * p->C;
+    const uint64_t elems = out->layout == AACG_PCM_PLANAR ? (uint64_t)n_streams * out_channels(p) * out->stride_frames * 1024u : (uint64_t)n * 1024u * out_channels(p);
     const uint64_t need = elems * pcm_elem(p);
     if ((uint64_t)out->d_pcm_bytes < need) { p->err = "aacg_pipeline_submit_device: d_pcm_bytes is smaller than the batch needs (" + std::to_string(need) + " bytes)"; return AACG_ERR_CAPACITY; }
     if (out->layout == AACG_PCM_PLANAR && !aacg_planar_items(n_streams, out->stride_frames, (uint32_t)pcm_elem(p))) {
@@ -458,7 +475,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (W.st) (void)hipStreamDestroy(W.st);
     }
     for (auto& L : p->lane) {
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_mix, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
         for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.parser) aacg_parser_destroy(L.parser);
@@ -562,6 +579,62 @@ int aacg_pipeline_set_wait_limit_ms(aacg_pipeline* p, uint32_t ms)
     return AACG_OK;
 }
 
+int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* matrix)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (p->O) { p->err = "aacg_pipeline_set_mix: the pipeline has a mix already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_mix: a batch has been submitted (the mix is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (out_channels < 1 || out_channels > AACG_MIX_MAX_OUT) { p->err = "aacg_pipeline_set_mix: out_channels is not 1 or 2"; return AACG_ERR_INVALID_ARG; }
+    if (!matrix) { p->err = "aacg_pipeline_set_mix: no matrix"; return AACG_ERR_INVALID_ARG; }
+    for (uint32_t i = 0; i < out_channels * p->C; i++)
+        if (!std::isfinite(matrix[i])) { p->err = "aacg_pipeline_set_mix: coefficient " + std::to_string(i) + " of the matrix is not finite"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const size_t bytes = (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels * 1024u * pcm_elem(p);
+    for (int k = 0; k < p->n_lanes; k++)
+        if (hipMalloc(&p->lane[k].d_mix, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j <= k; j++) { if (p->lane[j].d_mix) (void)hipFree(p->lane[j].d_mix); p->lane[j].d_mix = nullptr; }
+            p->err = "aacg_pipeline_set_mix: no device memory for the lanes' mixed PCM";
+            return AACG_ERR_OUT_OF_MEMORY;
+        }
+    /* page-locked staging that a submission which failed half-way left behind has the unmixed size: it is made again, lazily */
+    for (int k = 0; k < p->n_lanes; k++) if (p->lane[k].h_pcm) { (void)hipHostFree(p->lane[k].h_pcm); p->lane[k].h_pcm = nullptr; }
+    std::memset(p->mix, 0, sizeof p->mix);
+    std::memcpy(p->mix, matrix, (size_t)out_channels * p->C * sizeof(float));
+    p->O = out_channels;
+    return AACG_OK;
+}
+
+int aacg_pipeline_out_channels(const aacg_pipeline* p) { return p ? (int)out_channels(p) : AACG_ERR_INVALID_ARG; }
+
+int aacg_mix_standard(uint32_t channels, uint32_t out_channels, float surround_gain, int normalise, float* matrix)
+{
+    /* what each position of the resident route's channel order gives the left and the right row (include/aacgpu.h has the table):
+     * F: all of it to its side, C: 1/sqrt 2 to both, S: the surround gain to its side, B: the surround gain / sqrt 2 to both, 0: nothing */
+    enum { Z, FL, FR, CC, SL, SR, BC };
+    static const uint8_t pos[9][8] = {{}, {CC}, {FL, FR}, {CC, FL, FR}, {CC, FL, FR, BC}, {CC, FL, FR, SL, SR}, {CC, FL, FR, SL, SR, Z}, {},
+                                      {CC, FL, FR, FL, FR, SL, SR, Z}};
+    if (channels < 1 || channels > 8 || channels == 7 || out_channels < 1 || out_channels > 2 || !matrix || !std::isfinite(surround_gain)) return AACG_ERR_INVALID_ARG;
+    const double a = (double)surround_gain, h = 1.0 / std::sqrt(2.0);
+    double row[2][8], sum[2] = {0.0, 0.0};
+    for (uint32_t c = 0; c < channels; c++) {
+        const int k = pos[channels][c];
+        row[0][c] = k == FL ? 1.0 : k == CC ? h : k == SL ? a : k == BC ? a * h : 0.0;
+        row[1][c] = k == FR ? 1.0 : k == CC ? h : k == SR ? a : k == BC ? a * h : 0.0;
+        sum[0] += row[0][c]; sum[1] += row[1][c];
+    }
+    if (normalise) {
+        if (!(sum[0] > 0.0) || !(sum[1] > 0.0)) return AACG_ERR_INVALID_ARG;      /* (a negative surround gain that cancels a row) */
+        for (uint32_t c = 0; c < channels; c++) { row[0][c] /= sum[0]; row[1][c] /= sum[1]; }
+    }
+    for (uint32_t c = 0; c < channels; c++) {
+        if (out_channels == 2) { matrix[c] = (float)row[0][c]; matrix[channels + c] = (float)row[1][c]; }
+        else matrix[c] = (float)((row[0][c] + row[1][c]) * 0.5);
+    }
+    return AACG_OK;
+}
+
 int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
 {
     if (!p || (int)slot >= p->cfg.max_streams) return AACG_ERR_INVALID_ARG;
@@ -613,14 +686,15 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     if (rc) return rc;
     L.d_frames = (char*)L.d_bytes + B.G.padded;
     B.planar = B.dev && B.dev->layout == AACG_PCM_PLANAR;
-    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed — the caller's in its place */
-    B.d_pcm = B.dev && !B.planar ? B.dev->d_pcm : L.d_pcm;
-    B.pcm_bytes = (size_t)B.n * p->C * 1024u * pcm_elem(p);
+    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed, and no mix in between — the caller's in its place */
+    B.d_pcm = B.dev && !B.planar && !p->O ? B.dev->d_pcm : L.d_pcm;
+    B.xform_bytes = (size_t)B.n * p->C * 1024u * pcm_elem(p);
+    B.pcm_bytes = (size_t)B.n * out_channels(p) * 1024u * pcm_elem(p);
     /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
      * lane's own page-locked staging and one host copy at collect */
     B.direct = B.dev || is_pinned(B.pcm_out);            /* (PCM left on the device: no staging either) */
     if (!B.direct && !L.h_pcm)
-        P_TRY(p, hipHostMalloc(&L.h_pcm, (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * p->C * 1024u * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
+        P_TRY(p, hipHostMalloc(&L.h_pcm, (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels(p) * 1024u * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
     return AACG_OK;
 }
 
@@ -649,7 +723,7 @@ int enqueue_front(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B)
     const uint32_t Cp = p->Cp, U = p->U;
     L.unlearnt.clear();
     if (p->learn) for (uint32_t s = 0, i = 0; s < B.n_streams; i += B.frames_of[s], s++) if (!p->layout[B.slots[s]].kept) L.unlearnt.push_back({i, B.frames_of[s]});
-    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(B.d_pcm, 0, B.pcm_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
+    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(B.d_pcm, 0, B.xform_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
     pipe_copy(L.h_in, L.d_bytes, B.G.up, st);             /* aacg_pipe_copy: not the SDMA engines, where it would queue behind other lanes' PCM */
     if (L.count_stale) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* a submission that failed half-way left its count behind */
     L.count_stale = true;
@@ -699,20 +773,31 @@ int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     return rc ? engine_fail(p, "transform: ", rc) : AACG_OK;
 }
 
-/* Step 7, the way out: the PCM (planar launch, copy down, or nothing), the results' copy, the lane's event, what finish_lane needs */
+/* Step 7, the way out: the mix if there is one, the PCM (planar launch, copy down, or nothing), the results' copy, the lane's event,
+ * what finish_lane needs */
 int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, uint64_t* ticket)
 {
+    const void* packed = L.d_pcm;                        /* what the planar launch or the copy down reads */
+    if (p->O) {
+        /* the lane's packed PCM of C channels into O: straight into a caller's packed buffer, else into the lane's d_mix */
+        aacg_mix_args M;
+        M.src = L.d_pcm; M.dst = B.dev && !B.planar ? B.dev->d_pcm : L.d_mix;
+        M.n_frames = B.n; M.channels = p->C; M.out_channels = p->O; M.elem = (uint32_t)pcm_elem(p);
+        std::memcpy(M.m, p->mix, sizeof M.m);
+        if (!aacg_mix_launch(M, L.st)) { p->err = "aacg_pcm_mix: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        packed = L.d_mix;
+    }
     if (B.planar) {
         /* the caller's tensor from the lane's packed PCM and the per-stream table that came up with the bytes (either plan mode's
          * record begins with frame_first and frames), padding included: where the copy down sits for a host batch */
         aacg_planar_args A;
-        A.src = L.d_pcm; A.dst = B.dev->d_pcm; A.tab = (const char*)L.d_bytes + B.G.extra_at;
+        A.src = packed; A.dst = B.dev->d_pcm; A.tab = (const char*)L.d_bytes + B.G.extra_at;
         A.tab_stride = (uint32_t)(p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
-        A.n_streams = B.n_streams; A.stride_frames = B.dev->stride_frames; A.channels = p->C; A.elem = (uint32_t)pcm_elem(p);
+        A.n_streams = B.n_streams; A.stride_frames = B.dev->stride_frames; A.channels = out_channels(p); A.elem = (uint32_t)pcm_elem(p);
         if (!aacg_planar_launch(A, L.st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
     } else if (!B.dev) {
         char* dst = (char*)(B.direct ? B.pcm_out : L.h_pcm);
-        P_TRY(p, hipMemcpyAsync(dst, L.d_pcm, B.pcm_bytes, hipMemcpyDeviceToHost, L.st), AACG_ERR_NO_DEVICE);      /* one SDMA copy per batch (see aacg_pipe_copy) */
+        P_TRY(p, hipMemcpyAsync(dst, packed, B.pcm_bytes, hipMemcpyDeviceToHost, L.st), AACG_ERR_NO_DEVICE);      /* one SDMA copy per batch (see aacg_pipe_copy) */
     }
     /* the results and, behind where the largest batch's would end, the refusal count: one small launch (a launch that writes to
      * host memory costs 50 us of the lane's time whatever it carries) */

@@ -394,10 +394,13 @@ GpuAACDecoder.prototype.fillBatch = function (part, blockBase, q, meta) {
 /* what a batch produced, into the queue in stream order: the frames' PCM (each its own array: the caller owns it), or the
  * engine's refusal in their place; then the parse error found behind them, if any */
 GpuAACDecoder.prototype.deliver = function (part, pcm, pcmBase, refused) {
-    const C = this.config.chanConfig;
+    const C = this.config.chanConfig, mix = this.mix;      // mix: a SharedEngine({ downmix }) decoder on the parsing route — the device's rule on the host (mix.js)
     if (part.frames.length) {
         if (refused) this.queue.push(refused);
-        else for (let i = 0; i < part.frames.length; i++) this.queue.push(pcm.slice(pcmBase + i * FRAME * C, pcmBase + (i + 1) * FRAME * C));
+        else for (let i = 0; i < part.frames.length; i++) {
+            const at = pcmBase + i * FRAME * C;
+            this.queue.push(mix ? require('./mix.js').mix(pcm.subarray(at, at + FRAME * C), C, mix.matrix, mix.outChannels) : pcm.slice(at, at + FRAME * C));
+        }
     }
     if (part.failed) this.queue.push(part.failed);
 };

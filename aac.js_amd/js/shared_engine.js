@@ -37,6 +37,11 @@
  * { resident: true, ragged: true, devicePlans: true } — ragged flushes seldom repeat a batch shape, and a kept plan per shape then
  * means a plan built, uploaded and evicted per flush; with devicePlans a pipeline has ONE plan, shaped on the device for every
  * batch (aacg_pipeline_config.plan_mode 1).  Off by default: INTEGRATION.md says when to switch it on.
+ * { resident: true, downmix: 'stereo' | 'mono' | { outChannels, matrix } } — every decoder of the engine delivers outChannels (1 or
+ * 2) channels instead of its stream's: the standard matrix for the stream's channel count (aacg_mix_standard) or the caller's, one per
+ * engine.  A resident pipeline mixes on the device (aacg_pipeline_set_mix: a 5.1 stream then costs the link what a stereo stream
+ * costs) and a decoder on the parsing route is mixed on the host by the same rule (mix.js), bit for bit; format.channelsPerFrame says
+ * outChannels either way.
  * Replaces, per batch, what src/decoder.js:125-216 does per frame.
  */
 'use strict';
@@ -64,6 +69,7 @@ function SharedEngine(opts) {
      * (lookahead frames) further ahead than they are consumed, and with pcmRing a frame is valid for one flush less.  On by
      * default since round 6 ({ overlap: false } for a flush that decodes what it returns). */
     this.overlap = opts.overlap === undefined ? this.resident : !!opts.overlap;
+    this.downmix = opts.downmix || null;                  // 'stereo' | 'mono' | { outChannels, matrix }: what every decoder delivers (mix.js)
     this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0, flushNs: 0n };   // flushNs: resident flushes, host side and native calls
 }
 
@@ -80,6 +86,10 @@ SharedEngine.prototype.attach = function (dec) {
     const cfg = dec.config;
     if (cfg.chanConfig + dec.maxCoupling > this.maxChannels) throw new Error('SharedEngine: ' + cfg.chanConfig + ' channels exceed maxChannels ' + this.maxChannels);
     if (dec.group) this.detach(dec);                       // a new cookie: a new stream
+    /* downmix: the matrix for this stream's channel count; the decoder says what it delivers, and mixes on the host where its
+     * frames do not come from a resident pipeline (GpuAACDecoder.deliver) */
+    dec.mix = this.downmix ? require('./mix.js').resolve(this.downmix, cfg.chanConfig, this.opts.addon || host.loadAddon()) : null;
+    if (dec.mix) dec.format.channelsPerFrame = dec.mix.outChannels;
     if (this.takesResident(dec)) return this.attachResident(dec);
     let g = this.groups.get(cfg.sampleIndex);
     if (!g) {
@@ -121,13 +131,15 @@ SharedEngine.prototype.attachResident = function (dec) {
     if (!g) {
         const addon = this.opts.addon || host.loadAddon(), rec = require('./codebooks.js').load(this.opts).toEntryRecords();
         const outI16 = (this.opts.outputKind | 0) === host.OUTPUT_I16;
-        const pipeline = addon.pipelineCreate({ deviceOrdinal: this.opts.deviceOrdinal | 0, sampleIndex: cfg.sampleIndex, maxStreams: this.maxStreams,
-                                                channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
-                                                parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0),
-                                                planMode: this.devicePlans ? 1 : 0,
-                                                stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) | (this.opts.carryWindowShape ? 4 : 0) },
-                                              rec.entries, rec.counts);
-        g = { resident: true, addon: addon, pipeline: pipeline, channels: cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
+        const create = { deviceOrdinal: this.opts.deviceOrdinal | 0, sampleIndex: cfg.sampleIndex, maxStreams: this.maxStreams,
+                         channels: cfg.chanConfig, maxFrames: this.lookahead, outputKind: this.opts.outputKind | 0,
+                         parseOptions: (this.opts.applyPulses ? 1 : 0) | (this.opts.referenceQuirks !== false ? 2 : 0),
+                         planMode: this.devicePlans ? 1 : 0,
+                         stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) | (this.opts.carryWindowShape ? 4 : 0) };
+        if (dec.mix) create.mix = { outChannels: dec.mix.outChannels, matrix: dec.mix.matrix };      // mixed on the device: outChannels leave
+        const pipeline = addon.pipelineCreate(create, rec.entries, rec.counts);
+        /* channels: of the PCM that comes back — what sizes a flush's PCM and slices it into frames */
+        g = { resident: true, addon: addon, pipeline: pipeline, channels: dec.mix ? dec.mix.outChannels : cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }
     const slot = g.free.length ? g.free.pop() : g.next++;

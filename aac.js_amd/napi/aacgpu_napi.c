@@ -62,6 +62,9 @@ static struct {
     int  (*pipeline_walk_submit)(aacg_pipeline*, const uint8_t*, size_t, const aacg_parse_frame*, uint32_t, uint32_t, aacg_parse_frame*,
                                  aacg_walk_result*, uint64_t*);
     int  (*pipeline_walk_collect)(aacg_pipeline*, uint64_t);
+    int  (*pipeline_set_mix)(aacg_pipeline*, uint32_t, const float*);
+    int  (*pipeline_out_channels)(const aacg_pipeline*);
+    int  (*mix_standard)(uint32_t, uint32_t, float, int, float*);
     void* (*host_alloc)(size_t);
     void (*host_free)(void*);
 } L;
@@ -102,6 +105,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_plan_builds, "aacg_pipeline_plan_builds");
     SYM(pipeline_launch_counts, "aacg_pipeline_launch_counts");
     SYM(pipeline_walk_submit, "aacg_pipeline_walk_submit"); SYM(pipeline_walk_collect, "aacg_pipeline_walk_collect");
+    SYM(pipeline_set_mix, "aacg_pipeline_set_mix"); SYM(pipeline_out_channels, "aacg_pipeline_out_channels"); SYM(mix_standard, "aacg_mix_standard");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
     return 1;
@@ -513,8 +517,10 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     free(b);
 }
 
-/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages}, entries, counts) -> external
- * (planMode 1: device plans, aacg_pipeline_config.plan_mode; stages: AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS | AACG_PIPELINE_STAGE_WINDOW_SHAPE,
+/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix}, entries, counts) -> external
+ * (mix: { outChannels: 1 | 2, matrix: Float32Array(outChannels * channels) } — aacg_pipeline_set_mix before the call returns: the PCM is
+ * mixed on the device and outChannels channels leave; a refused mix destroys the pipeline and throws with the reason;
+ * planMode 1: device plans, aacg_pipeline_config.plan_mode; stages: AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS | AACG_PIPELINE_STAGE_WINDOW_SHAPE,
  * aacg_pipeline_config.stages — bit 2 carries each channel's window shape from frame to frame on the device) */
 static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
 {
@@ -548,6 +554,20 @@ static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
         snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_create failed (%d) (is a GPU visible?)", rc);
         napi_throw_error(env, NULL, msg);
         return NULL;
+    }
+    {
+        napi_value mix; bool has = false; napi_valuetype vt = napi_undefined;
+        if (napi_has_named_property(env, argv[0], "mix", &has) == napi_ok && has && napi_get_named_property(env, argv[0], "mix", &mix) == napi_ok &&
+            napi_typeof(env, mix, &vt) == napi_ok && vt == napi_object) {
+            const int32_t oc = get_i32(env, mix, "outChannels", 0);
+            napi_value mv; napi_typedarray_type tm; size_t nm = 0; void* dm = NULL;
+            char msg[1024] = "";
+            if (napi_get_named_property(env, mix, "matrix", &mv) != napi_ok || !typed(env, mv, &tm, &nm, &dm) || tm != napi_float32_array || oc < 0 || nm != (size_t)oc * (size_t)cfg.channels)
+                snprintf(msg, sizeof msg, "pipelineCreate: mix is { outChannels, matrix: Float32Array(outChannels * channels) }");
+            else if ((rc = L.pipeline_set_mix(p, (uint32_t)oc, (const float*)dm)))
+                snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_mix failed (%d): %.800s", rc, L.pipeline_last_error(p));
+            if (msg[0]) { L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL; }
+        }
     }
     handle_box* b = box_new(BOX_PIPELINE, p);
     if (!b) { L.pipeline_destroy(p); napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
@@ -727,6 +747,10 @@ static pipe_job* pipe_prepare(napi_env env, napi_callback_info info, int keep_ar
         !typed(env, argv[5], &t, &nr, &dr) || t != napi_uint8_array || nr != total * sizeof(aacg_parse_result)) {
         napi_throw_type_error(env, NULL, "pipelineDecode(pipeline, Uint8Array bytes, Uint32Array frames (2 per frame), Uint32Array slots, framesPerStream | Uint32Array counts (one per stream), Uint8Array results (8 per frame), channels)");
         return NULL;
+    }
+    {   /* the PCM's size follows the pipeline: the mix's channels where it has one (aacg_pipeline_out_channels) */
+        const int oc = L.pipeline_out_channels((const aacg_pipeline*)pb->ptr);
+        if (oc > 0) C = (uint32_t)oc;
     }
     const size_t elems = total * 1024u * C, bytes = elems * (pb->out_i16 ? 2u : 4u);
     size_t got = 0;
@@ -972,6 +996,39 @@ static napi_value js_pipeline_stream_window_shape(napi_env env, napi_callback_in
     return out;
 }
 
+/* pipelineOutChannels(pipeline) -> the channels of the PCM the pipeline delivers (aacg_pipeline_out_channels) */
+static napi_value js_pipeline_out_channels(napi_env env, napi_callback_info info)
+{
+    size_t argc = 1; napi_value argv[1], out;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_box* pb = box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle");
+    if (!pb) return NULL;
+    CHECK(env, napi_create_int32(env, L.pipeline_out_channels((const aacg_pipeline*)pb->ptr), &out));
+    return out;
+}
+
+/* mixStandard(channels, outChannels, surroundGain, normalise) -> Float32Array(outChannels * channels): the project's standard downmix
+ * (aacg_mix_standard, include/aacgpu.h has the table); host code, no device */
+static napi_value js_mix_standard(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4; napi_value argv[4], ab, out;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (!L.dl) { napi_throw_error(env, NULL, "aacgpu: call load(path) first"); return NULL; }
+    uint32_t ch = 0, oc = 0; double gain = 0.70710678118654752440; bool norm = true;
+    if (argc < 2 || napi_get_value_uint32(env, argv[0], &ch) != napi_ok || napi_get_value_uint32(env, argv[1], &oc) != napi_ok ||
+        (argc >= 3 && napi_get_value_double(env, argv[2], &gain) != napi_ok) || (argc >= 4 && napi_coerce_to_bool(env, argv[3], &argv[3]) != napi_ok) ||
+        (argc >= 4 && napi_get_value_bool(env, argv[3], &norm) != napi_ok)) {
+        napi_throw_type_error(env, NULL, "mixStandard(channels, outChannels [, surroundGain, normalise])"); return NULL; }
+    float m[16];
+    const int rc = L.mix_standard(ch, oc, (float)gain, norm ? 1 : 0, m);
+    if (rc) { char msg[128]; snprintf(msg, sizeof msg, "aacgpu: aacg_mix_standard failed (%d)", rc); napi_throw_error(env, NULL, msg); return NULL; }
+    void* data = NULL;
+    CHECK(env, napi_create_arraybuffer(env, (size_t)ch * oc * sizeof(float), &data, &ab));
+    memcpy(data, m, (size_t)ch * oc * sizeof(float));
+    CHECK(env, napi_create_typedarray(env, napi_float32_array, (size_t)ch * oc, ab, 0, &out));
+    return out;
+}
+
 /* pipelinePlanBuilds(pipeline) -> how many plans the pipeline has built (one per batch shape it had not kept; aacgpu_tools.h) */
 static napi_value js_pipeline_plan_builds(napi_env env, napi_callback_info info)
 {
@@ -1039,6 +1096,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelineResetStream", NULL, js_pipeline_reset_stream, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineStreamWindowShape", NULL, js_pipeline_stream_window_shape, NULL, NULL, NULL, napi_default, NULL},
         {"pipelinePlanBuilds", NULL, js_pipeline_plan_builds, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelineOutChannels", NULL, js_pipeline_out_channels, NULL, NULL, NULL, napi_default, NULL},
+        {"mixStandard", NULL, js_mix_standard, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineLaunchCounts", NULL, js_pipeline_launch_counts, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkCollect", NULL, js_pipeline_walk_collect, NULL, NULL, NULL, napi_default, NULL},

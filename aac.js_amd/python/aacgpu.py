@@ -36,7 +36,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_walk_submit", "aacg_pipeline_walk_collect", "aacg_pipeline_decode_ragged", "aacg_pipeline_submit_ragged",
                "aacg_plan_create_shaped", "aacg_plan_create_shaped_stages", "aacg_plan_shape_table", "aacg_plan_shape_launch",
                "aacg_get_window_shape", "aacg_set_window_shape", "aacg_plan_carry_window_shape", "aacg_pipeline_stream_window_shape",
-               "aacg_pipeline_submit_device", "aacg_pipeline_wait_device"]
+               "aacg_pipeline_submit_device", "aacg_pipeline_wait_device",
+               "aacg_pipeline_set_mix", "aacg_pipeline_out_channels", "aacg_mix_standard"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -270,6 +271,9 @@ def load_library(path=LIB_PATH):
     L.aacg_plan_shape_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.aacg_pipeline_set_wait_limit_ms.argtypes = [C.c_void_p, C.c_uint32]
     L.aacg_pipeline_stream_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.aacg_pipeline_set_mix.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.aacg_pipeline_out_channels.argtypes = [C.c_void_p]
+    L.aacg_mix_standard.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -460,11 +464,13 @@ PARSE_LAYOUT = 16          # AACG_PARSE_LAYOUT: a frame whose elements are not i
 class Pipeline:
     """aacg_pipeline: bytes in, PCM out — device front end and transform behind one call per batch, `lanes` batches in flight
     (include/aacgpu.h).  channels = the streams' chanConfig (1..8).  device_plans: ONE plan shaped on the device for every batch
-    (aacg_pipeline_config.plan_mode 1) instead of a kept plan per batch shape: for feeds whose batches seldom repeat a shape."""
+    (aacg_pipeline_config.plan_mode 1) instead of a kept plan per batch shape: for feeds whose batches seldom repeat a shape.
+    mix: an (O, C) float matrix, O = 1 or 2 (aacg_pipeline_set_mix; mix_standard makes the usual one): the PCM is mixed on the device and
+    O channels leave — self.channels is then O wherever PCM is sized, self.in_channels stays C."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False):
+                 carry_window_shape=False, mix=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -478,7 +484,18 @@ class Pipeline:
             raise AacgError(rc, "aacg_pipeline_create failed (no GPU?%s)" % (" or no room for the device plan's buffers: see stderr" if device_plans else ""))
         self.device_plans = bool(device_plans)
         self.handle, self.channels, self.i16, self.device = h, channels, output_kind == OUTPUT_I16, device
+        self.in_channels = channels
         self._keep = {}
+        if mix is not None:
+            m = np.ascontiguousarray(mix, np.float32)
+            if m.ndim != 2 or m.shape[1] != channels:
+                self.close()
+                raise ValueError("Pipeline: mix is not an (O, %d) matrix" % channels)
+            try:
+                self.set_mix(m)
+            except AacgError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "handle", None):
@@ -514,6 +531,13 @@ class Pipeline:
     def reset_stream(self, slot):
         self._check(self.lib.aacg_pipeline_reset_stream(self.handle, slot))
 
+    def set_mix(self, matrix):
+        """aacg_pipeline_set_mix: an (O, C) float matrix, O = 1 or 2, before the first batch; from then on O channels leave."""
+        m = np.ascontiguousarray(matrix, np.float32)
+        assert m.ndim == 2 and m.shape[1] == self.in_channels
+        self._check(self.lib.aacg_pipeline_set_mix(self.handle, m.shape[0], m.ctypes.data))
+        self.channels = int(self.lib.aacg_pipeline_out_channels(self.handle))
+
     def stream_layout(self, slot):
         """(channels of every element of the slot's frames, how many of the elements are decoded); ([], 0) before it is learnt."""
         ch, kept = np.zeros(8, np.uint8), C.c_uint32()
@@ -527,7 +551,7 @@ class Pipeline:
         zeros otherwise).  Finishes the batches in flight first."""
         sh = np.zeros(8, np.uint8)
         self._check(self.lib.aacg_pipeline_stream_window_shape(self.handle, slot, sh.ctypes.data))
-        return [int(v) for v in sh[:self.channels]]
+        return [int(v) for v in sh[:self.in_channels]]
 
     def plan_builds(self):
         """how many plans the pipeline has built (one per batch shape it had not kept)"""
@@ -640,7 +664,8 @@ class Pipeline:
         self._check(self.lib.aacg_pipeline_wait_device(self.handle, ticket, C.c_void_p(int(stream) or None)))
 
     def decode_tensor(self, data, frames, slots, frames_per_stream, planar=True):
-        """One batch into a new torch tensor on the pipeline's device -> (tensor, lengths, results, n_refused).  planar:
+        """One batch into a new torch tensor on the pipeline's device -> (tensor, lengths, results, n_refused).  C below is
+        self.channels: the channels that leave, O for a pipeline with a mix.  planar:
         (B, C, max count * 1024) with lengths[s] = count * 1024 samples of stream s and zeros behind them; packed: (n, 1024, C),
         the n frames stream after stream.  The tensor is torch's current stream's: that stream is synchronised before the batch is
         submitted, because the allocator may hand out a block whose previous user's kernels are still queued there and the lane's
@@ -656,6 +681,16 @@ class Pipeline:
         self.wait_device(t)
         out, res, refused = self.collect(t)
         return out, counts.astype(np.int64) * 1024, res, refused
+
+
+def mix_standard(channels, out_channels, surround_gain=2 ** -0.5, normalise=True):
+    """The project's standard downmix (aacg_mix_standard, include/aacgpu.h has the table) as an (out_channels, channels) float32 matrix
+    for Pipeline(mix=...): host code, no device."""
+    m = np.zeros((int(out_channels), int(channels)), np.float32)
+    rc = load_library().aacg_mix_standard(int(channels), int(out_channels), float(surround_gain), 1 if normalise else 0, m.ctypes.data)
+    if rc != 0:
+        raise AacgError(rc, "aacg_mix_standard(%d channels to %d)" % (channels, out_channels))
+    return m
 
 
 class Plan:

@@ -840,6 +840,39 @@ int  aacg_pipeline_stream_layout(aacg_pipeline* p, uint32_t slot, uint8_t elemen
  * without it): shapes[c] for c < channels, 0 behind them.  Finishes the batches in flight first (bounded, as
  * aacg_pipeline_reset_stream). */
 int  aacg_pipeline_stream_window_shape(aacg_pipeline* p, uint32_t slot, uint8_t shapes[8]);
+/* A mix on the device: O = out_channels (1 or 2) channels leave a pipeline made for C = channels, so that a surround stream costs the
+ * link what a stereo stream costs.  matrix is M, O rows of C floats, row-major.  THE RULE, bit for bit: for every sample t of every
+ * frame a batch decodes and every output channel o, in float32 throughout,
+ *     acc = M[o][0] * x[0]                           (rounded to float)
+ *     acc = acc + (M[o][c] * x[c])    c = 1 .. C-1   (the product rounded, then the sum rounded: NOT fused, in this order)
+ * Every term is computed, also those with a zero coefficient.  x[c] is the sample the unmixed pipeline would have delivered in channel
+ * c, by position: channel c of a frame's PCM, whatever the stream's layout covers — a stream whose learnt layout covers fewer
+ * channels than `channels` is mixed by position all the same, its uncovered channels are zeros.  numpy float32 arithmetic reproduces
+ * the result exactly.
+ *   AACG_OUTPUT_F32: out[o] = acc, no clamp.
+ *   AACG_OUTPUT_I16: x[c] is the int16 sample converted to float (exact) — the ALREADY ROUNDED int16 the unmixed pipeline delivers, not
+ *     the transform's float before its rounding — and out[o] is acc rounded to nearest even and saturated to [-32768, 32767].
+ * Output layouts: as described above with O in the place of `channels` — host PCM and AACG_PCM_PACKED [first_s + f][1024][O],
+ * AACG_PCM_PLANAR [stream][O][stride_frames * 1024] with its padding written; d_pcm_bytes and the host buffer need n x 1024 x O
+ * (n_streams x O x stride_frames x 1024) elements.  A refused frame and a frame of an unlearnt stream are the mix of zeros.
+ * Results, refusal counts, tickets, lanes, plan modes, `stages`, ragged batches and span walks are untouched: one more launch per
+ * batch (aacg_pcm_mix_*) on the lane's stream, behind the transform, and with no mix set nothing differs.
+ * Called once, before the pipeline's first submitted batch.  AACG_ERR_INVALID_ARG, with the reason in aacg_pipeline_last_error and the
+ * pipeline exactly as it was: out_channels not 1 or 2, a null matrix, a coefficient that is not finite, a call after the first batch,
+ * a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the lanes' mixed PCM; the pipeline stays unmixed. */
+int  aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* matrix);
+/* The channels of the PCM the pipeline delivers: O with a mix set, `channels` otherwise. */
+int  aacg_pipeline_out_channels(const aacg_pipeline* p);
+/* The project's standard downmix for aacg_pipeline_set_mix, host code only (no device, no pipeline): matrix receives out_channels x
+ * channels floats for the positions the resident route deals out, the element order of channel_configuration:
+ *     channels 1: [C]            2: [L R]            3: [C L R]            4: [C L R Cs]
+ *              5: [C L R Ls Rs]  6: [C L R Ls Rs LFE]                      8: [C Lc Rc L R Ls Rs LFE]        (7: AACG_ERR_INVALID_ARG)
+ * Left row, with a = surround_gain: L and Lc 1, C 1/sqrt(2), Ls a, Cs a/sqrt(2), everything else 0 — the LFE included; the right row
+ * mirrors it (R, Rc, C, Rs, Cs).  normalise != 0 divides each row by its sum (5.1 with a = 1/sqrt(2): the familiar 1 / (1 + 1/sqrt(2)
+ * + 1/sqrt(2))).  out_channels 1: the one row (left + right) / 2.  Computed in double, each coefficient rounded to float once.  The
+ * table is positional, like the mix.  AACG_ERR_INVALID_ARG: channels 0, 7 or above 8, out_channels not 1 or 2, a null matrix, a gain
+ * that is not finite (or, with normalise, one that leaves a row without a positive sum). */
+int  aacg_mix_standard(uint32_t channels, uint32_t out_channels, float surround_gain, int normalise, float* matrix);
 
 #ifdef __cplusplus
 }

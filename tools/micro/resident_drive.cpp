@@ -6,7 +6,12 @@
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
- *                                         [--carry-shape] [--device-pcm [--planar]]
+ *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2]
+ *
+ * --mix O: the standard downmix to O = 1 or 2 channels on the device (aacg_mix_standard with a surround gain of 1/sqrt 2, normalised;
+ * aacg_pipeline_set_mix): one more launch per batch (aacg_pcm_mix_*), and O channels of PCM leave in the place of the stream's.  The
+ * line then carries the channels that leave and a device-to-device aacg_calib_copy of the UNMIXED PCM's bytes — what the mix kernel
+ * reads — timed in the same run: what its time in a kernel trace is read against.  Combines with everything else.
  *
  * --device-pcm: the PCM left on the device (aacg_pipeline_submit_device, AACG_PCM_PACKED: the transform writes the caller's buffer);
  * with --planar AACG_PCM_PLANAR, stride_frames = F (one more launch per batch, aacg_pcm_planar).  One device buffer per lane; nothing
@@ -51,6 +56,7 @@ int main(int argc, char** argv)
     int batches = 200, lanes = 3;
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
+    uint32_t mix = 0;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -69,6 +75,7 @@ int main(int argc, char** argv)
         else if (a == "--carry-shape") carry_shape = true;
         else if (a == "--device-pcm") device_pcm = true;
         else if (a == "--planar") planar = true;
+        else if (a == "--mix") mix = (uint32_t)std::atoi(val());
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -109,7 +116,13 @@ int main(int argc, char** argv)
     aacg_pipeline* p = nullptr;
     int rc = aacg_pipeline_create(&cfg, entries.data(), counts, &p);
     if (rc) { std::fprintf(stderr, "aacg_pipeline_create: %d\n", rc); return 2; }
-    const size_t pcm_bytes = (size_t)S * F * 1024 * channels * (i16 ? 2 : 4);
+    if (mix) {
+        float m[16];
+        if ((rc = aacg_mix_standard(channels, mix, 0.70710678118654752440f, 1, m))) { std::fprintf(stderr, "aacg_mix_standard(%u, %u): %d\n", channels, mix, rc); return 2; }
+        if ((rc = aacg_pipeline_set_mix(p, mix, m))) { std::fprintf(stderr, "aacg_pipeline_set_mix: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
+    const uint32_t out_channels = (uint32_t)aacg_pipeline_out_channels(p);      /* what leaves: the mix's rows, or the stream's channels */
+    const size_t pcm_bytes = (size_t)S * F * 1024 * out_channels * (i16 ? 2 : 4), unmixed_bytes = (size_t)S * F * 1024 * channels * (i16 ? 2 : 4);
     const int n_out = 4;
     void* out[n_out];
     for (auto& o : out) { o = pageable ? std::malloc(pcm_bytes) : aacg_host_alloc(pcm_bytes); if (!o) { std::fprintf(stderr, "allocation failed\n"); return 2; } std::memset(o, 0, pcm_bytes); }
@@ -174,21 +187,28 @@ int main(int argc, char** argv)
     std::sort(ms.begin(), ms.end());
     /* --device-pcm: what a device-to-device copy of a batch's PCM bytes takes here and now, and — outside the timed region — the last
      * warm buffer down for the output check (planar rows are as long as the packed frames of a stream when every stream brings F) */
-    double copy_us = 0;
-    if (device_pcm) {
-        void* spare = nullptr;
+    double copy_us = 0, unmixed_copy_us = 0;
+    /* a device-to-device aacg_calib_copy of `bytes` between two spare buffers (or from `from`), 20 launches between two events */
+    auto calib = [&](size_t bytes, const void* from) -> double {
+        void *spare = nullptr, *src = nullptr;
         hipEvent_t e0, e1;
         float span = 0;
-        if (hipMalloc(&spare, pcm_bytes) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); return 2; }
-        (void)aacg_calib_copy(spare, dev[0], pcm_bytes, nullptr);
+        if (hipMalloc(&spare, bytes) != hipSuccess || (!from && (hipMalloc(&src, bytes) != hipSuccess || hipMemset(src, 0, bytes) != hipSuccess)) ||
+            hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { std::fprintf(stderr, "hipMalloc failed\n"); std::exit(2); }
+        if (!from) from = src;
+        (void)aacg_calib_copy(spare, from, bytes, nullptr);
         (void)hipEventRecord(e0, nullptr);
-        for (int i = 0; i < 20; i++) (void)aacg_calib_copy(spare, dev[0], pcm_bytes, nullptr);
+        for (int i = 0; i < 20; i++) (void)aacg_calib_copy(spare, from, bytes, nullptr);
         (void)hipEventRecord(e1, nullptr);
-        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&span, e0, e1) != hipSuccess) { std::fprintf(stderr, "the calibration copy failed\n"); return 2; }
-        copy_us = span * 1e3 / 20.0;
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&span, e0, e1) != hipSuccess) { std::fprintf(stderr, "the calibration copy failed\n"); std::exit(2); }
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(spare); if (src) (void)hipFree(src);
+        return span * 1e3 / 20.0;
+    };
+    if (device_pcm) {
+        copy_us = calib(pcm_bytes, dev[0]);
         if (hipMemcpy(out[0], dev[0], pcm_bytes, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 2; }
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(spare);
     }
+    if (mix) unmixed_copy_us = calib(unmixed_bytes, nullptr);
     bool finite = true, nonzero = false;
     uint32_t bad = 0;
     for (int k = 0; k < n_out; k++) bad += refused[k];
@@ -196,13 +216,15 @@ int main(int argc, char** argv)
     else { const int16_t* w = (const int16_t*)out[0]; for (size_t i = 0; i < pcm_bytes / 2; i += 97) nonzero = nonzero || w[i] != 0; }
     char copy_key[64] = "";                                 /* only where it was measured: the host-PCM modes' lines are as they were */
     if (device_pcm) std::snprintf(copy_key, sizeof copy_key, "\"d2d_copy_of_pcm_us\": %.2f, ", copy_us);
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s"
+    char mix_key[128] = "";                                 /* --mix only */
+    if (mix) std::snprintf(mix_key, sizeof mix_key, "\"mix_out_channels\": %u, \"unmixed_pcm_bytes_per_batch\": %zu, \"d2d_copy_of_unmixed_pcm_us\": %.2f, ", out_channels, unmixed_bytes, unmixed_copy_us);
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
