@@ -57,8 +57,20 @@
  * and what leaves, n x O (pcm_bytes, h_pcm, finish_lane's copy, check_device_out's need).  Without a matrix the two are one and no call
  * or launch differs.
  *
+ * A resampler (aacg_pipeline_set_resample): a rational factor L / M and its polyphase table; each stream's PCM leaves at the new rate,
+ * a ragged count of samples per stream.  The transform then ALWAYS writes the lane's d_pcm (and the mix the lane's d_mix), and one
+ * launch of aacg_pcm_resample_* (aacg_pcm_resample.h, aacg_engine_resample.hip) behind them writes what leaves, packed or planar: into
+ * the caller's d_pcm for a device batch, else into the lane's d_rs, which the copy down reads — the planar kernel, which counts in
+ * frames, has no part.  A batch has a THIRD size from there on: the transform's n x C, the mix's n x O, and what leaves, sum n_out[s] x
+ * O (pcm_bytes, h_pcm, finish_lane's copy, check_device_out's need).  The resampler has state per slot — a clock, kept here modulo M,
+ * and on the device the last T - 1 samples per channel, double-buffered — which consecutive batches hand on ACROSS lanes: an event
+ * behind every resample launch, awaited by the next batch's on its own stream behind that lane's parse and transform (the order
+ * aacg_units_carry_shape's launches have from the engine).  Clocks and parities advance when a batch has been enqueued, not before.
+ * The per-stream records travel up in the lane's one staging block, behind the per-stream table.  Without a resampler no call or
+ * launch differs.
+ *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
- * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h for the tables it fills and the side launches it makes).
+ * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h for the tables it fills and the side launches it makes).
  */
 #include <hip/hip_runtime.h>
 
@@ -73,6 +85,7 @@
 #include "../../include/aacgpu_tools.h"
 #include "aacg_pcm_mix.h"
 #include "aacg_pcm_planar.h"
+#include "aacg_pcm_resample.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
@@ -85,6 +98,8 @@
 bool aacg_planar_launch(const aacg_planar_args& A, hipStream_t s);
 /* aacg_engine_mix.hip: a batch's packed PCM mixed to one or two channels (aacg_pcm_mix.h); false: not a launch it serves */
 bool aacg_mix_launch(const aacg_mix_args& A, hipStream_t s);
+/* aacg_engine_resample.hip: a batch's packed PCM resampled by L / M (aacg_pcm_resample.h); false: not a launch it serves */
+bool aacg_resample_launch(const aacg_resample_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -125,6 +140,16 @@ struct aacg_pipeline {
     uint32_t C = 2;                     /* channels of a frame's PCM (chanConfig) */
     uint32_t O = 0;                     /* aacg_pipeline_set_mix: channels that leave (1 or 2); 0: no mix, C leave */
     float mix[AACG_MIX_MAX_OUT * AACG_MIX_MAX_IN] = {};      /* M[o][c] at mix[o * C + c] */
+    /* aacg_pipeline_set_resample: L / M and the table's taps (L = 0: no resampler), the table and the slots' histories on the device
+     * ([slot][2][T - 1][channels out] floats), and per slot what the host keeps: the clock modulo M, which history buffer the slot's
+     * next batch reads, and whether it has consumed anything since its reset.  last: the event behind the latest resample launch */
+    struct resample_t {
+        uint32_t L = 0, M = 0, T = 0;
+        void *d_table = nullptr, *d_hist = nullptr;
+        std::vector<uint32_t> n0; std::vector<uint8_t> parity, fresh;
+        hipEvent_t last = nullptr;
+        size_t lane_elems = 0;          /* the largest batch's output: elements of a lane's d_rs and h_pcm */
+    } rs;
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -151,6 +176,8 @@ struct aacg_pipeline {
          * parser per lane the parses of consecutive batches run side by side. */
         void *d_bytes = nullptr, *d_frames = nullptr, *d_units = nullptr, *d_q = nullptr, *d_meta = nullptr, *d_res = nullptr, *d_pcm = nullptr, *d_refused = nullptr;
         void* d_mix = nullptr;            /* aacg_pipeline_set_mix: the mixed PCM of a host or planar batch, max_streams x max_frames x 1024 x O elements */
+        void* d_rs = nullptr;             /* aacg_pipeline_set_resample: the resampled PCM of a host batch, rs.lane_elems elements */
+        hipEvent_t rs_done = nullptr;     /* ... and the event behind this lane's latest resample launch */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
          * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
@@ -196,6 +223,12 @@ int engine_fail(aacg_pipeline* p, const char* what, int rc) { p->err = std::stri
 size_t pcm_elem(const aacg_pipeline* p) { return p->cfg.output_kind == AACG_OUTPUT_I16 ? 2 : 4; }
 /* the channels of the PCM that leaves: the mix's rows, or the transform's channels */
 uint32_t out_channels(const aacg_pipeline* p) { return p->O ? p->O : p->C; }
+/* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M) */
+uint32_t resample_count(const aacg_pipeline* p, uint32_t n0, uint32_t frames)
+{
+    const uint64_t L = p->rs.L, M = p->rs.M, n1 = (uint64_t)n0 + 1024ull * frames;
+    return (uint32_t)((n1 * L + M - 1u) / M - ((uint64_t)n0 * L + M - 1u) / M);
+}
 
 /* a slot's layout as plans and callers see it: the learnt one (n = 0: none yet), or, C <= 2, one element of C channels */
 aacg_pipeline::layout_t layout_of(const aacg_pipeline* p, uint32_t slot)
@@ -259,7 +292,10 @@ struct batch_t {
     uint32_t n, longest;                         /* check_batch: the batch's frames, the largest count of a stream */
     uint32_t set;                                /* the lane's index: the set of a plan's unit records that is this lane's */
     staging_t G; bool planar, direct; void* d_pcm;                        /* stage_batch (the per-stream table lies at G.extra_at) */
-    size_t xform_bytes, pcm_bytes;               /* what the transform writes at d_pcm, n x C, and what leaves, n x O (one size without a mix) */
+    size_t xform_bytes, mix_bytes, pcm_bytes;    /* what the transform writes at d_pcm, n x C; what the mix leaves, n x O; what leaves the pipeline: that, or — a resampler — sum n_out x O */
+    std::vector<aacg_resample_stream> rs;        /* check_batch, a resampler: the batch's records (what each stream emits, from the host's clocks) */
+    uint64_t rs_total;                           /* ... and the sum of their n_out */
+    size_t rs_at;                                /* stage_batch: where the records lie in the staging block */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
@@ -423,23 +459,29 @@ int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, const aacg_parse_frame
 
 /* aacg_pipeline_submit_device's own refusals, for a batch of n frames in n_streams streams whose largest count is `longest`: all on
  * the host, before anything is enqueued */
-int check_device_out(aacg_pipeline* p, const aacg_pcm_device_out* out, uint32_t n, uint32_t n_streams, uint32_t longest)
+int check_device_out(aacg_pipeline* p, const aacg_pcm_device_out* out, uint32_t n, uint32_t n_streams, uint32_t longest, const batch_t& B)
 {
+    const bool resampled = p->rs.L != 0;                 /* the rows hold samples at the new rate: B.rs has each stream's count, B.rs_total their sum */
     if (!out || !out->d_pcm) { p->err = "aacg_pipeline_submit_device: no device memory for the PCM (out or out->d_pcm is null)"; return AACG_ERR_INVALID_ARG; }
     if ((uintptr_t)out->d_pcm & 15u) { p->err = "aacg_pipeline_submit_device: d_pcm is not 16-byte aligned"; return AACG_ERR_INVALID_ARG; }
     if (out->layout != AACG_PCM_PACKED && out->layout != AACG_PCM_PLANAR) { p->err = "aacg_pipeline_submit_device: unknown layout (AACG_PCM_PACKED or AACG_PCM_PLANAR)"; return AACG_ERR_INVALID_ARG; }
     if (out->layout == AACG_PCM_PACKED && out->stride_frames) { p->err = "aacg_pipeline_submit_device: AACG_PCM_PACKED takes stride_frames 0"; return AACG_ERR_INVALID_ARG; }
-    if (out->layout == AACG_PCM_PLANAR && out->stride_frames < longest) { p->err = "aacg_pipeline_submit_device: stride_frames is below the batch's largest frame count"; return AACG_ERR_INVALID_ARG; }
+    if (out->layout == AACG_PCM_PLANAR && !resampled && out->stride_frames < longest) { p->err = "aacg_pipeline_submit_device: stride_frames is below the batch's largest frame count"; return AACG_ERR_INVALID_ARG; }
+    if (out->layout == AACG_PCM_PLANAR && resampled) {
+        if (!out->stride_frames || out->stride_frames > (1u << 21)) { p->err = "aacg_pipeline_submit_device: stride_frames is not in 1..2^21"; return AACG_ERR_INVALID_ARG; }
+        for (const auto& r : B.rs)
+            if ((uint64_t)out->stride_frames * 1024u < r.n_out) { p->err = "aacg_pipeline_submit_device: stride_frames x 1024 is below a stream's resampled count (aacg_pipeline_out_samples)"; return AACG_ERR_INVALID_ARG; }
+    }
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, out->d_pcm) != hipSuccess) { (void)hipGetLastError(); p->err = "aacg_pipeline_submit_device: d_pcm is not memory the HIP runtime knows (pageable host memory?)"; return AACG_ERR_INVALID_ARG; }
     if (a.type != hipMemoryTypeDevice || a.device != p->cfg.device_ordinal) {
         p->err = a.type == hipMemoryTypeDevice ? "aacg_pipeline_submit_device: d_pcm is another device's memory" : "aacg_pipeline_submit_device: d_pcm is not device memory (host memory, page-locked or not)";
         return AACG_ERR_INVALID_ARG;
     }
-    const uint64_t elems = out->layout == AACG_PCM_PLANAR ? (uint64_t)n_streams * out_channels(p) * out->stride_frames * 1024u : (uint64_t)n * 1024u * out_channels(p);
+    const uint64_t elems = out->layout == AACG_PCM_PLANAR ? (uint64_t)n_streams * out_channels(p) * out->stride_frames * 1024u : (resampled ? B.rs_total : (uint64_t)n * 1024u) * out_channels(p);
     const uint64_t need = elems * pcm_elem(p);
     if ((uint64_t)out->d_pcm_bytes < need) { p->err = "aacg_pipeline_submit_device: d_pcm_bytes is smaller than the batch needs (" + std::to_string(need) + " bytes)"; return AACG_ERR_CAPACITY; }
-    if (out->layout == AACG_PCM_PLANAR && !aacg_planar_items(n_streams, out->stride_frames, (uint32_t)pcm_elem(p))) {
+    if (out->layout == AACG_PCM_PLANAR && !resampled && !aacg_planar_items(n_streams, out->stride_frames, (uint32_t)pcm_elem(p))) {
         p->err = "aacg_pipeline_submit_device: n_streams x stride_frames is more than one aacg_pcm_planar launch addresses"; return AACG_ERR_CAPACITY;
     }
     return AACG_OK;
@@ -475,11 +517,13 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (W.st) (void)hipStreamDestroy(W.st);
     }
     for (auto& L : p->lane) {
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_mix, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_mix, L.d_rs, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
         for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
+        if (L.rs_done) (void)hipEventDestroy(L.rs_done);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
+    for (void* d : {p->rs.d_table, p->rs.d_hist}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -585,6 +629,7 @@ int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* 
     /* every refusal leaves the pipeline exactly as it was */
     if (p->O) { p->err = "aacg_pipeline_set_mix: the pipeline has a mix already"; return AACG_ERR_INVALID_ARG; }
     if (p->submitted) { p->err = "aacg_pipeline_set_mix: a batch has been submitted (the mix is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (p->rs.L) { p->err = "aacg_pipeline_set_mix: the pipeline has a resampler already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (out_channels < 1 || out_channels > AACG_MIX_MAX_OUT) { p->err = "aacg_pipeline_set_mix: out_channels is not 1 or 2"; return AACG_ERR_INVALID_ARG; }
     if (!matrix) { p->err = "aacg_pipeline_set_mix: no matrix"; return AACG_ERR_INVALID_ARG; }
     for (uint32_t i = 0; i < out_channels * p->C; i++)
@@ -607,6 +652,62 @@ int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* 
 }
 
 int aacg_pipeline_out_channels(const aacg_pipeline* p) { return p ? (int)out_channels(p) : AACG_ERR_INVALID_ARG; }
+
+int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_t taps, const float* table)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (p->rs.L) { p->err = "aacg_pipeline_set_resample: the pipeline has a resampler already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_resample: a batch has been submitted (the resampler is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int why = aacg_resample_check(L, M, taps)) { p->err = std::string("aacg_pipeline_set_resample: ") + aacg_resample_why(why); return AACG_ERR_INVALID_ARG; }
+    if (!table) { p->err = "aacg_pipeline_set_resample: no table"; return AACG_ERR_INVALID_ARG; }
+    const size_t n_table = (size_t)L * taps;
+    for (size_t i = 0; i < n_table; i++)
+        if (!std::isfinite(table[i])) { p->err = "aacg_pipeline_set_resample: coefficient " + std::to_string(i) + " of the table is not finite"; return AACG_ERR_INVALID_ARG; }
+    /* the largest batch's output: a stream of F frames emits at most ceil(1024 F L / M) samples, so a batch at most its frames' share
+     * and one more per stream.  The kernel and its records count samples in 32 bits */
+    const uint64_t n = (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames;
+    const uint64_t most = (n * 1024u * L + M - 1u) / M + (uint64_t)p->cfg.max_streams;
+    if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_resample: max_streams x max_frames x 1024 x L / M is 2^31 samples or more"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const uint32_t O = out_channels(p);
+    const size_t lane_elems = (size_t)most * O, hist_bytes = (size_t)p->cfg.max_streams * 2u * (taps - 1u) * O * sizeof(float);
+    void *d_table = nullptr, *d_hist = nullptr, *d_rs[AACG_PIPELINE_MAX_LANES] = {};
+    hipEvent_t ev[AACG_PIPELINE_MAX_LANES] = {};
+    bool good = hipMalloc(&d_table, n_table * sizeof(float)) == hipSuccess && hipMalloc(&d_hist, hist_bytes) == hipSuccess;
+    for (int k = 0; k < p->n_lanes && good; k++)
+        good = hipMalloc(&d_rs[k], lane_elems * pcm_elem(p)) == hipSuccess && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
+    /* the table, synchronously: nothing is in flight yet.  The history needs no clearing: a fresh slot's is not read */
+    good = good && hipMemcpy(d_table, table, n_table * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (!good) {
+        (void)hipGetLastError();
+        for (void* d : {d_table, d_hist}) if (d) (void)hipFree(d);
+        for (int k = 0; k < p->n_lanes; k++) { if (d_rs[k]) (void)hipFree(d_rs[k]); if (ev[k]) (void)hipEventDestroy(ev[k]); }
+        p->err = "aacg_pipeline_set_resample: no device memory for the table, the slots' histories and the lanes' resampled PCM";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    /* page-locked staging that a submission which failed half-way left behind has another size: it is made again, lazily */
+    for (int k = 0; k < p->n_lanes; k++) {
+        auto& Ln = p->lane[k];
+        if (Ln.h_pcm) { (void)hipHostFree(Ln.h_pcm); Ln.h_pcm = nullptr; }
+        Ln.d_rs = d_rs[k]; Ln.rs_done = ev[k];
+    }
+    p->rs.d_table = d_table; p->rs.d_hist = d_hist; p->rs.lane_elems = lane_elems;
+    p->rs.n0.assign((size_t)p->cfg.max_streams, 0u); p->rs.parity.assign((size_t)p->cfg.max_streams, 0); p->rs.fresh.assign((size_t)p->cfg.max_streams, 1);
+    p->rs.M = M; p->rs.T = taps; p->rs.L = L;
+    return AACG_OK;
+}
+
+int aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out)
+{
+    if (!p || !slots || !frames_of || !n_out) return AACG_ERR_INVALID_ARG;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        if ((int)slots[s] >= p->cfg.max_streams) { p->err = "aacg_pipeline_out_samples: stream slot out of range"; return AACG_ERR_INVALID_ARG; }
+        if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "aacg_pipeline_out_samples: a stream brings more frames than max_frames"; return AACG_ERR_INVALID_ARG; }
+    }
+    for (uint32_t s = 0; s < n_streams; s++) n_out[s] = p->rs.L ? resample_count(p, p->rs.n0[slots[s]], frames_of[s]) : frames_of[s] * 1024u;
+    return AACG_OK;
+}
 
 int aacg_mix_standard(uint32_t channels, uint32_t out_channels, float surround_gain, int normalise, float* matrix)
 {
@@ -643,6 +744,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     for (int k = 0; k < p->n_lanes; k++) { int rc = finish_lane(p, p->lane[k]); if (rc) return rc; }
     int rc = aacg_reset_stream(p->engine, slot);
     if (rc) return engine_fail(p, "", rc);
+    if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
         drop_plans_with(p, slot);
@@ -674,27 +776,40 @@ int check_batch(aacg_pipeline* p, batch_t& B)
     for (uint32_t i = 0; i < B.n; i++)
         if ((size_t)B.frames[i].byte_offset + B.frames[i].byte_length > B.n_bytes) { p->err = "a frame points outside the byte buffer"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
-    return B.pcm_out ? AACG_OK : check_device_out(p, B.dev, B.n, B.n_streams, B.longest);
+    B.rs_total = 0;
+    if (p->rs.L) {                                       /* what each stream emits, from the slots' clocks as they stand: they advance in enqueue_out */
+        B.rs.resize(B.n_streams);
+        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
+            const uint32_t slot = B.slots[s], n_out = resample_count(p, p->rs.n0[slot], B.frames_of[s]);
+            B.rs[s] = {first, B.frames_of[s], (uint32_t)B.rs_total, n_out, p->rs.n0[slot], slot, p->rs.parity[slot], p->rs.fresh[slot]};
+            B.rs_total += n_out;
+        }
+    }
+    return B.pcm_out ? AACG_OK : check_device_out(p, B.dev, B.n, B.n_streams, B.longest, B);
 }
 
 /* Step 3, staging: the bytes, the frame table and room for the per-stream table that aacg_pipe_map expands into the refresh map
  * (plan mode 1: that the shaping kernel reads) in one block, the tables behind the bytes on the device too; and where the PCM goes */
 int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
 {
-    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n,
-                   (size_t)B.n_streams * (p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)), B.G);
+    /* (a resampler's per-stream records lie behind the per-stream table, 16-byte aligned: one block, one copy up) */
+    const size_t tab_bytes = (size_t)B.n_streams * (p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)), tab16 = (tab_bytes + 15) & ~(size_t)15;
+    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, p->rs.L ? tab16 + B.rs.size() * sizeof(aacg_resample_stream) : tab_bytes, B.G);
     if (rc) return rc;
+    B.rs_at = B.G.extra_at + tab16;
+    if (p->rs.L) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), B.rs.size() * sizeof(aacg_resample_stream));
     L.d_frames = (char*)L.d_bytes + B.G.padded;
     B.planar = B.dev && B.dev->layout == AACG_PCM_PLANAR;
-    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed, and no mix in between — the caller's in its place */
-    B.d_pcm = B.dev && !B.planar && !p->O ? B.dev->d_pcm : L.d_pcm;
+    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed, and no mix or resampler in between — the caller's in its place */
+    B.d_pcm = B.dev && !B.planar && !p->O && !p->rs.L ? B.dev->d_pcm : L.d_pcm;
     B.xform_bytes = (size_t)B.n * p->C * 1024u * pcm_elem(p);
-    B.pcm_bytes = (size_t)B.n * out_channels(p) * 1024u * pcm_elem(p);
+    B.mix_bytes = (size_t)B.n * out_channels(p) * 1024u * pcm_elem(p);
+    B.pcm_bytes = p->rs.L ? (size_t)B.rs_total * out_channels(p) * pcm_elem(p) : B.mix_bytes;
     /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
      * lane's own page-locked staging and one host copy at collect */
     B.direct = B.dev || is_pinned(B.pcm_out);            /* (PCM left on the device: no staging either) */
     if (!B.direct && !L.h_pcm)
-        P_TRY(p, hipHostMalloc(&L.h_pcm, (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels(p) * 1024u * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
+        P_TRY(p, hipHostMalloc(&L.h_pcm, (p->rs.L ? p->rs.lane_elems : (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels(p) * 1024u) * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
     return AACG_OK;
 }
 
@@ -781,13 +896,28 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     if (p->O) {
         /* the lane's packed PCM of C channels into O: straight into a caller's packed buffer, else into the lane's d_mix */
         aacg_mix_args M;
-        M.src = L.d_pcm; M.dst = B.dev && !B.planar ? B.dev->d_pcm : L.d_mix;
+        M.src = L.d_pcm; M.dst = B.dev && !B.planar && !p->rs.L ? B.dev->d_pcm : L.d_mix;
         M.n_frames = B.n; M.channels = p->C; M.out_channels = p->O; M.elem = (uint32_t)pcm_elem(p);
         std::memcpy(M.m, p->mix, sizeof M.m);
         if (!aacg_mix_launch(M, L.st)) { p->err = "aacg_pcm_mix: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
         packed = L.d_mix;
     }
-    if (B.planar) {
+    if (p->rs.L) {
+        /* the packed PCM at the new rate, either layout: straight into a caller's device buffer, else into the lane's d_rs.  The slots'
+         * histories pass from batch to batch, and consecutive batches run on different streams: this launch waits for the one before
+         * it, here — behind this lane's parse, transform and mix, which need not wait */
+        aacg_resample_args A;
+        A.src = packed; A.dst = B.dev ? B.dev->d_pcm : L.d_rs; A.rec = (const aacg_resample_stream*)((const char*)L.d_bytes + B.rs_at);
+        A.table = (const float*)p->rs.d_table; A.hist = (float*)p->rs.d_hist;
+        A.n_streams = B.n_streams; A.n_frames = B.n; A.L = p->rs.L; A.M = p->rs.M; A.taps = p->rs.T;
+        A.row = B.planar ? B.dev->stride_frames * 1024u : 0u; A.channels = out_channels(p); A.elem = (uint32_t)pcm_elem(p);
+        if (p->rs.last && p->rs.last != L.rs_done) P_TRY(p, hipStreamWaitEvent(L.st, p->rs.last, 0), AACG_ERR_NO_DEVICE);
+        if (!aacg_resample_launch(A, L.st)) { p->err = "aacg_pcm_resample: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        P_TRY(p, hipEventRecord(L.rs_done, L.st), AACG_ERR_NO_DEVICE);
+        p->rs.last = L.rs_done;
+        packed = L.d_rs;
+    }
+    if (B.planar && !p->rs.L) {
         /* the caller's tensor from the lane's packed PCM and the per-stream table that came up with the bytes (either plan mode's
          * record begins with frame_first and frames), padding included: where the copy down sits for a host batch */
         aacg_planar_args A;
@@ -807,6 +937,12 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     P_TRY(p, hipEventRecord(L.done, L.st), AACG_ERR_NO_DEVICE);
     L.busy = true; L.ticket = ++p->submitted; L.user_pcm = B.pcm_out; L.direct = B.direct; L.pcm_bytes = B.pcm_bytes; L.device_out = B.dev != nullptr;
     L.user_results = B.results; L.user_refused = B.n_refused; L.n = B.n;
+    /* the batch is enqueued: its streams' resampler clocks advance and their histories change sides (a submission refused or failed
+     * before this point has left them alone, and what its launch wrote lies in the buffers the slots do not read) */
+    for (const auto& r : B.rs) {
+        p->rs.n0[r.slot] = (uint32_t)(((uint64_t)r.n0 + 1024ull * r.frames) % p->rs.M);
+        p->rs.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->rs.fresh[r.slot] = 0;
+    }
     *ticket = L.ticket;
     return AACG_OK;
 }

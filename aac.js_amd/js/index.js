@@ -395,11 +395,16 @@ GpuAACDecoder.prototype.fillBatch = function (part, blockBase, q, meta) {
  * engine's refusal in their place; then the parse error found behind them, if any */
 GpuAACDecoder.prototype.deliver = function (part, pcm, pcmBase, refused) {
     const C = this.config.chanConfig, mix = this.mix;      // mix: a SharedEngine({ downmix }) decoder on the parsing route — the device's rule on the host (mix.js)
+    const rs = this.resampler;                             // ... and of a SharedEngine({ sampleRate }): the device's rule again (resample.js), behind the mix
     if (part.frames.length) {
-        if (refused) this.queue.push(refused);
+        if (refused) {
+            this.queue.push(refused);
+            if (rs) for (let i = 0; i < part.frames.length; i++) rs.push(new Float32Array(FRAME * rs.C));      // silence flows through the filter: the clock goes on
+        }
         else for (let i = 0; i < part.frames.length; i++) {
             const at = pcmBase + i * FRAME * C;
-            this.queue.push(mix ? require('./mix.js').mix(pcm.subarray(at, at + FRAME * C), C, mix.matrix, mix.outChannels) : pcm.slice(at, at + FRAME * C));
+            const frame = mix ? require('./mix.js').mix(pcm.subarray(at, at + FRAME * C), C, mix.matrix, mix.outChannels) : rs ? pcm.subarray(at, at + FRAME * C) : pcm.slice(at, at + FRAME * C);
+            this.queue.push(rs ? rs.push(frame) : frame);
         }
     }
     if (part.failed) this.queue.push(part.failed);

@@ -42,6 +42,12 @@
  * engine.  A resident pipeline mixes on the device (aacg_pipeline_set_mix: a 5.1 stream then costs the link what a stereo stream
  * costs) and a decoder on the parsing route is mixed on the host by the same rule (mix.js), bit for bit; format.channelsPerFrame says
  * outChannels either way.
+ * { resident: true, sampleRate: 16000 } — every decoder of the engine delivers PCM at that rate instead of its stream's: the default
+ * table (aacg_resample_design, 32 taps) from the stream's rate, one per pipeline.  A resident pipeline resamples on the device, behind
+ * the mix (aacg_pipeline_set_resample: a 48 kHz stream at 16 kHz sends a third of the samples down the link), and readChunk() returns
+ * each frame's share of the output, 341 or 342 samples per channel for 1024 at 1 / 3 — a variable length; a decoder on the parsing
+ * route is resampled on the host by the same rule (resample.js), bit for bit; format.sampleRate says the new rate either way.  A stream
+ * that has the engine's rate already is left alone.
  * Replaces, per batch, what src/decoder.js:125-216 does per frame.
  */
 'use strict';
@@ -69,6 +75,7 @@ function SharedEngine(opts) {
      * (lookahead frames) further ahead than they are consumed, and with pcmRing a frame is valid for one flush less.  On by
      * default since round 6 ({ overlap: false } for a flush that decodes what it returns). */
     this.overlap = opts.overlap === undefined ? this.resident : !!opts.overlap;
+    this.sampleRate = opts.sampleRate ? opts.sampleRate | 0 : 0;      // the rate every decoder delivers (resample.js); 0: its stream's
     this.downmix = opts.downmix || null;                  // 'stereo' | 'mono' | { outChannels, matrix }: what every decoder delivers (mix.js)
     this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0, flushNs: 0n };   // flushNs: resident flushes, host side and native calls
 }
@@ -90,6 +97,11 @@ SharedEngine.prototype.attach = function (dec) {
      * frames do not come from a resident pipeline (GpuAACDecoder.deliver) */
     dec.mix = this.downmix ? require('./mix.js').resolve(this.downmix, cfg.chanConfig, this.opts.addon || host.loadAddon()) : null;
     if (dec.mix) dec.format.channelsPerFrame = dec.mix.outChannels;
+    /* sampleRate: the table from this stream's rate, and a resampler of the decoder's own — on the parsing route it filters the frames
+     * (GpuAACDecoder.deliver), on the resident route only its clock is used: it says each frame's share of a batch's ragged output */
+    dec.resampleSpec = this.sampleRate ? require('./resample.js').resolve(this.sampleRate, host.SAMPLE_RATES[cfg.sampleIndex], this.opts.addon || host.loadAddon()) : null;
+    dec.resampler = dec.resampleSpec ? new (require('./resample.js').Resampler)(dec.resampleSpec, dec.mix ? dec.mix.outChannels : cfg.chanConfig) : null;
+    if (dec.resampleSpec) dec.format.sampleRate = this.sampleRate;
     if (this.takesResident(dec)) return this.attachResident(dec);
     let g = this.groups.get(cfg.sampleIndex);
     if (!g) {
@@ -137,9 +149,10 @@ SharedEngine.prototype.attachResident = function (dec) {
                          planMode: this.devicePlans ? 1 : 0,
                          stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) | (this.opts.carryWindowShape ? 4 : 0) };
         if (dec.mix) create.mix = { outChannels: dec.mix.outChannels, matrix: dec.mix.matrix };      // mixed on the device: outChannels leave
+        if (dec.resampleSpec) create.resample = dec.resampleSpec;      // resampled on the device, behind the mix: ragged PCM comes back
         const pipeline = addon.pipelineCreate(create, rec.entries, rec.counts);
         /* channels: of the PCM that comes back — what sizes a flush's PCM and slices it into frames */
-        g = { resident: true, addon: addon, pipeline: pipeline, channels: dec.mix ? dec.mix.outChannels : cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
+        g = { resident: true, resample: dec.resampleSpec, addon: addon, pipeline: pipeline, channels: dec.mix ? dec.mix.outChannels : cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }
     const slot = g.free.length ? g.free.pop() : g.next++;
@@ -149,7 +162,7 @@ SharedEngine.prototype.attachResident = function (dec) {
     /* 'mp4a': the packets in order, each { bytes, at: first byte not walked yet, ready: its blocks found and not yet taken, done,
      * inflight }; a new object per stream, so that a walk still in flight for the stream before is dropped when it comes back */
     dec.packets = dec.format && dec.format.formatID === 'mp4a' ? { q: [] } : null;
-    dec.engine = { resetStream: function (s) { g.addon.pipelineResetStream(g.pipeline, s); } };
+    dec.engine = { resetStream: function (s) { g.addon.pipelineResetStream(g.pipeline, s); if (dec.resampler) dec.resampler.reset(); } };
     g.decoders.push(dec);
 };
 
@@ -314,6 +327,24 @@ SharedEngine.prototype.deliverResident = function (g, b, out, failed) {
     this.stats.batches++; this.stats.units += b.N;
     if (failed) { for (const dec of part) dec.queue.push(failed); return; }
     const pcm = out.pcm, refused = out.refused, per = 1024 * C;
+    if (g.resample) {
+        /* ragged: stream s's out.lengths[s] samples lie behind those of the streams before it, and frame f's share of them follows
+         * from the stream's clock, which the decoder's resampler keeps (a refused frame was silence: its share is skipped, the clock
+         * goes on) */
+        const rs = require('./resample.js'), R = g.resample;
+        for (let s = 0, at = 0; s < S; s++) {
+            const q = part[s].queue, r = part[s].resampler;
+            for (let f = 0, i = b.first[s]; f < b.counts[s]; f++, i++) {
+                const n = rs.count(R.L, R.M, r.n0, 1024);
+                r.n0 = (r.n0 + 1024) % R.M;
+                if (refused && results[8 * i]) q.push(new Error(g.addon.parseStatusString(results[8 * i])));
+                else q.push(pcm.subarray(at * C, (at + n) * C));
+                at += n;
+            }
+        }
+        this.stats.frames += b.N;
+        return;
+    }
     for (let s = 0; s < S; s++) {
         const q = part[s].queue;
         for (let f = 0, i = b.first[s]; f < b.counts[s]; f++, i++) {
@@ -352,7 +383,9 @@ SharedEngine.prototype.launchCounts = function () {
 };
 
 SharedEngine.prototype.flushResidentTimed = function (g) {
-    const L = this.lookahead, C = g.channels, ringElems = this.pcmRing ? this.maxStreams * L * 1024 * C : 0;
+    const L = this.lookahead, C = g.channels;
+    /* (a resampled batch: a stream of L frames emits at most ceil(1024 L x L' / M') samples whatever its clock) */
+    const ringElems = this.pcmRing ? this.maxStreams * (g.resample ? Math.ceil(L * 1024 * g.resample.L / g.resample.M) : L * 1024) * C : 0;
     const args = (b) => [g.pipeline, b.bytes, b.frames, b.slots, b.ragged ? b.counts : b.F, b.results, C, this.pcmRing, ringElems];
     const t0 = process.hrtime.bigint();
     let b = null, out = null, failed = null;

@@ -65,6 +65,9 @@ static struct {
     int  (*pipeline_set_mix)(aacg_pipeline*, uint32_t, const float*);
     int  (*pipeline_out_channels)(const aacg_pipeline*);
     int  (*mix_standard)(uint32_t, uint32_t, float, int, float*);
+    int  (*pipeline_set_resample)(aacg_pipeline*, uint32_t, uint32_t, uint32_t, const float*);
+    int  (*pipeline_out_samples)(aacg_pipeline*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*);
+    int  (*resample_design)(uint32_t, uint32_t, uint32_t, double, double, uint32_t*, uint32_t*, float*, size_t);
     void* (*host_alloc)(size_t);
     void (*host_free)(void*);
 } L;
@@ -106,6 +109,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_launch_counts, "aacg_pipeline_launch_counts");
     SYM(pipeline_walk_submit, "aacg_pipeline_walk_submit"); SYM(pipeline_walk_collect, "aacg_pipeline_walk_collect");
     SYM(pipeline_set_mix, "aacg_pipeline_set_mix"); SYM(pipeline_out_channels, "aacg_pipeline_out_channels"); SYM(mix_standard, "aacg_mix_standard");
+    SYM(pipeline_set_resample, "aacg_pipeline_set_resample"); SYM(pipeline_out_samples, "aacg_pipeline_out_samples"); SYM(resample_design, "aacg_resample_design");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
     return 1;
@@ -128,6 +132,7 @@ static int get_i32(napi_env env, napi_value obj, const char* key, int32_t dflt)
 #define BOX_PIPELINE 0x4150504cu /* 'APPL' */
 #define PCM_RING_MAX 16
 typedef struct { uint32_t kind; void* ptr; pthread_mutex_t lock; int out_i16; /* engine / pipeline: AACG_OUTPUT_I16 */
+                 int resampled;   /* pipeline: made with { resample } — a batch's PCM is ragged, sized by aacg_pipeline_out_samples */
                  /* pipeline, { pcmRing: K }: K page-locked PCM buffers made once and handed out in turn (pipelineDecode) */
                  napi_ref ring_ab[PCM_RING_MAX]; void* ring_ptr[PCM_RING_MAX]; size_t ring_bytes; int ring_n; unsigned ring_next;
                  /* pipeline: the batches submitted and not yet collected, oldest first (pipelineSubmit / pipelineCollect) */
@@ -517,8 +522,10 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     free(b);
 }
 
-/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix}, entries, counts) -> external
- * (mix: { outChannels: 1 | 2, matrix: Float32Array(outChannels * channels) } — aacg_pipeline_set_mix before the call returns: the PCM is
+/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix, resample}, entries, counts) -> external
+ * (resample: { L, M, taps, table: Float32Array(L * taps) } — aacg_pipeline_set_resample behind the mix, before the call returns: the PCM leaves
+ * at L / M times the streams' rate, ragged per stream (pipelineDecode's lengths); a refused resampler destroys the pipeline and throws;
+ * mix: { outChannels: 1 | 2, matrix: Float32Array(outChannels * channels) } — aacg_pipeline_set_mix before the call returns: the PCM is
  * mixed on the device and outChannels channels leave; a refused mix destroys the pipeline and throws with the reason;
  * planMode 1: device plans, aacg_pipeline_config.plan_mode; stages: AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS | AACG_PIPELINE_STAGE_WINDOW_SHAPE,
  * aacg_pipeline_config.stages — bit 2 carries each channel's window shape from frame to frame on the device) */
@@ -569,9 +576,26 @@ static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
             if (msg[0]) { L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL; }
         }
     }
+    int resampled = 0;
+    {   /* resample: { L, M, taps, table: Float32Array(L * taps) } — aacg_pipeline_set_resample, behind the mix */
+        napi_value rs; bool has = false; napi_valuetype vt = napi_undefined;
+        if (napi_has_named_property(env, argv[0], "resample", &has) == napi_ok && has && napi_get_named_property(env, argv[0], "resample", &rs) == napi_ok &&
+            napi_typeof(env, rs, &vt) == napi_ok && vt == napi_object) {
+            const int32_t rl = get_i32(env, rs, "L", 0), rm = get_i32(env, rs, "M", 0), rt = get_i32(env, rs, "taps", 0);
+            napi_value tv; napi_typedarray_type tt; size_t nt = 0; void* dt = NULL;
+            char msg[1024] = "";
+            if (napi_get_named_property(env, rs, "table", &tv) != napi_ok || !typed(env, tv, &tt, &nt, &dt) || tt != napi_float32_array || rl < 1 || rt < 1 || rm < 1 || nt != (size_t)rl * (size_t)rt)
+                snprintf(msg, sizeof msg, "pipelineCreate: resample is { L, M, taps, table: Float32Array(L * taps) }");
+            else if ((rc = L.pipeline_set_resample(p, (uint32_t)rl, (uint32_t)rm, (uint32_t)rt, (const float*)dt)))
+                snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_resample failed (%d): %.800s", rc, L.pipeline_last_error(p));
+            if (msg[0]) { L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL; }
+            resampled = 1;
+        }
+    }
     handle_box* b = box_new(BOX_PIPELINE, p);
     if (!b) { L.pipeline_destroy(p); napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
     b->out_i16 = cfg.output_kind == AACG_OUTPUT_I16;
+    b->resampled = resampled;
     CHECK(env, napi_create_external(env, b, pipeline_finalize, NULL, &out));
     return out;
 }
@@ -699,6 +723,8 @@ static void* pcm_take(size_t bytes, size_t* got)
 /* pipelineDecode(pipeline, bytes:Uint8Array, frames:Uint32Array(2 * S * F) [offset, length]..., slots:Uint32Array(S), framesPerStream,
  *                results:Uint8Array(8 * S * F), channels [, ring, ringElems])
  *   -> { pcm: Float32Array|Int16Array(S * F * 1024 * channels) on page-locked memory, refused }
+ * A pipeline made with { resample }: pcm holds what the batch emits at the new rate, stream after stream, and the result carries
+ * lengths: Uint32Array(S), the samples per channel of each stream (aacg_pipeline_out_samples, asked before the batch is submitted).
  * framesPerStream may be a Uint32Array(S) of per-stream counts instead (aacg_pipeline_decode_ragged / _submit_ragged): stream s
  * brings counts[s] frames, and S * F above reads as the counts' sum — frames, results and PCM are packed stream after stream.
  * ring = 0 / absent: the PCM array's memory is the caller's for as long as any view of it lives (a buffer per call, recycled by
@@ -709,6 +735,7 @@ typedef struct {
     const uint8_t* db; size_t nb; const aacg_parse_frame* df; const uint32_t* ds; size_t ns; uint32_t F; aacg_parse_result* dr;
     const uint32_t* counts;                            /* ragged: per-stream frame counts (read during the call only), else NULL */
     void* pcm; size_t got, elems; int slot;
+    uint32_t* lengths;                                 /* a resampled pipeline: each stream's samples per channel (malloc), else NULL */
     napi_ref keep[4];                                  /* the four argument arrays: theirs is the memory the native call reads and writes */
     int n_keep;
     uint64_t ticket; int submitted;                    /* pipelineSubmit: aacg_pipeline_submit's ticket */
@@ -752,12 +779,27 @@ static pipe_job* pipe_prepare(napi_env env, napi_callback_info info, int keep_ar
         const int oc = L.pipeline_out_channels((const aacg_pipeline*)pb->ptr);
         if (oc > 0) C = (uint32_t)oc;
     }
-    const size_t elems = total * 1024u * C, bytes = elems * (pb->out_i16 ? 2u : 4u);
+    size_t samples = total * 1024u;                     /* per channel, the whole batch */
+    uint32_t* lengths = NULL;
+    if (pb->resampled) {                                /* ragged: what the pipeline's clocks say these streams will emit */
+        uint32_t* cnt = (uint32_t*)malloc(2 * ns * sizeof(uint32_t));
+        if (!cnt) { napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
+        lengths = cnt + ns;
+        for (size_t s = 0; s < ns; s++) cnt[s] = ragged ? ((const uint32_t*)dc)[s] : F;
+        pthread_mutex_lock(&pb->lock);
+        const int rc = L.pipeline_out_samples((aacg_pipeline*)pb->ptr, (const uint32_t*)ds, cnt, (uint32_t)ns, lengths);
+        pthread_mutex_unlock(&pb->lock);
+        if (rc) { free(cnt); napi_throw_error(env, NULL, "aacgpu: aacg_pipeline_out_samples failed (a slot out of range, or more frames than maxFrames)"); return NULL; }
+        samples = 0;
+        for (size_t s = 0; s < ns; s++) { samples += lengths[s]; cnt[s] = lengths[s]; }
+        lengths = cnt;                                  /* (the block's first half now holds them: one allocation, freed as one) */
+    }
+    const size_t elems = samples * C, bytes = elems * (pb->out_i16 ? 2u : 4u);
     size_t got = 0;
     void* pcm = NULL;
     int slot = -1;
     if (ring) {
-        if (ring > PCM_RING_MAX || ring_elems < elems) { napi_throw_range_error(env, NULL, "aacgpu: pipelineDecode: ring of at most 16 buffers, each at least one batch long"); return NULL; }
+        if (ring > PCM_RING_MAX || ring_elems < elems) { free(lengths); napi_throw_range_error(env, NULL, "aacgpu: pipelineDecode: ring of at most 16 buffers, each at least one batch long"); return NULL; }
         if (!pb->ring_n) {                                 /* the pipeline's ring: made once, kept alive by references until the pipeline goes */
             pb->ring_bytes = (size_t)ring_elems * (pb->out_i16 ? 2u : 4u);
             uint32_t made = 0;
@@ -773,21 +815,23 @@ static pipe_job* pipe_prepare(napi_env env, napi_callback_info info, int keep_ar
             if (made < ring) {                             /* all K or none: a shorter ring would overwrite frames earlier than the caller was told */
                 for (uint32_t i = 0; i < made; i++) { napi_delete_reference(env, pb->ring_ab[i]); pb->ring_ab[i] = NULL; pb->ring_ptr[i] = NULL; }
                 napi_throw_error(env, NULL, "aacgpu: out of page-locked memory (pcmRing)");
+                free(lengths);
                 return NULL;
             }
             pb->ring_n = (int)ring;
         }
-        if (bytes > pb->ring_bytes) { napi_throw_range_error(env, NULL, "aacgpu: pipelineDecode: batch larger than the ring's buffers"); return NULL; }
+        if (bytes > pb->ring_bytes) { free(lengths); napi_throw_range_error(env, NULL, "aacgpu: pipelineDecode: batch larger than the ring's buffers"); return NULL; }
         slot = (int)(pb->ring_next++ % (unsigned)pb->ring_n);
         pcm = pb->ring_ptr[slot]; got = pb->ring_bytes;
     } else {
         pcm = pcm_take(bytes, &got);
-        if (!pcm) { napi_throw_error(env, NULL, "aacgpu: out of page-locked memory"); return NULL; }
+        if (!pcm) { free(lengths); napi_throw_error(env, NULL, "aacgpu: out of page-locked memory"); return NULL; }
     }
     pipe_job* j = (pipe_job*)calloc(1, sizeof *j);
-    if (!j) { if (slot < 0 && !pool_put(pcm, got)) pcm_discard(pcm); napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
+    if (!j) { free(lengths); if (slot < 0 && !pool_put(pcm, got)) pcm_discard(pcm); napi_throw_error(env, NULL, "aacgpu: out of memory"); return NULL; }
     j->pb = pb; j->db = (const uint8_t*)db; j->nb = nb; j->df = (const aacg_parse_frame*)df; j->ds = (const uint32_t*)ds; j->ns = ns; j->F = F;
     j->dr = (aacg_parse_result*)dr; j->pcm = pcm; j->got = got; j->elems = elems; j->slot = slot; j->counts = (const uint32_t*)dc;
+    j->lengths = lengths;
     if (keep_args) {
         const int which[4] = {1, 2, 3, 5};
         for (int k = 0; k < 4; k++)
@@ -833,11 +877,21 @@ static napi_value pipe_finish(napi_env env, pipe_job* j)
     if (j->rc) {
         if (j->slot < 0 && !pool_put(j->pcm, j->got)) pcm_discard(j->pcm);
         napi_throw_error(env, NULL, j->msg);
+        free(j->lengths);
         free(j);
         return NULL;
     }
+    uint32_t* lengths = j->lengths; const size_t n_streams = j->ns;
     const size_t elems = j->elems, got = j->got; void* pcm = j->pcm; const int slot = j->slot; const uint32_t refused = j->refused;
     free(j);
+    napi_value lv = NULL;
+    if (lengths) {                                      /* copied out first, so that no exit below leaves the block behind */
+        void* ld = NULL; napi_value lab;
+        const napi_status st = napi_create_arraybuffer(env, n_streams * sizeof(uint32_t), &ld, &lab);
+        if (st == napi_ok) memcpy(ld, lengths, n_streams * sizeof(uint32_t));
+        free(lengths);
+        if (st != napi_ok || napi_create_typedarray(env, napi_uint32_array, n_streams, lab, 0, &lv) != napi_ok) lv = NULL;
+    }
     if (slot >= 0) CHECK(env, napi_get_reference_value(env, pb->ring_ab[slot], &ab));
     else
     /* (the engine is not told about the buffer's size with napi_adjust_external_memory: it answers 33 MB of external memory
@@ -848,6 +902,7 @@ static napi_value pipe_finish(napi_env env, pipe_job* j)
     CHECK(env, napi_set_named_property(env, out, "pcm", v));
     CHECK(env, napi_create_uint32(env, refused, &v));
     CHECK(env, napi_set_named_property(env, out, "refused", v));
+    if (lv) CHECK(env, napi_set_named_property(env, out, "lengths", lv));
     return out;
 }
 
@@ -857,6 +912,7 @@ static void pipe_abandon(napi_env env, void* job)
     pipe_wait(j);                                       /* the device writes into j->pcm and the results array until then */
     for (int k = 0; k < j->n_keep; k++) napi_delete_reference(env, j->keep[k]);
     if (j->slot < 0) pcm_discard(j->pcm);
+    free(j->lengths);
     free(j);
 }
 
@@ -1029,6 +1085,33 @@ static napi_value js_mix_standard(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* resampleDesign(inRate, outRate, taps [, rolloff, beta]) -> { L, M, taps, table: Float32Array(L * taps) }: the project's default
+ * resampling table (aacg_resample_design, include/aacgpu.h), what pipelineCreate({ resample }) takes; host code, no device */
+static napi_value js_resample_design(napi_env env, napi_callback_info info)
+{
+    size_t argc = 5; napi_value argv[5], ab, out, v;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (!L.dl) { napi_throw_error(env, NULL, "aacgpu: call load(path) first"); return NULL; }
+    uint32_t in_rate = 0, out_rate = 0, taps = 0, rl = 0, rm = 0; double rolloff = 0.0, beta = 0.0;
+    if (argc < 3 || napi_get_value_uint32(env, argv[0], &in_rate) != napi_ok || napi_get_value_uint32(env, argv[1], &out_rate) != napi_ok ||
+        napi_get_value_uint32(env, argv[2], &taps) != napi_ok || (argc >= 4 && napi_get_value_double(env, argv[3], &rolloff) != napi_ok) ||
+        (argc >= 5 && napi_get_value_double(env, argv[4], &beta) != napi_ok)) {
+        napi_throw_type_error(env, NULL, "resampleDesign(inRate, outRate, taps [, rolloff, beta])"); return NULL; }
+    int rc = L.resample_design(in_rate, out_rate, taps, rolloff, beta, &rl, &rm, NULL, 0);      /* the ratio first: it sizes the table */
+    void* data = NULL;
+    if (!rc) {
+        CHECK(env, napi_create_arraybuffer(env, (size_t)rl * taps * sizeof(float), &data, &ab));
+        rc = L.resample_design(in_rate, out_rate, taps, rolloff, beta, &rl, &rm, (float*)data, (size_t)rl * taps);
+    }
+    if (rc) { char msg[128]; snprintf(msg, sizeof msg, "aacgpu: aacg_resample_design failed (%d)", rc); napi_throw_error(env, NULL, msg); return NULL; }
+    CHECK(env, napi_create_object(env, &out));
+    CHECK(env, napi_create_uint32(env, rl, &v)); CHECK(env, napi_set_named_property(env, out, "L", v));
+    CHECK(env, napi_create_uint32(env, rm, &v)); CHECK(env, napi_set_named_property(env, out, "M", v));
+    CHECK(env, napi_create_uint32(env, taps, &v)); CHECK(env, napi_set_named_property(env, out, "taps", v));
+    CHECK(env, napi_create_typedarray(env, napi_float32_array, (size_t)rl * taps, ab, 0, &v)); CHECK(env, napi_set_named_property(env, out, "table", v));
+    return out;
+}
+
 /* pipelinePlanBuilds(pipeline) -> how many plans the pipeline has built (one per batch shape it had not kept; aacgpu_tools.h) */
 static napi_value js_pipeline_plan_builds(napi_env env, napi_callback_info info)
 {
@@ -1098,6 +1181,7 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelinePlanBuilds", NULL, js_pipeline_plan_builds, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineOutChannels", NULL, js_pipeline_out_channels, NULL, NULL, NULL, napi_default, NULL},
         {"mixStandard", NULL, js_mix_standard, NULL, NULL, NULL, napi_default, NULL},
+        {"resampleDesign", NULL, js_resample_design, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineLaunchCounts", NULL, js_pipeline_launch_counts, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkCollect", NULL, js_pipeline_walk_collect, NULL, NULL, NULL, napi_default, NULL},

@@ -37,7 +37,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_plan_create_shaped", "aacg_plan_create_shaped_stages", "aacg_plan_shape_table", "aacg_plan_shape_launch",
                "aacg_get_window_shape", "aacg_set_window_shape", "aacg_plan_carry_window_shape", "aacg_pipeline_stream_window_shape",
                "aacg_pipeline_submit_device", "aacg_pipeline_wait_device",
-               "aacg_pipeline_set_mix", "aacg_pipeline_out_channels", "aacg_mix_standard"]
+               "aacg_pipeline_set_mix", "aacg_pipeline_out_channels", "aacg_mix_standard",
+               "aacg_pipeline_set_resample", "aacg_pipeline_out_samples", "aacg_resample_counts", "aacg_resample_design"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -117,6 +118,10 @@ class Batch(C.Structure):
     _fields_ = [("units", C.c_void_p), ("n_units", C.c_uint32), ("coeffs", C.c_void_p), ("n_coef_blocks", C.c_uint32),
                 ("meta", C.c_void_p), ("n_meta", C.c_uint32), ("tns", C.c_void_p), ("n_tns", C.c_uint32),
                 ("cce", C.c_void_p), ("n_cce", C.c_uint32), ("pcm_out", C.c_void_p), ("n_pcm_floats", C.c_size_t)]
+
+
+# the sample rates of the format's sampling_frequency_index (sample_index)
+SAMPLE_RATES = [96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350]
 
 
 class AacgError(RuntimeError):
@@ -274,6 +279,10 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_set_mix.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.aacg_pipeline_out_channels.argtypes = [C.c_void_p]
     L.aacg_mix_standard.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
+    L.aacg_pipeline_set_resample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.aacg_pipeline_out_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.aacg_resample_counts.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.aacg_resample_design.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     _lib = L
     return L
 
@@ -466,11 +475,15 @@ class Pipeline:
     (include/aacgpu.h).  channels = the streams' chanConfig (1..8).  device_plans: ONE plan shaped on the device for every batch
     (aacg_pipeline_config.plan_mode 1) instead of a kept plan per batch shape: for feeds whose batches seldom repeat a shape.
     mix: an (O, C) float matrix, O = 1 or 2 (aacg_pipeline_set_mix; mix_standard makes the usual one): the PCM is mixed on the device and
-    O channels leave — self.channels is then O wherever PCM is sized, self.in_channels stays C."""
+    O channels leave — self.channels is then O wherever PCM is sized, self.in_channels stays C.
+    resample: (L, M, table) with table an (L, taps) float matrix (aacg_pipeline_set_resample; resample_design makes the usual one), or
+    out_rate: a sample rate, for which the default table is designed from the rate of sample_index.  The PCM then leaves at L / M times
+    the streams' rate, a ragged count of samples per stream: decode and collect return (pcm, results, n_refused, lengths) with pcm flat,
+    stream after stream, lengths[s] samples of self.channels each; decode_tensor's lengths are those counts.  self.rate is the PCM's."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False, mix=None):
+                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -485,6 +498,7 @@ class Pipeline:
         self.device_plans = bool(device_plans)
         self.handle, self.channels, self.i16, self.device = h, channels, output_kind == OUTPUT_I16, device
         self.in_channels = channels
+        self.resample, self.rate = None, SAMPLE_RATES[sample_index]
         self._keep = {}
         if mix is not None:
             m = np.ascontiguousarray(mix, np.float32)
@@ -494,6 +508,18 @@ class Pipeline:
             try:
                 self.set_mix(m)
             except AacgError:
+                self.close()
+                raise
+        if out_rate is not None and resample is None:
+            try:
+                resample = resample_design(self.rate, int(out_rate), resample_taps)
+            except AacgError:
+                self.close()
+                raise
+        if resample is not None:
+            try:
+                self.set_resample(*resample)
+            except (AacgError, ValueError):
                 self.close()
                 raise
 
@@ -538,6 +564,24 @@ class Pipeline:
         self._check(self.lib.aacg_pipeline_set_mix(self.handle, m.shape[0], m.ctypes.data))
         self.channels = int(self.lib.aacg_pipeline_out_channels(self.handle))
 
+    def set_resample(self, L, M, table):
+        """aacg_pipeline_set_resample: the (L, taps) table of an L / M resampler, before the first batch and after the mix."""
+        h = np.ascontiguousarray(table, np.float32)
+        if h.ndim != 2 or h.shape[0] != int(L):
+            raise ValueError("Pipeline: the resampler's table is not an (L, taps) matrix")
+        self._check(self.lib.aacg_pipeline_set_resample(self.handle, int(L), int(M), h.shape[1], h.ctypes.data))
+        self.resample = (int(L), int(M), h)
+        self.rate = self.rate * int(L) / int(M)
+
+    def out_samples(self, slots, frames_per_stream):
+        """aacg_pipeline_out_samples: the samples per channel that the NEXT batch of these slots with these counts emits, per stream"""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
+        assert len(counts) == len(slots)
+        n = np.zeros(len(slots), np.uint32)
+        self._check(self.lib.aacg_pipeline_out_samples(self.handle, slots.ctypes.data, counts.ctypes.data, len(slots), n.ctypes.data))
+        return n
+
     def stream_layout(self, slot):
         """(channels of every element of the slot's frames, how many of the elements are decoded); ([], 0) before it is learnt."""
         ch, kept = np.zeros(8, np.uint8), C.c_uint32()
@@ -576,9 +620,12 @@ class Pipeline:
             counts, total = None, len(slots) * int(frames_per_stream)
         assert frames.dtype == PARSE_FRAME_DTYPE and len(frames) == total
         n = len(frames)
+        # a resampled pipeline: what each stream will emit (the clocks stand still until the batch is enqueued)
+        self._lengths = self.out_samples(slots, frames_per_stream).astype(np.int64) if self.resample else None
+        samples = int(self._lengths.sum()) if self.resample else n * 1024
         if pcm is None:
-            pcm = np.zeros(n * 1024 * self.channels, np.int16 if self.i16 else np.float32)
-        assert pcm.size >= n * 1024 * self.channels
+            pcm = np.zeros(samples * self.channels, np.int16 if self.i16 else np.float32)
+        assert pcm.size >= samples * self.channels
         return data, frames, slots, counts, pcm, np.zeros(n, PARSE_RESULT_DTYPE), C.c_uint32(0)
 
     def decode(self, data, frames, slots, frames_per_stream, pcm=None):
@@ -591,7 +638,7 @@ class Pipeline:
         else:
             self._check(self.lib.aacg_pipeline_decode_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                              counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
-        return pcm, res, int(refused.value)
+        return (pcm, res, int(refused.value)) + ((self._lengths,) if self.resample else ())
 
     def submit(self, data, frames, slots, frames_per_stream, pcm=None):
         """Asynchronous: returns a ticket; collect(ticket) -> (pcm, results, n_refused).  frames_per_stream as for decode."""
@@ -603,14 +650,14 @@ class Pipeline:
         else:
             self._check(self.lib.aacg_pipeline_submit_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                              counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused), C.byref(t)))
-        self._keep[t.value] = (pcm, res, refused)
+        self._keep[t.value] = (pcm, res, refused) + ((self._lengths,) if self.resample else ())
         return t.value
 
     def collect(self, ticket):
         """(pcm, results, n_refused) of a submitted batch; for a submit_device ticket pcm is the `out` that was given"""
         self._check(self.lib.aacg_pipeline_collect(self.handle, ticket))
-        pcm, res, refused = self._keep.pop(ticket)
-        return pcm, res, int(refused.value)
+        pcm, res, refused, *lengths = self._keep.pop(ticket)
+        return (pcm, res, int(refused.value)) + tuple(lengths)
 
     @staticmethod
     def _device_memory(out):
@@ -643,13 +690,14 @@ class Pipeline:
         slots = np.ascontiguousarray(slots, np.uint32)
         counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
         assert len(counts) == len(slots) and frames.dtype == PARSE_FRAME_DTYPE and len(frames) == int(counts.sum())
+        lengths = self.out_samples(slots, counts).astype(np.int64) if self.resample else None
         if planar and stride_frames is None:
-            stride_frames = int(counts.max()) if len(counts) else 0
+            stride_frames = (int(counts.max()) if len(counts) else 0) if lengths is None else (int(lengths.max()) + 1023) // 1024
         desc = PcmDeviceOut(addr, nbytes, (PCM_PLANAR if planar else PCM_PACKED) if layout is None else int(layout), int(stride_frames or 0))
         res, refused, t = np.zeros(len(frames), PARSE_RESULT_DTYPE), C.c_uint32(0), C.c_uint64()
         self._check(self.lib.aacg_pipeline_submit_device(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                          counts.ctypes.data, C.byref(desc), res.ctypes.data, C.byref(refused), C.byref(t)))
-        self._keep[t.value] = (out, res, refused)
+        self._keep[t.value] = (out, res, refused) + ((lengths,) if self.resample else ())
         return t.value
 
     def wait_device(self, ticket, stream=None):
@@ -675,12 +723,15 @@ class Pipeline:
         slots = np.ascontiguousarray(slots, np.uint32)
         counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
         shape = (len(slots), self.channels, int(counts.max()) * 1024) if planar else (int(counts.sum()), 1024, self.channels)
+        if self.resample:                                         # rows of whole kilosamples that hold the longest stream; packed: flat (samples, C)
+            n_out = self.out_samples(slots, counts)
+            shape = (len(slots), self.channels, (int(n_out.max()) + 1023) // 1024 * 1024) if planar else (int(n_out.sum()), self.channels)
         out = torch.empty(shape, dtype=torch.int16 if self.i16 else torch.float32, device="cuda:%d" % self.device)
         torch.cuda.current_stream(self.device).synchronize()      # nothing of the block's previous life is still queued when the lane writes it
         t = self.submit_device(data, frames, slots, counts, out, planar=bool(planar))
         self.wait_device(t)
-        out, res, refused = self.collect(t)
-        return out, counts.astype(np.int64) * 1024, res, refused
+        out, res, refused, *lengths = self.collect(t)
+        return out, lengths[0] if lengths else counts.astype(np.int64) * 1024, res, refused
 
 
 def mix_standard(channels, out_channels, surround_gain=2 ** -0.5, normalise=True):
@@ -691,6 +742,28 @@ def mix_standard(channels, out_channels, surround_gain=2 ** -0.5, normalise=True
     if rc != 0:
         raise AacgError(rc, "aacg_mix_standard(%d channels to %d)" % (channels, out_channels))
     return m
+
+
+def resample_design(in_rate, out_rate, taps=32, rolloff=0.0, beta=0.0):
+    """The project's default resampling table (aacg_resample_design, include/aacgpu.h): (L, M, table) with table (L, taps) float32, for
+    Pipeline(resample=...): host code, no device.  rolloff and beta 0: the defaults, 0.95 and 9."""
+    lib, L, M = load_library(), C.c_uint32(), C.c_uint32()
+    rc = lib.aacg_resample_design(int(in_rate), int(out_rate), int(taps), float(rolloff), float(beta), C.byref(L), C.byref(M), None, 0)
+    if rc == 0:
+        table = np.zeros((L.value, int(taps)), np.float32)
+        rc = lib.aacg_resample_design(int(in_rate), int(out_rate), int(taps), float(rolloff), float(beta), C.byref(L), C.byref(M), table.ctypes.data, table.size)
+    if rc != 0:
+        raise AacgError(rc, "aacg_resample_design(%d -> %d Hz, %d taps)" % (in_rate, out_rate, taps))
+    return int(L.value), int(M.value), table
+
+
+def resample_counts(L, M, n0, frames):
+    """aacg_resample_counts: (samples each of `frames` consecutive frames emits at L / M from the clock n0, the clock modulo M after them)"""
+    per, after = np.zeros(int(frames), np.uint32), C.c_uint32()
+    rc = load_library().aacg_resample_counts(int(L), int(M), int(n0), int(frames), per.ctypes.data, C.byref(after))
+    if rc != 0:
+        raise AacgError(rc, "aacg_resample_counts(%d / %d)" % (L, M))
+    return per, int(after.value)
 
 
 class Plan:

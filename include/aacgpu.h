@@ -873,6 +873,54 @@ int  aacg_pipeline_out_channels(const aacg_pipeline* p);
  * table is positional, like the mix.  AACG_ERR_INVALID_ARG: channels 0, 7 or above 8, out_channels not 1 or 2, a null matrix, a gain
  * that is not finite (or, with normalise, one that leaves a row without a positive sum). */
 int  aacg_mix_standard(uint32_t channels, uint32_t out_channels, float surround_gain, int normalise, float* matrix);
+/* A resampler on the device: the pipeline's PCM leaves at L / M times the streams' sample rate, so that a 16 kHz consumer of a 48 kHz
+ * stream pulls a third of the samples across the link.  table is the polyphase table h[L][taps], row-major float32: row p holds the
+ * `taps` coefficients of phase p (aacg_resample_design makes the usual one).  THE RULE, bit for bit.  Each stream slot has a clock N,
+ * the input samples per channel it has consumed since aacg_pipeline_reset_stream (or create).  Output sample m = 0, 1, 2, ... of a
+ * slot's channel since then is, with i = floor(m M / L) and p = (m M) mod L, in float32 throughout,
+ *     acc = h[p][0] * x[i]                             (rounded to float)
+ *     acc = acc + (h[p][t] * x[i - t])   t = 1 .. taps-1   (the product rounded, then the sum rounded: NOT fused, in this order)
+ * Every term is computed, whatever its coefficient; x[j] = 0 for j < 0.  x is the slot's PCM as the pipeline would have delivered it
+ * without a resampler, batch after batch — AFTER the mix if one is set, so the resampler works on the out_channels mixed channels; a
+ * refused frame and a frame of an unlearnt stream are 1024 zeros, and they advance the clock like any other.  numpy float32 arithmetic
+ * reproduces the result exactly.
+ *   AACG_OUTPUT_F32: out = acc, no clamp.
+ *   AACG_OUTPUT_I16: x is the ALREADY ROUNDED int16 sample converted to float (exact), and out is acc rounded to nearest even and
+ *     saturated to [-32768, 32767] — the mix's int16 rule.
+ * What a batch emits: a stream that brings F frames moves its clock from N to N' = N + 1024 F and emits the outputs m with
+ * N <= i(m) < N', ceil(N' L / M) - ceil(N L / M) samples (frame f of the batch owns those with i(m) inside it).  The count depends on
+ * N mod M only; aacg_pipeline_out_samples tells it for the next batch, aacg_resample_counts for any clock.  Any split of a stream's
+ * frames into batches gives the same bits.  A reset sets N = 0, and the history is then zero by the rule.
+ * Output layouts, with n_out[s] the samples of the batch's stream s and O the channels that leave: host PCM and AACG_PCM_PACKED
+ * [stream s][n_out[s]][O], tight, the streams one behind the other (sum n_out[s] x O elements); AACG_PCM_PLANAR
+ * [stream][O][stride_frames * 1024] with the padding behind n_out[s] written as zeros — stride_frames x 1024 must be at least every
+ * n_out[s], and need not reach the frame counts.
+ * Limits: taps a multiple of 4 in 4..64; L and M in 1..1024; L x taps <= 16384; 1/8 <= L / M <= 8; max_streams x max_frames x 1024 x
+ * L / M below 2^31.  The group delay of a linear-phase table is (L taps - 1) / (2 L) input samples.
+ * Results, refusal counts, tickets, lanes, plan modes, `stages`, ragged batches, span walks and the mix are untouched: one more launch
+ * per batch (aacg_pcm_resample_*) on the lane's stream, behind the transform and the mix, ordered behind the previous batch's; with no
+ * resampler set nothing differs.  Called once, before the pipeline's first submitted batch and after aacg_pipeline_set_mix if both
+ * are used.  AACG_ERR_INVALID_ARG, with the reason in aacg_pipeline_last_error and the pipeline exactly as it was: a limit broken, a
+ * null table, a coefficient that is not finite, a call after the first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory
+ * for the table, the histories and the lanes' output; the pipeline stays as it was. */
+int  aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_t taps, const float* table);
+/* What the NEXT submission of these streams with these frame counts will emit, per stream: n_out[s] samples per channel, from the
+ * slots' clocks as they stand (frames_of[s] x 1024 without a resampler).  The caller sizes pcm_out / d_pcm_bytes with it.  The clocks
+ * advance when a batch has been enqueued; a refused submission leaves them alone.  AACG_ERR_INVALID_ARG: a null pointer, a slot out of
+ * range, a count above max_frames. */
+int  aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out);
+/* Host code only (no device, no pipeline): what `frames` consecutive frames emit at L / M from the clock n0 (any value; only n0 mod M
+ * counts), frame by frame: per_frame[f] = ceil((n0 + 1024 (f + 1)) L / M) - ceil((n0 + 1024 f) L / M) (per_frame may be null), and
+ * n0_after = (n0 + 1024 frames) mod M, the clock to continue with.  AACG_ERR_INVALID_ARG: L or M outside 1..1024. */
+int  aacg_resample_counts(uint32_t L, uint32_t M, uint32_t n0, uint32_t frames, uint32_t* per_frame, uint32_t* n0_after);
+/* The project's default table for aacg_pipeline_set_resample, host code only: L / M = out_rate / in_rate reduced, and into table (room
+ * for `capacity` floats, at least L x taps) a Kaiser-windowed sinc: the prototype g[n], n = 0 .. L taps - 1, centred at (L taps - 1) /
+ * 2, is sinc(2 fc (n - centre)) under a Kaiser window of shape beta, with the cutoff fc = 0.5 rolloff / max(L, M) cycles per upsampled
+ * sample; h[p][t] = g[p + t L], each phase row divided by its sum, so that DC passes with gain 1 in every phase.  Computed in double,
+ * each coefficient rounded to float once.  rolloff 0: 0.95; beta 0: 9.  Group delay: (L taps - 1) / (2 L) input samples.  With table
+ * null and capacity 0 only L and M are written (to size the table).  AACG_ERR_INVALID_ARG: a rate of 0, a null L or M, taps or the
+ * reduced L / M outside aacg_pipeline_set_resample's limits, rolloff outside (0, 1], beta outside (0, 30], a capacity below L x taps. */
+int  aacg_resample_design(uint32_t in_rate, uint32_t out_rate, uint32_t taps, double rolloff, double beta, uint32_t* L, uint32_t* M, float* table, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,14 @@
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
- *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2]
+ *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT]
+ *
+ * --rate OUT: the PCM resampled to OUT Hz on the device (aacg_resample_design from the file's rate with 32 taps and the default roll-off
+ * and window; aacg_pipeline_set_resample): one more launch per batch (aacg_pcm_resample_*), behind the mix if there is one, and
+ * ceil-ish F x 1024 x OUT / rate samples per stream leave.  Buffers are sized for the most a batch can emit (a stream of F frames emits
+ * at most ceil(1024 F L / M) samples whatever its clock); planar rows are that many samples rounded up to whole kilosamples.  The line
+ * then carries the rate, L / M, and a device-to-device aacg_calib_copy of the bytes the resample kernel READS, timed in the same run.
+ * Combines with everything else.
  *
  * --mix O: the standard downmix to O = 1 or 2 channels on the device (aacg_mix_standard with a surround gain of 1/sqrt 2, normalised;
  * aacg_pipeline_set_mix): one more launch per batch (aacg_pcm_mix_*), and O channels of PCM leave in the place of the stream's.  The
@@ -56,7 +63,7 @@ int main(int argc, char** argv)
     int batches = 200, lanes = 3;
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
-    uint32_t mix = 0;
+    uint32_t mix = 0, rate = 0;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -76,6 +83,7 @@ int main(int argc, char** argv)
         else if (a == "--device-pcm") device_pcm = true;
         else if (a == "--planar") planar = true;
         else if (a == "--mix") mix = (uint32_t)std::atoi(val());
+        else if (a == "--rate") rate = (uint32_t)std::atoi(val());
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -122,7 +130,18 @@ int main(int argc, char** argv)
         if ((rc = aacg_pipeline_set_mix(p, mix, m))) { std::fprintf(stderr, "aacg_pipeline_set_mix: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
     const uint32_t out_channels = (uint32_t)aacg_pipeline_out_channels(p);      /* what leaves: the mix's rows, or the stream's channels */
-    const size_t pcm_bytes = (size_t)S * F * 1024 * out_channels * (i16 ? 2 : 4), unmixed_bytes = (size_t)S * F * 1024 * channels * (i16 ? 2 : 4);
+    uint32_t rs_L = 1, rs_M = 1;
+    if (rate) {
+        static const uint32_t rates[16] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350, 0, 0, 0};
+        std::vector<float> table(16384);
+        if (!rates[sample_index] || (rc = aacg_resample_design(rates[sample_index], rate, 32, 0.0, 0.0, &rs_L, &rs_M, table.data(), table.size()))) { std::fprintf(stderr, "aacg_resample_design(%u -> %u): %d\n", rates[sample_index], rate, rc); return 2; }
+        if ((rc = aacg_pipeline_set_resample(p, rs_L, rs_M, 32, table.data()))) { std::fprintf(stderr, "aacg_pipeline_set_resample: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
+    /* the most samples a stream of F frames emits, and the planar row that holds them; without --rate: F x 1024 and F */
+    const size_t most = ((size_t)F * 1024 * rs_L + rs_M - 1) / rs_M;
+    const uint32_t stride_frames = (uint32_t)((most + 1023) / 1024);
+    const size_t pcm_bytes = (size_t)S * (planar ? (size_t)stride_frames * 1024 : most) * out_channels * (i16 ? 2 : 4), unmixed_bytes = (size_t)S * F * 1024 * channels * (i16 ? 2 : 4);
+    const size_t resample_in_bytes = (size_t)S * F * 1024 * out_channels * (i16 ? 2 : 4);
     const int n_out = 4;
     void* out[n_out];
     for (auto& o : out) { o = pageable ? std::malloc(pcm_bytes) : aacg_host_alloc(pcm_bytes); if (!o) { std::fprintf(stderr, "allocation failed\n"); return 2; } std::memset(o, 0, pcm_bytes); }
@@ -147,7 +166,7 @@ int main(int argc, char** argv)
             if (b < n) {
                 const int k = b % n_out;
                 aacg_pcm_device_out where;
-                if (device_pcm) { where.d_pcm = dev[(size_t)(b % n_dev)]; where.d_pcm_bytes = pcm_bytes; where.layout = planar ? AACG_PCM_PLANAR : AACG_PCM_PACKED; where.stride_frames = planar ? F : 0u; }
+                if (device_pcm) { where.d_pcm = dev[(size_t)(b % n_dev)]; where.d_pcm_bytes = pcm_bytes; where.layout = planar ? AACG_PCM_PLANAR : AACG_PCM_PACKED; where.stride_frames = planar ? stride_frames : 0u; }
                 if (new_shapes) {
                     size_t at = 0;
                     for (uint32_t s = 0; s < S; s++) {
@@ -209,6 +228,7 @@ int main(int argc, char** argv)
         if (hipMemcpy(out[0], dev[0], pcm_bytes, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "hipMemcpy failed\n"); return 2; }
     }
     if (mix) unmixed_copy_us = calib(unmixed_bytes, nullptr);
+    const double resample_in_copy_us = rate ? calib(resample_in_bytes, nullptr) : 0.0;
     bool finite = true, nonzero = false;
     uint32_t bad = 0;
     for (int k = 0; k < n_out; k++) bad += refused[k];
@@ -218,13 +238,15 @@ int main(int argc, char** argv)
     if (device_pcm) std::snprintf(copy_key, sizeof copy_key, "\"d2d_copy_of_pcm_us\": %.2f, ", copy_us);
     char mix_key[128] = "";                                 /* --mix only */
     if (mix) std::snprintf(mix_key, sizeof mix_key, "\"mix_out_channels\": %u, \"unmixed_pcm_bytes_per_batch\": %zu, \"d2d_copy_of_unmixed_pcm_us\": %.2f, ", out_channels, unmixed_bytes, unmixed_copy_us);
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s"
+    char rate_key[192] = "";                                /* --rate only */
+    if (rate) std::snprintf(rate_key, sizeof rate_key, "\"rate_out\": %u, \"resample_L\": %u, \"resample_M\": %u, \"resample_taps\": 32, \"resample_in_bytes_per_batch\": %zu, \"d2d_copy_of_resample_in_us\": %.2f, ", rate, rs_L, rs_M, resample_in_bytes, resample_in_copy_us);
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, rate_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
