@@ -10,67 +10,51 @@
  * comes down into page-locked memory.  The host only finds the frame boundaries (ADTS frame_length) and says which stream slot
  * each run of frames belongs to.
  *
- * Round 6:
- *   - LANES.  Round 5 ran H2D -> parse -> refresh -> transform -> D2H -> hipStreamSynchronize on one stream, one batch at a
- *     time: 1.14 ms per 4096-frame stereo batch, of which the PCM's way down PCIe alone is 0.6.  Now a batch takes one of
- *     `lanes` sets of device buffers and a HIP stream of its own; aacg_pipeline_submit returns when the batch is enqueued,
- *     aacg_pipeline_collect waits for it (bounded).  Batch k's PCM goes down while batch k + 1's bytes go up and are parsed; the
- *     transform launches of consecutive batches go through aacg_decode_pipelined — the SAME plan continued launch after launch,
- *     its unit records kept in one set per lane (aacg_plan_set_unit_sets) so that refreshing the next batch's records does not
- *     wait for the launch that reads the previous ones — and so meet in the cross-launch rendezvous cells like bench.py's.
- *   - LAYOUTS.  Streams of up to eight channels: a stream's element layout (which SCE / CPE / LFE elements a frame has, in
- *     order — decoder.js:233-247 deals channels out in element order and drops what exceeds chanConfig) is learnt from its
- *     first frame (one small synchronous parse when a stream is new), the kept plan lists exactly those elements, and a
- *     later frame with other elements is refused as a whole (AACG_PARSE_LAYOUT).
+ * LANES.  A batch takes one of `lanes` sets of device buffers and a HIP stream of its own; aacg_pipeline_submit returns when the batch
+ * is enqueued, aacg_pipeline_collect waits for it (bounded).  Batch k's PCM goes down while batch k + 1's bytes go up and are parsed;
+ * the transform launches of consecutive batches go through aacg_decode_pipelined — the SAME plan continued launch after launch, its
+ * unit records kept in one set per lane (aacg_plan_set_unit_sets) so that refreshing the next batch's records does not wait for the
+ * launch that reads the previous ones — and so meet in the cross-launch rendezvous cells.  Why the bytes go up through a kernel, the
+ * lanes' streams have the priorities they have and every lane has a parser of its own is measured and written where each is made:
+ * at aacg_pipe_copy, in aacg_pipeline_create and at lane_t.
  *
- * Ragged batches (aacg_pipeline_submit_ragged): each stream brings its own frame count, packed stream after stream; the
- * rectangular call is the case of equal counts.  A batch's refresh map is expanded on the lane's stream (aacg_pipe_map) from a
- * per-stream table staged with the bytes, so a new shape costs the submit path no allocation and no synchronous copy.
+ * BATCHES are ragged (aacg_pipeline_submit_ragged): each stream brings its own frame count, packed stream after stream; the rectangular
+ * call is the case of equal counts.  Streams of up to eight channels: a stream's element layout (which SCE / CPE / LFE elements a frame
+ * has, in order — decoder.js:233-247 deals channels out in element order and drops what exceeds chanConfig) is learnt from its first
+ * frame (one small synchronous parse when a stream is new), the plan lists exactly those elements, and a later frame with other
+ * elements is refused as a whole (AACG_PARSE_LAYOUT).
  *
- * Device plans (aacg_pipeline_config.plan_mode 1): the pipeline makes ONE plan with its own capacity at create
- * (aacg_plan_create_shaped) and every batch shapes that plan's set of its lane on the device — aacg_plan_shape_table completes the
- * per-stream table in the staging, aacg_plan_shape_launch runs the shaping kernel in the place of aacg_pipe_map — so a batch of a
- * shape not seen before costs the submit path no plan build, no allocation, no upload of O(units) bytes and no eviction.  The two
- * modes part in submit_batch's choose_plan, where the plan is chosen, and enqueue_front, where the map / shaping kernel is launched.
+ * Two PLAN MODES (aacg_pipeline_config.plan_mode).  0, kept plans: a plan per batch shape (plan_for), its refresh map expanded on the
+ * lane's stream (aacg_pipe_map) from a per-stream table staged with the bytes, so a new shape costs the submit path no allocation and
+ * no synchronous copy.  1, device plans: ONE plan with the pipeline's capacity made at create (aacg_plan_create_shaped), whose set of
+ * the lane every batch shapes on the device — aacg_plan_shape_table completes the per-stream table in the staging,
+ * aacg_plan_shape_launch runs the shaping kernel in the place of aacg_pipe_map — so a new shape costs no plan build, no upload of
+ * O(units) bytes and no eviction either.  The modes part in choose_plan and in enqueue_front, nowhere else.
  *
- * The spec-correct stages (aacg_pipeline_config.stages): the engine is created with AACG_TNS_SPEC / AACG_PNS_SPEC, the parser writes
- * TNS side info into a buffer of the lane's, aacg_tns_records_from_parse makes the batch's TNS records and their matrices behind the
- * parse on the lane's stream, and the plans are plans for aacg_decode_pipelined_stages, which takes those records as a launch input
- * (aacg_plan_create_stages in plan mode 0, aacg_plan_create_shaped_stages in mode 1).  With stages = 0 no call differs from before.
+ * STAGES (aacg_pipeline_config.stages), each independent of the others and of the plan mode.  AACG_PIPELINE_STAGE_TNS / _PNS: the
+ * engine has AACG_TNS_SPEC / AACG_PNS_SPEC, the parser writes TNS side info into a buffer of the lane's, aacg_tns_records_from_parse
+ * makes the batch's TNS records behind the parse, and the plans are plans for aacg_decode_pipelined_stages, which takes those records
+ * as a launch input.  AACG_PIPELINE_STAGE_WINDOW_SHAPE: one launch of aacg_plan_carry_window_shape behind every refresh sets
+ * window_shape_prev of the batch's unit records from the frame before and, across batches, from the engine's per-channel state.
  *
- * Carried window shapes (AACG_PIPELINE_STAGE_WINDOW_SHAPE, the third bit of stages, independent of the two above): one launch of
- * aacg_plan_carry_window_shape behind every refresh, inside the stale-plan retry and in both plan modes, sets window_shape_prev of
- * the batch's unit records from the frame before and, across batches, from the engine's per-channel state (aacg_shape_carry.h).
+ * THE WAY OUT is a chain: transform -> mix (aacg_pipeline_set_mix: O = 1 or 2 channels leave in the place of C) -> resample
+ * (aacg_pipeline_set_resample: each stream's PCM leaves at L / M times the rate, a ragged count of samples per stream) -> tail (the
+ * planar launch for aacg_pipeline_submit_device with AACG_PCM_PLANAR, the copy down for a host batch, nothing for PCM left packed on
+ * the device).  Which links a batch has, which buffer each reads and writes — a lane's, or the caller's in the place of the last — and
+ * how many bytes is decided ONCE, in check_batch, by aacg_pipe::exit_plan (aacg_pipe_exit.h has the table, tests/test_pipe_exit_plan.py
+ * pins it); enqueue_transform and enqueue_out walk that plan.  The two submissions share one body (submit_batch); the results' copy and
+ * the lane's `done` event are the same whatever the way out, and aacg_pipeline_wait_device puts a consumer's stream behind that event.
+ * The resampler has state per slot — a clock, kept here modulo M, and on the device the last T - 1 samples per channel,
+ * double-buffered — which consecutive batches hand on ACROSS lanes: an event behind every resample launch, awaited by the next batch's
+ * on its own stream behind that lane's parse and transform.  Clocks and parities advance when a batch has been enqueued, not before;
+ * the per-stream records travel up in the lane's one staging block, behind the per-stream table.
  *
- * PCM left on the device (aacg_pipeline_submit_device): the same batch with a caller's device memory for the PCM.  AACG_PCM_PACKED: the
- * caller's pointer takes the place of the lane's d_pcm in the transform's launch (and in the clear for unlearnt streams) — the
- * cross-launch hand-over finds a successor's PCM through the pointer its cell carries, so a caller's buffer needs nothing new there.
- * AACG_PCM_PLANAR: the transform writes the lane's d_pcm and aacg_pcm_planar_* (aacg_pcm_planar.h, aacg_engine_planar.hip) writes the
- * caller's tensor from it and from the per-stream table the batch brought up, behind aacg_pipeline_join where a host batch's copy
- * down sits.  Neither has a copy down of PCM nor touches h_pcm; the results' copy and the lane's `done` event are as ever, and
- * aacg_pipeline_wait_device puts a consumer's stream behind that event.  The two submissions share one body (submit_batch).
- *
- * A mix matrix (aacg_pipeline_set_mix): O = 1 or 2 channels leave in the place of C.  The transform then ALWAYS writes the lane's d_pcm,
- * and one launch of aacg_pcm_mix_* (aacg_pcm_mix.h, aacg_engine_mix.hip) behind aacg_pipeline_join writes the mix: into the caller's
- * d_pcm for an AACG_PCM_PACKED batch, else into the lane's second buffer d_mix, which the copy down or the planar launch (with O for
- * its channels) then reads.  A batch has two sizes from there on: the transform's, n x C (the clear for unlearnt streams acts on it),
- * and what leaves, n x O (pcm_bytes, h_pcm, finish_lane's copy, check_device_out's need).  Without a matrix the two are one and no call
- * or launch differs.
- *
- * A resampler (aacg_pipeline_set_resample): a rational factor L / M and its polyphase table; each stream's PCM leaves at the new rate,
- * a ragged count of samples per stream.  The transform then ALWAYS writes the lane's d_pcm (and the mix the lane's d_mix), and one
- * launch of aacg_pcm_resample_* (aacg_pcm_resample.h, aacg_engine_resample.hip) behind them writes what leaves, packed or planar: into
- * the caller's d_pcm for a device batch, else into the lane's d_rs, which the copy down reads — the planar kernel, which counts in
- * frames, has no part.  A batch has a THIRD size from there on: the transform's n x C, the mix's n x O, and what leaves, sum n_out[s] x
- * O (pcm_bytes, h_pcm, finish_lane's copy, check_device_out's need).  The resampler has state per slot — a clock, kept here modulo M,
- * and on the device the last T - 1 samples per channel, double-buffered — which consecutive batches hand on ACROSS lanes: an event
- * behind every resample launch, awaited by the next batch's on its own stream behind that lane's parse and transform (the order
- * aacg_units_carry_shape's launches have from the engine).  Clocks and parities advance when a batch has been enqueued, not before.
- * The per-stream records travel up in the lane's one staging block, behind the per-stream table.  Without a resampler no call or
- * launch differs.
+ * On a lane's stream, in this order: clear (unlearnt streams) -> copy up -> stale count -> parse -> TNS records -> map / shape ->
+ * refresh -> carry -> fork -> transform -> join -> mix -> wait / resample / record -> planar or copy down -> results copy -> `done`.
  *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
- * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h for the tables it fills and the side launches it makes).
+ * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h for the tables it fills and the
+ * side launches it makes).  DESIGN.md 7a has how it came to be this way, round by round.
  */
 #include <hip/hip_runtime.h>
 
@@ -86,6 +70,7 @@
 #include "aacg_pcm_mix.h"
 #include "aacg_pcm_planar.h"
 #include "aacg_pcm_resample.h"
+#include "aacg_pipe_exit.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
@@ -186,8 +171,7 @@ struct aacg_pipeline {
         size_t bytes_cap = 0;             /* of h_in and of d_bytes: they grow together (grow_pair) */
         /* the batch in flight */
         bool count_stale = false;
-        void* user_pcm = nullptr; bool direct = false; size_t pcm_bytes = 0;
-        bool device_out = false;          /* aacg_pipeline_submit_device: the PCM stays on the device, nothing of it is the host's to copy */
+        void* collect_pcm = nullptr; size_t collect_bytes = 0;      /* the exit plan's collect part: h_pcm's bytes for the caller's pageable memory; 0: nothing to copy */
         aacg_parse_result* user_results = nullptr; uint32_t* user_refused = nullptr; uint32_t n = 0;
         struct span_t { uint32_t first, frames; };
         std::vector<span_t> unlearnt;     /* the packed frames of the batch's streams whose layout was not known: nothing of them was decoded */
@@ -223,11 +207,18 @@ int engine_fail(aacg_pipeline* p, const char* what, int rc) { p->err = std::stri
 size_t pcm_elem(const aacg_pipeline* p) { return p->cfg.output_kind == AACG_OUTPUT_I16 ? 2 : 4; }
 /* the channels of the PCM that leaves: the mix's rows, or the transform's channels */
 uint32_t out_channels(const aacg_pipeline* p) { return p->O ? p->O : p->C; }
-/* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M) */
+/* what the pipeline is, for aacg_pipe::exit_plan and what goes with it (aacg_pipe_exit.h) */
+aacg_exit_pipe exit_pipe(const aacg_pipeline* p)
+{
+    return {p->C, p->O, p->rs.L != 0, (uint32_t)pcm_elem(p), (uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.lane_elems};
+}
+/* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M), the first
+ * through ceil((q M + n) L / M) = q L + ceil(n L / M) so that the one formula (aacg_resample_ceil) sees the arguments it is made for */
 uint32_t resample_count(const aacg_pipeline* p, uint32_t n0, uint32_t frames)
 {
-    const uint64_t L = p->rs.L, M = p->rs.M, n1 = (uint64_t)n0 + 1024ull * frames;
-    return (uint32_t)((n1 * L + M - 1u) / M - ((uint64_t)n0 * L + M - 1u) / M);
+    const uint32_t L = p->rs.L, M = p->rs.M;
+    const uint64_t n1 = (uint64_t)n0 + 1024ull * frames;
+    return (uint32_t)(n1 / M * L) + aacg_resample_ceil((uint32_t)(n1 % M), L, M) - aacg_resample_ceil(n0, L, M);
 }
 
 /* a slot's layout as plans and callers see it: the learnt one (n = 0: none yet), or, C <= 2, one element of C channels */
@@ -269,6 +260,33 @@ int grow_pair(aacg_pipeline* p, void** h, void** d, size_t* cap, size_t need)
     return AACG_OK;
 }
 
+/* The buffers a lane gets after create (aacg_pipeline_set_mix, aacg_pipeline_set_resample): `bytes` of device memory at lane_t::*buf
+ * and, if asked for, an event at lane_t::*ev, for EVERY lane — or for none: false leaves the lanes as they were */
+typedef aacg_pipeline::lane_t lane_t;
+void lanes_release(aacg_pipeline* p, void* lane_t::*buf, hipEvent_t lane_t::*ev)
+{
+    for (auto& L : p->lane) {
+        if (L.*buf) { (void)hipFree(L.*buf); L.*buf = nullptr; }
+        if (ev && L.*ev) { (void)hipEventDestroy(L.*ev); L.*ev = nullptr; }
+    }
+}
+bool lanes_alloc(aacg_pipeline* p, void* lane_t::*buf, size_t bytes, hipEvent_t lane_t::*ev = nullptr)
+{
+    for (int k = 0; k < p->n_lanes; k++)
+        if (hipMalloc(&(p->lane[k].*buf), bytes) != hipSuccess || (ev && hipEventCreateWithFlags(&(p->lane[k].*ev), hipEventDisableTiming) != hipSuccess)) {
+            (void)hipGetLastError();
+            lanes_release(p, buf, ev);
+            return false;
+        }
+    return true;
+}
+/* A lane's page-locked PCM staging is made lazily, at the size of the largest batch's output (aacg_pipe::exit_host_capacity).  What a
+ * submission that failed half-way left behind has the size of before a mix or a resampler was set: it goes, and is made again */
+void drop_host_staging(aacg_pipeline* p)
+{
+    for (int k = 0; k < p->n_lanes; k++) if (p->lane[k].h_pcm) { (void)hipHostFree(p->lane[k].h_pcm); p->lane[k].h_pcm = nullptr; }
+}
+
 /* A staging block, made and filled: the bytes (16-byte aligned, AACG_PARSE_PAD readable bytes behind them), the table of frames or
  * spans, and at extra_at (16-byte aligned again) room for what else goes up with them: a batch's per-stream table.  Page-locked
  * and device copy have one layout and one size, `up`. */
@@ -291,13 +309,19 @@ struct batch_t {
     void* pcm_out; const aacg_pcm_device_out* dev; aacg_parse_result* results; uint32_t* n_refused;
     uint32_t n, longest;                         /* check_batch: the batch's frames, the largest count of a stream */
     uint32_t set;                                /* the lane's index: the set of a plan's unit records that is this lane's */
-    staging_t G; bool planar, direct; void* d_pcm;                        /* stage_batch (the per-stream table lies at G.extra_at) */
-    size_t xform_bytes, mix_bytes, pcm_bytes;    /* what the transform writes at d_pcm, n x C; what the mix leaves, n x O; what leaves the pipeline: that, or — a resampler — sum n_out x O */
     std::vector<aacg_resample_stream> rs;        /* check_batch, a resampler: the batch's records (what each stream emits, from the host's clocks) */
-    uint64_t rs_total;                           /* ... and the sum of their n_out */
+    aacg_exit_plan X;                            /* check_batch: the way out (aacg_pipe_exit.h) — which stage writes which buffer, and how many bytes */
+    staging_t G;                                 /* stage_batch (the per-stream table lies at G.extra_at) */
     size_t rs_at;                                /* stage_batch: where the records lie in the staging block */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
+
+/* a buffer of the exit plan, for this lane and this batch */
+void* exit_buf(const aacg_pipeline::lane_t& L, const batch_t& B, uint8_t id)
+{
+    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_CALLER */
+    return of[id];
+}
 
 std::string lanes_text(aacg_pipeline* p)
 {
@@ -338,7 +362,7 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
     if (!L.busy) return AACG_OK;
     int rc = wait_done(p, L, "aacg_pipeline_collect");
     if (rc) return rc;
-    if (!L.device_out && !L.direct) std::memcpy(L.user_pcm, L.h_pcm, L.pcm_bytes);
+    if (L.collect_bytes) std::memcpy(L.collect_pcm, L.h_pcm, L.collect_bytes);
     /* a stream whose first frame did not parse has no layout yet: every frame of it in this batch came out silent and says so */
     aacg_parse_result* res = (aacg_parse_result*)L.h_res;
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
@@ -457,34 +481,22 @@ int learn_layouts(aacg_pipeline* p, const uint8_t* bytes, const aacg_parse_frame
     return AACG_OK;
 }
 
-/* aacg_pipeline_submit_device's own refusals, for a batch of n frames in n_streams streams whose largest count is `longest`: all on
- * the host, before anything is enqueued */
-int check_device_out(aacg_pipeline* p, const aacg_pcm_device_out* out, uint32_t n, uint32_t n_streams, uint32_t longest, const batch_t& B)
+/* aacg_pipeline_submit_device's own refusals, all on the host, before anything is enqueued: what only the runtime can say about the
+ * pointer, here, in its place among the rules that need no runtime (aacg_pipe::exit_check; b is what B.X was made from) */
+int check_device_out(aacg_pipeline* p, const batch_t& B, const aacg_exit_batch& b)
 {
-    const bool resampled = p->rs.L != 0;                 /* the rows hold samples at the new rate: B.rs has each stream's count, B.rs_total their sum */
+    const aacg_pcm_device_out* out = B.dev;
     if (!out || !out->d_pcm) { p->err = "aacg_pipeline_submit_device: no device memory for the PCM (out or out->d_pcm is null)"; return AACG_ERR_INVALID_ARG; }
-    if ((uintptr_t)out->d_pcm & 15u) { p->err = "aacg_pipeline_submit_device: d_pcm is not 16-byte aligned"; return AACG_ERR_INVALID_ARG; }
-    if (out->layout != AACG_PCM_PACKED && out->layout != AACG_PCM_PLANAR) { p->err = "aacg_pipeline_submit_device: unknown layout (AACG_PCM_PACKED or AACG_PCM_PLANAR)"; return AACG_ERR_INVALID_ARG; }
-    if (out->layout == AACG_PCM_PACKED && out->stride_frames) { p->err = "aacg_pipeline_submit_device: AACG_PCM_PACKED takes stride_frames 0"; return AACG_ERR_INVALID_ARG; }
-    if (out->layout == AACG_PCM_PLANAR && !resampled && out->stride_frames < longest) { p->err = "aacg_pipeline_submit_device: stride_frames is below the batch's largest frame count"; return AACG_ERR_INVALID_ARG; }
-    if (out->layout == AACG_PCM_PLANAR && resampled) {
-        if (!out->stride_frames || out->stride_frames > (1u << 21)) { p->err = "aacg_pipeline_submit_device: stride_frames is not in 1..2^21"; return AACG_ERR_INVALID_ARG; }
-        for (const auto& r : B.rs)
-            if ((uint64_t)out->stride_frames * 1024u < r.n_out) { p->err = "aacg_pipeline_submit_device: stride_frames x 1024 is below a stream's resampled count (aacg_pipeline_out_samples)"; return AACG_ERR_INVALID_ARG; }
-    }
+    const aacg_exit_refusal no = aacg_pipe::exit_check(exit_pipe(p), b, B.X, *out, aacg_planar_items(B.n_streams, out->stride_frames, (uint32_t)pcm_elem(p)));
+    if (no.code && !no.late) { p->err = no.text; return no.code; }
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, out->d_pcm) != hipSuccess) { (void)hipGetLastError(); p->err = "aacg_pipeline_submit_device: d_pcm is not memory the HIP runtime knows (pageable host memory?)"; return AACG_ERR_INVALID_ARG; }
     if (a.type != hipMemoryTypeDevice || a.device != p->cfg.device_ordinal) {
         p->err = a.type == hipMemoryTypeDevice ? "aacg_pipeline_submit_device: d_pcm is another device's memory" : "aacg_pipeline_submit_device: d_pcm is not device memory (host memory, page-locked or not)";
         return AACG_ERR_INVALID_ARG;
     }
-    const uint64_t elems = out->layout == AACG_PCM_PLANAR ? (uint64_t)n_streams * out_channels(p) * out->stride_frames * 1024u : (resampled ? B.rs_total : (uint64_t)n * 1024u) * out_channels(p);
-    const uint64_t need = elems * pcm_elem(p);
-    if ((uint64_t)out->d_pcm_bytes < need) { p->err = "aacg_pipeline_submit_device: d_pcm_bytes is smaller than the batch needs (" + std::to_string(need) + " bytes)"; return AACG_ERR_CAPACITY; }
-    if (out->layout == AACG_PCM_PLANAR && !resampled && !aacg_planar_items(n_streams, out->stride_frames, (uint32_t)pcm_elem(p))) {
-        p->err = "aacg_pipeline_submit_device: n_streams x stride_frames is more than one aacg_pcm_planar launch addresses"; return AACG_ERR_CAPACITY;
-    }
-    return AACG_OK;
+    if (no.code) p->err = no.text;
+    return no.code;
 }
 
 }  // namespace
@@ -636,15 +648,8 @@ int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* 
         if (!std::isfinite(matrix[i])) { p->err = "aacg_pipeline_set_mix: coefficient " + std::to_string(i) + " of the matrix is not finite"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     const size_t bytes = (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels * 1024u * pcm_elem(p);
-    for (int k = 0; k < p->n_lanes; k++)
-        if (hipMalloc(&p->lane[k].d_mix, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int j = 0; j <= k; j++) { if (p->lane[j].d_mix) (void)hipFree(p->lane[j].d_mix); p->lane[j].d_mix = nullptr; }
-            p->err = "aacg_pipeline_set_mix: no device memory for the lanes' mixed PCM";
-            return AACG_ERR_OUT_OF_MEMORY;
-        }
-    /* page-locked staging that a submission which failed half-way left behind has the unmixed size: it is made again, lazily */
-    for (int k = 0; k < p->n_lanes; k++) if (p->lane[k].h_pcm) { (void)hipHostFree(p->lane[k].h_pcm); p->lane[k].h_pcm = nullptr; }
+    if (!lanes_alloc(p, &lane_t::d_mix, bytes)) { p->err = "aacg_pipeline_set_mix: no device memory for the lanes' mixed PCM"; return AACG_ERR_OUT_OF_MEMORY; }
+    drop_host_staging(p);
     std::memset(p->mix, 0, sizeof p->mix);
     std::memcpy(p->mix, matrix, (size_t)out_channels * p->C * sizeof(float));
     p->O = out_channels;
@@ -664,34 +669,24 @@ int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_
     const size_t n_table = (size_t)L * taps;
     for (size_t i = 0; i < n_table; i++)
         if (!std::isfinite(table[i])) { p->err = "aacg_pipeline_set_resample: coefficient " + std::to_string(i) + " of the table is not finite"; return AACG_ERR_INVALID_ARG; }
-    /* the largest batch's output: a stream of F frames emits at most ceil(1024 F L / M) samples, so a batch at most its frames' share
-     * and one more per stream.  The kernel and its records count samples in 32 bits */
-    const uint64_t n = (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames;
-    const uint64_t most = (n * 1024u * L + M - 1u) / M + (uint64_t)p->cfg.max_streams;
+    /* the largest batch's output, samples per channel: the kernel and its records count them in 32 bits */
+    const uint64_t most = aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, L, M);
     if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_resample: max_streams x max_frames x 1024 x L / M is 2^31 samples or more"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     const uint32_t O = out_channels(p);
     const size_t lane_elems = (size_t)most * O, hist_bytes = (size_t)p->cfg.max_streams * 2u * (taps - 1u) * O * sizeof(float);
-    void *d_table = nullptr, *d_hist = nullptr, *d_rs[AACG_PIPELINE_MAX_LANES] = {};
-    hipEvent_t ev[AACG_PIPELINE_MAX_LANES] = {};
-    bool good = hipMalloc(&d_table, n_table * sizeof(float)) == hipSuccess && hipMalloc(&d_hist, hist_bytes) == hipSuccess;
-    for (int k = 0; k < p->n_lanes && good; k++)
-        good = hipMalloc(&d_rs[k], lane_elems * pcm_elem(p)) == hipSuccess && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
-    /* the table, synchronously: nothing is in flight yet.  The history needs no clearing: a fresh slot's is not read */
-    good = good && hipMemcpy(d_table, table, n_table * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    if (!good) {
+    void *d_table = nullptr, *d_hist = nullptr;
+    /* (the table, synchronously: nothing is in flight yet.  The history needs no clearing: a fresh slot's is not read) */
+    if (hipMalloc(&d_table, n_table * sizeof(float)) != hipSuccess || hipMalloc(&d_hist, hist_bytes) != hipSuccess ||
+        !lanes_alloc(p, &lane_t::d_rs, lane_elems * pcm_elem(p), &lane_t::rs_done) ||
+        hipMemcpy(d_table, table, n_table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         for (void* d : {d_table, d_hist}) if (d) (void)hipFree(d);
-        for (int k = 0; k < p->n_lanes; k++) { if (d_rs[k]) (void)hipFree(d_rs[k]); if (ev[k]) (void)hipEventDestroy(ev[k]); }
+        lanes_release(p, &lane_t::d_rs, &lane_t::rs_done);
         p->err = "aacg_pipeline_set_resample: no device memory for the table, the slots' histories and the lanes' resampled PCM";
         return AACG_ERR_OUT_OF_MEMORY;
     }
-    /* page-locked staging that a submission which failed half-way left behind has another size: it is made again, lazily */
-    for (int k = 0; k < p->n_lanes; k++) {
-        auto& Ln = p->lane[k];
-        if (Ln.h_pcm) { (void)hipHostFree(Ln.h_pcm); Ln.h_pcm = nullptr; }
-        Ln.d_rs = d_rs[k]; Ln.rs_done = ev[k];
-    }
+    drop_host_staging(p);
     p->rs.d_table = d_table; p->rs.d_hist = d_hist; p->rs.lane_elems = lane_elems;
     p->rs.n0.assign((size_t)p->cfg.max_streams, 0u); p->rs.parity.assign((size_t)p->cfg.max_streams, 0); p->rs.fresh.assign((size_t)p->cfg.max_streams, 1);
     p->rs.M = M; p->rs.T = taps; p->rs.L = L;
@@ -776,20 +771,26 @@ int check_batch(aacg_pipeline* p, batch_t& B)
     for (uint32_t i = 0; i < B.n; i++)
         if ((size_t)B.frames[i].byte_offset + B.frames[i].byte_length > B.n_bytes) { p->err = "a frame points outside the byte buffer"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
-    B.rs_total = 0;
+    /* the way out, decided here and nowhere else.  Page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device;
+     * anything else goes through the lane's own page-locked staging and one host copy at collect */
+    aacg_exit_batch b = {B.n, B.n_streams, B.longest, 0u, B.dev ? B.dev->stride_frames : 0u, 0u, 0u};
+    b.dest = B.pcm_out ? (is_pinned(B.pcm_out) ? AACG_EXIT_HOST_PINNED : AACG_EXIT_HOST_PAGEABLE) : aacg_pipe::exit_dest_device(B.dev ? B.dev->layout : AACG_PCM_PACKED);
     if (p->rs.L) {                                       /* what each stream emits, from the slots' clocks as they stand: they advance in enqueue_out */
         B.rs.resize(B.n_streams);
         for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
             const uint32_t slot = B.slots[s], n_out = resample_count(p, p->rs.n0[slot], B.frames_of[s]);
-            B.rs[s] = {first, B.frames_of[s], (uint32_t)B.rs_total, n_out, p->rs.n0[slot], slot, p->rs.parity[slot], p->rs.fresh[slot]};
-            B.rs_total += n_out;
+            B.rs[s] = {first, B.frames_of[s], (uint32_t)b.rs_total, n_out, p->rs.n0[slot], slot, p->rs.parity[slot], p->rs.fresh[slot]};
+            b.rs_total += n_out;
+            if (n_out > b.rs_most) b.rs_most = n_out;
         }
     }
-    return B.pcm_out ? AACG_OK : check_device_out(p, B.dev, B.n, B.n_streams, B.longest, B);
+    B.X = aacg_pipe::exit_plan(exit_pipe(p), b);
+    return B.pcm_out ? AACG_OK : check_device_out(p, B, b);
 }
 
 /* Step 3, staging: the bytes, the frame table and room for the per-stream table that aacg_pipe_map expands into the refresh map
- * (plan mode 1: that the shaping kernel reads) in one block, the tables behind the bytes on the device too; and where the PCM goes */
+ * (plan mode 1: that the shaping kernel reads) in one block, the tables behind the bytes on the device too; and the lane's page-locked
+ * PCM staging, if the way out goes through it */
 int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
 {
     /* (a resampler's per-stream records lie behind the per-stream table, 16-byte aligned: one block, one copy up) */
@@ -799,17 +800,7 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     B.rs_at = B.G.extra_at + tab16;
     if (p->rs.L) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), B.rs.size() * sizeof(aacg_resample_stream));
     L.d_frames = (char*)L.d_bytes + B.G.padded;
-    B.planar = B.dev && B.dev->layout == AACG_PCM_PLANAR;
-    /* where the transform writes: the lane's buffer, or — PCM left on the device, packed, and no mix or resampler in between — the caller's in its place */
-    B.d_pcm = B.dev && !B.planar && !p->O && !p->rs.L ? B.dev->d_pcm : L.d_pcm;
-    B.xform_bytes = (size_t)B.n * p->C * 1024u * pcm_elem(p);
-    B.mix_bytes = (size_t)B.n * out_channels(p) * 1024u * pcm_elem(p);
-    B.pcm_bytes = p->rs.L ? (size_t)B.rs_total * out_channels(p) * pcm_elem(p) : B.mix_bytes;
-    /* page-locked caller memory (aacg_host_alloc) takes the PCM straight from the device; anything else goes through the
-     * lane's own page-locked staging and one host copy at collect */
-    B.direct = B.dev || is_pinned(B.pcm_out);            /* (PCM left on the device: no staging either) */
-    if (!B.direct && !L.h_pcm)
-        P_TRY(p, hipHostMalloc(&L.h_pcm, (p->rs.L ? p->rs.lane_elems : (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels(p) * 1024u) * pcm_elem(p), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
+    if (B.X.collect_copy && !L.h_pcm) P_TRY(p, hipHostMalloc(&L.h_pcm, aacg_pipe::exit_host_capacity(exit_pipe(p)), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
     return AACG_OK;
 }
 
@@ -838,7 +829,7 @@ int enqueue_front(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B)
     const uint32_t Cp = p->Cp, U = p->U;
     L.unlearnt.clear();
     if (p->learn) for (uint32_t s = 0, i = 0; s < B.n_streams; i += B.frames_of[s], s++) if (!p->layout[B.slots[s]].kept) L.unlearnt.push_back({i, B.frames_of[s]});
-    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(B.d_pcm, 0, B.xform_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames */
+    if (!L.unlearnt.empty()) P_TRY(p, hipMemsetAsync(exit_buf(L, B, B.X.stage[0].dst), 0, B.X.xform_bytes, st), AACG_ERR_NO_DEVICE);      /* no unit writes their frames: the transform's destination, cleared */
     pipe_copy(L.h_in, L.d_bytes, B.G.up, st);             /* aacg_pipe_copy: not the SDMA engines, where it would queue behind other lanes' PCM */
     if (L.count_stale) P_TRY(p, hipMemsetAsync(L.d_refused, 0, 16, st), AACG_ERR_NO_DEVICE);      /* a submission that failed half-way left its count behind */
     L.count_stale = true;
@@ -867,6 +858,7 @@ int enqueue_front(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B)
 int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
 {
     int rc = AACG_OK;
+    void* const d_pcm = exit_buf(L, B, B.X.stage[0].dst);      /* the exit plan's first stage is the transform */
     for (int attempt = 0; B.plan; attempt++) {
         /* this lane's set of the plan's unit records: the launch that read it last was this lane's previous batch, whose PCM has
          * come down on this stream since */
@@ -878,8 +870,8 @@ int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
         if (rc == AACG_OK) rc = aacg_pipeline_fork(p->engine, L.st);
-        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, B.plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? B.n * p->Cp : 0u, B.d_pcm)
-                                              : aacg_decode_pipelined(p->engine, B.plan, L.d_q, (const aacg_band_meta*)L.d_meta, B.d_pcm);
+        if (rc == AACG_OK) rc = p->spec_stages ? aacg_decode_pipelined_stages(p->engine, B.plan, L.d_q, (const aacg_band_meta*)L.d_meta, L.d_tns, L.d_tns ? B.n * p->Cp : 0u, d_pcm)
+                                              : aacg_decode_pipelined(p->engine, B.plan, L.d_q, (const aacg_band_meta*)L.d_meta, d_pcm);
         if (rc == AACG_OK) p->launches++;
         if (rc != AACG_ERR_STALE_PLAN || attempt || p->shaped) break;      /* (a shaped set is made from the engine's current state inside this call: never stale) */
         if ((rc = replan_stale(p, L, B))) return rc;        /* plan mode 0: once more, with a plan made now */
@@ -888,46 +880,36 @@ int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     return rc ? engine_fail(p, "transform: ", rc) : AACG_OK;
 }
 
-/* Step 7, the way out: the mix if there is one, the PCM (planar launch, copy down, or nothing), the results' copy, the lane's event,
- * what finish_lane needs */
+/* Step 7, the way out: the exit plan's stages behind the transform, each from the buffer the one before wrote; then the results' copy,
+ * the lane's event, what finish_lane needs */
 int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, uint64_t* ticket)
 {
-    const void* packed = L.d_pcm;                        /* what the planar launch or the copy down reads */
-    if (p->O) {
-        /* the lane's packed PCM of C channels into O: straight into a caller's packed buffer, else into the lane's d_mix */
-        aacg_mix_args M;
-        M.src = L.d_pcm; M.dst = B.dev && !B.planar && !p->rs.L ? B.dev->d_pcm : L.d_mix;
-        M.n_frames = B.n; M.channels = p->C; M.out_channels = p->O; M.elem = (uint32_t)pcm_elem(p);
-        std::memcpy(M.m, p->mix, sizeof M.m);
-        if (!aacg_mix_launch(M, L.st)) { p->err = "aacg_pcm_mix: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-        packed = L.d_mix;
-    }
-    if (p->rs.L) {
-        /* the packed PCM at the new rate, either layout: straight into a caller's device buffer, else into the lane's d_rs.  The slots'
-         * histories pass from batch to batch, and consecutive batches run on different streams: this launch waits for the one before
-         * it, here — behind this lane's parse, transform and mix, which need not wait */
-        aacg_resample_args A;
-        A.src = packed; A.dst = B.dev ? B.dev->d_pcm : L.d_rs; A.rec = (const aacg_resample_stream*)((const char*)L.d_bytes + B.rs_at);
-        A.table = (const float*)p->rs.d_table; A.hist = (float*)p->rs.d_hist;
-        A.n_streams = B.n_streams; A.n_frames = B.n; A.L = p->rs.L; A.M = p->rs.M; A.taps = p->rs.T;
-        A.row = B.planar ? B.dev->stride_frames * 1024u : 0u; A.channels = out_channels(p); A.elem = (uint32_t)pcm_elem(p);
-        if (p->rs.last && p->rs.last != L.rs_done) P_TRY(p, hipStreamWaitEvent(L.st, p->rs.last, 0), AACG_ERR_NO_DEVICE);
-        if (!aacg_resample_launch(A, L.st)) { p->err = "aacg_pcm_resample: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-        P_TRY(p, hipEventRecord(L.rs_done, L.st), AACG_ERR_NO_DEVICE);
-        p->rs.last = L.rs_done;
-        packed = L.d_rs;
-    }
-    if (B.planar && !p->rs.L) {
-        /* the caller's tensor from the lane's packed PCM and the per-stream table that came up with the bytes (either plan mode's
-         * record begins with frame_first and frames), padding included: where the copy down sits for a host batch */
-        aacg_planar_args A;
-        A.src = packed; A.dst = B.dev->d_pcm; A.tab = (const char*)L.d_bytes + B.G.extra_at;
-        A.tab_stride = (uint32_t)(p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream));
-        A.n_streams = B.n_streams; A.stride_frames = B.dev->stride_frames; A.channels = out_channels(p); A.elem = (uint32_t)pcm_elem(p);
-        if (!aacg_planar_launch(A, L.st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-    } else if (!B.dev) {
-        char* dst = (char*)(B.direct ? B.pcm_out : L.h_pcm);
-        P_TRY(p, hipMemcpyAsync(dst, packed, B.pcm_bytes, hipMemcpyDeviceToHost, L.st), AACG_ERR_NO_DEVICE);      /* one SDMA copy per batch (see aacg_pipe_copy) */
+    const uint32_t Oc = out_channels(p), E = (uint32_t)pcm_elem(p);
+    for (uint32_t i = 1; i < B.X.n_stages; i++) {
+        const aacg_exit_stage& S = B.X.stage[i];
+        const void* const src = exit_buf(L, B, S.src);
+        void* const dst = exit_buf(L, B, S.dst);
+        if (S.what == AACG_EXIT_MIX) {                   /* the packed PCM of C channels into O */
+            aacg_mix_args M = {src, dst, B.n, p->C, p->O, E, {}};
+            std::memcpy(M.m, p->mix, sizeof M.m);
+            if (!aacg_mix_launch(M, L.st)) { p->err = "aacg_pcm_mix: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        } else if (S.what == AACG_EXIT_RESAMPLE) {
+            /* the packed PCM at the new rate, either layout.  The slots' histories pass from batch to batch, and consecutive batches run on
+             * different streams: this launch waits for the one before it, here — behind this lane's parse, transform and mix, which need not wait */
+            const aacg_resample_args A = {src, dst, (const aacg_resample_stream*)((const char*)L.d_bytes + B.rs_at), (const float*)p->rs.d_table, (float*)p->rs.d_hist,
+                                          B.n_streams, B.n, p->rs.L, p->rs.M, p->rs.T, B.X.row, Oc, E};
+            if (p->rs.last && p->rs.last != L.rs_done) P_TRY(p, hipStreamWaitEvent(L.st, p->rs.last, 0), AACG_ERR_NO_DEVICE);
+            if (!aacg_resample_launch(A, L.st)) { p->err = "aacg_pcm_resample: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+            P_TRY(p, hipEventRecord(L.rs_done, L.st), AACG_ERR_NO_DEVICE);
+            p->rs.last = L.rs_done;
+        } else if (S.tail == AACG_EXIT_TAIL_PLANAR_LAUNCH) {
+            /* the caller's tensor from the packed PCM and the per-stream table that came up with the bytes (either plan mode's record
+             * begins with frame_first and frames), padding included: where the copy down sits for a host batch */
+            const aacg_planar_args A = {src, dst, (const char*)L.d_bytes + B.G.extra_at, (uint32_t)(p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)),
+                                        B.n_streams, B.dev->stride_frames, Oc, E};
+            if (!aacg_planar_launch(A, L.st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        } else                                           /* AACG_EXIT_TAIL_COPY_DOWN: one SDMA copy per batch (see aacg_pipe_copy) */
+            P_TRY(p, hipMemcpyAsync(dst, src, S.bytes, hipMemcpyDeviceToHost, L.st), AACG_ERR_NO_DEVICE);
     }
     /* the results and, behind where the largest batch's would end, the refusal count: one small launch (a launch that writes to
      * host memory costs 50 us of the lane's time whatever it carries) */
@@ -935,7 +917,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     pipe_copy(L.d_res, L.h_res, p->res_cap16 + 16, L.st, true);         /* ... and the count is cleared for the lane's next batch (set to zero at create) */
     P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
     P_TRY(p, hipEventRecord(L.done, L.st), AACG_ERR_NO_DEVICE);
-    L.busy = true; L.ticket = ++p->submitted; L.user_pcm = B.pcm_out; L.direct = B.direct; L.pcm_bytes = B.pcm_bytes; L.device_out = B.dev != nullptr;
+    L.busy = true; L.ticket = ++p->submitted; L.collect_pcm = B.pcm_out; L.collect_bytes = B.X.collect_copy ? (size_t)B.X.out_bytes : 0;
     L.user_results = B.results; L.user_refused = B.n_refused; L.n = B.n;
     /* the batch is enqueued: its streams' resampler clocks advance and their histories change sides (a submission refused or failed
      * before this point has left them alone, and what its launch wrote lies in the buffers the slots do not read) */
