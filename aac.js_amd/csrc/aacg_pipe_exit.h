@@ -13,13 +13,20 @@
  *   mix        O != 0         LANE_PCM                    CALLER if DEV_PACKED and no resampler, else LANE_MIX       n O 1024 E
  *   resample   a resampler    LANE_MIX if O, else         CALLER for either device layout (row = stride_frames x     sum n_out Oc E
  *                             LANE_PCM                    1024 if planar, else 0), else LANE_RS
- *   tail       see `writes`   the last lane buffer        PLANAR_LAUNCH -> CALLER if DEV_PLANAR and no resampler;    out_bytes
- *                             written                     COPY_DOWN -> CALLER (page-locked) or LANE_HOST (pageable,
- *                                                         and collect copies it to the caller) for a host batch;
- *                                                         else there is no tail
+ *   features   a feature      LANE_RS, LANE_MIX or        CALLER for either device layout (ft_row = stride_frames,    sum ft_out n_mels 4
+ *              stage          LANE_PCM: the last written  FEATURE frames, if planar, else 0), else LANE_FT
+ *   tail       see `writes`   the last lane buffer        PLANAR_LAUNCH -> CALLER if DEV_PLANAR and neither resampler out_bytes
+ *                             written                     nor feature stage; COPY_DOWN -> CALLER (page-locked) or
+ *                                                         LANE_HOST (pageable, and collect copies it to the caller)
+ *                                                         for a host batch; else there is no tail
  *
- * out_bytes, what leaves: sum n_out Oc E with a resampler, else n Oc 1024 E.  device_need, what a caller's device buffer must hold:
- * n_streams Oc stride_frames 1024 E planar, out_bytes packed.  The caller's memory is written by exactly one stage, the last.
+ * With a feature stage (aacg_pipeline_set_features: n_mels float32 per feature frame leave in the place of Oc = 1 channel of PCM) the
+ * stages in front of it write lane buffers whatever the destination — the transform LANE_PCM, the mix LANE_MIX, the resampler LANE_RS
+ * with row 0 — and the feature stage is the one that writes the caller's device memory.
+ *
+ * out_bytes, what leaves: sum ft_out n_mels 4 with a feature stage, else sum n_out Oc E with a resampler, else n Oc 1024 E.
+ * device_need, what a caller's device buffer must hold: n_streams n_mels stride_frames 4 (features) or n_streams Oc stride_frames 1024
+ * E planar, out_bytes packed.  The caller's memory is written by exactly one stage, the last.
  *
  * A stage more on the way out (a gain, a limiter, another layout) is a row more here and a block more in enqueue_out's walk.
  */
@@ -34,10 +41,11 @@
 #include "../../include/aacgpu.h"
 
 /* a buffer a stage reads or writes: the lane's d_pcm, d_mix, d_rs, its page-locked h_pcm, or the caller's memory (host or device) */
-enum { AACG_EXIT_BUF_NONE = 0, AACG_EXIT_LANE_PCM, AACG_EXIT_LANE_MIX, AACG_EXIT_LANE_RS, AACG_EXIT_LANE_HOST, AACG_EXIT_CALLER };
+enum { AACG_EXIT_BUF_NONE = 0, AACG_EXIT_LANE_PCM, AACG_EXIT_LANE_MIX, AACG_EXIT_LANE_RS, AACG_EXIT_LANE_HOST, AACG_EXIT_CALLER,
+       AACG_EXIT_LANE_FT };    /* (the lane's d_ft: a host batch's feature frames) */
 /* where the caller wants the batch's PCM */
 enum { AACG_EXIT_HOST_PINNED = 0, AACG_EXIT_HOST_PAGEABLE, AACG_EXIT_DEV_PACKED, AACG_EXIT_DEV_PLANAR };
-enum { AACG_EXIT_XFORM = 0, AACG_EXIT_MIX, AACG_EXIT_RESAMPLE, AACG_EXIT_TAIL };
+enum { AACG_EXIT_XFORM = 0, AACG_EXIT_MIX, AACG_EXIT_RESAMPLE, AACG_EXIT_TAIL, AACG_EXIT_FEATURES };
 enum { AACG_EXIT_TAIL_NONE = 0, AACG_EXIT_TAIL_PLANAR_LAUNCH, AACG_EXIT_TAIL_COPY_DOWN };
 
 /* what the pipeline is */
@@ -47,6 +55,8 @@ typedef struct aacg_exit_pipe {
     uint32_t elem;             /* 4 or 2                                                                                        */
     uint32_t max_streams, max_frames;
     uint64_t lane_elems;       /* a resampler: elements of the largest batch's output (aacg_pipe::exit_resample_most x Oc)      */
+    uint32_t n_mels;           /* a feature stage: floats per feature frame (0: none)                                           */
+    uint64_t ft_lane_elems;    /* ... and the floats of the largest batch's output (aacg_pipe::exit_features_most x n_mels)     */
 } aacg_exit_pipe;
 
 /* what the batch is */
@@ -56,6 +66,8 @@ typedef struct aacg_exit_batch {
     uint32_t stride_frames;               /* a device batch's (aacg_pcm_device_out)                                             */
     uint32_t rs_most;                     /* a resampler: the largest n_out of a stream ...                                     */
     uint64_t rs_total;                    /* ... and the sum of them                                                            */
+    uint32_t ft_most;                     /* a feature stage: the largest count of feature frames of a stream ...               */
+    uint64_t ft_total;                    /* ... and the sum of them                                                            */
 } aacg_exit_batch;
 
 typedef struct aacg_exit_stage {
@@ -64,13 +76,14 @@ typedef struct aacg_exit_stage {
 } aacg_exit_stage;
 
 typedef struct aacg_exit_plan {
-    aacg_exit_stage stage[4];             /* in the order they are enqueued; the first is the transform                         */
+    aacg_exit_stage stage[5];             /* in the order they are enqueued; the first is the transform                         */
     uint32_t n_stages;
     uint32_t row;                         /* a planar resample: elements per row; else 0                                        */
     uint64_t xform_bytes;                 /* what the transform writes: the clear for unlearnt streams acts on it               */
     uint64_t out_bytes;                   /* what leaves                                                                        */
     uint64_t device_need;                 /* a device batch: the bytes the caller's buffer must hold                            */
     uint32_t collect_copy;                /* collect copies out_bytes from LANE_HOST to the caller                              */
+    uint32_t ft_row;                      /* planar features: feature frames per row; else 0                                    */
 } aacg_exit_plan;
 
 /* a refusal of aacg_pipeline_submit_device: AACG_OK, or the code and the text.  late: the rule comes BEHIND the runtime's answer
@@ -88,9 +101,17 @@ inline uint64_t exit_resample_most(uint32_t max_streams, uint32_t max_frames, ui
     return ((uint64_t)max_streams * max_frames * 1024u * L + M - 1u) / M + max_streams;
 }
 
+/* the most feature frames a batch can emit: a stream that brings n samples completes at most n / H + 1 frames.  most_samples: the
+ * batch's most samples, exit_resample_most with a resampler, else max_streams x max_frames x 1024 */
+inline uint64_t exit_features_most(uint32_t max_streams, uint64_t most_samples, uint32_t H)
+{
+    return most_samples / H + max_streams;
+}
+
 /* bytes of a lane's page-locked staging (h_pcm): the largest batch's out_bytes */
 inline size_t exit_host_capacity(const aacg_exit_pipe& P)
 {
+    if (P.n_mels) return (size_t)P.ft_lane_elems * 4u;
     return (size_t)(P.resampled ? P.lane_elems : (uint64_t)P.max_streams * P.max_frames * exit_out_channels(P) * 1024u) * P.elem;
 }
 
@@ -99,7 +120,9 @@ inline uint32_t exit_dest_device(int32_t layout) { return layout == AACG_PCM_PLA
 inline aacg_exit_plan exit_plan(const aacg_exit_pipe& P, const aacg_exit_batch& B)
 {
     const uint64_t E = P.elem, Oc = exit_out_channels(P);
-    const bool packed = B.dest == AACG_EXIT_DEV_PACKED, planar = B.dest == AACG_EXIT_DEV_PLANAR, rs = P.resampled != 0;
+    const bool ft = P.n_mels != 0, to_dev = B.dest == AACG_EXIT_DEV_PACKED || B.dest == AACG_EXIT_DEV_PLANAR;
+    /* (the stages in front of a feature stage see neither device destination: they write lane buffers) */
+    const bool packed = B.dest == AACG_EXIT_DEV_PACKED && !ft, planar = B.dest == AACG_EXIT_DEV_PLANAR && !ft, rs = P.resampled != 0;
     aacg_exit_plan X = {};
     uint8_t last = AACG_EXIT_BUF_NONE;                   /* the buffer the stage before wrote */
     auto push = [&](uint8_t what, uint8_t dst, uint64_t bytes, uint8_t tail) { X.stage[X.n_stages++] = {what, last, dst, tail, bytes}; last = dst; };
@@ -111,8 +134,14 @@ inline aacg_exit_plan exit_plan(const aacg_exit_pipe& P, const aacg_exit_batch& 
     push(AACG_EXIT_XFORM, packed && !P.O && !rs ? AACG_EXIT_CALLER : AACG_EXIT_LANE_PCM, X.xform_bytes, AACG_EXIT_TAIL_NONE);
     if (P.O) push(AACG_EXIT_MIX, packed && !rs ? AACG_EXIT_CALLER : AACG_EXIT_LANE_MIX, mix_bytes, AACG_EXIT_TAIL_NONE);
     if (rs) push(AACG_EXIT_RESAMPLE, packed || planar ? AACG_EXIT_CALLER : AACG_EXIT_LANE_RS, X.out_bytes, AACG_EXIT_TAIL_NONE);
+    if (ft) {
+        X.out_bytes = B.ft_total * P.n_mels * 4u;        /* (the stage in front has its own bytes in its row) */
+        X.ft_row = B.dest == AACG_EXIT_DEV_PLANAR ? B.stride_frames : 0u;
+        X.device_need = B.dest == AACG_EXIT_DEV_PLANAR ? (uint64_t)B.n_streams * P.n_mels * B.stride_frames * 4u : to_dev ? X.out_bytes : 0u;
+        push(AACG_EXIT_FEATURES, to_dev ? AACG_EXIT_CALLER : AACG_EXIT_LANE_FT, X.out_bytes, AACG_EXIT_TAIL_NONE);
+    }
     if (planar && !rs) push(AACG_EXIT_TAIL, AACG_EXIT_CALLER, X.out_bytes, AACG_EXIT_TAIL_PLANAR_LAUNCH);
-    else if (!packed && !planar) {
+    else if (!to_dev) {
         X.collect_copy = B.dest == AACG_EXIT_HOST_PAGEABLE;
         push(AACG_EXIT_TAIL, X.collect_copy ? AACG_EXIT_LANE_HOST : AACG_EXIT_CALLER, X.out_bytes, AACG_EXIT_TAIL_COPY_DOWN);
     }
@@ -128,6 +157,14 @@ inline aacg_exit_refusal exit_check(const aacg_exit_pipe& P, const aacg_exit_bat
     if ((uintptr_t)out.d_pcm & 15u) return no(AACG_ERR_INVALID_ARG, false, "d_pcm is not 16-byte aligned");
     if (out.layout != AACG_PCM_PACKED && out.layout != AACG_PCM_PLANAR) return no(AACG_ERR_INVALID_ARG, false, "unknown layout (AACG_PCM_PACKED or AACG_PCM_PLANAR)");
     if (out.layout == AACG_PCM_PACKED && out.stride_frames) return no(AACG_ERR_INVALID_ARG, false, "AACG_PCM_PACKED takes stride_frames 0");
+    if (P.n_mels) {                                      /* a feature stage: stride_frames counts FEATURE frames per row, and no aacg_pcm_planar launch is involved */
+        if (out.layout == AACG_PCM_PLANAR) {
+            if (!out.stride_frames || out.stride_frames > (1u << 21)) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is not in 1..2^21");
+            if (out.stride_frames < B.ft_most) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is below a stream's count of feature frames (aacg_pipeline_out_samples)");
+        }
+        if ((uint64_t)out.d_pcm_bytes < X.device_need) return no(AACG_ERR_CAPACITY, true, "d_pcm_bytes is smaller than the batch needs (" + std::to_string(X.device_need) + " bytes)");
+        return {AACG_OK, false, std::string()};
+    }
     if (out.layout == AACG_PCM_PLANAR && !rs && out.stride_frames < B.longest) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is below the batch's largest frame count");
     if (out.layout == AACG_PCM_PLANAR && rs) {
         if (!out.stride_frames || out.stride_frames > (1u << 21)) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is not in 1..2^21");

@@ -38,7 +38,8 @@
  * window_shape_prev of the batch's unit records from the frame before and, across batches, from the engine's per-channel state.
  *
  * THE WAY OUT is a chain: transform -> mix (aacg_pipeline_set_mix: O = 1 or 2 channels leave in the place of C) -> resample
- * (aacg_pipeline_set_resample: each stream's PCM leaves at L / M times the rate, a ragged count of samples per stream) -> tail (the
+ * (aacg_pipeline_set_resample: each stream's PCM leaves at L / M times the rate, a ragged count of samples per stream) -> features
+ * (aacg_pipeline_set_features: one channel of PCM framed and transformed, float32 (log-)mel feature frames leave in its place) -> tail (the
  * planar launch for aacg_pipeline_submit_device with AACG_PCM_PLANAR, the copy down for a host batch, nothing for PCM left packed on
  * the device).  Which links a batch has, which buffer each reads and writes — a lane's, or the caller's in the place of the last — and
  * how many bytes is decided ONCE, in check_batch, by aacg_pipe::exit_plan (aacg_pipe_exit.h has the table, tests/test_pipe_exit_plan.py
@@ -47,13 +48,14 @@
  * The resampler has state per slot — a clock, kept here modulo M, and on the device the last T - 1 samples per channel,
  * double-buffered — which consecutive batches hand on ACROSS lanes: an event behind every resample launch, awaited by the next batch's
  * on its own stream behind that lane's parse and transform.  Clocks and parities advance when a batch has been enqueued, not before;
- * the per-stream records travel up in the lane's one staging block, behind the per-stream table.
+ * the per-stream records travel up in the lane's one staging block, behind the per-stream table.  The feature stage has the same kind
+ * of state — a clock, kept here in 64 bits, and on the device the last K - 1 samples — and is ordered and advanced in the same way.
  *
  * On a lane's stream, in this order: clear (unlearnt streams) -> copy up -> stale count -> parse -> TNS records -> map / shape ->
- * refresh -> carry -> fork -> transform -> join -> mix -> wait / resample / record -> planar or copy down -> results copy -> `done`.
+ * refresh -> carry -> fork -> transform -> join -> mix -> wait / resample / record -> wait / features / record -> planar or copy down -> results copy -> `done`.
  *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
- * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h for the tables it fills and the
+ * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h / aacg_pcm_features.h for the tables it fills and the
  * side launches it makes).  DESIGN.md 7a has how it came to be this way, round by round.
  */
 #include <hip/hip_runtime.h>
@@ -70,6 +72,8 @@
 #include "aacg_pcm_mix.h"
 #include "aacg_pcm_planar.h"
 #include "aacg_pcm_resample.h"
+#define AACG_FEATURES_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_features.hip's */
+#include "aacg_pcm_features.h"
 #include "aacg_pipe_exit.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
@@ -85,6 +89,8 @@ bool aacg_planar_launch(const aacg_planar_args& A, hipStream_t s);
 bool aacg_mix_launch(const aacg_mix_args& A, hipStream_t s);
 /* aacg_engine_resample.hip: a batch's packed PCM resampled by L / M (aacg_pcm_resample.h); false: not a launch it serves */
 bool aacg_resample_launch(const aacg_resample_args& A, hipStream_t s);
+/* aacg_engine_features.hip: a batch's one-channel PCM to (log-)mel feature frames (aacg_pcm_features.h); false: not a launch it serves */
+bool aacg_features_launch(const aacg_features_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -135,6 +141,17 @@ struct aacg_pipeline {
         hipEvent_t last = nullptr;
         size_t lane_elems = 0;          /* the largest batch's output: elements of a lane's d_rs and h_pcm */
     } rs;
+    /* aacg_pipeline_set_features: the stage's parameters (K = 0: none), its tables and the slots' histories on the device ([slot][2][K - 1]
+     * floats), and per slot what the host keeps: the clock (input samples of the stage since the slot's reset), which history buffer the
+     * slot's next batch reads, and whether it has consumed anything since its reset.  last: the event behind the latest features launch */
+    struct features_t {
+        uint32_t K = 0, H = 0, P = 0, R = 0, n_mels = 0, log = 0;
+        float floor = 0.0f;
+        void *d_basis = nullptr, *d_fb = nullptr, *d_hist = nullptr;
+        std::vector<uint64_t> N; std::vector<uint8_t> parity, fresh;
+        hipEvent_t last = nullptr;
+        size_t lane_elems = 0;          /* the largest batch's output: floats of a lane's d_ft and h_pcm */
+    } ft;
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -163,6 +180,8 @@ struct aacg_pipeline {
         void* d_mix = nullptr;            /* aacg_pipeline_set_mix: the mixed PCM of a host or planar batch, max_streams x max_frames x 1024 x O elements */
         void* d_rs = nullptr;             /* aacg_pipeline_set_resample: the resampled PCM of a host batch, rs.lane_elems elements */
         hipEvent_t rs_done = nullptr;     /* ... and the event behind this lane's latest resample launch */
+        void* d_ft = nullptr;             /* aacg_pipeline_set_features: the feature frames of a host batch, ft.lane_elems floats */
+        hipEvent_t ft_done = nullptr;     /* ... and the event behind this lane's latest features launch */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
          * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
@@ -210,7 +229,8 @@ uint32_t out_channels(const aacg_pipeline* p) { return p->O ? p->O : p->C; }
 /* what the pipeline is, for aacg_pipe::exit_plan and what goes with it (aacg_pipe_exit.h) */
 aacg_exit_pipe exit_pipe(const aacg_pipeline* p)
 {
-    return {p->C, p->O, p->rs.L != 0, (uint32_t)pcm_elem(p), (uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.lane_elems};
+    return {p->C, p->O, p->rs.L != 0, (uint32_t)pcm_elem(p), (uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.lane_elems,
+            p->ft.K ? p->ft.n_mels : 0u, p->ft.lane_elems};
 }
 /* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M), the first
  * through ceil((q M + n) L / M) = q L + ceil(n L / M) so that the one formula (aacg_resample_ceil) sees the arguments it is made for */
@@ -313,13 +333,15 @@ struct batch_t {
     aacg_exit_plan X;                            /* check_batch: the way out (aacg_pipe_exit.h) — which stage writes which buffer, and how many bytes */
     staging_t G;                                 /* stage_batch (the per-stream table lies at G.extra_at) */
     size_t rs_at;                                /* stage_batch: where the records lie in the staging block */
+    std::vector<aacg_features_stream> ft;        /* check_batch, a feature stage: the batch's records, from the host's clocks */
+    size_t ft_at;                                /* stage_batch: where those lie, behind the resampler's */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
 /* a buffer of the exit plan, for this lane and this batch */
 void* exit_buf(const aacg_pipeline::lane_t& L, const batch_t& B, uint8_t id)
 {
-    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_CALLER */
+    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out, L.d_ft};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_LANE_FT */
     return of[id];
 }
 
@@ -529,13 +551,14 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (W.st) (void)hipStreamDestroy(W.st);
     }
     for (auto& L : p->lane) {
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_mix, L.d_rs, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
         for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.rs_done) (void)hipEventDestroy(L.rs_done);
+        if (L.ft_done) (void)hipEventDestroy(L.ft_done);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
-    for (void* d : {p->rs.d_table, p->rs.d_hist}) if (d) (void)hipFree(d);
+    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -642,6 +665,7 @@ int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* 
     if (p->O) { p->err = "aacg_pipeline_set_mix: the pipeline has a mix already"; return AACG_ERR_INVALID_ARG; }
     if (p->submitted) { p->err = "aacg_pipeline_set_mix: a batch has been submitted (the mix is set before the first)"; return AACG_ERR_INVALID_ARG; }
     if (p->rs.L) { p->err = "aacg_pipeline_set_mix: the pipeline has a resampler already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (p->ft.K) { p->err = "aacg_pipeline_set_mix: the pipeline has a feature stage already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (out_channels < 1 || out_channels > AACG_MIX_MAX_OUT) { p->err = "aacg_pipeline_set_mix: out_channels is not 1 or 2"; return AACG_ERR_INVALID_ARG; }
     if (!matrix) { p->err = "aacg_pipeline_set_mix: no matrix"; return AACG_ERR_INVALID_ARG; }
     for (uint32_t i = 0; i < out_channels * p->C; i++)
@@ -664,6 +688,7 @@ int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_
     /* every refusal leaves the pipeline exactly as it was */
     if (p->rs.L) { p->err = "aacg_pipeline_set_resample: the pipeline has a resampler already"; return AACG_ERR_INVALID_ARG; }
     if (p->submitted) { p->err = "aacg_pipeline_set_resample: a batch has been submitted (the resampler is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (p->ft.K) { p->err = "aacg_pipeline_set_resample: the pipeline has a feature stage already (the resampler is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (const int why = aacg_resample_check(L, M, taps)) { p->err = std::string("aacg_pipeline_set_resample: ") + aacg_resample_why(why); return AACG_ERR_INVALID_ARG; }
     if (!table) { p->err = "aacg_pipeline_set_resample: no table"; return AACG_ERR_INVALID_ARG; }
     const size_t n_table = (size_t)L * taps;
@@ -693,6 +718,49 @@ int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_
     return AACG_OK;
 }
 
+int aacg_pipeline_set_features(aacg_pipeline* p, const aacg_features_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (!cfg) { p->err = "aacg_pipeline_set_features: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (p->ft.K) { p->err = "aacg_pipeline_set_features: the pipeline has a feature stage already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_features: a batch has been submitted (the stage is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    const uint32_t K = cfg->frame_length, H = cfg->hop, R = cfg->n_rows, NM = cfg->n_mels;
+    if (const int why = aacg_features_check(K, H, cfg->pad_left, R, NM)) { p->err = std::string("aacg_pipeline_set_features: ") + aacg_features_why(why); return AACG_ERR_INVALID_ARG; }
+    if (!(cfg->floor > 0.0f) || !std::isfinite(cfg->floor)) { p->err = "aacg_pipeline_set_features: floor is not positive and finite"; return AACG_ERR_INVALID_ARG; }
+    if (out_channels(p) != 1u) { p->err = "aacg_pipeline_set_features: the stage takes ONE channel (channels == 1, or a mix with out_channels 1)"; return AACG_ERR_INVALID_ARG; }
+    if (!cfg->basis || !cfg->fb) { p->err = "aacg_pipeline_set_features: no table"; return AACG_ERR_INVALID_ARG; }
+    const size_t n_basis = (size_t)R * K, n_fb = (size_t)NM * (R / 2u);
+    for (size_t i = 0; i < n_basis; i++)
+        if (!std::isfinite(cfg->basis[i])) { p->err = "aacg_pipeline_set_features: entry " + std::to_string(i) + " of basis is not finite"; return AACG_ERR_INVALID_ARG; }
+    for (size_t i = 0; i < n_fb; i++)
+        if (!std::isfinite(cfg->fb[i])) { p->err = "aacg_pipeline_set_features: entry " + std::to_string(i) + " of fb is not finite"; return AACG_ERR_INVALID_ARG; }
+    /* the largest batch's output, floats: the kernel and its records count them in 32 bits */
+    const uint64_t samples = p->rs.L ? aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.L, p->rs.M)
+                                     : (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * 1024u;
+    const uint64_t most = aacg_pipe::exit_features_most((uint32_t)p->cfg.max_streams, samples, H) * NM;
+    if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_features: max_streams x max_frames x 1024 x (L / M) / hop x n_mels is 2^31 or more"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const size_t hist_bytes = (size_t)p->cfg.max_streams * 2u * (K - 1u) * sizeof(float);
+    void *d_basis = nullptr, *d_fb = nullptr, *d_hist = nullptr;
+    /* (the tables, synchronously: nothing is in flight yet.  The history needs no clearing: a fresh slot's is not read) */
+    if (hipMalloc(&d_basis, n_basis * sizeof(float)) != hipSuccess || hipMalloc(&d_fb, n_fb * sizeof(float)) != hipSuccess || hipMalloc(&d_hist, hist_bytes) != hipSuccess ||
+        !lanes_alloc(p, &lane_t::d_ft, (size_t)most * sizeof(float), &lane_t::ft_done) ||
+        hipMemcpy(d_basis, cfg->basis, n_basis * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_fb, cfg->fb, n_fb * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* d : {d_basis, d_fb, d_hist}) if (d) (void)hipFree(d);
+        lanes_release(p, &lane_t::d_ft, &lane_t::ft_done);
+        p->err = "aacg_pipeline_set_features: no device memory for the tables, the slots' histories and the lanes' feature frames";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    drop_host_staging(p);
+    p->ft.d_basis = d_basis; p->ft.d_fb = d_fb; p->ft.d_hist = d_hist; p->ft.lane_elems = (size_t)most;
+    p->ft.N.assign((size_t)p->cfg.max_streams, 0u); p->ft.parity.assign((size_t)p->cfg.max_streams, 0); p->ft.fresh.assign((size_t)p->cfg.max_streams, 1);
+    p->ft.H = H; p->ft.P = cfg->pad_left; p->ft.R = R; p->ft.n_mels = NM; p->ft.log = cfg->log ? 1u : 0u; p->ft.floor = cfg->floor; p->ft.K = K;
+    return AACG_OK;
+}
+
 int aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out)
 {
     if (!p || !slots || !frames_of || !n_out) return AACG_ERR_INVALID_ARG;
@@ -701,6 +769,8 @@ int aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uin
         if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "aacg_pipeline_out_samples: a stream brings more frames than max_frames"; return AACG_ERR_INVALID_ARG; }
     }
     for (uint32_t s = 0; s < n_streams; s++) n_out[s] = p->rs.L ? resample_count(p, p->rs.n0[slots[s]], frames_of[s]) : frames_of[s] * 1024u;
+    if (p->ft.K)                                         /* feature frames: what the samples above complete at the slots' clocks */
+        for (uint32_t s = 0; s < n_streams; s++) { aacg_features_stream r; aacg_features_span(p->ft.K, p->ft.H, p->ft.P, p->ft.N[slots[s]], n_out[s], &r); n_out[s] = r.n_out; }
     return AACG_OK;
 }
 
@@ -740,6 +810,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     int rc = aacg_reset_stream(p->engine, slot);
     if (rc) return engine_fail(p, "", rc);
     if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
+    if (p->ft.K) { p->ft.N[slot] = 0; p->ft.fresh[slot] = 1; }       /* ... and the feature stage's */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
         drop_plans_with(p, slot);
@@ -784,6 +855,21 @@ int check_batch(aacg_pipeline* p, batch_t& B)
             if (n_out > b.rs_most) b.rs_most = n_out;
         }
     }
+    if (p->ft.K) {                                       /* what each stream's samples complete, from the slots' clocks as they stand: one channel, so samples are elements */
+        B.ft.resize(B.n_streams);
+        uint32_t items = 0;
+        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
+            const uint32_t slot = B.slots[s];
+            aacg_features_stream& r = B.ft[s];
+            aacg_features_span(p->ft.K, p->ft.H, p->ft.P, p->ft.N[slot], p->rs.L ? B.rs[s].n_out : B.frames_of[s] * 1024u, &r);
+            r.in_first = p->rs.L ? B.rs[s].out_first : first * 1024u;
+            r.out_first = (uint32_t)b.ft_total; r.item_first = items; r.slot = slot;
+            r.flags = (uint32_t)p->ft.parity[slot] | (p->ft.fresh[slot] ? 2u : 0u);
+            items += aacg_features_items(r.n_out);
+            b.ft_total += r.n_out;
+            if (r.n_out > b.ft_most) b.ft_most = r.n_out;
+        }
+    }
     B.X = aacg_pipe::exit_plan(exit_pipe(p), b);
     return B.pcm_out ? AACG_OK : check_device_out(p, B, b);
 }
@@ -795,10 +881,14 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
 {
     /* (a resampler's per-stream records lie behind the per-stream table, 16-byte aligned: one block, one copy up) */
     const size_t tab_bytes = (size_t)B.n_streams * (p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)), tab16 = (tab_bytes + 15) & ~(size_t)15;
-    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, p->rs.L ? tab16 + B.rs.size() * sizeof(aacg_resample_stream) : tab_bytes, B.G);
+    /* (... and a feature stage's behind those: both records are 32 bytes) */
+    const size_t rs_bytes = B.rs.size() * sizeof(aacg_resample_stream), ft_bytes = B.ft.size() * sizeof(aacg_features_stream);
+    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, rs_bytes + ft_bytes ? tab16 + rs_bytes + ft_bytes : tab_bytes, B.G);
     if (rc) return rc;
     B.rs_at = B.G.extra_at + tab16;
-    if (p->rs.L) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), B.rs.size() * sizeof(aacg_resample_stream));
+    B.ft_at = B.rs_at + rs_bytes;
+    if (rs_bytes) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), rs_bytes);
+    if (ft_bytes) std::memcpy((char*)L.h_in + B.ft_at, B.ft.data(), ft_bytes);
     L.d_frames = (char*)L.d_bytes + B.G.padded;
     if (B.X.collect_copy && !L.h_pcm) P_TRY(p, hipHostMalloc(&L.h_pcm, aacg_pipe::exit_host_capacity(exit_pipe(p)), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
     return AACG_OK;
@@ -902,6 +992,17 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
             if (!aacg_resample_launch(A, L.st)) { p->err = "aacg_pcm_resample: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
             P_TRY(p, hipEventRecord(L.rs_done, L.st), AACG_ERR_NO_DEVICE);
             p->rs.last = L.rs_done;
+        } else if (S.what == AACG_EXIT_FEATURES) {
+            /* the one channel of PCM, as the stage before left it, into feature frames, either layout.  The slots' histories pass from batch
+             * to batch like the resampler's: this launch waits for the one before it, here */
+            uint32_t items = 0;
+            for (const auto& r : B.ft) items += aacg_features_items(r.n_out);
+            const aacg_features_args A = {src, (float*)dst, (const aacg_features_stream*)((const char*)L.d_bytes + B.ft_at), (const float*)p->ft.d_basis, (const float*)p->ft.d_fb,
+                                          (float*)p->ft.d_hist, B.n_streams, items, p->ft.K, p->ft.H, p->ft.R, p->ft.n_mels, p->ft.floor, p->ft.log, B.X.ft_row, E};
+            if (p->ft.last && p->ft.last != L.ft_done) P_TRY(p, hipStreamWaitEvent(L.st, p->ft.last, 0), AACG_ERR_NO_DEVICE);
+            if (!aacg_features_launch(A, L.st)) { p->err = "aacg_pcm_features: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+            P_TRY(p, hipEventRecord(L.ft_done, L.st), AACG_ERR_NO_DEVICE);
+            p->ft.last = L.ft_done;
         } else if (S.tail == AACG_EXIT_TAIL_PLANAR_LAUNCH) {
             /* the caller's tensor from the packed PCM and the per-stream table that came up with the bytes (either plan mode's record
              * begins with frame_first and frames), padding included: where the copy down sits for a host batch */
@@ -925,6 +1026,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
         p->rs.n0[r.slot] = (uint32_t)(((uint64_t)r.n0 + 1024ull * r.frames) % p->rs.M);
         p->rs.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->rs.fresh[r.slot] = 0;
     }
+    for (const auto& r : B.ft) { p->ft.N[r.slot] += r.n_in; p->ft.parity[r.slot] = (uint8_t)((r.flags & 1u) ^ 1u); p->ft.fresh[r.slot] = 0; }
     *ticket = L.ticket;
     return AACG_OK;
 }

@@ -38,7 +38,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_get_window_shape", "aacg_set_window_shape", "aacg_plan_carry_window_shape", "aacg_pipeline_stream_window_shape",
                "aacg_pipeline_submit_device", "aacg_pipeline_wait_device",
                "aacg_pipeline_set_mix", "aacg_pipeline_out_channels", "aacg_mix_standard",
-               "aacg_pipeline_set_resample", "aacg_pipeline_out_samples", "aacg_resample_counts", "aacg_resample_design"]
+               "aacg_pipeline_set_resample", "aacg_pipeline_out_samples", "aacg_resample_counts", "aacg_resample_design",
+               "aacg_pipeline_set_features", "aacg_features_counts", "aacg_features_design"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -106,6 +107,12 @@ AACG_PCM_PACKED, AACG_PCM_PLANAR = PCM_PACKED, PCM_PLANAR
 
 class PcmDeviceOut(C.Structure):
     _fields_ = [("d_pcm", C.c_void_p), ("d_pcm_bytes", C.c_size_t), ("layout", C.c_int32), ("stride_frames", C.c_uint32)]
+
+
+# aacg_features_config: the feature stage's parameters and tables (aacg_pipeline_set_features)
+class FeaturesConfig(C.Structure):
+    _fields_ = [("frame_length", C.c_uint32), ("hop", C.c_uint32), ("pad_left", C.c_uint32), ("n_rows", C.c_uint32), ("n_mels", C.c_uint32),
+                ("log", C.c_uint32), ("floor", C.c_float), ("basis", C.c_void_p), ("fb", C.c_void_p)]
 
 
 # aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
@@ -283,6 +290,9 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_out_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.aacg_resample_counts.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.aacg_resample_design.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.aacg_pipeline_set_features.argtypes = [C.c_void_p, C.POINTER(FeaturesConfig)]
+    L.aacg_features_counts.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.aacg_features_design.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     _lib = L
     return L
 
@@ -479,11 +489,15 @@ class Pipeline:
     resample: (L, M, table) with table an (L, taps) float matrix (aacg_pipeline_set_resample; resample_design makes the usual one), or
     out_rate: a sample rate, for which the default table is designed from the rate of sample_index.  The PCM then leaves at L / M times
     the streams' rate, a ragged count of samples per stream: decode and collect return (pcm, results, n_refused, lengths) with pcm flat,
-    stream after stream, lengths[s] samples of self.channels each; decode_tensor's lengths are those counts.  self.rate is the PCM's."""
+    stream after stream, lengths[s] samples of self.channels each; decode_tensor's lengths are those counts.  self.rate is the PCM's.
+    features: a dict for set_features (aacg_pipeline_set_features; features_design makes the usual tables) — frame_length, hop, basis
+    (2 x bins, frame_length), fb (n_mels, bins) and optionally pad_left, log, floor.  The last stage of the way out: float32 feature
+    frames leave in the place of one channel of PCM, ragged like a resampler's samples: decode and collect return (frames, results,
+    n_refused, lengths) with frames flat, lengths[s] feature frames of n_mels floats each; decode_tensor returns (S, n_mels, T)."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32):
+                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -499,6 +513,7 @@ class Pipeline:
         self.handle, self.channels, self.i16, self.device = h, channels, output_kind == OUTPUT_I16, device
         self.in_channels = channels
         self.resample, self.rate = None, SAMPLE_RATES[sample_index]
+        self.features = None
         self._keep = {}
         if mix is not None:
             m = np.ascontiguousarray(mix, np.float32)
@@ -520,6 +535,12 @@ class Pipeline:
             try:
                 self.set_resample(*resample)
             except (AacgError, ValueError):
+                self.close()
+                raise
+        if features is not None:
+            try:
+                self.set_features(**features)
+            except (AacgError, ValueError, TypeError):
                 self.close()
                 raise
 
@@ -573,8 +594,20 @@ class Pipeline:
         self.resample = (int(L), int(M), h)
         self.rate = self.rate * int(L) / int(M)
 
+    def set_features(self, frame_length, hop, basis, fb, pad_left=0, log=True, floor=1e-10):
+        """aacg_pipeline_set_features: basis (2 x bins, frame_length) and fb (n_mels, bins) float matrices, before the first batch and
+        after the mix and the resampler; from then on feature frames of n_mels float32 leave instead of PCM."""
+        basis, fb = np.ascontiguousarray(basis, np.float32), np.ascontiguousarray(fb, np.float32)
+        if basis.ndim != 2 or fb.ndim != 2 or basis.shape[1] != int(frame_length) or basis.shape[0] != 2 * fb.shape[1]:
+            raise ValueError("Pipeline: the feature stage's tables are not (2 x bins, frame_length) and (n_mels, bins) matrices")
+        cfg = FeaturesConfig(int(frame_length), int(hop), int(pad_left), basis.shape[0], fb.shape[0], 1 if log else 0, float(floor), basis.ctypes.data, fb.ctypes.data)
+        self._check(self.lib.aacg_pipeline_set_features(self.handle, C.byref(cfg)))
+        self.features = {"frame_length": int(frame_length), "hop": int(hop), "pad_left": int(pad_left), "n_mels": int(fb.shape[0]), "log": bool(log),
+                         "floor": float(np.float32(floor)), "basis": basis, "fb": fb}
+
     def out_samples(self, slots, frames_per_stream):
-        """aacg_pipeline_out_samples: the samples per channel that the NEXT batch of these slots with these counts emits, per stream"""
+        """aacg_pipeline_out_samples: the samples per channel that the NEXT batch of these slots with these counts emits, per stream —
+        with a feature stage the feature frames"""
         slots = np.ascontiguousarray(slots, np.uint32)
         counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
         assert len(counts) == len(slots)
@@ -621,11 +654,13 @@ class Pipeline:
         assert frames.dtype == PARSE_FRAME_DTYPE and len(frames) == total
         n = len(frames)
         # a resampled pipeline: what each stream will emit (the clocks stand still until the batch is enqueued)
-        self._lengths = self.out_samples(slots, frames_per_stream).astype(np.int64) if self.resample else None
-        samples = int(self._lengths.sum()) if self.resample else n * 1024
+        self._ragged = bool(self.resample or self.features)
+        self._lengths = self.out_samples(slots, frames_per_stream).astype(np.int64) if self._ragged else None
+        samples = int(self._lengths.sum()) if self._ragged else n * 1024
+        width, dtype = (self.features["n_mels"], np.float32) if self.features else (self.channels, np.int16 if self.i16 else np.float32)
         if pcm is None:
-            pcm = np.zeros(samples * self.channels, np.int16 if self.i16 else np.float32)
-        assert pcm.size >= samples * self.channels
+            pcm = np.zeros(samples * width, dtype)
+        assert pcm.size >= samples * width and (not self.features or pcm.dtype == np.float32)
         return data, frames, slots, counts, pcm, np.zeros(n, PARSE_RESULT_DTYPE), C.c_uint32(0)
 
     def decode(self, data, frames, slots, frames_per_stream, pcm=None):
@@ -638,7 +673,7 @@ class Pipeline:
         else:
             self._check(self.lib.aacg_pipeline_decode_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                              counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
-        return (pcm, res, int(refused.value)) + ((self._lengths,) if self.resample else ())
+        return (pcm, res, int(refused.value)) + ((self._lengths,) if self._ragged else ())
 
     def submit(self, data, frames, slots, frames_per_stream, pcm=None):
         """Asynchronous: returns a ticket; collect(ticket) -> (pcm, results, n_refused).  frames_per_stream as for decode."""
@@ -650,7 +685,7 @@ class Pipeline:
         else:
             self._check(self.lib.aacg_pipeline_submit_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                              counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused), C.byref(t)))
-        self._keep[t.value] = (pcm, res, refused) + ((self._lengths,) if self.resample else ())
+        self._keep[t.value] = (pcm, res, refused) + ((self._lengths,) if self._ragged else ())
         return t.value
 
     def collect(self, ticket):
@@ -690,14 +725,17 @@ class Pipeline:
         slots = np.ascontiguousarray(slots, np.uint32)
         counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
         assert len(counts) == len(slots) and frames.dtype == PARSE_FRAME_DTYPE and len(frames) == int(counts.sum())
-        lengths = self.out_samples(slots, counts).astype(np.int64) if self.resample else None
+        lengths = self.out_samples(slots, counts).astype(np.int64) if self.resample or self.features else None
         if planar and stride_frames is None:
-            stride_frames = (int(counts.max()) if len(counts) else 0) if lengths is None else (int(lengths.max()) + 1023) // 1024
+            if self.features:                                     # rows of feature frames: the longest stream's count (at least one)
+                stride_frames = max(int(lengths.max()) if len(lengths) else 0, 1)
+            else:
+                stride_frames = (int(counts.max()) if len(counts) else 0) if lengths is None else (int(lengths.max()) + 1023) // 1024
         desc = PcmDeviceOut(addr, nbytes, (PCM_PLANAR if planar else PCM_PACKED) if layout is None else int(layout), int(stride_frames or 0))
         res, refused, t = np.zeros(len(frames), PARSE_RESULT_DTYPE), C.c_uint32(0), C.c_uint64()
         self._check(self.lib.aacg_pipeline_submit_device(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                          counts.ctypes.data, C.byref(desc), res.ctypes.data, C.byref(refused), C.byref(t)))
-        self._keep[t.value] = (out, res, refused) + ((lengths,) if self.resample else ())
+        self._keep[t.value] = (out, res, refused) + ((lengths,) if lengths is not None else ())
         return t.value
 
     def wait_device(self, ticket, stream=None):
@@ -726,7 +764,10 @@ class Pipeline:
         if self.resample:                                         # rows of whole kilosamples that hold the longest stream; packed: flat (samples, C)
             n_out = self.out_samples(slots, counts)
             shape = (len(slots), self.channels, (int(n_out.max()) + 1023) // 1024 * 1024) if planar else (int(n_out.sum()), self.channels)
-        out = torch.empty(shape, dtype=torch.int16 if self.i16 else torch.float32, device="cuda:%d" % self.device)
+        if self.features:                                         # (S, n_mels, T) with T the longest stream's feature frames; packed: flat (frames, n_mels)
+            n_out = self.out_samples(slots, counts)
+            shape = (len(slots), self.features["n_mels"], max(int(n_out.max()), 1)) if planar else (int(n_out.sum()), self.features["n_mels"])
+        out = torch.empty(shape, dtype=torch.int16 if self.i16 and not self.features else torch.float32, device="cuda:%d" % self.device)
         torch.cuda.current_stream(self.device).synchronize()      # nothing of the block's previous life is still queued when the lane writes it
         t = self.submit_device(data, frames, slots, counts, out, planar=bool(planar))
         self.wait_device(t)
@@ -755,6 +796,28 @@ def resample_design(in_rate, out_rate, taps=32, rolloff=0.0, beta=0.0):
     if rc != 0:
         raise AacgError(rc, "aacg_resample_design(%d -> %d Hz, %d taps)" % (in_rate, out_rate, taps))
     return int(L.value), int(M.value), table
+
+
+def features_design(rate=16000, frame_length=400, hop=160, n_bins=None, n_mels=80, f_min=0.0, f_max=0.0):
+    """The usual tables of a feature stage (aacg_features_design, include/aacgpu.h): a dict for Pipeline(features=...) with the
+    periodic-Hann Fourier basis (2 n_bins, frame_length) and the Slaney mel filterbank (n_mels, n_bins); host code, no device.
+    n_bins None: frame_length // 2 + 1; f_max 0: rate / 2.  The defaults are Whisper's; add pad_left, log and floor as wanted."""
+    n_bins = int(frame_length) // 2 + 1 if n_bins is None else int(n_bins)
+    basis, fb = np.zeros((2 * n_bins, int(frame_length)), np.float32), np.zeros((int(n_mels), n_bins), np.float32)
+    rc = load_library().aacg_features_design(int(rate), int(frame_length), int(hop), n_bins, int(n_mels), float(f_min), float(f_max),
+                                             basis.ctypes.data, basis.size, fb.ctypes.data, fb.size)
+    if rc != 0:
+        raise AacgError(rc, "aacg_features_design(%d Hz, %d / %d, %d bins, %d mels)" % (rate, frame_length, hop, n_bins, n_mels))
+    return {"frame_length": int(frame_length), "hop": int(hop), "basis": basis, "fb": fb}
+
+
+def features_counts(frame_length, hop, pad_left, n0, samples):
+    """aacg_features_counts: the feature frames that `samples` further samples complete at the clock n0"""
+    n = C.c_uint64()
+    rc = load_library().aacg_features_counts(int(frame_length), int(hop), int(pad_left), int(n0), int(samples), C.byref(n))
+    if rc != 0:
+        raise AacgError(rc, "aacg_features_counts(%d / %d, pad %d)" % (frame_length, hop, pad_left))
+    return int(n.value)
 
 
 def resample_counts(L, M, n0, frames):

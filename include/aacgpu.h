@@ -921,6 +921,65 @@ int  aacg_resample_counts(uint32_t L, uint32_t M, uint32_t n0, uint32_t frames, 
  * null and capacity 0 only L and M are written (to size the table).  AACG_ERR_INVALID_ARG: a rate of 0, a null L or M, taps or the
  * reduced L / M outside aacg_pipeline_set_resample's limits, rolloff outside (0, 1], beta outside (0, 30], a capacity below L x taps. */
 int  aacg_resample_design(uint32_t in_rate, uint32_t out_rate, uint32_t taps, double rolloff, double beta, uint32_t* L, uint32_t* M, float* table, size_t capacity);
+/* A feature stage on the device, the LAST stage of the way out: (log-)mel feature frames leave in the place of PCM, for a model that
+ * computes on the card it decodes on (Whisper-style front ends: 400-sample frames every 160 samples of 16 kHz mono, 80 or 128 bands).
+ * The stage is set by caller-supplied tables (aacg_features_design makes the usual ones), all row-major float32, every entry finite:
+ *     K = frame_length, a multiple of 4 in 32..1024;  H = hop, 1..K;  P = pad_left, 0..K-1, the zeros assumed in front of the stream
+ *     (P = 0: an un-centred STFT; P = K / 2: a centred one with zero padding on the left);  R = n_rows, even, 2..1026, the rows of
+ *     basis[R][K], B = R / 2 bins whose two quadrature rows are rows 2b and 2b+1;  n_mels in 1..128 with fb[n_mels][B];  floor > 0
+ *     and finite;  log, a flag.
+ * The input x is the slot's PCM as the pipeline would have delivered it without the stage, batch after batch — after the mix and after
+ * the resampler if they are set — and it must be ONE channel: channels == 1, or a mix with out_channels 1.  On an AACG_OUTPUT_I16
+ * pipeline x is the already rounded int16 times 2^-15 (exact), so that both output kinds feed the stage the same scale.  x[n] = 0 for
+ * n < 0; a refused frame and a frame of an unlearnt stream are zeros, and they advance the clock like any other.
+ * THE RULE, bit for bit, in float32 throughout.  Feature frame j = 0, 1, ... of a slot since its reset covers x[j H - P + k], k = 0..K-1:
+ *     lin[r] = fmaf(basis[r][K-1], x[jH-P+K-1], ... fmaf(basis[r][1], x[jH-P+1], fmaf(basis[r][0], x[jH-P], +0)) ...)
+ *              one k-ordered FUSED chain from +0, every term computed
+ *     pw[b]  = lin[2b] * lin[2b] + lin[2b+1] * lin[2b+1]          each product rounded, then the sum rounded: nothing fused
+ *     mel[m] = the b-ordered fmaf chain of fb[m][b] * pw[b] from +0, over all B bins whatever their coefficient
+ *     out[m] = mel[m], or with log: log10f(max(mel[m], floor)), the library function (within its 3 ulp, not bit-exact across libraries)
+ * The output is float32 whatever the pipeline's output kind.
+ * Counts: after N consumed samples a slot has emitted count(N) = max(0, floor((N + P - K) / H) + 1) frames; a batch that moves the
+ * clock from N to N' emits count(N') - count(N), possibly none.  aacg_pipeline_out_samples answers in FEATURE FRAMES when the stage is
+ * set, aacg_features_counts for any clock.  Any split of a stream's frames into batches gives the same bits.  A reset sets N = 0.
+ * State per slot: the clock and the last K - 1 input samples, handed from batch to batch across lanes as the resampler's.
+ * Output layouts, with n_out[s] the feature frames of the batch's stream s: host memory and AACG_PCM_PACKED [stream s][n_out[s]][n_mels],
+ * tight, the streams one behind the other; AACG_PCM_PLANAR [stream][n_mels][stride_frames], a (B, n_mels, T) tensor — stride_frames
+ * then counts FEATURE frames per row, 1..2^21 and at least every n_out[s], and the padding behind n_out[s] is written with the value
+ * the rule gives for mel = 0: 0, or log10f(floor) with log.  Every element of the block is written exactly once, nothing outside it.
+ * Limit: max_streams x max_frames x 1024 x (L / M) / H x n_mels below 2^31.
+ * Results, refusal counts, tickets, lanes, plan modes, `stages`, ragged batches, span walks, the mix and the resampler are untouched:
+ * one more launch per batch (aacg_pcm_features_*) on the lane's stream, ordered behind the previous batch's; with no stage set nothing
+ * differs.  Called once, before the pipeline's first submitted batch and after aacg_pipeline_set_mix / aacg_pipeline_set_resample.
+ * AACG_ERR_INVALID_ARG, with the reason in aacg_pipeline_last_error and the pipeline exactly as it was: a limit broken, a null table,
+ * an entry that is not finite, a floor that is not positive and finite, more than one output channel, a call after the first batch, a
+ * second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the tables, the histories and the lanes' output; the pipeline stays as it was. */
+typedef struct aacg_features_config {
+    uint32_t frame_length;   /* K */
+    uint32_t hop;            /* H */
+    uint32_t pad_left;       /* P */
+    uint32_t n_rows;         /* R = 2 B */
+    uint32_t n_mels;
+    uint32_t log;            /* != 0: out = log10f(max(mel, floor)) */
+    float    floor;
+    const float* basis;      /* [n_rows][frame_length] */
+    const float* fb;         /* [n_mels][n_rows / 2] */
+} aacg_features_config;
+int  aacg_pipeline_set_features(aacg_pipeline* p, const aacg_features_config* cfg);
+/* Host code only: the feature frames that `samples` further samples complete at the clock n0, count(n0 + samples) - count(n0).
+ * AACG_ERR_INVALID_ARG: frame_length, hop or pad_left outside aacg_pipeline_set_features's limits, a null n_frames. */
+int  aacg_features_counts(uint32_t frame_length, uint32_t hop, uint32_t pad_left, uint64_t n0, uint64_t samples, uint64_t* n_frames);
+/* The usual tables for aacg_pipeline_set_features, host code only: into basis (room for basis_capacity floats, at least 2 n_bins x
+ * frame_length) the periodic Hann window w[k] = 0.5 - 0.5 cos(2 pi k / K) on a Fourier basis, basis[2b][k] = w[k] cos(2 pi b k / K) and
+ * basis[2b+1][k] = -w[k] sin(2 pi b k / K) (the angle taken from (b k) mod K), and into fb (fb_capacity, at least n_mels x n_bins) the
+ * Slaney mel filterbank with Slaney's area normalisation: the mel scale is 200 / 3 Hz per mel below 1 kHz and steps of ln(6.4) / 27
+ * above it; n_mels + 2 edges f[] equally spaced in mel from f_min to f_max (0: rate / 2); row m is the triangle over f[m], f[m+1],
+ * f[m+2] at the bins' frequencies b rate / K, scaled by 2 / (f[m+2] - f[m]).  Computed in double, each entry rounded to float once.
+ * hop takes no part in the tables and is checked only.  Whisper's: rate 16000, frame_length 400, hop 160, n_bins 201, n_mels 80 or 128.
+ * AACG_ERR_INVALID_ARG: a rate of 0, a null table, a parameter outside aacg_pipeline_set_features's limits (n_rows = 2 n_bins), f_min
+ * negative, f_max not above f_min or above rate / 2, a capacity too small. */
+int  aacg_features_design(uint32_t rate, uint32_t frame_length, uint32_t hop, uint32_t n_bins, uint32_t n_mels, double f_min, double f_max,
+                          float* basis, size_t basis_capacity, float* fb, size_t fb_capacity);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,13 @@
  *
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
- *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT]
+ *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
+ *
+ * --features: Whisper's front end as the last stage of the way out (aacg_features_design at the rate that leaves: 400-sample frames every
+ * 160, 201 bins, 80 Slaney bands, centred with pad_left 200, log10 with a floor of 1e-10; aacg_pipeline_set_features): one more launch
+ * per batch (aacg_pcm_features_*), and float32 feature frames leave in the place of one channel of PCM — so it goes behind --mix 1 (or a
+ * mono file), usually with --rate 16000.  Buffers are sized for the most a batch can emit (a stream of n samples completes at most
+ * n / 160 + 1 frames); planar rows hold that many feature frames.  The line then carries the stage's parameters.
  *
  * --rate OUT: the PCM resampled to OUT Hz on the device (aacg_resample_design from the file's rate with 32 taps and the default roll-off
  * and window; aacg_pipeline_set_resample): one more launch per batch (aacg_pcm_resample_*), behind the mix if there is one, and
@@ -64,6 +70,7 @@ int main(int argc, char** argv)
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     uint32_t mix = 0, rate = 0;
+    bool features = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -84,6 +91,7 @@ int main(int argc, char** argv)
         else if (a == "--planar") planar = true;
         else if (a == "--mix") mix = (uint32_t)std::atoi(val());
         else if (a == "--rate") rate = (uint32_t)std::atoi(val());
+        else if (a == "--features") features = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -137,10 +145,21 @@ int main(int argc, char** argv)
         if (!rates[sample_index] || (rc = aacg_resample_design(rates[sample_index], rate, 32, 0.0, 0.0, &rs_L, &rs_M, table.data(), table.size()))) { std::fprintf(stderr, "aacg_resample_design(%u -> %u): %d\n", rates[sample_index], rate, rc); return 2; }
         if ((rc = aacg_pipeline_set_resample(p, rs_L, rs_M, 32, table.data()))) { std::fprintf(stderr, "aacg_pipeline_set_resample: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
-    /* the most samples a stream of F frames emits, and the planar row that holds them; without --rate: F x 1024 and F */
-    const size_t most = ((size_t)F * 1024 * rs_L + rs_M - 1) / rs_M;
-    const uint32_t stride_frames = (uint32_t)((most + 1023) / 1024);
-    const size_t pcm_bytes = (size_t)S * (planar ? (size_t)stride_frames * 1024 : most) * out_channels * (i16 ? 2 : 4), unmixed_bytes = (size_t)S * F * 1024 * channels * (i16 ? 2 : 4);
+    const uint32_t ft_K = 400, ft_H = 160, ft_bins = 201, ft_mels = 80;
+    if (features) {
+        static const uint32_t rates[16] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350, 0, 0, 0};
+        std::vector<float> basis((size_t)2 * ft_bins * ft_K), fb((size_t)ft_mels * ft_bins);
+        const uint32_t rate_out = rate ? rate : rates[sample_index];
+        if ((rc = aacg_features_design(rate_out, ft_K, ft_H, ft_bins, ft_mels, 0.0, 0.0, basis.data(), basis.size(), fb.data(), fb.size()))) { std::fprintf(stderr, "aacg_features_design(%u): %d\n", rate_out, rc); return 2; }
+        const aacg_features_config fc = {ft_K, ft_H, ft_K / 2, 2 * ft_bins, ft_mels, 1u, 1e-10f, basis.data(), fb.data()};
+        if ((rc = aacg_pipeline_set_features(p, &fc))) { std::fprintf(stderr, "aacg_pipeline_set_features: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
+    /* the most samples a stream of F frames emits, and the planar row that holds them; without --rate: F x 1024 and F.  --features: the most
+     * feature frames those samples complete, which is the planar row too, and ft_mels floats each whatever the PCM's element */
+    const size_t most = ((size_t)F * 1024 * rs_L + rs_M - 1) / rs_M, most_ft = most / ft_H + 1;
+    const uint32_t stride_frames = features ? (uint32_t)most_ft : (uint32_t)((most + 1023) / 1024);
+    const size_t pcm_bytes = features ? (size_t)S * most_ft * ft_mels * 4 : (size_t)S * (planar ? (size_t)stride_frames * 1024 : most) * out_channels * (i16 ? 2 : 4);
+    const size_t unmixed_bytes = (size_t)S * F * 1024 * channels * (i16 ? 2 : 4);
     const size_t resample_in_bytes = (size_t)S * F * 1024 * out_channels * (i16 ? 2 : 4);
     const int n_out = 4;
     void* out[n_out];
@@ -232,7 +251,7 @@ int main(int argc, char** argv)
     bool finite = true, nonzero = false;
     uint32_t bad = 0;
     for (int k = 0; k < n_out; k++) bad += refused[k];
-    if (!i16) { const float* w = (const float*)out[0]; for (size_t i = 0; i < pcm_bytes / 4; i += 97) { finite = finite && std::isfinite(w[i]); nonzero = nonzero || w[i] != 0.0f; } }
+    if (!i16 || features) { const float* w = (const float*)out[0]; for (size_t i = 0; i < pcm_bytes / 4; i += 97) { finite = finite && std::isfinite(w[i]); nonzero = nonzero || w[i] != 0.0f; } }
     else { const int16_t* w = (const int16_t*)out[0]; for (size_t i = 0; i < pcm_bytes / 2; i += 97) nonzero = nonzero || w[i] != 0; }
     char copy_key[64] = "";                                 /* only where it was measured: the host-PCM modes' lines are as they were */
     if (device_pcm) std::snprintf(copy_key, sizeof copy_key, "\"d2d_copy_of_pcm_us\": %.2f, ", copy_us);
@@ -240,13 +259,15 @@ int main(int argc, char** argv)
     if (mix) std::snprintf(mix_key, sizeof mix_key, "\"mix_out_channels\": %u, \"unmixed_pcm_bytes_per_batch\": %zu, \"d2d_copy_of_unmixed_pcm_us\": %.2f, ", out_channels, unmixed_bytes, unmixed_copy_us);
     char rate_key[192] = "";                                /* --rate only */
     if (rate) std::snprintf(rate_key, sizeof rate_key, "\"rate_out\": %u, \"resample_L\": %u, \"resample_M\": %u, \"resample_taps\": 32, \"resample_in_bytes_per_batch\": %zu, \"d2d_copy_of_resample_in_us\": %.2f, ", rate, rs_L, rs_M, resample_in_bytes, resample_in_copy_us);
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s"
+    char features_key[192] = "";                            /* --features only */
+    if (features) std::snprintf(features_key, sizeof features_key, "\"features\": \"log-mel\", \"frame_length\": %u, \"hop\": %u, \"n_bins\": %u, \"n_mels\": %u, \"feature_frames_per_stream_most\": %zu, ", ft_K, ft_H, ft_bins, ft_mels, most_ft);
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, rate_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, rate_key, features_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
