@@ -74,6 +74,8 @@
 #include "aacg_pcm_resample.h"
 #define AACG_FEATURES_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_features.hip's */
 #include "aacg_pcm_features.h"
+#define AACG_LOUDNESS_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_loudness.hip's */
+#include "aacg_pcm_loudness.h"
 #include "aacg_pipe_exit.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
@@ -91,6 +93,8 @@ bool aacg_mix_launch(const aacg_mix_args& A, hipStream_t s);
 bool aacg_resample_launch(const aacg_resample_args& A, hipStream_t s);
 /* aacg_engine_features.hip: a batch's one-channel PCM to (log-)mel feature frames (aacg_pcm_features.h); false: not a launch it serves */
 bool aacg_features_launch(const aacg_features_args& A, hipStream_t s);
+/* aacg_engine_loudness.hip: a loudness tap on a batch's transform PCM (aacg_pcm_loudness.h); false: not a launch it serves */
+bool aacg_loudness_launch(const aacg_loudness_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -152,6 +156,20 @@ struct aacg_pipeline {
         hipEvent_t last = nullptr;
         size_t lane_elems = 0;          /* the largest batch's output: floats of a lane's d_ft and h_pcm */
     } ft;
+    /* aacg_pipeline_set_loudness: the meter's hop (0: none) and sections, the slots' state on the device ([slot][2][C][6] floats), and per
+     * slot what the host keeps: the clock (samples since the slot's reset), which state buffer the slot's next batch reads, and whether
+     * it has consumed anything since its reset.  last: the event behind the latest loudness launch.  front16: the bytes IN FRONT of a
+     * lane's results (d_res, h_res) that take a batch's records, right-aligned, so that the results' copy brings them down too.  out,
+     * out_cap, out_counts: the destination named for the next submission (aacg_pipeline_loudness_out) while `armed` */
+    struct loudness_t {
+        uint32_t hop = 0;
+        float coeffs[10] = {};
+        void* d_state = nullptr;
+        std::vector<uint64_t> N; std::vector<uint8_t> parity, fresh;
+        hipEvent_t last = nullptr;
+        size_t front16 = 0;
+        float* out = nullptr; size_t out_cap = 0; uint32_t* out_counts = nullptr; bool armed = false;
+    } ld;
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -182,6 +200,8 @@ struct aacg_pipeline {
         hipEvent_t rs_done = nullptr;     /* ... and the event behind this lane's latest resample launch */
         void* d_ft = nullptr;             /* aacg_pipeline_set_features: the feature frames of a host batch, ft.lane_elems floats */
         hipEvent_t ft_done = nullptr;     /* ... and the event behind this lane's latest features launch */
+        hipEvent_t ld_done = nullptr;     /* aacg_pipeline_set_loudness: the event behind this lane's latest loudness launch */
+        float* ld_user = nullptr; size_t ld_bytes = 0;      /* ... and the batch in flight's records: where they go at collect, and how many bytes */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
          * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
@@ -335,6 +355,9 @@ struct batch_t {
     size_t rs_at;                                /* stage_batch: where the records lie in the staging block */
     std::vector<aacg_features_stream> ft;        /* check_batch, a feature stage: the batch's records, from the host's clocks */
     size_t ft_at;                                /* stage_batch: where those lie, behind the resampler's */
+    std::vector<aacg_loudness_stream> ld;        /* check_batch, a meter: the batch's records, from the host's clocks */
+    size_t ld_at;                                /* stage_batch: where those lie, behind the feature stage's */
+    size_t ld_floats;                            /* check_batch: the floats the batch's loudness records take */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
@@ -385,6 +408,7 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
     int rc = wait_done(p, L, "aacg_pipeline_collect");
     if (rc) return rc;
     if (L.collect_bytes) std::memcpy(L.collect_pcm, L.h_pcm, L.collect_bytes);
+    if (L.ld_bytes) std::memcpy(L.ld_user, (const char*)L.h_res - ((L.ld_bytes + 15) & ~(size_t)15), L.ld_bytes);      /* the meter's records lie in front of the results */
     /* a stream whose first frame did not parse has no layout yet: every frame of it in this batch came out silent and says so */
     aacg_parse_result* res = (aacg_parse_result*)L.h_res;
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
@@ -551,14 +575,16 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (W.st) (void)hipStreamDestroy(W.st);
     }
     for (auto& L : p->lane) {
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);      /* (d_frames lies in d_bytes, d_refused in d_res) */
-        for (void* h : {L.h_in, L.h_pcm, L.h_res}) if (h) (void)hipHostFree(h);
+        /* (d_frames lies in d_bytes, d_refused in d_res; a meter's records lie in front of d_res and h_res, in their blocks) */
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
+        for (void* h : {L.h_in, L.h_pcm, L.h_res ? (void*)((char*)L.h_res - p->ld.front16) : nullptr}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.rs_done) (void)hipEventDestroy(L.rs_done);
         if (L.ft_done) (void)hipEventDestroy(L.ft_done);
+        if (L.ld_done) (void)hipEventDestroy(L.ld_done);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
-    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist}) if (d) (void)hipFree(d);
+    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -761,6 +787,74 @@ int aacg_pipeline_set_features(aacg_pipeline* p, const aacg_features_config* cfg
     return AACG_OK;
 }
 
+int aacg_pipeline_set_loudness(aacg_pipeline* p, const aacg_loudness_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (!cfg) { p->err = "aacg_pipeline_set_loudness: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (p->ld.hop) { p->err = "aacg_pipeline_set_loudness: the pipeline has a meter already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_loudness: a batch has been submitted (the meter is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (cfg->hop < 1u || cfg->hop > AACG_LOUDNESS_MAX_HOP) { p->err = "aacg_pipeline_set_loudness: hop is not in 1..2^20"; return AACG_ERR_INVALID_ARG; }
+    for (int i = 0; i < 10; i++)
+        if (!std::isfinite(cfg->coeffs[i / 5][i % 5])) { p->err = "aacg_pipeline_set_loudness: coefficient " + std::to_string(i) + " is not finite"; return AACG_ERR_INVALID_ARG; }
+    /* the largest batch's records per channel: every stream may complete a hop that earlier batches began */
+    const uint64_t most = (uint64_t)p->cfg.max_streams * ((uint64_t)p->cfg.max_frames * 1024u / cfg->hop + 1u);
+    if (most * p->C >= (1ull << 27)) { p->err = "aacg_pipeline_set_loudness: max_streams x (max_frames x 1024 / hop + 1) x channels is 2^27 records or more"; return AACG_ERR_INVALID_ARG; }
+    /* (... and the kernel's lanes count a batch's PCM in 16-byte vectors, in 32 bits) */
+    if ((uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * (1024u * p->C * pcm_elem(p) / 16u) > AACG_LOUDNESS_MAX_VECTORS) { p->err = "aacg_pipeline_set_loudness: max_streams x max_frames frames of PCM are 64 GiB or more"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const size_t front16 = ((size_t)most * p->C * 2u * sizeof(float) + 15) & ~(size_t)15, block = front16 + p->res_cap16 + 16;
+    const size_t state_bytes = (size_t)p->cfg.max_streams * 2u * p->C * AACG_LOUDNESS_STATE * sizeof(float);
+    /* a lane's results get a block with room for the records in front of them, device and page-locked: new blocks for every lane or
+     * for none (nothing is in flight yet; the state needs no clearing: a fresh slot's is not read) */
+    void *d_state = nullptr, *d_new[AACG_PIPELINE_MAX_LANES] = {}, *h_new[AACG_PIPELINE_MAX_LANES] = {};
+    hipEvent_t ev[AACG_PIPELINE_MAX_LANES] = {};
+    bool good = hipMalloc(&d_state, state_bytes) == hipSuccess;
+    for (int k = 0; k < p->n_lanes && good; k++)
+        good = hipMalloc(&d_new[k], block) == hipSuccess && hipMemset(d_new[k], 0, block) == hipSuccess &&
+               hipHostMalloc(&h_new[k], block, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
+    if (!good) {
+        (void)hipGetLastError();
+        if (d_state) (void)hipFree(d_state);
+        for (int k = 0; k < p->n_lanes; k++) { if (d_new[k]) (void)hipFree(d_new[k]); if (h_new[k]) (void)hipHostFree(h_new[k]); if (ev[k]) (void)hipEventDestroy(ev[k]); }
+        p->err = "aacg_pipeline_set_loudness: no device memory for the slots' state and the lanes' records";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    for (int k = 0; k < p->n_lanes; k++) {
+        auto& L = p->lane[k];
+        (void)hipFree(L.d_res); (void)hipHostFree(L.h_res);
+        L.d_res = (char*)d_new[k] + front16; L.h_res = (char*)h_new[k] + front16; L.d_refused = (char*)L.d_res + p->res_cap16;
+        L.count_stale = false;                          /* (the new block's count is zero) */
+        L.ld_done = ev[k];
+    }
+    p->ld.d_state = d_state; p->ld.front16 = front16;
+    p->ld.N.assign((size_t)p->cfg.max_streams, 0u); p->ld.parity.assign((size_t)p->cfg.max_streams, 0); p->ld.fresh.assign((size_t)p->cfg.max_streams, 1);
+    std::memcpy(p->ld.coeffs, cfg->coeffs, sizeof p->ld.coeffs);
+    p->ld.hop = cfg->hop;
+    return AACG_OK;
+}
+
+int aacg_pipeline_loudness_out(aacg_pipeline* p, float* records, size_t capacity_floats, uint32_t* n_out_of)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    if (!p->ld.hop) { p->err = "aacg_pipeline_loudness_out: the pipeline has no meter (aacg_pipeline_set_loudness)"; return AACG_ERR_INVALID_ARG; }
+    if (!records && capacity_floats) { p->err = "aacg_pipeline_loudness_out: no memory for the records"; return AACG_ERR_INVALID_ARG; }
+    p->ld.out = records; p->ld.out_cap = capacity_floats; p->ld.out_counts = n_out_of; p->ld.armed = true;
+    return AACG_OK;
+}
+
+int aacg_pipeline_loudness_counts(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out)
+{
+    if (!p || !slots || !frames_of || !n_out) return AACG_ERR_INVALID_ARG;
+    if (!p->ld.hop) { p->err = "aacg_pipeline_loudness_counts: the pipeline has no meter (aacg_pipeline_set_loudness)"; return AACG_ERR_INVALID_ARG; }
+    for (uint32_t s = 0; s < n_streams; s++) {
+        if ((int)slots[s] >= p->cfg.max_streams) { p->err = "aacg_pipeline_loudness_counts: stream slot out of range"; return AACG_ERR_INVALID_ARG; }
+        if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "aacg_pipeline_loudness_counts: a stream brings more frames than max_frames"; return AACG_ERR_INVALID_ARG; }
+    }
+    for (uint32_t s = 0; s < n_streams; s++) n_out[s] = (uint32_t)aacg_loudness_emits(p->ld.hop, p->ld.N[slots[s]], 1024ull * frames_of[s]);
+    return AACG_OK;
+}
+
 int aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out)
 {
     if (!p || !slots || !frames_of || !n_out) return AACG_ERR_INVALID_ARG;
@@ -811,6 +905,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     if (rc) return engine_fail(p, "", rc);
     if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
     if (p->ft.K) { p->ft.N[slot] = 0; p->ft.fresh[slot] = 1; }       /* ... and the feature stage's */
+    if (p->ld.hop) { p->ld.N[slot] = 0; p->ld.fresh[slot] = 1; }     /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
         drop_plans_with(p, slot);
@@ -870,6 +965,18 @@ int check_batch(aacg_pipeline* p, batch_t& B)
             if (r.n_out > b.ft_most) b.ft_most = r.n_out;
         }
     }
+    if (p->ld.hop) {                                     /* a meter: what each stream's frames complete, and whether the named destination holds it */
+        if (!p->ld.armed) { p->err = "the pipeline has a meter and no destination is named for this submission's records (aacg_pipeline_loudness_out)"; return AACG_ERR_INVALID_ARG; }
+        B.ld.resize(B.n_streams);
+        uint64_t total = 0;
+        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
+            const uint32_t slot = B.slots[s], n_out = (uint32_t)aacg_loudness_emits(p->ld.hop, p->ld.N[slot], 1024ull * B.frames_of[s]);
+            B.ld[s] = {first, B.frames_of[s], (uint32_t)total, n_out, (uint32_t)(p->ld.N[slot] % p->ld.hop), slot, p->ld.parity[slot], p->ld.fresh[slot]};
+            total += n_out;
+        }
+        B.ld_floats = (size_t)total * p->C * 2u;
+        if (B.ld_floats > p->ld.out_cap) { p->err = "the destination named for the loudness records is too small for this submission"; return AACG_ERR_CAPACITY; }
+    }
     B.X = aacg_pipe::exit_plan(exit_pipe(p), b);
     return B.pcm_out ? AACG_OK : check_device_out(p, B, b);
 }
@@ -883,10 +990,13 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     const size_t tab_bytes = (size_t)B.n_streams * (p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)), tab16 = (tab_bytes + 15) & ~(size_t)15;
     /* (... and a feature stage's behind those: both records are 32 bytes) */
     const size_t rs_bytes = B.rs.size() * sizeof(aacg_resample_stream), ft_bytes = B.ft.size() * sizeof(aacg_features_stream);
-    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, rs_bytes + ft_bytes ? tab16 + rs_bytes + ft_bytes : tab_bytes, B.G);
+    const size_t ld_bytes = B.ld.size() * sizeof(aacg_loudness_stream);      /* (... and a meter's behind those) */
+    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, rs_bytes + ft_bytes + ld_bytes ? tab16 + rs_bytes + ft_bytes + ld_bytes : tab_bytes, B.G);
     if (rc) return rc;
     B.rs_at = B.G.extra_at + tab16;
     B.ft_at = B.rs_at + rs_bytes;
+    B.ld_at = B.ft_at + ft_bytes;
+    if (ld_bytes) std::memcpy((char*)L.h_in + B.ld_at, B.ld.data(), ld_bytes);
     if (rs_bytes) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), rs_bytes);
     if (ft_bytes) std::memcpy((char*)L.h_in + B.ft_at, B.ft.data(), ft_bytes);
     L.d_frames = (char*)L.d_bytes + B.G.padded;
@@ -1015,7 +1125,21 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     /* the results and, behind where the largest batch's would end, the refusal count: one small launch (a launch that writes to
      * host memory costs 50 us of the lane's time whatever it carries) */
     L.count_stale = false;
-    pipe_copy(L.d_res, L.h_res, p->res_cap16 + 16, L.st, true);         /* ... and the count is cleared for the lane's next batch (set to zero at create) */
+    size_t ld16 = 0;
+    if (p->ld.hop) {
+        /* the meter: the transform's PCM, wherever the exit plan's first stage put it, into records that lie right in front of the lane's
+         * results, so that the one copy below brings both down.  The slots' state passes from batch to batch like the resampler's history:
+         * this launch waits for the one before it, here — behind this lane's parse, transform and way out, which need not wait */
+        ld16 = (B.ld_floats * sizeof(float) + 15) & ~(size_t)15;
+        aacg_loudness_args A = {exit_buf(L, B, B.X.stage[0].dst), (float*)((char*)L.d_res - ld16), (const aacg_loudness_stream*)((const char*)L.d_bytes + B.ld_at),
+                                (float*)p->ld.d_state, B.n_streams, B.n, p->ld.hop, {}, p->C, E};
+        std::memcpy(A.coeffs, p->ld.coeffs, sizeof A.coeffs);
+        if (p->ld.last && p->ld.last != L.ld_done) P_TRY(p, hipStreamWaitEvent(L.st, p->ld.last, 0), AACG_ERR_NO_DEVICE);
+        if (!aacg_loudness_launch(A, L.st)) { p->err = "aacg_pcm_loudness: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        P_TRY(p, hipEventRecord(L.ld_done, L.st), AACG_ERR_NO_DEVICE);
+        p->ld.last = L.ld_done;
+    }
+    pipe_copy((const char*)L.d_res - ld16, (char*)L.h_res - ld16, ld16 + p->res_cap16 + 16, L.st, true);      /* ... and the count is cleared for the lane's next batch (set to zero at create) */
     P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
     P_TRY(p, hipEventRecord(L.done, L.st), AACG_ERR_NO_DEVICE);
     L.busy = true; L.ticket = ++p->submitted; L.collect_pcm = B.pcm_out; L.collect_bytes = B.X.collect_copy ? (size_t)B.X.out_bytes : 0;
@@ -1027,6 +1151,13 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
         p->rs.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->rs.fresh[r.slot] = 0;
     }
     for (const auto& r : B.ft) { p->ft.N[r.slot] += r.n_in; p->ft.parity[r.slot] = (uint8_t)((r.flags & 1u) ^ 1u); p->ft.fresh[r.slot] = 0; }
+    /* ... and the meter's; its destination is this batch's now, and the next submission names its own */
+    for (const auto& r : B.ld) { p->ld.N[r.slot] += 1024ull * r.frames; p->ld.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->ld.fresh[r.slot] = 0; }
+    L.ld_user = p->ld.out; L.ld_bytes = B.ld_floats * sizeof(float);
+    if (p->ld.hop) {
+        if (p->ld.out_counts) for (uint32_t s = 0; s < B.n_streams; s++) p->ld.out_counts[s] = B.ld[s].n_out;
+        p->ld.armed = false;
+    }
     *ticket = L.ticket;
     return AACG_OK;
 }

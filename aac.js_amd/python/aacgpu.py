@@ -39,7 +39,9 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_submit_device", "aacg_pipeline_wait_device",
                "aacg_pipeline_set_mix", "aacg_pipeline_out_channels", "aacg_mix_standard",
                "aacg_pipeline_set_resample", "aacg_pipeline_out_samples", "aacg_resample_counts", "aacg_resample_design",
-               "aacg_pipeline_set_features", "aacg_features_counts", "aacg_features_design"]
+               "aacg_pipeline_set_features", "aacg_features_counts", "aacg_features_design",
+               "aacg_pipeline_set_loudness", "aacg_pipeline_loudness_out", "aacg_pipeline_loudness_counts", "aacg_loudness_counts",
+               "aacg_loudness_design", "aacg_loudness_integrate"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -113,6 +115,11 @@ class PcmDeviceOut(C.Structure):
 class FeaturesConfig(C.Structure):
     _fields_ = [("frame_length", C.c_uint32), ("hop", C.c_uint32), ("pad_left", C.c_uint32), ("n_rows", C.c_uint32), ("n_mels", C.c_uint32),
                 ("log", C.c_uint32), ("floor", C.c_float), ("basis", C.c_void_p), ("fb", C.c_void_p)]
+
+
+# aacg_loudness_config: the meter's hop and its two biquad sections (aacg_pipeline_set_loudness)
+class LoudnessConfig(C.Structure):
+    _fields_ = [("hop", C.c_uint32), ("coeffs", (C.c_float * 5) * 2)]
 
 
 # aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
@@ -293,6 +300,12 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_set_features.argtypes = [C.c_void_p, C.POINTER(FeaturesConfig)]
     L.aacg_features_counts.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.aacg_features_design.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.aacg_pipeline_set_loudness.argtypes = [C.c_void_p, C.POINTER(LoudnessConfig)]
+    L.aacg_pipeline_loudness_out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.aacg_pipeline_loudness_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.aacg_loudness_counts.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.aacg_loudness_design.argtypes = [C.c_uint32, C.c_void_p]
+    L.aacg_loudness_integrate.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -493,11 +506,14 @@ class Pipeline:
     features: a dict for set_features (aacg_pipeline_set_features; features_design makes the usual tables) — frame_length, hop, basis
     (2 x bins, frame_length), fb (n_mels, bins) and optionally pad_left, log, floor.  The last stage of the way out: float32 feature
     frames leave in the place of one channel of PCM, ragged like a resampler's samples: decode and collect return (frames, results,
-    n_refused, lengths) with frames flat, lengths[s] feature frames of n_mels floats each; decode_tensor returns (S, n_mels, T)."""
+    n_refused, lengths) with frames flat, lengths[s] feature frames of n_mels floats each; decode_tensor returns (S, n_mels, T).
+    loudness: a dict for set_loudness (aacg_pipeline_set_loudness; loudness_design makes BS.1770's) — hop and coeffs (2, 5).  A tap on the
+    transform's PCM, beside whatever else leaves: decode, submit, collect and decode_tensor return what they return without it, and
+    take_loudness gives a batch's records, a list of (n_out[s], in_channels, 2) float32 arrays of {energy, sample peak} per hop."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None):
+                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -514,6 +530,7 @@ class Pipeline:
         self.in_channels = channels
         self.resample, self.rate = None, SAMPLE_RATES[sample_index]
         self.features = None
+        self.loudness, self._loud, self._loud_last = None, {}, None
         self._keep = {}
         if mix is not None:
             m = np.ascontiguousarray(mix, np.float32)
@@ -540,6 +557,12 @@ class Pipeline:
         if features is not None:
             try:
                 self.set_features(**features)
+            except (AacgError, ValueError, TypeError):
+                self.close()
+                raise
+        if loudness is not None:
+            try:
+                self.set_loudness(**loudness)
             except (AacgError, ValueError, TypeError):
                 self.close()
                 raise
@@ -605,6 +628,49 @@ class Pipeline:
         self.features = {"frame_length": int(frame_length), "hop": int(hop), "pad_left": int(pad_left), "n_mels": int(fb.shape[0]), "log": bool(log),
                          "floor": float(np.float32(floor)), "basis": basis, "fb": fb}
 
+    def set_loudness(self, hop, coeffs):
+        """aacg_pipeline_set_loudness: a meter of `hop` samples with the two biquad sections coeffs (2, 5), before the first batch"""
+        k = np.ascontiguousarray(coeffs, np.float32)
+        if k.shape != (2, 5):
+            raise ValueError("Pipeline: the meter's coefficients are not a (2, 5) matrix")
+        cfg = LoudnessConfig(int(hop))
+        C.memmove(cfg.coeffs, k.ctypes.data, 40)
+        self._check(self.lib.aacg_pipeline_set_loudness(self.handle, C.byref(cfg)))
+        self.loudness = {"hop": int(hop), "coeffs": k}
+
+    def loudness_counts(self, slots, frames_per_stream):
+        """aacg_pipeline_loudness_counts: the records per channel that the NEXT batch of these slots with these counts emits, per stream"""
+        slots = np.ascontiguousarray(slots, np.uint32)
+        counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
+        assert len(counts) == len(slots)
+        n = np.zeros(len(slots), np.uint32)
+        self._check(self.lib.aacg_pipeline_loudness_counts(self.handle, slots.ctypes.data, counts.ctypes.data, len(slots), n.ctypes.data))
+        return n
+
+    def _arm_loudness(self, slots, frames_per_stream):
+        """a metered pipeline: buffers of the wrapper's own for the next submission's records, named to the library; else None"""
+        if not self.loudness:
+            return None
+        n = self.loudness_counts(slots, frames_per_stream)
+        rec = np.zeros(int(n.sum()) * self.in_channels * 2, np.float32)
+        self._check(self.lib.aacg_pipeline_loudness_out(self.handle, rec.ctypes.data, rec.size, n.ctypes.data))
+        return rec, n
+
+    def take_loudness(self, ticket=None):
+        """The meter's records of a batch: a list with one (n_out[s], in_channels, 2) float32 array per stream, [..., 0] the hop's
+        energy and [..., 1] its sample peak.  ticket: a submitted batch's, which is finished first if it is still in flight (collect
+        still returns its PCM); None: the batch of the last decode."""
+        if ticket is None:
+            held = self._loud_last
+        else:
+            self._check(self.lib.aacg_pipeline_collect(self.handle, ticket))
+            held = self._loud.pop(ticket, None)
+        if held is None:
+            raise ValueError("Pipeline.take_loudness: no records are held for that batch (no meter, or taken already)")
+        rec, n = held
+        ends = np.cumsum(n.astype(np.int64))
+        return [rec[(e - k) * self.in_channels * 2:e * self.in_channels * 2].reshape(int(k), self.in_channels, 2) for e, k in zip(ends, n.astype(np.int64))]
+
     def out_samples(self, slots, frames_per_stream):
         """aacg_pipeline_out_samples: the samples per channel that the NEXT batch of these slots with these counts emits, per stream —
         with a feature stage the feature frames"""
@@ -667,6 +733,7 @@ class Pipeline:
         """Synchronous: (pcm, results, n_refused).  frames[s * F + f] = frame f of stream s in `data`.  frames_per_stream may be a
         sequence of per-stream counts (aacg_pipeline_decode_ragged): frames, PCM and results are then packed stream after stream."""
         data, frames, slots, counts, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
+        self._loud_last = self._arm_loudness(slots, frames_per_stream)
         if counts is None:
             self._check(self.lib.aacg_pipeline_decode(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                       frames_per_stream, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
@@ -678,6 +745,7 @@ class Pipeline:
     def submit(self, data, frames, slots, frames_per_stream, pcm=None):
         """Asynchronous: returns a ticket; collect(ticket) -> (pcm, results, n_refused).  frames_per_stream as for decode."""
         data, frames, slots, counts, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
+        loud = self._arm_loudness(slots, frames_per_stream)
         t = C.c_uint64()
         if counts is None:
             self._check(self.lib.aacg_pipeline_submit(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
@@ -686,6 +754,8 @@ class Pipeline:
             self._check(self.lib.aacg_pipeline_submit_ragged(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                              counts.ctypes.data, pcm.ctypes.data, res.ctypes.data, C.byref(refused), C.byref(t)))
         self._keep[t.value] = (pcm, res, refused) + ((self._lengths,) if self._ragged else ())
+        if loud is not None:
+            self._loud[t.value] = loud
         return t.value
 
     def collect(self, ticket):
@@ -733,9 +803,12 @@ class Pipeline:
                 stride_frames = (int(counts.max()) if len(counts) else 0) if lengths is None else (int(lengths.max()) + 1023) // 1024
         desc = PcmDeviceOut(addr, nbytes, (PCM_PLANAR if planar else PCM_PACKED) if layout is None else int(layout), int(stride_frames or 0))
         res, refused, t = np.zeros(len(frames), PARSE_RESULT_DTYPE), C.c_uint32(0), C.c_uint64()
+        loud = self._arm_loudness(slots, counts)
         self._check(self.lib.aacg_pipeline_submit_device(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                          counts.ctypes.data, C.byref(desc), res.ctypes.data, C.byref(refused), C.byref(t)))
         self._keep[t.value] = (out, res, refused) + ((lengths,) if lengths is not None else ())
+        if loud is not None:
+            self._loud[t.value] = self._loud_last = loud
         return t.value
 
     def wait_device(self, ticket, stream=None):
@@ -796,6 +869,43 @@ def resample_design(in_rate, out_rate, taps=32, rolloff=0.0, beta=0.0):
     if rc != 0:
         raise AacgError(rc, "aacg_resample_design(%d -> %d Hz, %d taps)" % (in_rate, out_rate, taps))
     return int(L.value), int(M.value), table
+
+
+def loudness_design(rate, hop=None):
+    """BS.1770's K-weighting at `rate` (aacg_loudness_design, include/aacgpu.h): a dict for Pipeline(loudness=...) with the two biquad
+    sections as a (2, 5) float32 matrix; host code, no device.  hop None: rate // 10, so that four hops are the standard's 400 ms block."""
+    k = np.zeros((2, 5), np.float32)
+    rc = load_library().aacg_loudness_design(int(rate), k.ctypes.data)
+    if rc != 0:
+        raise AacgError(rc, "aacg_loudness_design(%d Hz)" % rate)
+    return {"hop": int(rate) // 10 if hop is None else int(hop), "coeffs": k}
+
+
+def loudness_counts(hop, n0, samples):
+    """aacg_loudness_counts: the records per channel that `samples` further samples complete at the clock n0"""
+    n = C.c_uint64()
+    rc = load_library().aacg_loudness_counts(int(hop), int(n0), int(samples), C.byref(n))
+    if rc != 0:
+        raise AacgError(rc, "aacg_loudness_counts(hop %d)" % hop)
+    return int(n.value)
+
+
+def loudness_integrate(records, hop, weights=None, momentary=False):
+    """aacg_loudness_integrate: the gated loudness in LUFS (-inf: nothing above the gates) of one stream's records (n_hops, channels, 2)
+    as take_loudness gives them — concatenate a stream's batches first.  weights: per channel, None all 1.  momentary: also the
+    400 ms-block loudness of every block, (integrated, array of n_hops - 3)."""
+    r = np.ascontiguousarray(records, np.float32)
+    if r.ndim != 3 or r.shape[2] != 2:
+        raise ValueError("loudness_integrate: records are not (n_hops, channels, 2)")
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64)
+    if w is not None and w.shape != (r.shape[1],):
+        raise ValueError("loudness_integrate: one weight per channel")
+    out, mom = C.c_double(), np.zeros(max(r.shape[0] - 3, 0), np.float64)
+    rc = load_library().aacg_loudness_integrate(r.ctypes.data, r.shape[0], r.shape[1], int(hop), None if w is None else w.ctypes.data, C.byref(out),
+                                                mom.ctypes.data if momentary else None)
+    if rc != 0:
+        raise AacgError(rc, "aacg_loudness_integrate(%d hops of %d channels)" % r.shape[:2])
+    return (out.value, mom) if momentary else out.value
 
 
 def features_design(rate=16000, frame_length=400, hop=160, n_bins=None, n_mels=80, f_min=0.0, f_max=0.0):

@@ -980,6 +980,71 @@ int  aacg_features_counts(uint32_t frame_length, uint32_t hop, uint32_t pad_left
  * negative, f_max not above f_min or above rate / 2, a capacity too small. */
 int  aacg_features_design(uint32_t rate, uint32_t frame_length, uint32_t hop, uint32_t n_bins, uint32_t n_mels, double f_min, double f_max,
                           float* basis, size_t basis_capacity, float* fb, size_t fb_capacity);
+/* A loudness meter on the device: a TAP, not a stage.  It reads the PCM the pipeline's TRANSFORM delivers and writes a few floats per
+ * hop beside it, for a consumer that normalises what it decodes (EBU R 128 / ReplayGain) without pulling the full-rate, full-channel
+ * PCM across the link; the PCM's own way out — the mix, the resampler, the feature stage, every destination — is untouched.
+ *     hop: samples, 1..2^20;  coeffs[2][5]: two biquad sections {b0, b1, b2, a1, a2}, all finite (aacg_loudness_design makes BS.1770's).
+ * The input x of channel c of a slot is the sample the transform delivers in channel c: BEFORE the mix, the resampler and the feature
+ * stage, at the stream's own rate, in all `channels` channels by position.  On an AACG_OUTPUT_I16 pipeline x is the already rounded
+ * int16 times 2^-15 (exact).  A refused frame and a frame of an unlearnt stream are 1024 zeros; they pass through the filters like any
+ * other and advance the clock.
+ * THE RULE, bit for bit, in float32 throughout, every operation rounded on its own, nothing fused, subnormals kept.  Per sample, for
+ * section i = 0 then 1, with v = x going into section 0:
+ *     y  = (b0 v) + z1
+ *     z1 = ((b1 v) - (a1 y)) + z2
+ *     z2 = (b2 v) - (a2 y)
+ *     v  = y
+ * then  e = e + (v v)  and  peak = max(peak, |x|).  After every `hop` samples since the slot's reset one record per channel leaves,
+ * {e, peak}, two floats, and e and peak restart at +0.  A reset (aacg_pipeline_reset_stream) zeroes the clock, the four z of every
+ * channel, e and peak.  Counts: count(N) = floor(N / hop); a batch that moves a slot's clock from N to N' emits count(N') - count(N)
+ * records per channel, possibly none (aacg_pipeline_loudness_counts; aacg_loudness_counts for any clock).  Any split of a stream's
+ * frames into batches gives the same bits.
+ * Records of a submission: packed [stream s][n_out[s]][channels][2] float32, the streams one behind the other, in HOST memory that the
+ * caller names with aacg_pipeline_loudness_out before every submission; they are there when the submission's ticket has been collected.
+ * State per slot: the clock on the host; z1, z2 of both sections, the partial e and the partial peak per channel on the device, handed
+ * from batch to batch across lanes as the resampler's history.  One more launch per batch (aacg_pcm_loudness_*) on the lane's stream
+ * behind the transform; it goes with both output kinds, every `stages` bit, both plan modes, ragged and device batches and span walks,
+ * and is independent of aacg_pipeline_set_mix / _set_resample / _set_features in order and in effect.  With no meter set nothing differs.
+ * Called once, before the pipeline's first submitted batch.  AACG_ERR_INVALID_ARG, with the reason in aacg_pipeline_last_error and the
+ * pipeline exactly as it was: a null config, a hop outside 1..2^20, a coefficient that is not finite, a call after the first batch, a
+ * second call; and a pipeline beyond the meter's limits — max_streams x (max_frames x 1024 / hop + 1) x channels of 2^27 records or
+ * more, max_streams x max_frames frames of PCM of 64 GiB or more.  AACG_ERR_OUT_OF_MEMORY: no device memory for the slots' state and the lanes' records; the pipeline stays as it was.
+ * Not here: true (oversampled) peak, short-term windows and loudness range, a gain or limiter that applies the result, a meter behind
+ * the mix or the resampler. */
+typedef struct aacg_loudness_config {
+    uint32_t hop;
+    float    coeffs[2][5];
+} aacg_loudness_config;
+int  aacg_pipeline_set_loudness(aacg_pipeline* p, const aacg_loudness_config* cfg);
+/* Where the NEXT enqueued submission's records go: `records`, host memory with room for capacity_floats floats, valid until that
+ * submission's ticket has been collected (the records are written at the collect); n_out_of (may be null) receives, when the
+ * submission is enqueued, stream s's record count per channel at n_out_of[s].  One call arms one submission.  A submission on a
+ * metered pipeline with no destination named is refused with AACG_ERR_INVALID_ARG, one whose destination is smaller than the sum of
+ * n_out[s] x channels x 2 floats with AACG_ERR_CAPACITY: nothing is enqueued, no ticket is taken, no clock moves, and the destination
+ * stays armed.  AACG_ERR_INVALID_ARG: a pipeline without a meter, null records with a capacity above 0. */
+int  aacg_pipeline_loudness_out(aacg_pipeline* p, float* records, size_t capacity_floats, uint32_t* n_out_of);
+/* What the NEXT submission of these streams with these frame counts will emit, per stream: n_out[s] records per channel, from the
+ * slots' clocks as they stand.  aacg_pipeline_out_samples keeps its meaning.  AACG_ERR_INVALID_ARG: a null pointer, a pipeline without
+ * a meter, a slot out of range, a count above max_frames. */
+int  aacg_pipeline_loudness_counts(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out);
+/* Host code only: the records per channel that `samples` further samples complete at the clock n0, floor((n0 + samples) / hop) -
+ * floor(n0 / hop).  AACG_ERR_INVALID_ARG: a hop outside 1..2^20, a null n. */
+int  aacg_loudness_counts(uint32_t hop, uint64_t n0, uint64_t samples, uint64_t* n);
+/* Host code only: ITU-R BS.1770's K-weighting re-derived for any rate, in double, each value rounded to float once.  Row 0, the shelf:
+ * f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / rate), Vh = 10^(G / 20),
+ * Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;  b = {(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0},
+ * a = {2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0}.  Row 1, the high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, b = {1, -2, 1},
+ * a of the same form.  At 48000 these are the standard's published coefficients.  AACG_ERR_INVALID_ARG: a rate of 0, null coeffs. */
+int  aacg_loudness_design(uint32_t rate, float coeffs[2][5]);
+/* Host code only, in double: gated loudness of one stream's records ([n_hops][channels][2] floats as the meter emits them; only e is
+ * read).  Blocks are four consecutive hops, advancing one hop at a time, n_hops - 3 of them (none with fewer than four hops):
+ * z = sum over c of w_c (sum of e_c over the four) / (4 hop), l = -0.691 + 10 log10 z (-inf for z = 0).  The absolute gate keeps the
+ * blocks with l > -70; the relative gate lies 10 LU below -0.691 + 10 log10(mean z of those).  *integrated_lufs = -0.691 + 10 log10
+ * of the mean z over the blocks above both gates, or -inf if there are none.  Null weights: all 1 (BS.1770 gives the surround channels
+ * 1.41 and leaves the LFE out: 0).  momentary_lufs, if not null, receives l of every block (with hop = rate / 10: the 400 ms momentary
+ * loudness every 100 ms).  AACG_ERR_INVALID_ARG: null records with hops, a null integrated_lufs, channels outside 1..8, a hop outside 1..2^20. */
+int  aacg_loudness_integrate(const float* records, size_t n_hops, uint32_t channels, uint32_t hop, const double* weights,
+                             double* integrated_lufs, double* momentary_lufs);
 
 #ifdef __cplusplus
 }

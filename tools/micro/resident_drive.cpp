@@ -7,6 +7,12 @@
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
+ *                                         [--loudness]
+ *
+ * --loudness: a loudness meter beside whatever leaves (aacg_loudness_design at the file's rate, BS.1770's K-weighting, with a hop of a
+ * tenth of a second; aacg_pipeline_set_loudness): one more launch per batch (aacg_pcm_loudness_*) over the transform's PCM, and two floats
+ * per hop and channel come down with the results into a buffer named before every submission (aacg_pipeline_loudness_out).  The line then
+ * carries the hop and the records a batch emits at most.  Combines with everything else.
  *
  * --features: Whisper's front end as the last stage of the way out (aacg_features_design at the rate that leaves: 400-sample frames every
  * 160, 201 bins, 80 Slaney bands, centred with pad_left 200, log10 with a floor of 1e-10; aacg_pipeline_set_features): one more launch
@@ -70,7 +76,7 @@ int main(int argc, char** argv)
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     uint32_t mix = 0, rate = 0;
-    bool features = false;
+    bool features = false, loudness = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -92,6 +98,7 @@ int main(int argc, char** argv)
         else if (a == "--mix") mix = (uint32_t)std::atoi(val());
         else if (a == "--rate") rate = (uint32_t)std::atoi(val());
         else if (a == "--features") features = true;
+        else if (a == "--loudness") loudness = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -154,6 +161,14 @@ int main(int argc, char** argv)
         const aacg_features_config fc = {ft_K, ft_H, ft_K / 2, 2 * ft_bins, ft_mels, 1u, 1e-10f, basis.data(), fb.data()};
         if ((rc = aacg_pipeline_set_features(p, &fc))) { std::fprintf(stderr, "aacg_pipeline_set_features: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
+    uint32_t ld_hop = 0;
+    if (loudness) {
+        static const uint32_t rates[16] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350, 0, 0, 0};
+        aacg_loudness_config lc;
+        lc.hop = ld_hop = rates[sample_index] / 10u;
+        if (!ld_hop || (rc = aacg_loudness_design(rates[sample_index], lc.coeffs))) { std::fprintf(stderr, "aacg_loudness_design(%u): %d\n", rates[sample_index], rc); return 2; }
+        if ((rc = aacg_pipeline_set_loudness(p, &lc))) { std::fprintf(stderr, "aacg_pipeline_set_loudness: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
     /* the most samples a stream of F frames emits, and the planar row that holds them; without --rate: F x 1024 and F.  --features: the most
      * feature frames those samples complete, which is the planar row too, and ft_mels floats each whatever the PCM's element */
     const size_t most = ((size_t)F * 1024 * rs_L + rs_M - 1) / rs_M, most_ft = most / ft_H + 1;
@@ -163,6 +178,9 @@ int main(int argc, char** argv)
     const size_t resample_in_bytes = (size_t)S * F * 1024 * out_channels * (i16 ? 2 : 4);
     const int n_out = 4;
     void* out[n_out];
+    /* --loudness: the most records a batch emits (a stream of F frames completes at most F x 1024 / hop + 1 hops), per PCM buffer */
+    const size_t ld_most = loudness ? (size_t)S * ((size_t)F * 1024 / ld_hop + 1) : 0, ld_floats = ld_most * channels * 2;
+    std::vector<std::vector<float>> ld_rec((size_t)n_out, std::vector<float>(ld_floats));
     for (auto& o : out) { o = pageable ? std::malloc(pcm_bytes) : aacg_host_alloc(pcm_bytes); if (!o) { std::fprintf(stderr, "allocation failed\n"); return 2; } std::memset(o, 0, pcm_bytes); }
     /* --device-pcm: a device buffer per lane (a batch in flight keeps its own until it is collected); planar rows of F frames */
     const int n_dev = device_pcm ? (sync ? 1 : lanes) : 0;
@@ -184,6 +202,7 @@ int main(int argc, char** argv)
         for (int b = 0; b < n + depth; b++) {
             if (b < n) {
                 const int k = b % n_out;
+                if (loudness && (rc = aacg_pipeline_loudness_out(p, ld_rec[(size_t)k].data(), ld_floats, nullptr))) fail("aacg_pipeline_loudness_out", rc);
                 aacg_pcm_device_out where;
                 if (device_pcm) { where.d_pcm = dev[(size_t)(b % n_dev)]; where.d_pcm_bytes = pcm_bytes; where.layout = planar ? AACG_PCM_PLANAR : AACG_PCM_PACKED; where.stride_frames = planar ? stride_frames : 0u; }
                 if (new_shapes) {
@@ -259,15 +278,20 @@ int main(int argc, char** argv)
     if (mix) std::snprintf(mix_key, sizeof mix_key, "\"mix_out_channels\": %u, \"unmixed_pcm_bytes_per_batch\": %zu, \"d2d_copy_of_unmixed_pcm_us\": %.2f, ", out_channels, unmixed_bytes, unmixed_copy_us);
     char rate_key[192] = "";                                /* --rate only */
     if (rate) std::snprintf(rate_key, sizeof rate_key, "\"rate_out\": %u, \"resample_L\": %u, \"resample_M\": %u, \"resample_taps\": 32, \"resample_in_bytes_per_batch\": %zu, \"d2d_copy_of_resample_in_us\": %.2f, ", rate, rs_L, rs_M, resample_in_bytes, resample_in_copy_us);
+    char loudness_key[160] = "";                            /* --loudness only */
+    if (loudness) {
+        for (float v : ld_rec[0]) finite = finite && std::isfinite(v);
+        std::snprintf(loudness_key, sizeof loudness_key, "\"loudness\": \"bs1770\", \"loudness_hop\": %u, \"loudness_records_per_batch_most\": %zu, ", ld_hop, ld_most);
+    }
     char features_key[192] = "";                            /* --features only */
     if (features) std::snprintf(features_key, sizeof features_key, "\"features\": \"log-mel\", \"frame_length\": %u, \"hop\": %u, \"n_bins\": %u, \"n_mels\": %u, \"feature_frames_per_stream_most\": %zu, ", ft_K, ft_H, ft_bins, ft_mels, most_ft);
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s"
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, rate_key, features_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, rate_key, features_key, loudness_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
