@@ -11,10 +11,13 @@
  *   transform  always         —                           CALLER if DEV_PACKED and neither mix nor resampler,        n C 1024 E
  *                                                         else LANE_PCM
  *   mix        O != 0         LANE_PCM                    CALLER if DEV_PACKED and no resampler, else LANE_MIX       n O 1024 E
- *   resample   a resampler    LANE_MIX if O, else         CALLER for either device layout (row = stride_frames x     sum n_out Oc E
- *                             LANE_PCM                    1024 if planar, else 0), else LANE_RS
- *   features   a feature      LANE_RS, LANE_MIX or        CALLER for either device layout (ft_row = stride_frames,    sum ft_out n_mels 4
- *              stage          LANE_PCM: the last written  FEATURE frames, if planar, else 0), else LANE_FT
+ *   limit      a limiter      LANE_MIX if O, else         CALLER if DEV_PACKED and neither resampler nor feature     n Oc 1024 E
+ *                             LANE_PCM                    stage, else LANE_LIM
+ *   resample   a resampler    LANE_LIM, LANE_MIX or       CALLER for either device layout (row = stride_frames x     sum n_out Oc E
+ *                             LANE_PCM: the last written  1024 if planar, else 0), else LANE_RS
+ *   features   a feature      LANE_RS, LANE_LIM, LANE_MIX CALLER for either device layout (ft_row = stride_frames,    sum ft_out n_mels 4
+ *              stage          or LANE_PCM: the last       FEATURE frames, if planar, else 0), else LANE_FT
+ *                             written
  *   tail       see `writes`   the last lane buffer        PLANAR_LAUNCH -> CALLER if DEV_PLANAR and neither resampler out_bytes
  *                             written                     nor feature stage; COPY_DOWN -> CALLER (page-locked) or
  *                                                         LANE_HOST (pageable, and collect copies it to the caller)
@@ -24,11 +27,15 @@
  * stages in front of it write lane buffers whatever the destination — the transform LANE_PCM, the mix LANE_MIX, the resampler LANE_RS
  * with row 0 — and the feature stage is the one that writes the caller's device memory.
  *
+ * With a limiter (aacg_pipeline_set_limiter: a gain per stream and a look-ahead limiter, sample for sample) the stages in front of it
+ * write lane buffers whatever the destination too — the transform LANE_PCM, the mix LANE_MIX — and the stages behind it read LANE_LIM
+ * as the last written.  It emits what it receives: out_bytes, device_need and exit_host_capacity do not know it.
+ *
  * out_bytes, what leaves: sum ft_out n_mels 4 with a feature stage, else sum n_out Oc E with a resampler, else n Oc 1024 E.
  * device_need, what a caller's device buffer must hold: n_streams n_mels stride_frames 4 (features) or n_streams Oc stride_frames 1024
  * E planar, out_bytes packed.  The caller's memory is written by exactly one stage, the last.
  *
- * A stage more on the way out (a gain, a limiter, another layout) is a row more here and a block more in enqueue_out's walk.
+ * A stage more on the way out (another layout, a filter) is a row more here and a block more in enqueue_out's walk.
  */
 #ifndef AACG_PIPE_EXIT_H
 #define AACG_PIPE_EXIT_H
@@ -42,10 +49,11 @@
 
 /* a buffer a stage reads or writes: the lane's d_pcm, d_mix, d_rs, its page-locked h_pcm, or the caller's memory (host or device) */
 enum { AACG_EXIT_BUF_NONE = 0, AACG_EXIT_LANE_PCM, AACG_EXIT_LANE_MIX, AACG_EXIT_LANE_RS, AACG_EXIT_LANE_HOST, AACG_EXIT_CALLER,
-       AACG_EXIT_LANE_FT };    /* (the lane's d_ft: a host batch's feature frames) */
+       AACG_EXIT_LANE_FT,      /* (the lane's d_ft: a host batch's feature frames) */
+       AACG_EXIT_LANE_LIM };   /* (the lane's d_lim: the limiter's PCM wherever it is not the last stage of a packed device batch) */
 /* where the caller wants the batch's PCM */
 enum { AACG_EXIT_HOST_PINNED = 0, AACG_EXIT_HOST_PAGEABLE, AACG_EXIT_DEV_PACKED, AACG_EXIT_DEV_PLANAR };
-enum { AACG_EXIT_XFORM = 0, AACG_EXIT_MIX, AACG_EXIT_RESAMPLE, AACG_EXIT_TAIL, AACG_EXIT_FEATURES };
+enum { AACG_EXIT_XFORM = 0, AACG_EXIT_MIX, AACG_EXIT_RESAMPLE, AACG_EXIT_TAIL, AACG_EXIT_FEATURES, AACG_EXIT_LIMIT };
 enum { AACG_EXIT_TAIL_NONE = 0, AACG_EXIT_TAIL_PLANAR_LAUNCH, AACG_EXIT_TAIL_COPY_DOWN };
 
 /* what the pipeline is */
@@ -57,6 +65,7 @@ typedef struct aacg_exit_pipe {
     uint64_t lane_elems;       /* a resampler: elements of the largest batch's output (aacg_pipe::exit_resample_most x Oc)      */
     uint32_t n_mels;           /* a feature stage: floats per feature frame (0: none)                                           */
     uint64_t ft_lane_elems;    /* ... and the floats of the largest batch's output (aacg_pipe::exit_features_most x n_mels)     */
+    uint32_t limited;          /* a limiter is set (the last field: the drivers that build this positionally leave it 0)        */
 } aacg_exit_pipe;
 
 /* what the batch is */
@@ -76,7 +85,7 @@ typedef struct aacg_exit_stage {
 } aacg_exit_stage;
 
 typedef struct aacg_exit_plan {
-    aacg_exit_stage stage[5];             /* in the order they are enqueued; the first is the transform                         */
+    aacg_exit_stage stage[6];             /* in the order they are enqueued; the first is the transform                         */
     uint32_t n_stages;
     uint32_t row;                         /* a planar resample: elements per row; else 0                                        */
     uint64_t xform_bytes;                 /* what the transform writes: the clear for unlearnt streams acts on it               */
@@ -123,6 +132,7 @@ inline aacg_exit_plan exit_plan(const aacg_exit_pipe& P, const aacg_exit_batch& 
     const bool ft = P.n_mels != 0, to_dev = B.dest == AACG_EXIT_DEV_PACKED || B.dest == AACG_EXIT_DEV_PLANAR;
     /* (the stages in front of a feature stage see neither device destination: they write lane buffers) */
     const bool packed = B.dest == AACG_EXIT_DEV_PACKED && !ft, planar = B.dest == AACG_EXIT_DEV_PLANAR && !ft, rs = P.resampled != 0;
+    const bool lim = P.limited != 0;                     /* (... and so do the stages in front of a limiter) */
     aacg_exit_plan X = {};
     uint8_t last = AACG_EXIT_BUF_NONE;                   /* the buffer the stage before wrote */
     auto push = [&](uint8_t what, uint8_t dst, uint64_t bytes, uint8_t tail) { X.stage[X.n_stages++] = {what, last, dst, tail, bytes}; last = dst; };
@@ -131,8 +141,9 @@ inline aacg_exit_plan exit_plan(const aacg_exit_pipe& P, const aacg_exit_batch& 
     X.out_bytes = rs ? B.rs_total * Oc * E : mix_bytes;
     X.device_need = planar ? (uint64_t)B.n_streams * Oc * B.stride_frames * 1024u * E : packed ? X.out_bytes : 0u;
     X.row = rs && planar ? B.stride_frames * 1024u : 0u;
-    push(AACG_EXIT_XFORM, packed && !P.O && !rs ? AACG_EXIT_CALLER : AACG_EXIT_LANE_PCM, X.xform_bytes, AACG_EXIT_TAIL_NONE);
-    if (P.O) push(AACG_EXIT_MIX, packed && !rs ? AACG_EXIT_CALLER : AACG_EXIT_LANE_MIX, mix_bytes, AACG_EXIT_TAIL_NONE);
+    push(AACG_EXIT_XFORM, packed && !P.O && !rs && !lim ? AACG_EXIT_CALLER : AACG_EXIT_LANE_PCM, X.xform_bytes, AACG_EXIT_TAIL_NONE);
+    if (P.O) push(AACG_EXIT_MIX, packed && !rs && !lim ? AACG_EXIT_CALLER : AACG_EXIT_LANE_MIX, mix_bytes, AACG_EXIT_TAIL_NONE);
+    if (lim) push(AACG_EXIT_LIMIT, packed && !rs ? AACG_EXIT_CALLER : AACG_EXIT_LANE_LIM, mix_bytes, AACG_EXIT_TAIL_NONE);
     if (rs) push(AACG_EXIT_RESAMPLE, packed || planar ? AACG_EXIT_CALLER : AACG_EXIT_LANE_RS, X.out_bytes, AACG_EXIT_TAIL_NONE);
     if (ft) {
         X.out_bytes = B.ft_total * P.n_mels * 4u;        /* (the stage in front has its own bytes in its row) */

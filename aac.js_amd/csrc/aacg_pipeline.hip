@@ -37,7 +37,8 @@
  * as a launch input.  AACG_PIPELINE_STAGE_WINDOW_SHAPE: one launch of aacg_plan_carry_window_shape behind every refresh sets
  * window_shape_prev of the batch's unit records from the frame before and, across batches, from the engine's per-channel state.
  *
- * THE WAY OUT is a chain: transform -> mix (aacg_pipeline_set_mix: O = 1 or 2 channels leave in the place of C) -> resample
+ * THE WAY OUT is a chain: transform -> mix (aacg_pipeline_set_mix: O = 1 or 2 channels leave in the place of C) -> limit
+ * (aacg_pipeline_set_limiter: a gain per stream and a look-ahead limiter, sample for sample, state per slot like the resampler's) -> resample
  * (aacg_pipeline_set_resample: each stream's PCM leaves at L / M times the rate, a ragged count of samples per stream) -> features
  * (aacg_pipeline_set_features: one channel of PCM framed and transformed, float32 (log-)mel feature frames leave in its place) -> tail (the
  * planar launch for aacg_pipeline_submit_device with AACG_PCM_PLANAR, the copy down for a host batch, nothing for PCM left packed on
@@ -52,10 +53,10 @@
  * of state — a clock, kept here in 64 bits, and on the device the last K - 1 samples — and is ordered and advanced in the same way.
  *
  * On a lane's stream, in this order: clear (unlearnt streams) -> copy up -> stale count -> parse -> TNS records -> map / shape ->
- * refresh -> carry -> fork -> transform -> join -> mix -> wait / resample / record -> wait / features / record -> planar or copy down -> results copy -> `done`.
+ * refresh -> carry -> fork -> transform -> join -> mix -> wait / limit / record -> wait / resample / record -> wait / features / record -> planar or copy down -> results copy -> `done`.
  *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
- * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h / aacg_pcm_features.h for the tables it fills and the
+ * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h / aacg_pcm_features.h / aacg_pcm_limit.h for the tables it fills and the
  * side launches it makes).  DESIGN.md 7a has how it came to be this way, round by round.
  */
 #include <hip/hip_runtime.h>
@@ -76,6 +77,8 @@
 #include "aacg_pcm_features.h"
 #define AACG_LOUDNESS_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_loudness.hip's */
 #include "aacg_pcm_loudness.h"
+#define AACG_LIMIT_HOST_ONLY                              /* the limits and the records: the body is aacg_engine_limit.hip's */
+#include "aacg_pcm_limit.h"
 #include "aacg_pipe_exit.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
@@ -95,6 +98,8 @@ bool aacg_resample_launch(const aacg_resample_args& A, hipStream_t s);
 bool aacg_features_launch(const aacg_features_args& A, hipStream_t s);
 /* aacg_engine_loudness.hip: a loudness tap on a batch's transform PCM (aacg_pcm_loudness.h); false: not a launch it serves */
 bool aacg_loudness_launch(const aacg_loudness_args& A, hipStream_t s);
+/* aacg_engine_limit.hip: a gain per stream and a look-ahead limiter on a batch's packed PCM (aacg_pcm_limit.h); false: not a launch it serves */
+bool aacg_limit_launch(const aacg_limit_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -170,6 +175,16 @@ struct aacg_pipeline {
         size_t front16 = 0;
         float* out = nullptr; size_t out_cap = 0; uint32_t* out_counts = nullptr; bool armed = false;
     } ld;
+    /* aacg_pipeline_set_limiter: the two settings (on: a limiter is set), the slots' state on the device ([slot][2][AACG_LIMIT_STATE(Oc)]
+     * floats), and per slot what the host keeps: the gain (the caller's: a reset leaves it), which state buffer the slot's next batch
+     * reads, and whether it has consumed anything since its reset.  last: the event behind the latest limiter launch */
+    struct limiter_t {
+        bool on = false;
+        float ceiling = 0.0f, release = 0.0f;
+        void* d_state = nullptr;
+        std::vector<float> gain; std::vector<uint8_t> parity, fresh;
+        hipEvent_t last = nullptr;
+    } lim;
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -201,6 +216,8 @@ struct aacg_pipeline {
         void* d_ft = nullptr;             /* aacg_pipeline_set_features: the feature frames of a host batch, ft.lane_elems floats */
         hipEvent_t ft_done = nullptr;     /* ... and the event behind this lane's latest features launch */
         hipEvent_t ld_done = nullptr;     /* aacg_pipeline_set_loudness: the event behind this lane's latest loudness launch */
+        void* d_lim = nullptr;            /* aacg_pipeline_set_limiter: the limited PCM wherever it is not a packed device batch's last stage, max_streams x max_frames x 1024 x Oc elements */
+        hipEvent_t lim_done = nullptr;    /* ... and the event behind this lane's latest limiter launch */
         float* ld_user = nullptr; size_t ld_bytes = 0;      /* ... and the batch in flight's records: where they go at collect, and how many bytes */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
@@ -250,7 +267,7 @@ uint32_t out_channels(const aacg_pipeline* p) { return p->O ? p->O : p->C; }
 aacg_exit_pipe exit_pipe(const aacg_pipeline* p)
 {
     return {p->C, p->O, p->rs.L != 0, (uint32_t)pcm_elem(p), (uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.lane_elems,
-            p->ft.K ? p->ft.n_mels : 0u, p->ft.lane_elems};
+            p->ft.K ? p->ft.n_mels : 0u, p->ft.lane_elems, p->lim.on ? 1u : 0u};
 }
 /* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M), the first
  * through ceil((q M + n) L / M) = q L + ceil(n L / M) so that the one formula (aacg_resample_ceil) sees the arguments it is made for */
@@ -358,13 +375,15 @@ struct batch_t {
     std::vector<aacg_loudness_stream> ld;        /* check_batch, a meter: the batch's records, from the host's clocks */
     size_t ld_at;                                /* stage_batch: where those lie, behind the feature stage's */
     size_t ld_floats;                            /* check_batch: the floats the batch's loudness records take */
+    std::vector<aacg_limit_stream> lim;          /* check_batch, a limiter: the batch's records, with the slots' gains as they stand */
+    size_t lim_at;                               /* stage_batch: where those lie, behind the meter's */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
 /* a buffer of the exit plan, for this lane and this batch */
 void* exit_buf(const aacg_pipeline::lane_t& L, const batch_t& B, uint8_t id)
 {
-    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out, L.d_ft};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_LANE_FT */
+    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out, L.d_ft, L.d_lim};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_LANE_LIM */
     return of[id];
 }
 
@@ -576,15 +595,16 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
     }
     for (auto& L : p->lane) {
         /* (d_frames lies in d_bytes, d_refused in d_res; a meter's records lie in front of d_res and h_res, in their blocks) */
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_lim, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
         for (void* h : {L.h_in, L.h_pcm, L.h_res ? (void*)((char*)L.h_res - p->ld.front16) : nullptr}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.rs_done) (void)hipEventDestroy(L.rs_done);
         if (L.ft_done) (void)hipEventDestroy(L.ft_done);
         if (L.ld_done) (void)hipEventDestroy(L.ld_done);
+        if (L.lim_done) (void)hipEventDestroy(L.lim_done);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
-    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state}) if (d) (void)hipFree(d);
+    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -692,6 +712,7 @@ int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* 
     if (p->submitted) { p->err = "aacg_pipeline_set_mix: a batch has been submitted (the mix is set before the first)"; return AACG_ERR_INVALID_ARG; }
     if (p->rs.L) { p->err = "aacg_pipeline_set_mix: the pipeline has a resampler already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (p->ft.K) { p->err = "aacg_pipeline_set_mix: the pipeline has a feature stage already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (p->lim.on) { p->err = "aacg_pipeline_set_mix: the pipeline has a limiter already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (out_channels < 1 || out_channels > AACG_MIX_MAX_OUT) { p->err = "aacg_pipeline_set_mix: out_channels is not 1 or 2"; return AACG_ERR_INVALID_ARG; }
     if (!matrix) { p->err = "aacg_pipeline_set_mix: no matrix"; return AACG_ERR_INVALID_ARG; }
     for (uint32_t i = 0; i < out_channels * p->C; i++)
@@ -834,6 +855,50 @@ int aacg_pipeline_set_loudness(aacg_pipeline* p, const aacg_loudness_config* cfg
     return AACG_OK;
 }
 
+int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (!cfg) { p->err = "aacg_pipeline_set_limiter: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (p->lim.on) { p->err = "aacg_pipeline_set_limiter: the pipeline has a limiter already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_limiter: a batch has been submitted (the limiter is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (!(cfg->ceiling > 0.0f) || !std::isfinite(cfg->ceiling)) { p->err = "aacg_pipeline_set_limiter: ceiling is not positive and finite"; return AACG_ERR_INVALID_ARG; }
+    if (!(cfg->release > 0.0f) || !(cfg->release <= 1.0f)) { p->err = "aacg_pipeline_set_limiter: release is not in (0, 1]"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const uint32_t Oc = out_channels(p);
+    const size_t bytes = (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * Oc * 1024u * pcm_elem(p);
+    const size_t state_bytes = (size_t)p->cfg.max_streams * 2u * AACG_LIMIT_STATE(Oc) * sizeof(float);
+    void* d_state = nullptr;
+    /* (the state needs no clearing: a fresh slot's is not read) */
+    if (hipMalloc(&d_state, state_bytes) != hipSuccess || !lanes_alloc(p, &lane_t::d_lim, bytes, &lane_t::lim_done)) {
+        (void)hipGetLastError();
+        if (d_state) (void)hipFree(d_state);
+        p->err = "aacg_pipeline_set_limiter: no device memory for the slots' state and the lanes' limited PCM";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    p->lim.d_state = d_state; p->lim.ceiling = cfg->ceiling; p->lim.release = cfg->release;
+    p->lim.gain.assign((size_t)p->cfg.max_streams, 1.0f); p->lim.parity.assign((size_t)p->cfg.max_streams, 0); p->lim.fresh.assign((size_t)p->cfg.max_streams, 1);
+    p->lim.on = true;
+    return AACG_OK;
+}
+
+int aacg_pipeline_set_gain(aacg_pipeline* p, uint32_t slot, float gain)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    if (!p->lim.on) { p->err = "aacg_pipeline_set_gain: the pipeline has no limiter (aacg_pipeline_set_limiter)"; return AACG_ERR_INVALID_ARG; }
+    if ((int)slot >= p->cfg.max_streams) { p->err = "aacg_pipeline_set_gain: stream slot out of range"; return AACG_ERR_INVALID_ARG; }
+    if (!aacg_limit_gain_ok(gain)) { p->err = "aacg_pipeline_set_gain: gain is not in 0..1024"; return AACG_ERR_INVALID_ARG; }
+    p->lim.gain[slot] = gain;                            /* nothing in flight reads it: a batch's gains went up in its records */
+    return AACG_OK;
+}
+
+int aacg_pipeline_gain(const aacg_pipeline* p, uint32_t slot, float* gain)
+{
+    if (!p || !gain || !p->lim.on || (int)slot >= p->cfg.max_streams) return AACG_ERR_INVALID_ARG;
+    *gain = p->lim.gain[slot];
+    return AACG_OK;
+}
+
 int aacg_pipeline_loudness_out(aacg_pipeline* p, float* records, size_t capacity_floats, uint32_t* n_out_of)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
@@ -906,6 +971,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
     if (p->ft.K) { p->ft.N[slot] = 0; p->ft.fresh[slot] = 1; }       /* ... and the feature stage's */
     if (p->ld.hop) { p->ld.N[slot] = 0; p->ld.fresh[slot] = 1; }     /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
+    if (p->lim.on) p->lim.fresh[slot] = 1;                           /* ... and the limiter's held block and nodes; the slot's gain is the caller's and stays */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
         drop_plans_with(p, slot);
@@ -977,6 +1043,13 @@ int check_batch(aacg_pipeline* p, batch_t& B)
         B.ld_floats = (size_t)total * p->C * 2u;
         if (B.ld_floats > p->ld.out_cap) { p->err = "the destination named for the loudness records is too small for this submission"; return AACG_ERR_CAPACITY; }
     }
+    if (p->lim.on) {                                     /* a limiter: the slots' gains as they stand */
+        B.lim.resize(B.n_streams);
+        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
+            const uint32_t slot = B.slots[s];
+            B.lim[s] = {first, B.frames_of[s], slot, p->lim.parity[slot], p->lim.fresh[slot], p->lim.gain[slot], {0u, 0u}};
+        }
+    }
     B.X = aacg_pipe::exit_plan(exit_pipe(p), b);
     return B.pcm_out ? AACG_OK : check_device_out(p, B, b);
 }
@@ -991,11 +1064,15 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     /* (... and a feature stage's behind those: both records are 32 bytes) */
     const size_t rs_bytes = B.rs.size() * sizeof(aacg_resample_stream), ft_bytes = B.ft.size() * sizeof(aacg_features_stream);
     const size_t ld_bytes = B.ld.size() * sizeof(aacg_loudness_stream);      /* (... and a meter's behind those) */
-    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, rs_bytes + ft_bytes + ld_bytes ? tab16 + rs_bytes + ft_bytes + ld_bytes : tab_bytes, B.G);
+    const size_t lim_bytes = B.lim.size() * sizeof(aacg_limit_stream);      /* (... and a limiter's behind those: every record is 32 bytes) */
+    const size_t more = rs_bytes + ft_bytes + ld_bytes + lim_bytes;
+    int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, more ? tab16 + more : tab_bytes, B.G);
     if (rc) return rc;
     B.rs_at = B.G.extra_at + tab16;
     B.ft_at = B.rs_at + rs_bytes;
     B.ld_at = B.ft_at + ft_bytes;
+    B.lim_at = B.ld_at + ld_bytes;
+    if (lim_bytes) std::memcpy((char*)L.h_in + B.lim_at, B.lim.data(), lim_bytes);
     if (ld_bytes) std::memcpy((char*)L.h_in + B.ld_at, B.ld.data(), ld_bytes);
     if (rs_bytes) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), rs_bytes);
     if (ft_bytes) std::memcpy((char*)L.h_in + B.ft_at, B.ft.data(), ft_bytes);
@@ -1093,6 +1170,15 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
             aacg_mix_args M = {src, dst, B.n, p->C, p->O, E, {}};
             std::memcpy(M.m, p->mix, sizeof M.m);
             if (!aacg_mix_launch(M, L.st)) { p->err = "aacg_pcm_mix: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        } else if (S.what == AACG_EXIT_LIMIT) {
+            /* the packed PCM of Oc channels, gained and limited, sample for sample.  The slots' held blocks and nodes pass from batch to
+             * batch like the resampler's history: this launch waits for the one before it, here — behind this lane's parse, transform and mix */
+            const aacg_limit_args A = {src, dst, (const aacg_limit_stream*)((const char*)L.d_bytes + B.lim_at), (float*)p->lim.d_state, B.n_streams, B.n,
+                                       p->lim.ceiling, p->lim.release, Oc, E};
+            if (p->lim.last && p->lim.last != L.lim_done) P_TRY(p, hipStreamWaitEvent(L.st, p->lim.last, 0), AACG_ERR_NO_DEVICE);
+            if (!aacg_limit_launch(A, L.st)) { p->err = "aacg_pcm_limit: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+            P_TRY(p, hipEventRecord(L.lim_done, L.st), AACG_ERR_NO_DEVICE);
+            p->lim.last = L.lim_done;
         } else if (S.what == AACG_EXIT_RESAMPLE) {
             /* the packed PCM at the new rate, either layout.  The slots' histories pass from batch to batch, and consecutive batches run on
              * different streams: this launch waits for the one before it, here — behind this lane's parse, transform and mix, which need not wait */
@@ -1153,6 +1239,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     for (const auto& r : B.ft) { p->ft.N[r.slot] += r.n_in; p->ft.parity[r.slot] = (uint8_t)((r.flags & 1u) ^ 1u); p->ft.fresh[r.slot] = 0; }
     /* ... and the meter's; its destination is this batch's now, and the next submission names its own */
     for (const auto& r : B.ld) { p->ld.N[r.slot] += 1024ull * r.frames; p->ld.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->ld.fresh[r.slot] = 0; }
+    for (const auto& r : B.lim) { p->lim.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->lim.fresh[r.slot] = 0; }      /* ... and the limiter's held blocks change sides */
     L.ld_user = p->ld.out; L.ld_bytes = B.ld_floats * sizeof(float);
     if (p->ld.hop) {
         if (p->ld.out_counts) for (uint32_t s = 0; s < B.n_streams; s++) p->ld.out_counts[s] = B.ld[s].n_out;

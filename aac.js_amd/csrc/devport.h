@@ -16,6 +16,7 @@
 #ifdef AACG_EMU_BUILD
 #include "devport_emu.h"
 #include "devport_mfma_emu.h"
+#include "devport_limit_emu.h"
 #else
 
 #include <hip/hip_runtime.h>
@@ -161,6 +162,19 @@ DP_DEVICE void dp_shfl(double (&v)[N], int src)
 {
 #pragma unroll
     for (int i = 0; i < N; i++) v[i] = __shfl(v[i], src, 64);
+}
+
+/* v[i] <- the largest v[i] of the wave's 64 lanes, in every lane: a butterfly of six exchanges per value (lane ^ 32 .. lane ^ 1), the
+ * N values' exchanges of a step side by side.  No value may be a NaN: the callers' are maxima taken from +0.  The maximum is exact, so
+ * the order is free (the CPU twin, tests/emu/devport_limit_emu.h, takes the lanes in turn). */
+template <int N>
+DP_DEVICE void dp_wave_max(float (&v)[N])
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int i = 0; i < N; i++) v[i] = __builtin_fmaxf(v[i], __shfl_xor(v[i], m, 64));
+    }
 }
 
 extern __shared__ __attribute__((aligned(16))) unsigned char dp_lds_raw[];

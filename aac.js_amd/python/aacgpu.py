@@ -41,7 +41,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_set_resample", "aacg_pipeline_out_samples", "aacg_resample_counts", "aacg_resample_design",
                "aacg_pipeline_set_features", "aacg_features_counts", "aacg_features_design",
                "aacg_pipeline_set_loudness", "aacg_pipeline_loudness_out", "aacg_pipeline_loudness_counts", "aacg_loudness_counts",
-               "aacg_loudness_design", "aacg_loudness_integrate"]
+               "aacg_loudness_design", "aacg_loudness_integrate",
+               "aacg_pipeline_set_limiter", "aacg_pipeline_set_gain", "aacg_pipeline_gain", "aacg_limiter_design"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -120,6 +121,14 @@ class FeaturesConfig(C.Structure):
 # aacg_loudness_config: the meter's hop and its two biquad sections (aacg_pipeline_set_loudness)
 class LoudnessConfig(C.Structure):
     _fields_ = [("hop", C.c_uint32), ("coeffs", (C.c_float * 5) * 2)]
+
+
+# aacg_limiter_config: the limiter's ceiling (full-scale units) and release (the share of the way back per block of 64 samples)
+class LimiterConfig(C.Structure):
+    _fields_ = [("ceiling", C.c_float), ("release", C.c_float)]
+
+
+LIMIT_BLOCK = 64                                     # AACG_LIMIT_BLOCK: samples of a limiter block, and its delay
 
 
 # aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
@@ -306,6 +315,10 @@ def load_library(path=LIB_PATH):
     L.aacg_loudness_counts.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.aacg_loudness_design.argtypes = [C.c_uint32, C.c_void_p]
     L.aacg_loudness_integrate.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.aacg_pipeline_set_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterConfig)]
+    L.aacg_pipeline_set_gain.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
+    L.aacg_pipeline_gain.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+    L.aacg_limiter_design.argtypes = [C.c_uint32, C.c_double, C.c_double, C.POINTER(LimiterConfig)]
     _lib = L
     return L
 
@@ -509,11 +522,14 @@ class Pipeline:
     n_refused, lengths) with frames flat, lengths[s] feature frames of n_mels floats each; decode_tensor returns (S, n_mels, T).
     loudness: a dict for set_loudness (aacg_pipeline_set_loudness; loudness_design makes BS.1770's) — hop and coeffs (2, 5).  A tap on the
     transform's PCM, beside whatever else leaves: decode, submit, collect and decode_tensor return what they return without it, and
-    take_loudness gives a batch's records, a list of (n_out[s], in_channels, 2) float32 arrays of {energy, sample peak} per hop."""
+    take_loudness gives a batch's records, a list of (n_out[s], in_channels, 2) float32 arrays of {energy, sample peak} per hop.
+    limiter: a LimiterConfig or a (ceiling, release) pair for set_limiter (aacg_pipeline_set_limiter; limiter_design makes one from dB and
+    milliseconds).  A stage behind the mix and in front of the resampler: every stream's PCM is scaled by its slot's gain (set_gain, 1
+    until set) and held below the ceiling, all channels alike, delayed by 64 samples; shapes and counts are what they are without it."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None):
+                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -531,6 +547,7 @@ class Pipeline:
         self.resample, self.rate = None, SAMPLE_RATES[sample_index]
         self.features = None
         self.loudness, self._loud, self._loud_last = None, {}, None
+        self.limiter = None
         self._keep = {}
         if mix is not None:
             m = np.ascontiguousarray(mix, np.float32)
@@ -540,6 +557,12 @@ class Pipeline:
             try:
                 self.set_mix(m)
             except AacgError:
+                self.close()
+                raise
+        if limiter is not None:
+            try:
+                self.set_limiter(limiter)
+            except (AacgError, ValueError, TypeError):
                 self.close()
                 raise
         if out_rate is not None and resample is None:
@@ -637,6 +660,24 @@ class Pipeline:
         C.memmove(cfg.coeffs, k.ctypes.data, 40)
         self._check(self.lib.aacg_pipeline_set_loudness(self.handle, C.byref(cfg)))
         self.loudness = {"hop": int(hop), "coeffs": k}
+
+    def set_limiter(self, config):
+        """aacg_pipeline_set_limiter: a LimiterConfig or a (ceiling, release) pair, before the first batch and after the mix"""
+        cfg = config if isinstance(config, LimiterConfig) else LimiterConfig(*[float(v) for v in config])
+        self._check(self.lib.aacg_pipeline_set_limiter(self.handle, C.byref(cfg)))
+        self.limiter = LimiterConfig(cfg.ceiling, cfg.release)
+
+    def set_gain(self, slot, gain):
+        """aacg_pipeline_set_gain: the slot's gain (0..1024) from the next batch enqueued that holds the slot; a reset leaves it"""
+        self._check(self.lib.aacg_pipeline_set_gain(self.handle, int(slot), float(gain)))
+
+    def gain(self, slot):
+        """aacg_pipeline_gain: the slot's gain as it stands"""
+        g = C.c_float()
+        rc = self.lib.aacg_pipeline_gain(self.handle, int(slot), C.byref(g))
+        if rc != 0:
+            raise AacgError(rc, "aacg_pipeline_gain(slot %d): no limiter, or no such slot" % int(slot))
+        return float(g.value)
 
     def loudness_counts(self, slots, frames_per_stream):
         """aacg_pipeline_loudness_counts: the records per channel that the NEXT batch of these slots with these counts emits, per stream"""
@@ -879,6 +920,16 @@ def loudness_design(rate, hop=None):
     if rc != 0:
         raise AacgError(rc, "aacg_loudness_design(%d Hz)" % rate)
     return {"hop": int(rate) // 10 if hop is None else int(hop), "coeffs": k}
+
+
+def limiter_design(rate, ceiling_db=-1.0, release_ms=200.0):
+    """aacg_limiter_design: a LimiterConfig for Pipeline(limiter=...) — ceiling = 10^(ceiling_db / 20) in full-scale units, release = the
+    share of the way back to a slot's gain that a block of 64 samples covers at a time constant of release_ms at `rate`"""
+    cfg = LimiterConfig()
+    rc = load_library().aacg_limiter_design(int(rate), float(ceiling_db), float(release_ms), C.byref(cfg))
+    if rc != 0:
+        raise AacgError(rc, "aacg_limiter_design(%d Hz, %g dB, %g ms)" % (rate, ceiling_db, release_ms))
+    return cfg
 
 
 def loudness_counts(hop, n0, samples):

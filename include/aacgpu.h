@@ -1009,8 +1009,7 @@ int  aacg_features_design(uint32_t rate, uint32_t frame_length, uint32_t hop, ui
  * pipeline exactly as it was: a null config, a hop outside 1..2^20, a coefficient that is not finite, a call after the first batch, a
  * second call; and a pipeline beyond the meter's limits — max_streams x (max_frames x 1024 / hop + 1) x channels of 2^27 records or
  * more, max_streams x max_frames frames of PCM of 64 GiB or more.  AACG_ERR_OUT_OF_MEMORY: no device memory for the slots' state and the lanes' records; the pipeline stays as it was.
- * Not here: true (oversampled) peak, short-term windows and loudness range, a gain or limiter that applies the result, a meter behind
- * the mix or the resampler. */
+ * Not here: true (oversampled) peak, short-term windows and loudness range, a meter behind the mix or the resampler. */
 typedef struct aacg_loudness_config {
     uint32_t hop;
     float    coeffs[2][5];
@@ -1045,6 +1044,62 @@ int  aacg_loudness_design(uint32_t rate, float coeffs[2][5]);
  * loudness every 100 ms).  AACG_ERR_INVALID_ARG: null records with hops, a null integrated_lufs, channels outside 1..8, a hop outside 1..2^20. */
 int  aacg_loudness_integrate(const float* records, size_t n_hops, uint32_t channels, uint32_t hop, const double* weights,
                              double* integrated_lufs, double* momentary_lufs);
+
+/* A gain per stream and a look-ahead limiter on the device: a STAGE of the way out, BEHIND the mix and IN FRONT of the resampler and the
+ * feature stage, for a consumer that has a gain for a stream (from the meter above, from ReplayGain tags) and wants it applied, with
+ * full scale protected, before the PCM leaves — a 5.1 -> stereo mix without `normalise` exceeds full scale on ordinary material, and on
+ * a float pipeline nothing else catches that.  The same gain goes to every channel of a stream (the limiter is channel-linked).
+ *     ceiling c: finite and above 0, in full-scale units for both output kinds;  release r: in (0, 1];
+ *     per slot a gain G (aacg_pipeline_set_gain): finite, 0 <= G <= 1024, 1 until it is set.
+ * The input x of a slot is its PCM as the pipeline would have delivered it without the stage, after the mix if one is set: Oc =
+ * out_channels or `channels` channels, at the stream's own rate, so every stream brings a multiple of 1024 samples.  Blocks are
+ * AACG_LIMIT_BLOCK = 64 samples x Oc channels and never straddle a frame.  A refused frame and a frame of an unlearnt stream are zeros
+ * and pass through like any other.  On an AACG_OUTPUT_I16 pipeline x is the already rounded int16 times 2^-15 (exact).
+ * THE RULE, bit for bit, in float32 throughout, every operation rounded on its own, nothing fused, subnormals kept.  Per slot the stage
+ * holds one block xh, the node gain a0 at its start and the block's target th.  For every arriving block xk of the slot, in order:
+ *     p  = max over the block's 64 x Oc samples of |x|      (fmaxf from +0: a NaN sample is ignored here)
+ *     tk = (G p > c) ? c / p : G                            (the product rounded, then compared)
+ *     u  = a0 + (r (G - a0))
+ *     a1 = fminf(fminf(th, tk), u)
+ *     d  = a1 - a0
+ *     out[i][ch] = (a0 + (d w[i])) xh[i][ch]                i = 0..63, w[i] = i / 64 (exact)
+ *     xh = xk;  a0 = a1;  th = tk
+ * AACG_OUTPUT_F32: out as computed, no clamp.  AACG_OUTPUT_I16: out x 2^15 rounded to nearest even and saturated, the mix's int16 rule.
+ * A fresh slot (create, aacg_pipeline_reset_stream) holds a block of zeros, with a0 = th = G as G stands at the slot's next batch.  A
+ * batch emits exactly as many samples as it brings, delayed by 64: the last 64 samples of a stream stay inside, as the resampler's
+ * group delay keeps its share, and there is no flush.  Any split of a stream's frames into batches gives the same bits.
+ * What follows from the rule: (a) for finite input |out| <= c (1 + 2^-21) — the gain inside a block lies between its two nodes, both
+ * are <= th <= c / p, and four roundings of 2^-24 each lie between the exact bound and the stored sample; (b) a fall of G, or a peak
+ * that arrives, reaches the output within one block, as a linear ramp; (c) a rise approaches G at the rate r per block;  (d) a limiter
+ * behind an int16 transform or mix cannot undo THEIR saturation: it serves a boost there, not a rescue.
+ * State per slot: G on the host; xh, a0 and th on the device, handed from batch to batch across lanes as the resampler's history.  One
+ * more launch per batch (aacg_pcm_limit_*) on the lane's stream behind the mix; it goes with both output kinds, every `stages` bit, both
+ * plan modes, ragged, device and host batches, span walks, the mix, the resampler, the feature stage and the meter — which taps the
+ * transform's PCM in front of all this and does not see it.  aacg_pipeline_out_samples and every buffer size keep their values: the
+ * stage emits what it receives.  With no limiter set nothing differs, call for call.
+ * Called once, before the pipeline's first submitted batch, and after aacg_pipeline_set_mix if both are used (a mix set behind it is
+ * refused); its order relative to _set_resample, _set_features and _set_loudness is free.  AACG_ERR_INVALID_ARG, with the reason in
+ * aacg_pipeline_last_error and the pipeline exactly as it was: a null config, a ceiling or release outside the limits, a call after
+ * the first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the slots' state and the lanes' buffer; the pipeline
+ * stays as it was.
+ * Not here: true-peak (oversampled) limiting, a limiter behind the resampler, a flush of the last 64 samples. */
+#define AACG_LIMIT_BLOCK 64
+typedef struct aacg_limiter_config {
+    float ceiling;
+    float release;
+} aacg_limiter_config;
+int  aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg);
+/* A slot's gain G.  May be called at any time on a pipeline with a limiter; it takes effect with the next batch ENQUEUED that holds the
+ * slot and does not wait for batches in flight (the gain travels with the launch).  It survives aacg_pipeline_reset_stream: it is the
+ * caller's setting, not the stream's state.  AACG_ERR_INVALID_ARG: a pipeline without a limiter, a slot out of range, a gain that is
+ * not finite or outside 0..1024. */
+int  aacg_pipeline_set_gain(aacg_pipeline* p, uint32_t slot, float gain);
+/* ... and reads it back.  AACG_ERR_INVALID_ARG: a pipeline without a limiter, a slot out of range, a null gain. */
+int  aacg_pipeline_gain(const aacg_pipeline* p, uint32_t slot, float* gain);
+/* Host code only, in double, each value rounded to float once: ceiling = 10^(ceiling_db / 20), release = 1 - exp(-64 / (rate x
+ * release_ms / 1000)) — the share of the way back to G that a block of 64 samples covers at a time constant of release_ms.
+ * AACG_ERR_INVALID_ARG: a rate of 0, a null cfg, a result outside aacg_pipeline_set_limiter's limits. */
+int  aacg_limiter_design(uint32_t rate, double ceiling_db, double release_ms, aacg_limiter_config* cfg);
 
 #ifdef __cplusplus
 }

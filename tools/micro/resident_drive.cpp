@@ -7,7 +7,12 @@
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
- *                                         [--loudness]
+ *                                         [--loudness] [--limiter]
+ *
+ * --limiter: a gain per stream and a look-ahead limiter behind the mix and in front of the resampler (aacg_limiter_design at the file's
+ * rate with a ceiling of -1 dB and a release of 200 ms; aacg_pipeline_set_limiter; slot s gets the gain 0.5 + 0.5 (s mod 8) through
+ * aacg_pipeline_set_gain, so that some streams are boosted into the ceiling): one more launch per batch (aacg_pcm_limit_*).  The line
+ * then carries the two settings and the bytes that launch reads and writes.  Combines with everything else.
  *
  * --loudness: a loudness meter beside whatever leaves (aacg_loudness_design at the file's rate, BS.1770's K-weighting, with a hop of a
  * tenth of a second; aacg_pipeline_set_loudness): one more launch per batch (aacg_pcm_loudness_*) over the transform's PCM, and two floats
@@ -76,7 +81,7 @@ int main(int argc, char** argv)
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     uint32_t mix = 0, rate = 0;
-    bool features = false, loudness = false;
+    bool features = false, loudness = false, limiter = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -99,6 +104,7 @@ int main(int argc, char** argv)
         else if (a == "--rate") rate = (uint32_t)std::atoi(val());
         else if (a == "--features") features = true;
         else if (a == "--loudness") loudness = true;
+        else if (a == "--limiter") limiter = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -145,6 +151,14 @@ int main(int argc, char** argv)
         if ((rc = aacg_pipeline_set_mix(p, mix, m))) { std::fprintf(stderr, "aacg_pipeline_set_mix: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
     const uint32_t out_channels = (uint32_t)aacg_pipeline_out_channels(p);      /* what leaves: the mix's rows, or the stream's channels */
+    aacg_limiter_config lim_cfg = {0.0f, 0.0f};
+    if (limiter) {                                          /* behind the mix, in front of the resampler */
+        static const uint32_t rates[16] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350, 0, 0, 0};
+        if ((rc = aacg_limiter_design(rates[sample_index], -1.0, 200.0, &lim_cfg))) { std::fprintf(stderr, "aacg_limiter_design(%u): %d\n", rates[sample_index], rc); return 2; }
+        if ((rc = aacg_pipeline_set_limiter(p, &lim_cfg))) { std::fprintf(stderr, "aacg_pipeline_set_limiter: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+        for (uint32_t s = 0; s < S; s++)
+            if ((rc = aacg_pipeline_set_gain(p, s, 0.5f + 0.5f * (float)(s % 8u)))) { std::fprintf(stderr, "aacg_pipeline_set_gain: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
     uint32_t rs_L = 1, rs_M = 1;
     if (rate) {
         static const uint32_t rates[16] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350, 0, 0, 0};
@@ -283,15 +297,18 @@ int main(int argc, char** argv)
         for (float v : ld_rec[0]) finite = finite && std::isfinite(v);
         std::snprintf(loudness_key, sizeof loudness_key, "\"loudness\": \"bs1770\", \"loudness_hop\": %u, \"loudness_records_per_batch_most\": %zu, ", ld_hop, ld_most);
     }
+    char limiter_key[192] = "";                             /* --limiter only: what aacg_pcm_limit_* reads and writes is 2 n Oc 1024 E */
+    if (limiter) std::snprintf(limiter_key, sizeof limiter_key, "\"limiter\": \"-1 dB, 200 ms\", \"limiter_ceiling\": %.6f, \"limiter_release\": %.6g, \"limiter_bytes_moved_per_batch\": %zu, ",
+                               (double)lim_cfg.ceiling, (double)lim_cfg.release, 2 * resample_in_bytes);
     char features_key[192] = "";                            /* --features only */
     if (features) std::snprintf(features_key, sizeof features_key, "\"features\": \"log-mel\", \"frame_length\": %u, \"hop\": %u, \"n_bins\": %u, \"n_mels\": %u, \"feature_frames_per_stream_most\": %zu, ", ft_K, ft_H, ft_bins, ft_mels, most_ft);
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s"
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, rate_key, features_key, loudness_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, limiter_key, rate_key, features_key, loudness_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
