@@ -79,6 +79,8 @@
 #include "aacg_pcm_loudness.h"
 #define AACG_LIMIT_HOST_ONLY                              /* the limits and the records: the body is aacg_engine_limit.hip's */
 #include "aacg_pcm_limit.h"
+#define AACG_TRUEPEAK_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_truepeak.hip's */
+#include "aacg_pcm_truepeak.h"
 #include "aacg_pipe_exit.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
@@ -100,6 +102,8 @@ bool aacg_features_launch(const aacg_features_args& A, hipStream_t s);
 bool aacg_loudness_launch(const aacg_loudness_args& A, hipStream_t s);
 /* aacg_engine_limit.hip: a gain per stream and a look-ahead limiter on a batch's packed PCM (aacg_pcm_limit.h); false: not a launch it serves */
 bool aacg_limit_launch(const aacg_limit_args& A, hipStream_t s);
+/* aacg_engine_truepeak.hip: the true peak of a batch's transform PCM (aacg_pcm_truepeak.h); false: not a launch it serves */
+bool aacg_truepeak_launch(const aacg_truepeak_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -175,6 +179,16 @@ struct aacg_pipeline {
         size_t front16 = 0;
         float* out = nullptr; size_t out_cap = 0; uint32_t* out_counts = nullptr; bool armed = false;
     } ld;
+    /* aacg_pipeline_set_true_peak: the table's shape (L 0: none), the table and the slots' state on the device ([slot][2][T x C] words:
+     * the history and the partial maximum).  The clock, the parities, the fresh flags, the records and the event are the meter's: the
+     * launch stands between the meter's and the meter's event.  A batch's floats lie in front of the meter's records in the lane's
+     * block (ld.front16 covers both).  out, out_cap: the destination named for the next submission (aacg_pipeline_true_peak_out) while
+     * `armed` */
+    struct truepeak_t {
+        uint32_t L = 0, T = 0;
+        void *d_table = nullptr, *d_state = nullptr;
+        float* out = nullptr; size_t out_cap = 0; bool armed = false;
+    } tp;
     /* aacg_pipeline_set_limiter: the two settings (on: a limiter is set), the slots' state on the device ([slot][2][AACG_LIMIT_STATE(Oc)]
      * floats), and per slot what the host keeps: the gain (the caller's: a reset leaves it), which state buffer the slot's next batch
      * reads, and whether it has consumed anything since its reset.  last: the event behind the latest limiter launch */
@@ -219,6 +233,7 @@ struct aacg_pipeline {
         void* d_lim = nullptr;            /* aacg_pipeline_set_limiter: the limited PCM wherever it is not a packed device batch's last stage, max_streams x max_frames x 1024 x Oc elements */
         hipEvent_t lim_done = nullptr;    /* ... and the event behind this lane's latest limiter launch */
         float* ld_user = nullptr; size_t ld_bytes = 0;      /* ... and the batch in flight's records: where they go at collect, and how many bytes */
+        float* tp_user = nullptr; size_t tp_bytes = 0;      /* aacg_pipeline_set_true_peak: the same for the batch in flight's true-peak floats */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
         /* aacg_pipeline_config.stages with AACG_PIPELINE_STAGE_TNS: the parser's TNS side info (max_streams x max_frames x Cp records)
          * and what aacg_tns_records_from_parse makes of it, the batch's records and their matrices — a launch input like d_q */
@@ -375,6 +390,7 @@ struct batch_t {
     std::vector<aacg_loudness_stream> ld;        /* check_batch, a meter: the batch's records, from the host's clocks */
     size_t ld_at;                                /* stage_batch: where those lie, behind the feature stage's */
     size_t ld_floats;                            /* check_batch: the floats the batch's loudness records take */
+    size_t tp_floats;                            /* check_batch: ... and its true-peak records, 0 without the stage */
     std::vector<aacg_limit_stream> lim;          /* check_batch, a limiter: the batch's records, with the slots' gains as they stand */
     size_t lim_at;                               /* stage_batch: where those lie, behind the meter's */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
@@ -428,6 +444,7 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
     if (rc) return rc;
     if (L.collect_bytes) std::memcpy(L.collect_pcm, L.h_pcm, L.collect_bytes);
     if (L.ld_bytes) std::memcpy(L.ld_user, (const char*)L.h_res - ((L.ld_bytes + 15) & ~(size_t)15), L.ld_bytes);      /* the meter's records lie in front of the results */
+    if (L.tp_bytes) std::memcpy(L.tp_user, (const char*)L.h_res - ((L.ld_bytes + 15) & ~(size_t)15) - ((L.tp_bytes + 15) & ~(size_t)15), L.tp_bytes);      /* ... and the true-peak floats in front of those */
     /* a stream whose first frame did not parse has no layout yet: every frame of it in this batch came out silent and says so */
     aacg_parse_result* res = (aacg_parse_result*)L.h_res;
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
@@ -604,7 +621,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (L.lim_done) (void)hipEventDestroy(L.lim_done);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
-    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state}) if (d) (void)hipFree(d);
+    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state, p->tp.d_table, p->tp.d_state}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -908,6 +925,62 @@ int aacg_pipeline_loudness_out(aacg_pipeline* p, float* records, size_t capacity
     return AACG_OK;
 }
 
+int aacg_pipeline_set_true_peak(aacg_pipeline* p, const aacg_true_peak_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (!cfg) { p->err = "aacg_pipeline_set_true_peak: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (!p->ld.hop) { p->err = "aacg_pipeline_set_true_peak: the pipeline has no meter (aacg_pipeline_set_loudness comes first)"; return AACG_ERR_INVALID_ARG; }
+    if (p->tp.L) { p->err = "aacg_pipeline_set_true_peak: the pipeline has a true-peak stage already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_true_peak: a batch has been submitted (the stage is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int why = aacg_truepeak_check(cfg->phases, cfg->taps)) { p->err = std::string("aacg_pipeline_set_true_peak: ") + aacg_truepeak_why(why); return AACG_ERR_INVALID_ARG; }
+    if (!cfg->table) { p->err = "aacg_pipeline_set_true_peak: no table"; return AACG_ERR_INVALID_ARG; }
+    const size_t n_table = (size_t)cfg->phases * cfg->taps;
+    for (size_t i = 0; i < n_table; i++)
+        if (!std::isfinite(cfg->table[i])) { p->err = "aacg_pipeline_set_true_peak: coefficient " + std::to_string(i) + " is not finite"; return AACG_ERR_INVALID_ARG; }
+    if ((uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames > AACG_TRUEPEAK_MAX_FRAMES) { p->err = "aacg_pipeline_set_true_peak: max_streams x max_frames is more than 2^21 frames"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    /* the largest batch's floats, one per meter's record and channel (the meter's limit holds: below 2^27), in front of the meter's in
+     * a lane's block: new blocks for every lane or for none, as aacg_pipeline_set_loudness makes them (nothing is in flight yet).  The
+     * state IS cleared: a batch finds the partial maximum it writes to empty (aacg_pcm_truepeak.h) */
+    const uint64_t most = (uint64_t)p->cfg.max_streams * ((uint64_t)p->cfg.max_frames * 1024u / p->ld.hop + 1u);
+    const size_t tp16 = ((size_t)most * p->C * sizeof(float) + 15) & ~(size_t)15, front16 = p->ld.front16 + tp16, block = front16 + p->res_cap16 + 16;
+    const size_t state_bytes = (size_t)p->cfg.max_streams * 2u * AACG_TRUEPEAK_STATE(cfg->taps, p->C) * sizeof(float);
+    void *d_table = nullptr, *d_state = nullptr, *d_new[AACG_PIPELINE_MAX_LANES] = {}, *h_new[AACG_PIPELINE_MAX_LANES] = {};
+    bool good = hipMalloc(&d_table, n_table * sizeof(float)) == hipSuccess && hipMemcpy(d_table, cfg->table, n_table * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+                hipMalloc(&d_state, state_bytes) == hipSuccess && hipMemset(d_state, 0, state_bytes) == hipSuccess;
+    for (int k = 0; k < p->n_lanes && good; k++)
+        good = hipMalloc(&d_new[k], block) == hipSuccess && hipMemset(d_new[k], 0, block) == hipSuccess &&
+               hipHostMalloc(&h_new[k], block, hipHostMallocDefault) == hipSuccess;
+    if (!good) {
+        (void)hipGetLastError();
+        if (d_table) (void)hipFree(d_table);
+        if (d_state) (void)hipFree(d_state);
+        for (int k = 0; k < p->n_lanes; k++) { if (d_new[k]) (void)hipFree(d_new[k]); if (h_new[k]) (void)hipHostFree(h_new[k]); }
+        p->err = "aacg_pipeline_set_true_peak: no device memory for the table, the slots' state and the lanes' records";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    for (int k = 0; k < p->n_lanes; k++) {
+        auto& L = p->lane[k];
+        (void)hipFree((char*)L.d_res - p->ld.front16); (void)hipHostFree((char*)L.h_res - p->ld.front16);
+        L.d_res = (char*)d_new[k] + front16; L.h_res = (char*)h_new[k] + front16; L.d_refused = (char*)L.d_res + p->res_cap16;
+        L.count_stale = false;                          /* (the new block's count is zero) */
+    }
+    p->ld.front16 = front16;
+    p->tp.d_table = d_table; p->tp.d_state = d_state; p->tp.T = cfg->taps;
+    p->tp.L = cfg->phases;
+    return AACG_OK;
+}
+
+int aacg_pipeline_true_peak_out(aacg_pipeline* p, float* peaks, size_t capacity_floats)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    if (!p->tp.L) { p->err = "aacg_pipeline_true_peak_out: the pipeline has no true-peak stage (aacg_pipeline_set_true_peak)"; return AACG_ERR_INVALID_ARG; }
+    if (!peaks && capacity_floats) { p->err = "aacg_pipeline_true_peak_out: no memory for the records"; return AACG_ERR_INVALID_ARG; }
+    p->tp.out = peaks; p->tp.out_cap = capacity_floats; p->tp.armed = true;
+    return AACG_OK;
+}
+
 int aacg_pipeline_loudness_counts(aacg_pipeline* p, const uint32_t* slots, const uint32_t* frames_of, uint32_t n_streams, uint32_t* n_out)
 {
     if (!p || !slots || !frames_of || !n_out) return AACG_ERR_INVALID_ARG;
@@ -1042,6 +1115,11 @@ int check_batch(aacg_pipeline* p, batch_t& B)
         }
         B.ld_floats = (size_t)total * p->C * 2u;
         if (B.ld_floats > p->ld.out_cap) { p->err = "the destination named for the loudness records is too small for this submission"; return AACG_ERR_CAPACITY; }
+        if (p->tp.L) {                                   /* ... and the true-peak stage's, a float where the meter has two */
+            if (!p->tp.armed) { p->err = "the pipeline has a true-peak stage and no destination is named for this submission's records (aacg_pipeline_true_peak_out)"; return AACG_ERR_INVALID_ARG; }
+            B.tp_floats = (size_t)total * p->C;
+            if (B.tp_floats > p->tp.out_cap) { p->err = "the destination named for the true-peak records is too small for this submission"; return AACG_ERR_CAPACITY; }
+        }
     }
     if (p->lim.on) {                                     /* a limiter: the slots' gains as they stand */
         B.lim.resize(B.n_streams);
@@ -1211,7 +1289,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     /* the results and, behind where the largest batch's would end, the refusal count: one small launch (a launch that writes to
      * host memory costs 50 us of the lane's time whatever it carries) */
     L.count_stale = false;
-    size_t ld16 = 0;
+    size_t ld16 = 0, tp16 = 0;
     if (p->ld.hop) {
         /* the meter: the transform's PCM, wherever the exit plan's first stage put it, into records that lie right in front of the lane's
          * results, so that the one copy below brings both down.  The slots' state passes from batch to batch like the resampler's history:
@@ -1222,10 +1300,20 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
         std::memcpy(A.coeffs, p->ld.coeffs, sizeof A.coeffs);
         if (p->ld.last && p->ld.last != L.ld_done) P_TRY(p, hipStreamWaitEvent(L.st, p->ld.last, 0), AACG_ERR_NO_DEVICE);
         if (!aacg_loudness_launch(A, L.st)) { p->err = "aacg_pcm_loudness: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        if (p->tp.L) {
+            /* the true peak, beside the meter: the same PCM and the same records, into floats that lie in front of the meter's and are
+             * cleared first (hops that straddle frames arrive as atomic maxima).  Its slots' state is ordered by the meter's event, which
+             * is recorded behind both launches */
+            tp16 = (B.tp_floats * sizeof(float) + 15) & ~(size_t)15;
+            uint32_t* const d_tp = (uint32_t*)((char*)L.d_res - ld16 - tp16);
+            if (tp16) P_TRY(p, hipMemsetAsync(d_tp, 0, tp16, L.st), AACG_ERR_NO_DEVICE);
+            const aacg_truepeak_args Q = {A.src, d_tp, A.rec, (const float*)p->tp.d_table, (float*)p->tp.d_state, B.n_streams, B.n, p->ld.hop, p->tp.L, p->tp.T, p->C, E};
+            if (!aacg_truepeak_launch(Q, L.st)) { p->err = "aacg_pcm_truepeak: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        }
         P_TRY(p, hipEventRecord(L.ld_done, L.st), AACG_ERR_NO_DEVICE);
         p->ld.last = L.ld_done;
     }
-    pipe_copy((const char*)L.d_res - ld16, (char*)L.h_res - ld16, ld16 + p->res_cap16 + 16, L.st, true);      /* ... and the count is cleared for the lane's next batch (set to zero at create) */
+    pipe_copy((const char*)L.d_res - ld16 - tp16, (char*)L.h_res - ld16 - tp16, tp16 + ld16 + p->res_cap16 + 16, L.st, true);      /* ... and the count is cleared for the lane's next batch (set to zero at create) */
     P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
     P_TRY(p, hipEventRecord(L.done, L.st), AACG_ERR_NO_DEVICE);
     L.busy = true; L.ticket = ++p->submitted; L.collect_pcm = B.pcm_out; L.collect_bytes = B.X.collect_copy ? (size_t)B.X.out_bytes : 0;
@@ -1241,6 +1329,8 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     for (const auto& r : B.ld) { p->ld.N[r.slot] += 1024ull * r.frames; p->ld.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->ld.fresh[r.slot] = 0; }
     for (const auto& r : B.lim) { p->lim.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->lim.fresh[r.slot] = 0; }      /* ... and the limiter's held blocks change sides */
     L.ld_user = p->ld.out; L.ld_bytes = B.ld_floats * sizeof(float);
+    L.tp_user = p->tp.out; L.tp_bytes = B.tp_floats * sizeof(float);
+    if (p->tp.L) p->tp.armed = false;
     if (p->ld.hop) {
         if (p->ld.out_counts) for (uint32_t s = 0; s < B.n_streams; s++) p->ld.out_counts[s] = B.ld[s].n_out;
         p->ld.armed = false;

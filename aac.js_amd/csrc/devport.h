@@ -17,6 +17,7 @@
 #include "devport_emu.h"
 #include "devport_mfma_emu.h"
 #include "devport_limit_emu.h"
+#include "devport_truepeak_emu.h"
 #else
 
 #include <hip/hip_runtime.h>
@@ -287,6 +288,12 @@ DP_DEVICE unsigned dp_g_load_u32(const unsigned* p) { return __hip_atomic_load(p
 DP_DEVICE void dp_g_store_u32(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 /* a counter in global memory that lanes of any workgroup bump (the refresh's refusal count): atomicAdd as it is, the old value */
 DP_DEVICE unsigned dp_g_atomic_add_u32(unsigned* p, unsigned v) { return atomicAdd(p, v); }
+/* *p <- the larger of *p and v, unsigned, in global memory that lanes of any workgroup of the launch aim at (the true-peak records,
+ * aacg_pcm_truepeak.h: the bits of non-negative floats, whose order as integers is their order as values).  A VECTOR atomic without a
+ * return value, atomicMax as it is: device scope, carried out in the L2, in any order — a maximum commutes.  Nothing is read back in the
+ * launch: the next launch on the stream, or the one an event orders behind it, sees the result.  The CPU twin:
+ * tests/emu/devport_truepeak_emu.h. */
+DP_DEVICE void dp_g_atomic_max_u32(unsigned* p, unsigned v) { (void)atomicMax(p, v); }
 DP_DEVICE void dp_vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 /* lane 0's value in every lane (a 64-bit scalar) */
 DP_DEVICE dp_u64 dp_first_u64(dp_u64 v)

@@ -42,7 +42,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_set_features", "aacg_features_counts", "aacg_features_design",
                "aacg_pipeline_set_loudness", "aacg_pipeline_loudness_out", "aacg_pipeline_loudness_counts", "aacg_loudness_counts",
                "aacg_loudness_design", "aacg_loudness_integrate",
-               "aacg_pipeline_set_limiter", "aacg_pipeline_set_gain", "aacg_pipeline_gain", "aacg_limiter_design"]
+               "aacg_pipeline_set_limiter", "aacg_pipeline_set_gain", "aacg_pipeline_gain", "aacg_limiter_design",
+               "aacg_pipeline_set_true_peak", "aacg_pipeline_true_peak_out", "aacg_true_peak_design"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -124,6 +125,11 @@ class LoudnessConfig(C.Structure):
 
 
 # aacg_limiter_config: the limiter's ceiling (full-scale units) and release (the share of the way back per block of 64 samples)
+# aacg_true_peak_config: the oversampling table's shape and the table (aacg_pipeline_set_true_peak)
+class TruePeakConfig(C.Structure):
+    _fields_ = [("phases", C.c_uint32), ("taps", C.c_uint32), ("table", C.c_void_p)]
+
+
 class LimiterConfig(C.Structure):
     _fields_ = [("ceiling", C.c_float), ("release", C.c_float)]
 
@@ -319,6 +325,9 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_set_gain.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
     L.aacg_pipeline_gain.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
     L.aacg_limiter_design.argtypes = [C.c_uint32, C.c_double, C.c_double, C.POINTER(LimiterConfig)]
+    L.aacg_pipeline_set_true_peak.argtypes = [C.c_void_p, C.POINTER(TruePeakConfig)]
+    L.aacg_pipeline_true_peak_out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.aacg_true_peak_design.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_size_t]
     _lib = L
     return L
 
@@ -525,11 +534,14 @@ class Pipeline:
     take_loudness gives a batch's records, a list of (n_out[s], in_channels, 2) float32 arrays of {energy, sample peak} per hop.
     limiter: a LimiterConfig or a (ceiling, release) pair for set_limiter (aacg_pipeline_set_limiter; limiter_design makes one from dB and
     milliseconds).  A stage behind the mix and in front of the resampler: every stream's PCM is scaled by its slot's gain (set_gain, 1
-    until set) and held below the ceiling, all channels alike, delayed by 64 samples; shapes and counts are what they are without it."""
+    until set) and held below the ceiling, all channels alike, delayed by 64 samples; shapes and counts are what they are without it.
+    true_peak: a dict for set_true_peak (aacg_pipeline_set_true_peak; true_peak_design makes the usual table) — phases, taps and table
+    (phases, taps) —, on a pipeline with loudness: the oversampled peak of every hop of the meter, beside its records;
+    take_true_peak gives a batch's, a list of (n_out[s], in_channels) float32 arrays.  Every other call returns what it returns without it."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None):
+                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None, true_peak=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -548,6 +560,7 @@ class Pipeline:
         self.features = None
         self.loudness, self._loud, self._loud_last = None, {}, None
         self.limiter = None
+        self.true_peak, self._tp, self._tp_last, self._tp_armed = None, {}, None, None
         self._keep = {}
         if mix is not None:
             m = np.ascontiguousarray(mix, np.float32)
@@ -586,6 +599,12 @@ class Pipeline:
         if loudness is not None:
             try:
                 self.set_loudness(**loudness)
+            except (AacgError, ValueError, TypeError):
+                self.close()
+                raise
+        if true_peak is not None:
+            try:
+                self.set_true_peak(**true_peak)
             except (AacgError, ValueError, TypeError):
                 self.close()
                 raise
@@ -679,6 +698,16 @@ class Pipeline:
             raise AacgError(rc, "aacg_pipeline_gain(slot %d): no limiter, or no such slot" % int(slot))
         return float(g.value)
 
+    def set_true_peak(self, phases, taps, table):
+        """aacg_pipeline_set_true_peak: the oversampled peak per hop of the meter with the polyphase table (phases, taps), on a pipeline
+        with a meter, before the first batch"""
+        h = np.ascontiguousarray(table, np.float32)
+        if h.shape != (int(phases), int(taps)):
+            raise ValueError("Pipeline: the true-peak table is not a (phases, taps) matrix")
+        cfg = TruePeakConfig(int(phases), int(taps), h.ctypes.data)
+        self._check(self.lib.aacg_pipeline_set_true_peak(self.handle, C.byref(cfg)))
+        self.true_peak = {"phases": int(phases), "taps": int(taps), "table": h}
+
     def loudness_counts(self, slots, frames_per_stream):
         """aacg_pipeline_loudness_counts: the records per channel that the NEXT batch of these slots with these counts emits, per stream"""
         slots = np.ascontiguousarray(slots, np.uint32)
@@ -695,6 +724,11 @@ class Pipeline:
         n = self.loudness_counts(slots, frames_per_stream)
         rec = np.zeros(int(n.sum()) * self.in_channels * 2, np.float32)
         self._check(self.lib.aacg_pipeline_loudness_out(self.handle, rec.ctypes.data, rec.size, n.ctypes.data))
+        self._tp_armed = None
+        if self.true_peak:                               # ... and for its true-peak floats, a float where the meter has two
+            tp = np.zeros(int(n.sum()) * self.in_channels, np.float32)
+            self._check(self.lib.aacg_pipeline_true_peak_out(self.handle, tp.ctypes.data, tp.size))
+            self._tp_armed = (tp, n)
         return rec, n
 
     def take_loudness(self, ticket=None):
@@ -711,6 +745,21 @@ class Pipeline:
         rec, n = held
         ends = np.cumsum(n.astype(np.int64))
         return [rec[(e - k) * self.in_channels * 2:e * self.in_channels * 2].reshape(int(k), self.in_channels, 2) for e, k in zip(ends, n.astype(np.int64))]
+
+    def take_true_peak(self, ticket=None):
+        """The true-peak records of a batch: a list with one (n_out[s], in_channels) float32 array per stream, a float per hop of the
+        meter.  ticket: a submitted batch's, which is finished first if it is still in flight (collect still returns its PCM and
+        take_loudness its records, in any order); None: the batch of the last decode."""
+        if ticket is None:
+            held = self._tp_last
+        else:
+            self._check(self.lib.aacg_pipeline_collect(self.handle, ticket))
+            held = self._tp.pop(ticket, None)
+        if held is None:
+            raise ValueError("Pipeline.take_true_peak: no records are held for that batch (no true-peak stage, or taken already)")
+        tp, n = held
+        ends = np.cumsum(n.astype(np.int64))
+        return [tp[(e - k) * self.in_channels:e * self.in_channels].reshape(int(k), self.in_channels) for e, k in zip(ends, n.astype(np.int64))]
 
     def out_samples(self, slots, frames_per_stream):
         """aacg_pipeline_out_samples: the samples per channel that the NEXT batch of these slots with these counts emits, per stream —
@@ -775,6 +824,7 @@ class Pipeline:
         sequence of per-stream counts (aacg_pipeline_decode_ragged): frames, PCM and results are then packed stream after stream."""
         data, frames, slots, counts, pcm, res, refused = self._args(data, frames, slots, frames_per_stream, pcm)
         self._loud_last = self._arm_loudness(slots, frames_per_stream)
+        self._tp_last = self._tp_armed
         if counts is None:
             self._check(self.lib.aacg_pipeline_decode(self.handle, data.ctypes.data, data.size, frames.ctypes.data, slots.ctypes.data, len(slots),
                                                       frames_per_stream, pcm.ctypes.data, res.ctypes.data, C.byref(refused)))
@@ -797,6 +847,8 @@ class Pipeline:
         self._keep[t.value] = (pcm, res, refused) + ((self._lengths,) if self._ragged else ())
         if loud is not None:
             self._loud[t.value] = loud
+        if self._tp_armed is not None:
+            self._tp[t.value] = self._tp_armed
         return t.value
 
     def collect(self, ticket):
@@ -850,6 +902,8 @@ class Pipeline:
         self._keep[t.value] = (out, res, refused) + ((lengths,) if lengths is not None else ())
         if loud is not None:
             self._loud[t.value] = self._loud_last = loud
+        if self._tp_armed is not None:
+            self._tp[t.value] = self._tp_last = self._tp_armed
         return t.value
 
     def wait_device(self, ticket, stream=None):
@@ -920,6 +974,17 @@ def loudness_design(rate, hop=None):
     if rc != 0:
         raise AacgError(rc, "aacg_loudness_design(%d Hz)" % rate)
     return {"hop": int(rate) // 10 if hop is None else int(hop), "coeffs": k}
+
+
+def true_peak_design(phases=4, taps=24, rolloff=0.95, beta=5.0):
+    """aacg_true_peak_design: a dict for Pipeline(true_peak=...) with the oversampling table (phases, taps) float32 — the resampler's
+    default design for 1 -> phases; host code, no device.  The defaults read sines up to 20 kHz at 48 kHz within EBU Tech 3341's
+    tolerance."""
+    table = np.zeros((int(phases), int(taps)), np.float32)
+    rc = load_library().aacg_true_peak_design(int(phases), int(taps), float(rolloff), float(beta), table.ctypes.data, table.size)
+    if rc != 0:
+        raise AacgError(rc, "aacg_true_peak_design(%d phases of %d taps)" % (phases, taps))
+    return {"phases": int(phases), "taps": int(taps), "table": table}
 
 
 def limiter_design(rate, ceiling_db=-1.0, release_ms=200.0):

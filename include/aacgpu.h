@@ -1009,7 +1009,7 @@ int  aacg_features_design(uint32_t rate, uint32_t frame_length, uint32_t hop, ui
  * pipeline exactly as it was: a null config, a hop outside 1..2^20, a coefficient that is not finite, a call after the first batch, a
  * second call; and a pipeline beyond the meter's limits — max_streams x (max_frames x 1024 / hop + 1) x channels of 2^27 records or
  * more, max_streams x max_frames frames of PCM of 64 GiB or more.  AACG_ERR_OUT_OF_MEMORY: no device memory for the slots' state and the lanes' records; the pipeline stays as it was.
- * Not here: true (oversampled) peak, short-term windows and loudness range, a meter behind the mix or the resampler. */
+ * Not here: short-term windows and loudness range, a meter behind the mix or the resampler.  True (oversampled) peak: aacg_pipeline_set_true_peak, below. */
 typedef struct aacg_loudness_config {
     uint32_t hop;
     float    coeffs[2][5];
@@ -1044,6 +1044,59 @@ int  aacg_loudness_design(uint32_t rate, float coeffs[2][5]);
  * loudness every 100 ms).  AACG_ERR_INVALID_ARG: null records with hops, a null integrated_lufs, channels outside 1..8, a hop outside 1..2^20. */
 int  aacg_loudness_integrate(const float* records, size_t n_hops, uint32_t channels, uint32_t hop, const double* weights,
                              double* integrated_lufs, double* momentary_lufs);
+/* True peak on the device, the third member of the R 128 triplet beside the meter's energy and sample peak: the largest magnitude of
+ * the signal OVERSAMPLED by a polyphase FIR, one float per hop and channel, for a consumer whose ceiling is stated in dBTP.  It is set on
+ * a pipeline that already has a meter (aacg_pipeline_set_loudness) and shares the meter's input, hop, counts and clock.
+ *     phases L: 1..8;  taps T: a multiple of 4 in 4..64;  table: h[L][T], row-major float32, every entry finite (aacg_true_peak_design
+ *     makes the usual one).
+ * The input x of channel c of a slot is exactly the meter's: the sample the transform delivers, BEFORE the mix, the limiter, the
+ * resampler and the feature stage, in all `channels` channels by position; on an AACG_OUTPUT_I16 pipeline the already rounded int16
+ * times 2^-15 (exact); a refused frame and a frame of an unlearnt stream are 1024 zeros that advance the clock; x[j] = 0 for j < 0 since
+ * the slot's reset.
+ * THE RULE, bit for bit, in float32 throughout.  For input index i and phase p = 0 .. L-1,
+ *     acc = h[p][0] * x[i]                             (rounded to float)
+ *     acc = acc + (h[p][t] * x[i - t])   t = 1 .. T-1   (the product rounded, then the sum rounded: NOT fused, in this order)
+ * every term computed whatever its coefficient, subnormals kept: aacg_pipeline_set_resample's rule with M = 1.  tp of hop k is the
+ * largest |acc| over i in [k hop, (k + 1) hop) and all L phases — a NaN if any of those acc is a NaN (which NaN is not defined).  A
+ * maximum does not depend on order, so nothing in the result depends on how the device splits the work.  numpy float32 arithmetic
+ * reproduces the result exactly.
+ * One float per hop and channel leaves whenever the meter emits a record: the same counts (aacg_pipeline_loudness_counts), the same
+ * clock, hop `hop` of the meter.  Any split of a stream's frames into batches gives the same bits.  A reset (aacg_pipeline_reset_stream)
+ * zeroes the history and the partial maximum.
+ * The filter is causal: a hop's tp sees the signal (L T - 1) / (2 L) samples LATE, the group delay of a linear-phase table, so a peak
+ * in a hop's last samples is reported by the next hop.  Phase 0 is NOT the identity — a designed table has no phase that passes the
+ * samples through — so tp may lie a little below the hop's sample peak where a sample sits on a crest: a consumer takes
+ * max(peak, tp) of the meter's record and this one.
+ * Records of a submission: packed [stream s][n_out[s]][channels] float32, n_out the meter's count, in HOST memory that the caller names
+ * with aacg_pipeline_true_peak_out before every submission; they are there when the submission's ticket has been collected.
+ * State per slot: the last T - 1 input samples and the partial maximum per channel on the device, handed from batch to batch across
+ * lanes as the resampler's history.  One more launch per batch (aacg_pcm_truepeak_*) on the lane's stream beside the meter's, in front
+ * of it a clear of the batch's records; it goes with everything the meter goes with.  With no true-peak stage set nothing differs, call
+ * for call.
+ * Called once, before the pipeline's first submitted batch, on a pipeline with a meter.  AACG_ERR_INVALID_ARG, with the reason in
+ * aacg_pipeline_last_error and the pipeline exactly as it was: no meter, a null config or table, phases or taps outside the limits, an
+ * entry that is not finite, a call after the first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the table, the
+ * slots' state and the lanes' records; the pipeline stays as it was.
+ * Not here: short-term windows, a true peak behind the mix or the limiter, a table of more than 8 phases. */
+typedef struct aacg_true_peak_config {
+    uint32_t phases;         /* L */
+    uint32_t taps;           /* T */
+    const float* table;      /* [phases][taps] */
+} aacg_true_peak_config;
+int  aacg_pipeline_set_true_peak(aacg_pipeline* p, const aacg_true_peak_config* cfg);
+/* Where the NEXT enqueued submission's true-peak records go: `peaks`, host memory with room for capacity_floats floats, valid until
+ * that submission's ticket has been collected (the records are written at the collect).  One call arms one submission, as
+ * aacg_pipeline_loudness_out does for the meter's.  A submission on a pipeline with the stage and no destination named is refused with
+ * AACG_ERR_INVALID_ARG, one whose destination is smaller than the sum of n_out[s] x channels floats with AACG_ERR_CAPACITY — behind the
+ * meter's own two refusals, which come first: nothing is enqueued, no ticket is taken, no clock moves, and both destinations stay
+ * armed.  AACG_ERR_INVALID_ARG: a pipeline without the stage, null peaks with a capacity above 0. */
+int  aacg_pipeline_true_peak_out(aacg_pipeline* p, float* peaks, size_t capacity_floats);
+/* The project's default table for aacg_pipeline_set_true_peak, host code only: float for float the table that
+ * aacg_resample_design(1, phases, taps, rolloff, beta, ...) writes — a Kaiser-windowed sinc with its cutoff at rolloff x the input's
+ * Nyquist, every phase row of sum 1 — with the same defaults for 0 (rolloff 0.95, beta 9) and the same refusals, and phases and taps
+ * within aacg_pipeline_set_true_peak's limits.  `table` has room for `capacity` floats, at least phases x taps.  Four phases of 24 taps
+ * with beta 5 read a sine of any frequency up to 20 kHz at 48 kHz within +0.2 / -0.4 dB (EBU Tech 3341's tolerance). */
+int  aacg_true_peak_design(uint32_t phases, uint32_t taps, double rolloff, double beta, float* table, size_t capacity);
 
 /* A gain per stream and a look-ahead limiter on the device: a STAGE of the way out, BEHIND the mix and IN FRONT of the resampler and the
  * feature stage, for a consumer that has a gain for a stream (from the meter above, from ReplayGain tags) and wants it applied, with

@@ -7,12 +7,17 @@
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
- *                                         [--loudness] [--limiter]
+ *                                         [--loudness [--true-peak]] [--limiter]
  *
  * --limiter: a gain per stream and a look-ahead limiter behind the mix and in front of the resampler (aacg_limiter_design at the file's
  * rate with a ceiling of -1 dB and a release of 200 ms; aacg_pipeline_set_limiter; slot s gets the gain 0.5 + 0.5 (s mod 8) through
  * aacg_pipeline_set_gain, so that some streams are boosted into the ceiling): one more launch per batch (aacg_pcm_limit_*).  The line
  * then carries the two settings and the bytes that launch reads and writes.  Combines with everything else.
+ *
+ * --true-peak (with --loudness): the oversampled peak of every hop of the meter beside its records (aacg_true_peak_design's four phases
+ * of 24 taps with beta 5; aacg_pipeline_set_true_peak): one more launch per batch (aacg_pcm_truepeak_*) over the transform's PCM, and a
+ * float per hop and channel comes down with the meter's records into a buffer named before every submission
+ * (aacg_pipeline_true_peak_out).  The line then carries the table's shape.
  *
  * --loudness: a loudness meter beside whatever leaves (aacg_loudness_design at the file's rate, BS.1770's K-weighting, with a hop of a
  * tenth of a second; aacg_pipeline_set_loudness): one more launch per batch (aacg_pcm_loudness_*) over the transform's PCM, and two floats
@@ -81,7 +86,7 @@ int main(int argc, char** argv)
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     uint32_t mix = 0, rate = 0;
-    bool features = false, loudness = false, limiter = false;
+    bool features = false, loudness = false, limiter = false, true_peak = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -104,6 +109,7 @@ int main(int argc, char** argv)
         else if (a == "--rate") rate = (uint32_t)std::atoi(val());
         else if (a == "--features") features = true;
         else if (a == "--loudness") loudness = true;
+        else if (a == "--true-peak") true_peak = true;
         else if (a == "--limiter") limiter = true;
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -192,9 +198,19 @@ int main(int argc, char** argv)
     const size_t resample_in_bytes = (size_t)S * F * 1024 * out_channels * (i16 ? 2 : 4);
     const int n_out = 4;
     void* out[n_out];
+    const uint32_t tp_L = 4, tp_T = 24;
+    if (true_peak) {
+        if (!loudness) { std::fprintf(stderr, "--true-peak requires --loudness\n"); return 2; }
+        std::vector<float> table((size_t)tp_L * tp_T);
+        if ((rc = aacg_true_peak_design(tp_L, tp_T, 0.95, 5.0, table.data(), table.size()))) { std::fprintf(stderr, "aacg_true_peak_design: %d\n", rc); return 2; }
+        const aacg_true_peak_config tc = {tp_L, tp_T, table.data()};
+        if ((rc = aacg_pipeline_set_true_peak(p, &tc))) { std::fprintf(stderr, "aacg_pipeline_set_true_peak: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
     /* --loudness: the most records a batch emits (a stream of F frames completes at most F x 1024 / hop + 1 hops), per PCM buffer */
     const size_t ld_most = loudness ? (size_t)S * ((size_t)F * 1024 / ld_hop + 1) : 0, ld_floats = ld_most * channels * 2;
     std::vector<std::vector<float>> ld_rec((size_t)n_out, std::vector<float>(ld_floats));
+    const size_t tp_floats = true_peak ? ld_most * channels : 0;      /* --true-peak: a float where the meter has two */
+    std::vector<std::vector<float>> tp_rec((size_t)n_out, std::vector<float>(tp_floats));
     for (auto& o : out) { o = pageable ? std::malloc(pcm_bytes) : aacg_host_alloc(pcm_bytes); if (!o) { std::fprintf(stderr, "allocation failed\n"); return 2; } std::memset(o, 0, pcm_bytes); }
     /* --device-pcm: a device buffer per lane (a batch in flight keeps its own until it is collected); planar rows of F frames */
     const int n_dev = device_pcm ? (sync ? 1 : lanes) : 0;
@@ -217,6 +233,7 @@ int main(int argc, char** argv)
             if (b < n) {
                 const int k = b % n_out;
                 if (loudness && (rc = aacg_pipeline_loudness_out(p, ld_rec[(size_t)k].data(), ld_floats, nullptr))) fail("aacg_pipeline_loudness_out", rc);
+                if (true_peak && (rc = aacg_pipeline_true_peak_out(p, tp_rec[(size_t)k].data(), tp_floats))) fail("aacg_pipeline_true_peak_out", rc);
                 aacg_pcm_device_out where;
                 if (device_pcm) { where.d_pcm = dev[(size_t)(b % n_dev)]; where.d_pcm_bytes = pcm_bytes; where.layout = planar ? AACG_PCM_PLANAR : AACG_PCM_PACKED; where.stride_frames = planar ? stride_frames : 0u; }
                 if (new_shapes) {
@@ -292,10 +309,15 @@ int main(int argc, char** argv)
     if (mix) std::snprintf(mix_key, sizeof mix_key, "\"mix_out_channels\": %u, \"unmixed_pcm_bytes_per_batch\": %zu, \"d2d_copy_of_unmixed_pcm_us\": %.2f, ", out_channels, unmixed_bytes, unmixed_copy_us);
     char rate_key[192] = "";                                /* --rate only */
     if (rate) std::snprintf(rate_key, sizeof rate_key, "\"rate_out\": %u, \"resample_L\": %u, \"resample_M\": %u, \"resample_taps\": 32, \"resample_in_bytes_per_batch\": %zu, \"d2d_copy_of_resample_in_us\": %.2f, ", rate, rs_L, rs_M, resample_in_bytes, resample_in_copy_us);
-    char loudness_key[160] = "";                            /* --loudness only */
+    char loudness_key[288] = "";                            /* --loudness only, and behind it --true-peak's */
     if (loudness) {
         for (float v : ld_rec[0]) finite = finite && std::isfinite(v);
-        std::snprintf(loudness_key, sizeof loudness_key, "\"loudness\": \"bs1770\", \"loudness_hop\": %u, \"loudness_records_per_batch_most\": %zu, ", ld_hop, ld_most);
+        int at = std::snprintf(loudness_key, sizeof loudness_key, "\"loudness\": \"bs1770\", \"loudness_hop\": %u, \"loudness_records_per_batch_most\": %zu, ", ld_hop, ld_most);
+        if (true_peak) {
+            float largest = 0.0f;
+            for (float v : tp_rec[0]) { finite = finite && std::isfinite(v); largest = v > largest ? v : largest; }
+            std::snprintf(loudness_key + at, sizeof loudness_key - (size_t)at, "\"true_peak\": \"kaiser\", \"true_peak_phases\": %u, \"true_peak_taps\": %u, \"true_peak_largest\": %.6g, ", tp_L, tp_T, largest);
+        }
     }
     char limiter_key[192] = "";                             /* --limiter only: what aacg_pcm_limit_* reads and writes is 2 n Oc 1024 E */
     if (limiter) std::snprintf(limiter_key, sizeof limiter_key, "\"limiter\": \"-1 dB, 200 ms\", \"limiter_ceiling\": %.6f, \"limiter_release\": %.6g, \"limiter_bytes_moved_per_batch\": %zu, ",
