@@ -27,6 +27,7 @@
 #include "aacg_routes.h"
 #include "aacg_plan_shape.h"
 #include "aacg_shape_carry.h"
+#include "aacg_units_conceal.h"
 #include "aacg_tns_prep.h"
 #include "aacg_wait.h"
 
@@ -42,6 +43,8 @@ void aacg_refresh_launch(aacg_dev_unit* units, const aacg_unit_desc* parsed, aac
 void aacg_shape_launch(const aacg_shape_args& A, hipStream_t s);
 /* aacg_engine_carry.hip: window_shape_prev of a set's refreshed records, from frame to frame and batch to batch (aacg_shape_carry.h) */
 void aacg_carry_launch(const aacg_carry_args& A, hipStream_t s);
+/* aacg_engine_conceal.hip: a refused frame's records replaced by its stream's last good frame, faded (aacg_units_conceal.h) */
+void aacg_conceal_launch(const aacg_conceal_args& A, hipStream_t s);
 /* aacg_engine_spectral.hip: the optional stages (AACG_PNS_SPEC noise bands, AACG_TNS_SPEC filters) -> f32 spectra */
 int aacg_spectral_ex_set_lds_limits(void);
 void aacg_spectral_ex_launch(bool quant, int n_units, hipStream_t s, const aacg_kparams& P);
@@ -113,6 +116,7 @@ struct aacg_engine {
     uint32_t* d_wshape = nullptr;           /* [max_streams][max_channels] entries (before | after << 1 | serial << 2) */
     hipEvent_t carried = nullptr;           /* behind the most recent carry launch: the next one's stream waits for it */
     bool carried_any = false;
+    hipEvent_t concealed = nullptr;         /* behind the most recent conceal launch (aacg_plan_conceal_refused; made at the first): the next one's stream waits for it */
     uint32_t carry_serial = 0;              /* of the most recent carry launch */
     bool carry_open = false;                /* no launch has taken that carry's records yet: a carry now repeats its batch (same serial) */
     aacg_tables h_tab;
@@ -823,6 +827,7 @@ void aacg_destroy(aacg_engine* e)
     if (e->d_overlap) (void)hipFree(e->d_overlap);
     if (e->d_wshape) (void)hipFree(e->d_wshape);
     if (e->carried) (void)hipEventDestroy(e->carried);
+    if (e->concealed) (void)hipEventDestroy(e->concealed);
     for (auto& sl : e->slot) {
         for (void* p : sl.b.p) if (p) (void)hipFree(p);
         for (void* p : {sl.d_coeffs, sl.d_meta, sl.d_pcm}) if (p) (void)hipFree(p);
@@ -1634,6 +1639,51 @@ int aacg_plan_carry_window_shape(aacg_engine* e, aacg_plan* p, const aacg_refres
     HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
     HIP_TRY(e, hipEventRecord(e->carried, s), AACG_ERR_NO_DEVICE);
     e->carried_any = true;
+    return AACG_OK;
+}
+
+/* a refused frame's records replaced by its stream's last good frame, faded, behind the refresh on the same stream (aacg_units_conceal.h) */
+size_t aacg_conceal_state_bytes(uint32_t n_slots, uint32_t parse_channels)
+{
+    return parse_channels >= 1u && parse_channels <= AACG_MAX_CHANNELS ? (size_t)n_slots * 2u * AACG_CONCEAL_SIDE_BYTES(parse_channels) : 0;
+}
+
+int aacg_plan_conceal_refused(aacg_engine* e, aacg_plan* p, uint32_t set, aacg_parse_result* d_results, int16_t* d_q, aacg_band_meta* d_meta,
+                              uint32_t parse_channels, const aacg_conceal_stream* d_streams, uint32_t n_streams, uint32_t longest,
+                              void* d_state, uint32_t n_slots, uint32_t fade_steps, uint32_t hold_frames, void* hip_stream)
+{
+    if (!e || !p || p->e != e || !d_results || !d_q || !d_meta || !d_streams || !d_state || set >= p->unit_sets) return AACG_ERR_INVALID_ARG;
+    if (e->cfg.input_kind != AACG_INPUT_QUANT_I16) { e->err = "aacg_plan_conceal_refused needs a QUANT_I16 engine"; return AACG_ERR_INVALID_ARG; }
+    if (e->cfg.tns_mode == AACG_TNS_SPEC || e->cfg.pns_mode == AACG_PNS_SPEC) {
+        e->err = "aacg_plan_conceal_refused: not on an engine with AACG_TNS_SPEC or AACG_PNS_SPEC (the TNS records of a repeated frame and repeated noise bands are not served)";
+        return AACG_ERR_UNSUPPORTED;
+    }
+    if (!p->sh) {
+        e->err = "aacg_plan_conceal_refused: a shaped plan only (aacg_plan_create_shaped) — a kept plan's refresh may be repeated when the plan has gone stale, and the stage is not idempotent";
+        return AACG_ERR_UNSUPPORTED;
+    }
+    if (!p->sh->ready || set != p->cur_set) { e->err = "aacg_plan_conceal_refused: a shaped plan conceals in the set shaped and refreshed last"; return AACG_ERR_INVALID_ARG; }
+    if (fade_steps > 64u || hold_frames < 1u || hold_frames > 255u) { e->err = "aacg_plan_conceal_refused: fade_steps is not in 0..64 or hold_frames not in 1..255"; return AACG_ERR_INVALID_ARG; }
+    if (parse_channels < 1u || parse_channels > AACG_MAX_CHANNELS || ((uintptr_t)d_state & 15u) || ((uintptr_t)d_q & 15u) || ((uintptr_t)d_meta & 15u)) {
+        e->err = "aacg_plan_conceal_refused: parse_channels is not in 1..8, or d_state, d_q or d_meta is not 16-byte aligned"; return AACG_ERR_INVALID_ARG;
+    }
+    if ((uint64_t)n_streams * longest * parse_channels > 0x7fffffffull) { e->err = "aacg_plan_conceal_refused: more jobs than a launch indexes"; return AACG_ERR_CAPACITY; }
+    if (!n_streams || !longest || !p->sh->set_units[set]) return AACG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : e->stream;
+    note_stream(e, s);
+    /* behind the conceal launch before it, whatever stream that took: it reads the side that one wrote (the wait stands behind this
+     * stream's own parse and refresh) */
+    if (e->concealed) HIP_TRY(e, hipStreamWaitEvent(s, e->concealed, 0), AACG_ERR_NO_DEVICE);
+    else HIP_TRY(e, hipEventCreateWithFlags(&e->concealed, hipEventDisableTiming), AACG_ERR_NO_DEVICE);
+    aacg_conceal_args A;
+    std::memset(&A, 0, sizeof A);
+    A.units = p->b.units() + (size_t)set * p->unit_stride(); A.results = d_results; A.q = d_q; A.meta = d_meta; A.tab = d_streams;
+    A.state = (unsigned char*)d_state; A.n_streams = n_streams; A.longest = longest; A.Cp = parse_channels; A.n_slots = n_slots;
+    A.fade_steps = fade_steps; A.hold_frames = hold_frames;
+    aacg_conceal_launch(A, s);
+    HIP_TRY(e, hipGetLastError(), AACG_ERR_NO_DEVICE);
+    HIP_TRY(e, hipEventRecord(e->concealed, s), AACG_ERR_NO_DEVICE);
     return AACG_OK;
 }
 

@@ -36,6 +36,10 @@
  * makes the batch's TNS records behind the parse, and the plans are plans for aacg_decode_pipelined_stages, which takes those records
  * as a launch input.  AACG_PIPELINE_STAGE_WINDOW_SHAPE: one launch of aacg_plan_carry_window_shape behind every refresh sets
  * window_shape_prev of the batch's unit records from the frame before and, across batches, from the engine's per-channel state.
+ * aacg_pipeline_set_concealment (plan mode 1): one launch of aacg_plan_conceal_refused between the two replaces a refused frame's records by
+ * its stream's last good frame, faded; the slots' state — that frame's records, two sides per slot — passes from batch to batch
+ * like the resampler's history, its parities advance when a batch has been enqueued, and the per-stream records travel up in the
+ * lane's staging block behind the limiter's.
  *
  * THE WAY OUT is a chain: transform -> mix (aacg_pipeline_set_mix: O = 1 or 2 channels leave in the place of C) -> limit
  * (aacg_pipeline_set_limiter: a gain per stream and a look-ahead limiter, sample for sample, state per slot like the resampler's) -> resample
@@ -53,7 +57,7 @@
  * of state — a clock, kept here in 64 bits, and on the device the last K - 1 samples — and is ordered and advanced in the same way.
  *
  * On a lane's stream, in this order: clear (unlearnt streams) -> copy up -> stale count -> parse -> TNS records -> map / shape ->
- * refresh -> carry -> fork -> transform -> join -> mix -> wait / limit / record -> wait / resample / record -> wait / features / record -> planar or copy down -> results copy -> `done`.
+ * refresh -> conceal -> carry -> fork -> transform -> join -> mix -> wait / limit / record -> wait / resample / record -> wait / features / record -> planar or copy down -> results copy -> `done`.
  *
  * Host code apart from two small kernels (aacg_pipe_copy, aacg_pipe_map); it uses nothing but the public ABI of parser and engine
  * (and aacg_pipe_map.h / aacg_plan_shape.h / aacg_pcm_planar.h / aacg_pcm_mix.h / aacg_pcm_resample.h / aacg_pcm_features.h / aacg_pcm_limit.h for the tables it fills and the
@@ -199,6 +203,16 @@ struct aacg_pipeline {
         std::vector<float> gain; std::vector<uint8_t> parity, fresh;
         hipEvent_t last = nullptr;
     } lim;
+    /* aacg_pipeline_set_concealment: the two settings (on: the stage is set), the slots' state on the device ([slot][2] sides, aacg_conceal_state_bytes),
+     * and per slot what the host keeps: which side the slot's next batch reads, and whether it has been through a batch since its reset.
+     * total: the concealed frames of collected batches */
+    struct conceal_t {
+        bool on = false;
+        uint32_t fade_steps = 0, hold_frames = 0;
+        void* d_state = nullptr;
+        std::vector<uint8_t> parity, fresh;
+        uint64_t total = 0;
+    } cn;
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -393,6 +407,8 @@ struct batch_t {
     size_t tp_floats;                            /* check_batch: ... and its true-peak records, 0 without the stage */
     std::vector<aacg_limit_stream> lim;          /* check_batch, a limiter: the batch's records, with the slots' gains as they stand */
     size_t lim_at;                               /* stage_batch: where those lie, behind the meter's */
+    std::vector<aacg_conceal_stream> cn;         /* check_batch, concealment: the batch's records, with the slots' sides as they stand */
+    size_t cn_at;                                /* stage_batch: where those lie, behind the limiter's */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
@@ -450,6 +466,7 @@ int finish_lane(aacg_pipeline* p, aacg_pipeline::lane_t& L)
     uint32_t* refused = (uint32_t*)((char*)L.h_res + p->res_cap16);
     for (const auto& u : L.unlearnt)
         for (uint32_t f = 0; f < u.frames; f++) { aacg_parse_result& r = res[(size_t)u.first + f]; if (r.status == AACG_PARSE_OK) r.status = AACG_PARSE_LAYOUT; (*refused)++; }
+    if (p->cn.on) for (uint32_t i = 0; i < L.n; i++) p->cn.total += (res[i].flags & AACG_PARSE_CONCEALED) ? 1u : 0u;
     if (L.user_results) std::memcpy(L.user_results, res, (size_t)L.n * sizeof(aacg_parse_result));
     if (L.user_refused) std::memcpy(L.user_refused, refused, 4);
     L.busy = false;
@@ -621,7 +638,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         if (L.lim_done) (void)hipEventDestroy(L.lim_done);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
-    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state, p->tp.d_table, p->tp.d_state}) if (d) (void)hipFree(d);
+    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state, p->tp.d_table, p->tp.d_state, p->cn.d_state}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -899,6 +916,46 @@ int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
     return AACG_OK;
 }
 
+int aacg_pipeline_set_concealment(aacg_pipeline* p, const aacg_conceal_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (!cfg) { p->err = "aacg_pipeline_set_concealment: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (p->cn.on) { p->err = "aacg_pipeline_set_concealment: the pipeline conceals already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_concealment: a batch has been submitted (concealment is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (cfg->fade_steps > 64u) { p->err = "aacg_pipeline_set_concealment: fade_steps is not in 0..64"; return AACG_ERR_INVALID_ARG; }
+    if (cfg->hold_frames < 1u || cfg->hold_frames > 255u) { p->err = "aacg_pipeline_set_concealment: hold_frames is not in 1..255"; return AACG_ERR_INVALID_ARG; }
+    if (!p->shaped) {
+        p->err = "aacg_pipeline_set_concealment: plan_mode 0 — its retry of a stale plan would run the stage twice for one batch; plan_mode 1's shaped set is never stale";
+        return AACG_ERR_UNSUPPORTED;
+    }
+    if (p->spec_stages) {
+        p->err = "aacg_pipeline_set_concealment: not with AACG_PIPELINE_STAGE_TNS or AACG_PIPELINE_STAGE_PNS (the TNS records of a repeated frame and repeated noise bands are not served)";
+        return AACG_ERR_UNSUPPORTED;
+    }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    const size_t state_bytes = aacg_conceal_state_bytes((uint32_t)p->cfg.max_streams, p->Cp);
+    void* d_state = nullptr;
+    /* (cleared: a slot that has been through no batch is fresh and its side is not read, but the block is small and this is once) */
+    if (hipMalloc(&d_state, state_bytes) != hipSuccess || hipMemset(d_state, 0, state_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d_state) (void)hipFree(d_state);
+        p->err = "aacg_pipeline_set_concealment: no device memory for the slots' state";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    p->cn.d_state = d_state; p->cn.fade_steps = cfg->fade_steps; p->cn.hold_frames = cfg->hold_frames;
+    p->cn.parity.assign((size_t)p->cfg.max_streams, 0); p->cn.fresh.assign((size_t)p->cfg.max_streams, 1);
+    p->cn.on = true;
+    return AACG_OK;
+}
+
+int aacg_pipeline_concealed(const aacg_pipeline* p, uint64_t* count)
+{
+    if (!p || !count) return AACG_ERR_INVALID_ARG;
+    *count = p->cn.total;
+    return AACG_OK;
+}
+
 int aacg_pipeline_set_gain(aacg_pipeline* p, uint32_t slot, float gain)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
@@ -1044,6 +1101,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
     if (p->ft.K) { p->ft.N[slot] = 0; p->ft.fresh[slot] = 1; }       /* ... and the feature stage's */
     if (p->ld.hop) { p->ld.N[slot] = 0; p->ld.fresh[slot] = 1; }     /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
+    if (p->cn.on) p->cn.fresh[slot] = 1;                             /* ... and the last good frame: the slot's next batch starts with none */
     if (p->lim.on) p->lim.fresh[slot] = 1;                           /* ... and the limiter's held block and nodes; the slot's gain is the caller's and stays */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
@@ -1128,6 +1186,7 @@ int check_batch(aacg_pipeline* p, batch_t& B)
             B.lim[s] = {first, B.frames_of[s], slot, p->lim.parity[slot], p->lim.fresh[slot], p->lim.gain[slot], {0u, 0u}};
         }
     }
+    if (p->cn.on) B.cn.assign(B.n_streams, aacg_conceal_stream());      /* concealment: a record per stream, filled in with the plan's table (choose_plan) */
     B.X = aacg_pipe::exit_plan(exit_pipe(p), b);
     return B.pcm_out ? AACG_OK : check_device_out(p, B, b);
 }
@@ -1143,13 +1202,15 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     const size_t rs_bytes = B.rs.size() * sizeof(aacg_resample_stream), ft_bytes = B.ft.size() * sizeof(aacg_features_stream);
     const size_t ld_bytes = B.ld.size() * sizeof(aacg_loudness_stream);      /* (... and a meter's behind those) */
     const size_t lim_bytes = B.lim.size() * sizeof(aacg_limit_stream);      /* (... and a limiter's behind those: every record is 32 bytes) */
-    const size_t more = rs_bytes + ft_bytes + ld_bytes + lim_bytes;
+    const size_t cn_bytes = B.cn.size() * sizeof(aacg_conceal_stream);      /* (... and the concealment's behind those, 32 bytes too) */
+    const size_t more = rs_bytes + ft_bytes + ld_bytes + lim_bytes + cn_bytes;
     int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, more ? tab16 + more : tab_bytes, B.G);
     if (rc) return rc;
     B.rs_at = B.G.extra_at + tab16;
     B.ft_at = B.rs_at + rs_bytes;
     B.ld_at = B.ft_at + ft_bytes;
     B.lim_at = B.ld_at + ld_bytes;
+    B.cn_at = B.lim_at + lim_bytes;
     if (lim_bytes) std::memcpy((char*)L.h_in + B.lim_at, B.lim.data(), lim_bytes);
     if (ld_bytes) std::memcpy((char*)L.h_in + B.ld_at, B.ld.data(), ld_bytes);
     if (rs_bytes) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), rs_bytes);
@@ -1173,6 +1234,12 @@ int choose_plan(aacg_pipeline* p, const aacg_pipeline::lane_t& L, batch_t& B)
     aacg_pipe::shape_table(p->batch_layout.data(), B.slots, B.frames_of, B.n_streams, (aacg_shape_stream*)tab);
     int rc = aacg_plan_shape_table(p->engine, p->shaped, B.set, (aacg_shape_stream*)tab, B.n_streams, p->Cp, &n_units);
     B.plan = n_units ? p->shaped : nullptr;              /* (no stream of the batch has a layout yet: nothing to transform, as with kept plans) */
+    /* concealment: the stream's words of the table again, with the side of the slot's state this batch reads */
+    for (uint32_t s = 0; s < B.n_streams && !B.cn.empty(); s++) {
+        const aacg_shape_stream& t = ((const aacg_shape_stream*)tab)[s];
+        B.cn[s] = {t.frame_first, t.frames, t.unit_first, t.frame_units, t.slot, t.nch, (uint32_t)p->cn.parity[t.slot] | (p->cn.fresh[t.slot] ? 2u : 0u), 0u};
+    }
+    if (!B.cn.empty()) std::memcpy((char*)L.h_in + B.cn_at, B.cn.data(), B.cn.size() * sizeof(aacg_conceal_stream));
     return rc ? engine_fail(p, "aacg_plan_shape_table: ", rc) : AACG_OK;
 }
 
@@ -1221,6 +1288,12 @@ int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
                                              (const aacg_refresh_map*)L.d_map, B.set, (uint32_t*)L.d_refused, L.st);
         /* AACG_PIPELINE_STAGE_WINDOW_SHAPE: the refreshed shapes are final — each frame's first half takes the shape of the frame
          * before, a stream's first frame the one its previous batch left (a second attempt starts from where the first started) */
+        /* aacg_pipeline_set_concealment: a refused frame takes its stream's last good frame, faded — in front of the carry, so that the
+         * shape carried behind a concealed frame is that frame's */
+        if (rc == AACG_OK && p->cn.on)
+            rc = aacg_plan_conceal_refused(p->engine, B.plan, B.set, (aacg_parse_result*)L.d_res, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, p->Cp,
+                                           (const aacg_conceal_stream*)((const char*)L.d_bytes + B.cn_at), B.n_streams, B.longest, p->cn.d_state,
+                                           (uint32_t)p->cfg.max_streams, p->cn.fade_steps, p->cn.hold_frames, L.st);
         if (rc == AACG_OK && p->carry_shape) rc = aacg_plan_carry_window_shape(p->engine, B.plan, (const aacg_refresh_map*)L.d_map, B.set, L.st);
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
          * one shape are consecutive launches of one plan and overlap through the rendezvous cells */
@@ -1328,6 +1401,8 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     /* ... and the meter's; its destination is this batch's now, and the next submission names its own */
     for (const auto& r : B.ld) { p->ld.N[r.slot] += 1024ull * r.frames; p->ld.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->ld.fresh[r.slot] = 0; }
     for (const auto& r : B.lim) { p->lim.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->lim.fresh[r.slot] = 0; }      /* ... and the limiter's held blocks change sides */
+    /* ... and the last good frames: a stream with units has been through the launch, which wrote the other side of its slot's state */
+    if (B.plan) for (const auto& r : B.cn) if ((r.frame_units >> 8) & 0xffu) { p->cn.parity[r.slot] = (uint8_t)((r.state & 1u) ^ 1u); p->cn.fresh[r.slot] = 0; }
     L.ld_user = p->ld.out; L.ld_bytes = B.ld_floats * sizeof(float);
     L.tp_user = p->tp.out; L.tp_bytes = B.tp_floats * sizeof(float);
     if (p->tp.L) p->tp.armed = false;

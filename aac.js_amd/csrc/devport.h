@@ -18,6 +18,7 @@
 #include "devport_mfma_emu.h"
 #include "devport_limit_emu.h"
 #include "devport_truepeak_emu.h"
+#include "devport_conceal_emu.h"
 #else
 
 #include <hip/hip_runtime.h>
@@ -336,6 +337,13 @@ DP_DEVICE dp_su8 dp_sload8(const void* p, const void* also) { dp_su8 r; asm("s_l
 DP_DEVICE int dp_lds_atomic_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 DP_DEVICE bool dp_any(bool p) { return __any(p) != 0; }
+/* the lowest lane of the wave in which the predicate holds, in every lane; 64: in none (the conceal stage's look back over a stream's
+ * statuses: a ballot and a count of trailing zeros on the scalar unit.  The CPU twin: tests/emu/devport_conceal_emu.h) */
+DP_DEVICE unsigned dp_wave_first(bool p)
+{
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(p);
+    return m ? (unsigned)__builtin_ctzll(m) : 64u;
+}
 
 /* A set of lanes as a value: the wave's lane mask in a scalar register pair (what a compare produces anyway). */
 typedef unsigned long long dp_lanes;

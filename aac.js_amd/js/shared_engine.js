@@ -48,6 +48,12 @@
  * each frame's share of the output, 341 or 342 samples per channel for 1024 at 1 / 3 — a variable length; a decoder on the parsing
  * route is resampled on the host by the same rule (resample.js), bit for bit; format.sampleRate says the new rate either way.  A stream
  * that has the engine's rate already is left alone.
+ * { resident: true, ragged: true, devicePlans: true, conceal: true | { fadeSteps, holdFrames } } — a frame the device refuses (a cut
+ * packet, a bad scalefactor, a changed layout) repeats its stream's last good frame, fadeSteps scalefactor steps (1.5 dB; default 2)
+ * further down per lost frame, for at most holdFrames (default 6) frames in a row (aacg_pipeline_set_concealment: the frame's records
+ * are substituted on the device, in front of the transform).  readChunk() then delivers that frame's PCM instead of queueing the
+ * reference's Error, and stats.concealedFrames counts such frames; a refused frame that was not concealed — no good frame yet, or the
+ * run is longer than holdFrames — still throws.  The option needs devicePlans and throws at construction without it.
  * Replaces, per batch, what src/decoder.js:125-216 does per frame.
  */
 'use strict';
@@ -77,11 +83,19 @@ function SharedEngine(opts) {
     this.overlap = opts.overlap === undefined ? this.resident : !!opts.overlap;
     this.sampleRate = opts.sampleRate ? opts.sampleRate | 0 : 0;      // the rate every decoder delivers (resample.js); 0: its stream's
     this.downmix = opts.downmix || null;                  // 'stereo' | 'mono' | { outChannels, matrix }: what every decoder delivers (mix.js)
-    this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0, flushNs: 0n };   // flushNs: resident flushes, host side and native calls
+    /* resident, devicePlans: refused frames repeat the stream's last good frame, fading (aacg_pipeline_set_concealment) */
+    this.conceal = null;
+    if (opts.conceal) {
+        if (!this.resident || !this.devicePlans) throw new Error('SharedEngine: conceal needs { resident: true, devicePlans: true } (the stage runs on a plan shaped on the device)');
+        const c = opts.conceal === true ? {} : opts.conceal;
+        this.conceal = { fadeSteps: c.fadeSteps === undefined ? 2 : c.fadeSteps | 0, holdFrames: c.holdFrames === undefined ? 6 : c.holdFrames | 0 };
+    }
+    this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0, flushNs: 0n, concealedFrames: 0 };   // flushNs: resident flushes, host side and native calls
 }
 
 /* error codes the engine raises before it has launched anything (include/aacgpu.h): a batch refused with one of these has
  * advanced no stream, and may be retried in parts */
+const PARSE_CONCEALED = 0x8;                              // AACG_PARSE_CONCEALED: byte 3 (flags) of a frame's 8-byte result
 const BEFORE_LAUNCH = [-1, -4, -5, -6];                   // INVALID_ARG, CAPACITY, UNSUPPORTED, LAYOUT_CHANGE
 function refusedBeforeLaunch(err) {
     const m = /failed \((-?\d+)\)/.exec(String(err && err.message));
@@ -150,6 +164,7 @@ SharedEngine.prototype.attachResident = function (dec) {
                          stages: ((this.opts.tnsMode | 0) ? 1 : 0) | ((this.opts.pnsMode | 0) ? 2 : 0) | (this.opts.carryWindowShape ? 4 : 0) };
         if (dec.mix) create.mix = { outChannels: dec.mix.outChannels, matrix: dec.mix.matrix };      // mixed on the device: outChannels leave
         if (dec.resampleSpec) create.resample = dec.resampleSpec;      // resampled on the device, behind the mix: ragged PCM comes back
+        if (this.conceal) create.conceal = this.conceal;      // refused frames repeat the stream's last good frame on the device
         const pipeline = addon.pipelineCreate(create, rec.entries, rec.counts);
         /* channels: of the PCM that comes back — what sizes a flush's PCM and slices it into frames */
         g = { resident: true, resample: dec.resampleSpec, addon: addon, pipeline: pipeline, channels: dec.mix ? dec.mix.outChannels : cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
@@ -337,7 +352,9 @@ SharedEngine.prototype.deliverResident = function (g, b, out, failed) {
             for (let f = 0, i = b.first[s]; f < b.counts[s]; f++, i++) {
                 const n = rs.count(R.L, R.M, r.n0, 1024);
                 r.n0 = (r.n0 + 1024) % R.M;
-                if (refused && results[8 * i]) q.push(new Error(g.addon.parseStatusString(results[8 * i])));
+                const concealed = (results[8 * i + 3] & PARSE_CONCEALED) !== 0;
+                if (concealed) this.stats.concealedFrames++;
+                if (refused && results[8 * i] && !concealed) q.push(new Error(g.addon.parseStatusString(results[8 * i])));
                 else q.push(pcm.subarray(at * C, (at + n) * C));
                 at += n;
             }
@@ -351,7 +368,11 @@ SharedEngine.prototype.deliverResident = function (g, b, out, failed) {
             /* a frame the device refused: the reference's message for its status where the frame is reached (it was decoded as
              * silence: the stream goes on); a frame whose elements are not the ones its stream began with has a status of its own
              * (AACG_PARSE_LAYOUT, set where the plan's records are refreshed) */
-            if (refused && results[8 * i]) q.push(new Error(g.addon.parseStatusString(results[8 * i])));
+            /* ... unless the device concealed it (AACG_PARSE_CONCEALED in the result's flags): then its PCM is the stream's last good
+             * frame, faded, and is delivered */
+            const concealed = (results[8 * i + 3] & PARSE_CONCEALED) !== 0;
+            if (concealed) this.stats.concealedFrames++;
+            if (refused && results[8 * i] && !concealed) q.push(new Error(g.addon.parseStatusString(results[8 * i])));
             else q.push(pcm.subarray(i * per, (i + 1) * per));
         }
     }

@@ -68,6 +68,7 @@ static struct {
     int  (*pipeline_set_resample)(aacg_pipeline*, uint32_t, uint32_t, uint32_t, const float*);
     int  (*pipeline_out_samples)(aacg_pipeline*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*);
     int  (*resample_design)(uint32_t, uint32_t, uint32_t, double, double, uint32_t*, uint32_t*, float*, size_t);
+    int  (*pipeline_set_concealment)(aacg_pipeline*, const aacg_conceal_config*);
     void* (*host_alloc)(size_t);
     void (*host_free)(void*);
 } L;
@@ -110,6 +111,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_walk_submit, "aacg_pipeline_walk_submit"); SYM(pipeline_walk_collect, "aacg_pipeline_walk_collect");
     SYM(pipeline_set_mix, "aacg_pipeline_set_mix"); SYM(pipeline_out_channels, "aacg_pipeline_out_channels"); SYM(mix_standard, "aacg_mix_standard");
     SYM(pipeline_set_resample, "aacg_pipeline_set_resample"); SYM(pipeline_out_samples, "aacg_pipeline_out_samples"); SYM(resample_design, "aacg_resample_design");
+    SYM(pipeline_set_concealment, "aacg_pipeline_set_concealment");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
     return 1;
@@ -522,8 +524,10 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     free(b);
 }
 
-/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix, resample}, entries, counts) -> external
- * (resample: { L, M, taps, table: Float32Array(L * taps) } — aacg_pipeline_set_resample behind the mix, before the call returns: the PCM leaves
+/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix, resample, conceal}, entries, counts) -> external
+ * (conceal: { fadeSteps, holdFrames } — aacg_pipeline_set_concealment before the call returns, with planMode 1: a refused frame repeats its
+ * stream's last good frame, fading, and its result carries AACG_PARSE_CONCEALED in byte 3; a refused setting destroys the pipeline and throws;
+ * resample: { L, M, taps, table: Float32Array(L * taps) } — aacg_pipeline_set_resample behind the mix, before the call returns: the PCM leaves
  * at L / M times the streams' rate, ragged per stream (pipelineDecode's lengths); a refused resampler destroys the pipeline and throws;
  * mix: { outChannels: 1 | 2, matrix: Float32Array(outChannels * channels) } — aacg_pipeline_set_mix before the call returns: the PCM is
  * mixed on the device and outChannels channels leave; a refused mix destroys the pipeline and throws with the reason;
@@ -590,6 +594,20 @@ static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
                 snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_resample failed (%d): %.800s", rc, L.pipeline_last_error(p));
             if (msg[0]) { L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL; }
             resampled = 1;
+        }
+    }
+    {   /* conceal: { fadeSteps, holdFrames } — aacg_pipeline_set_concealment */
+        napi_value cn; bool has = false; napi_valuetype vt = napi_undefined;
+        if (napi_has_named_property(env, argv[0], "conceal", &has) == napi_ok && has && napi_get_named_property(env, argv[0], "conceal", &cn) == napi_ok &&
+            napi_typeof(env, cn, &vt) == napi_ok && vt == napi_object) {
+            const int32_t fs = get_i32(env, cn, "fadeSteps", 2), hf = get_i32(env, cn, "holdFrames", 6);
+            char msg[1024] = "";
+            aacg_conceal_config cc;
+            cc.fade_steps = (uint32_t)fs; cc.hold_frames = (uint32_t)hf;
+            if (fs < 0 || hf < 0) snprintf(msg, sizeof msg, "pipelineCreate: conceal is { fadeSteps: 0..64, holdFrames: 1..255 }");
+            else if ((rc = L.pipeline_set_concealment(p, &cc)))
+                snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_concealment failed (%d): %.800s", rc, L.pipeline_last_error(p));
+            if (msg[0]) { L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL; }
         }
     }
     handle_box* b = box_new(BOX_PIPELINE, p);

@@ -43,7 +43,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_set_loudness", "aacg_pipeline_loudness_out", "aacg_pipeline_loudness_counts", "aacg_loudness_counts",
                "aacg_loudness_design", "aacg_loudness_integrate",
                "aacg_pipeline_set_limiter", "aacg_pipeline_set_gain", "aacg_pipeline_gain", "aacg_limiter_design",
-               "aacg_pipeline_set_true_peak", "aacg_pipeline_true_peak_out", "aacg_true_peak_design"]
+               "aacg_pipeline_set_true_peak", "aacg_pipeline_true_peak_out", "aacg_true_peak_design",
+               "aacg_conceal_state_bytes", "aacg_plan_conceal_refused", "aacg_pipeline_set_concealment", "aacg_pipeline_concealed"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -132,6 +133,16 @@ class TruePeakConfig(C.Structure):
 
 class LimiterConfig(C.Structure):
     _fields_ = [("ceiling", C.c_float), ("release", C.c_float)]
+
+
+# aacg_conceal_config: how a refused frame repeats its stream's last good frame (aacg_pipeline_set_concealment)
+class ConcealConfig(C.Structure):
+    _fields_ = [("fade_steps", C.c_uint32), ("hold_frames", C.c_uint32)]
+
+
+CONCEAL_FADE_STEPS, CONCEAL_HOLD_FRAMES = 2, 6       # what conceal=True sets: 3 dB a lost frame, six frames in a row
+# aacg_conceal_stream: one stream of a batch as aacg_plan_conceal_refused takes it
+CONCEAL_STREAM_DTYPE = np.dtype([(n, "<u4") for n in ("frame_first", "frames", "unit_first", "frame_units", "slot", "nch", "state", "reserved")])
 
 
 LIMIT_BLOCK = 64                                     # AACG_LIMIT_BLOCK: samples of a limiter block, and its delay
@@ -324,6 +335,12 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_set_limiter.argtypes = [C.c_void_p, C.POINTER(LimiterConfig)]
     L.aacg_pipeline_set_gain.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
     L.aacg_pipeline_gain.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+    L.aacg_pipeline_set_concealment.argtypes = [C.c_void_p, C.POINTER(ConcealConfig)]
+    L.aacg_pipeline_concealed.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.aacg_conceal_state_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    L.aacg_conceal_state_bytes.restype = C.c_size_t
+    L.aacg_plan_conceal_refused.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.aacg_limiter_design.argtypes = [C.c_uint32, C.c_double, C.c_double, C.POINTER(LimiterConfig)]
     L.aacg_pipeline_set_true_peak.argtypes = [C.c_void_p, C.POINTER(TruePeakConfig)]
     L.aacg_pipeline_true_peak_out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -513,6 +530,7 @@ class Parser:
 
 REFRESH_MAP_DTYPE = np.dtype([("parsed_index", "<u4"), ("frame_units", "<u4")])
 PARSE_LAYOUT = 16          # AACG_PARSE_LAYOUT: a frame whose elements are not its stream's
+PARSE_CONCEALED = 0x8      # AACG_PARSE_CONCEALED in aacg_parse_result.flags: a refused frame that repeats its stream's last good frame, faded
 
 
 class Pipeline:
@@ -537,11 +555,15 @@ class Pipeline:
     until set) and held below the ceiling, all channels alike, delayed by 64 samples; shapes and counts are what they are without it.
     true_peak: a dict for set_true_peak (aacg_pipeline_set_true_peak; true_peak_design makes the usual table) — phases, taps and table
     (phases, taps) —, on a pipeline with loudness: the oversampled peak of every hop of the meter, beside its records;
-    take_true_peak gives a batch's, a list of (n_out[s], in_channels) float32 arrays.  Every other call returns what it returns without it."""
+    take_true_peak gives a batch's, a list of (n_out[s], in_channels) float32 arrays.  Every other call returns what it returns without it.
+    conceal: True, or a dict(fade_steps=, hold_frames=), for set_concealment (aacg_pipeline_set_concealment), with device_plans: a frame
+    the parser or the refresh refuses repeats its stream's last good frame, fading, instead of going silent; its result keeps its status
+    and gains PARSE_CONCEALED in `flags`.  concealed() counts such frames of collected batches."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
-                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None, true_peak=None):
+                 carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None, true_peak=None,
+                 conceal=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -562,6 +584,13 @@ class Pipeline:
         self.limiter = None
         self.true_peak, self._tp, self._tp_last, self._tp_armed = None, {}, None, None
         self._keep = {}
+        self.conceal = None
+        if conceal is not None and conceal is not False:
+            try:
+                self.set_concealment(**({} if conceal is True else dict(conceal)))
+            except (AacgError, ValueError, TypeError):
+                self.close()
+                raise
         if mix is not None:
             m = np.ascontiguousarray(mix, np.float32)
             if m.ndim != 2 or m.shape[1] != channels:
@@ -685,6 +714,23 @@ class Pipeline:
         cfg = config if isinstance(config, LimiterConfig) else LimiterConfig(*[float(v) for v in config])
         self._check(self.lib.aacg_pipeline_set_limiter(self.handle, C.byref(cfg)))
         self.limiter = LimiterConfig(cfg.ceiling, cfg.release)
+
+    def set_concealment(self, fade_steps=CONCEAL_FADE_STEPS, hold_frames=CONCEAL_HOLD_FRAMES):
+        """aacg_pipeline_set_concealment: refused frames repeat the stream's last good frame, fade_steps scalefactor steps (1.5 dB) down
+        per lost frame, for at most hold_frames frames in a row; before the first batch, on a pipeline with device_plans"""
+        if int(fade_steps) < 0 or int(hold_frames) < 0:
+            raise ValueError("Pipeline: fade_steps and hold_frames are not negative")
+        cfg = ConcealConfig(int(fade_steps), int(hold_frames))
+        self._check(self.lib.aacg_pipeline_set_concealment(self.handle, C.byref(cfg)))
+        self.conceal = {"fade_steps": int(fade_steps), "hold_frames": int(hold_frames)}
+
+    def concealed(self):
+        """aacg_pipeline_concealed: the frames concealed so far in batches that have been collected"""
+        n = C.c_uint64()
+        rc = self.lib.aacg_pipeline_concealed(self.handle, C.byref(n))
+        if rc != 0:
+            raise AacgError(rc, "aacg_pipeline_concealed")
+        return int(n.value)
 
     def set_gain(self, slot, gain):
         """aacg_pipeline_set_gain: the slot's gain (0..1024) from the next batch enqueued that holds the slot; a reset leaves it"""

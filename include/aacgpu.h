@@ -475,12 +475,15 @@ enum {                         /* aacg_parse_result.status; the reference's mess
 #define AACG_PARSE_HAS_TNS 0x2
 #define AACG_PARSE_HAS_CCE 0x4   /* the frame held a coupling channel element: parsed and dropped (what aac.js executes); a host that
                                     applies coupling (AACG_CCE_SPEC) takes such a frame's records from a front end that keeps them */
+#define AACG_PARSE_CONCEALED 0x8 /* never written by the parser: the conceal stage (aacg_plan_conceal_refused, aacg_pipeline_set_concealment)
+                                    marks a refused frame whose records it replaced by its stream's last good frame, faded; status,
+                                    n_units and bits_used still tell of the refusal */
 typedef struct aacg_parse_result {
     uint8_t  status;           /* AACG_PARSE_*; a failed frame's output records are unspecified
                                   (partially written; never uninitialised memory)                  */
     uint8_t  n_units;          /* SCE/LFE/CPE elements found = records written for this frame      */
     uint8_t  n_channels;
-    uint8_t  flags;            /* AACG_PARSE_HAS_*                                                 */
+    uint8_t  flags;            /* AACG_PARSE_HAS_*, AACG_PARSE_CONCEALED                           */
     uint32_t bits_used;        /* consumed from byte_offset on, byte-aligned at the end            */
 } aacg_parse_result;
 
@@ -597,6 +600,62 @@ int aacg_plan_refresh_from_parse_ex(aacg_engine* e, aacg_plan* p, const aacg_uni
  * does not list each stream's frames one behind the other with the same elements next to each other in every frame is refused:
  * AACG_ERR_UNSUPPORTED, the reason in aacg_last_error. */
 int aacg_plan_carry_window_shape(aacg_engine* e, aacg_plan* p, const aacg_refresh_map* d_map, uint32_t set, void* hip_stream);
+
+/* ---- refused frames concealed on the device -------------------------------------------------------------------------------------
+ * A frame the parser or the refresh refuses is a silent unit: 1024 zeros per channel that move the stream's overlap state on.  This
+ * call, behind aacg_plan_refresh_from_parse_ex on the same hip_stream and in front of aacg_plan_carry_window_shape and the launch,
+ * repeats the stream's last good frame in its place with a fade — by substituting RECORDS: the transform then produces exactly what
+ * it would produce for a stream that held the substituted frame.  One small launch (aacg_units_conceal).
+ *
+ * THE RULE.  Each stream slot holds G, the records of its last good frame, or nothing, and r, the number of refused frames since G.
+ * G is empty and r is 0 in a new state block's slots and for a stream whose record says `fresh`.  Take a stream's frames of the batch
+ * in order; the stream has `kept` decoded elements (a stream with kept = 0 — no layout learnt — has no unit and is not touched, its
+ * state neither).  A frame is REFUSED iff d_results[frame].status != AACG_PARSE_OK after the refresh: parse errors,
+ * AACG_PARSE_LAYOUT, and on an engine without AACG_PNS_SPEC a frame whose unit has noise bands.
+ *   A good frame.     G := the frame's kept elements — for each kept unit its refreshed flags and ch[0..1]; for each of its channels
+ *                     the 1024 int16 of its spectrum block and the 120 words of its aacg_band_meta block.  r := 0.  The frame itself
+ *                     is untouched.
+ *   A refused frame.  r := min(r + 1, hold_frames + 1).  If G exists and r <= hold_frames the frame is CONCEALED:
+ *                     - each kept element's plan unit takes G's flags and ch[] verbatim — window sequence, shape, max_sfb, grouping,
+ *                       the MS flags; window_shape_prev is left to the carry stage — and the group map derived from them.  The
+ *                       planner's fields stay: stream, pcm_offset, channel, n_out_ch, n_ch, coef_offset, meta_offset; tns_offset
+ *                       stays 0;
+ *                     - the frame's OWN spectrum blocks are overwritten with G's, all 1024 values per channel;
+ *                     - its own band-word blocks are overwritten with G's words, all 120: in every word whose band type (bits
+ *                       12..15) is 1..11 the scalefactor field (bits 0..8) becomes max(0, sf - r * fade_steps); words of band type
+ *                       0, 13, 14 and 15 are copied unchanged; bits 9..11 are kept;
+ *                     - d_results[frame].flags gains AACG_PARSE_CONCEALED.
+ *                     Otherwise the frame stays the silent unit the refresh made.  status, n_units, bits_used and the refusal count
+ *                     are NOT changed: the host still learns of every refusal.
+ * Sources are good frames or G, never a concealed frame: a run of refused frames repeats ONE frame, each time fade_steps further
+ * down (one step is the scalefactor table's 2^(1/4), 1.5 dB), and falls silent after hold_frames.
+ *
+ * d_state: aacg_conceal_state_bytes(n_slots, parse_channels) bytes of device memory, 16-byte aligned, zero when first used — two sides
+ * per slot; a stream's record names the side its batch READS (bit 0 of `state`), the launch writes the other (the batch's last good
+ * frame, or the old G carried over with the new r), and the caller flips the bit for the slot's next batch once this one is enqueued
+ * (what a call that failed wrote lies in the side the slot does not read).  Consecutive calls are ordered on the device whatever
+ * their streams: the engine records an event behind every launch and puts the next one behind it.
+ * d_streams: one record per stream of the batch, in the batch's order (device memory; e.g. brought up with the batch's bytes).
+ * longest: the largest `frames` among them.  d_results / d_q / d_meta: what aacg_parse_device wrote for the batch (parse_channels its
+ * max_channels) and the refresh has marked; the blocks of refused frames and the results' flags are written.
+ * fade_steps 0..64, hold_frames 1..255 (AACG_ERR_INVALID_ARG otherwise).  Shaped plans (aacg_plan_create_shaped) and the set shaped
+ * and refreshed last only — a kept plan's refresh may be repeated when the plan has gone stale, and the stage is not idempotent:
+ * AACG_ERR_UNSUPPORTED, as on an engine with AACG_TNS_SPEC or AACG_PNS_SPEC (the TNS records of a repeated frame and repeated noise
+ * bands are not served); the reason in aacg_last_error. */
+typedef struct aacg_conceal_stream {
+    uint32_t frame_first;      /* the stream's first frame in the batch's packed order (aacg_shape_stream)                       */
+    uint32_t frames;           /* its frames in this batch                                                                       */
+    uint32_t unit_first;       /* its first plan unit                                                                            */
+    uint32_t frame_units;      /* bits 0..7: the elements of its frames; bits 8..15: how many of them are decoded (kept)         */
+    uint32_t slot;             /* the stream slot: owner of the state                                                            */
+    uint32_t nch;              /* 2 bits per element 0..7: its channels (1 or 2), in the frame's order                           */
+    uint32_t state;            /* bit 0: the side of the slot's state this batch reads; bit 1: fresh — that side counts as empty */
+    uint32_t reserved;         /* zero                                                                                           */
+} aacg_conceal_stream;
+size_t aacg_conceal_state_bytes(uint32_t n_slots, uint32_t parse_channels);
+int aacg_plan_conceal_refused(aacg_engine* e, aacg_plan* p, uint32_t set, aacg_parse_result* d_results, int16_t* d_q, aacg_band_meta* d_meta,
+                              uint32_t parse_channels, const aacg_conceal_stream* d_streams, uint32_t n_streams, uint32_t longest,
+                              void* d_state, uint32_t n_slots, uint32_t fade_steps, uint32_t hold_frames, void* hip_stream);
 
 /* ---- TNS records made on the device (AACG_TNS_SPEC) ---------------------------------------------------------------------------
  * What the host planner makes of an aacg_tns_info before a launch can run its filters — per filter the sample range, the
@@ -1153,6 +1212,30 @@ int  aacg_pipeline_gain(const aacg_pipeline* p, uint32_t slot, float* gain);
  * release_ms / 1000)) — the share of the way back to G that a block of 64 samples covers at a time constant of release_ms.
  * AACG_ERR_INVALID_ARG: a rate of 0, a null cfg, a result outside aacg_pipeline_set_limiter's limits. */
 int  aacg_limiter_design(uint32_t rate, double ceiling_db, double release_ms, aacg_limiter_config* cfg);
+
+/* ---- the resident route: refused frames concealed ----------------------------------------------------------------------------------
+ * An optional stage in front of the transform: a frame the parser or the refresh refused repeats its stream's last good frame, fading
+ * fade_steps scalefactor steps (1.5 dB each) per lost frame, for at most hold_frames frames in a row; then silence as before.  THE RULE
+ * is aacg_plan_conceal_refused's, above: G and r per stream slot, empty / 0 at create and after aacg_pipeline_reset_stream — which
+ * takes effect with the slot's next batch, as the resampler's and the limiter's histories are reset.  One more launch per batch
+ * (aacg_units_conceal) on the lane's stream behind the refresh and in front of the window-shape carry: the shape carried behind a
+ * concealed frame is G's.  A concealed frame's result keeps its status, n_units and bits_used and gains AACG_PARSE_CONCEALED in
+ * `flags`; *n_refused counts it as ever.  A stream without a learnt layout is not touched; a submission refused before anything is
+ * enqueued changes no state.  With no concealment set nothing differs, call for call.
+ * It goes with AACG_PIPELINE_STAGE_WINDOW_SHAPE, both output kinds, every delivery (host, device packed or planar) and every exit
+ * stage (mix, limiter, resampler, features, meter, true peak), which see the concealed PCM.
+ * Called once, before the pipeline's first submitted batch.  AACG_ERR_UNSUPPORTED, with the reason in aacg_pipeline_last_error and the
+ * pipeline exactly as it was: plan_mode 0 (its retry of a stale plan would run the stage twice for one batch; plan_mode 1's shaped
+ * set is never stale), AACG_PIPELINE_STAGE_TNS or AACG_PIPELINE_STAGE_PNS (the TNS records of a repeated frame and repeated noise
+ * bands are not served).  AACG_ERR_INVALID_ARG: a null config, fade_steps above 64, hold_frames outside 1..255, a call after the
+ * first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the slots' state. */
+typedef struct aacg_conceal_config {
+    uint32_t fade_steps;       /* 0..64 scalefactor steps per lost frame; 2 is a usual value (3 dB a frame)  */
+    uint32_t hold_frames;      /* 1..255 frames in a row that repeat G; 6 is a usual value (128 ms at 48 kHz) */
+} aacg_conceal_config;
+int  aacg_pipeline_set_concealment(aacg_pipeline* p, const aacg_conceal_config* cfg);
+/* The frames concealed so far in batches that have been collected.  AACG_ERR_INVALID_ARG: a null pipeline or count. */
+int  aacg_pipeline_concealed(const aacg_pipeline* p, uint64_t* count);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,13 @@
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
- *                                         [--loudness [--true-peak]] [--limiter]
+ *                                         [--loudness [--true-peak]] [--limiter] [--conceal] [--drop-every N]
+ *
+ * --conceal (with --device-plans): refused frames repeat their stream's last good frame, fading 2 scalefactor steps a frame for at most
+ * 6 frames (aacg_pipeline_set_concealment): one more small launch per batch (aacg_units_conceal) between the refresh and the carry.
+ * --drop-every N: every N-th frame of the batch (N, 2 N, ... in the packed order) has its table entry cut to 9 bytes, so that the parser
+ * refuses it; the line then carries the frames dropped per batch, the refusals are expected and do not fail the run, and with --conceal
+ * the frames the pipeline counted as concealed.  Combine them to see what a lossy feed costs; --conceal alone for what a clean one costs.
  *
  * --limiter: a gain per stream and a look-ahead limiter behind the mix and in front of the resampler (aacg_limiter_design at the file's
  * rate with a ceiling of -1 dB and a release of 200 ms; aacg_pipeline_set_limiter; slot s gets the gain 0.5 + 0.5 (s mod 8) through
@@ -86,7 +92,8 @@ int main(int argc, char** argv)
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     uint32_t mix = 0, rate = 0;
-    bool features = false, loudness = false, limiter = false, true_peak = false;
+    bool features = false, loudness = false, limiter = false, true_peak = false, conceal = false;
+    uint32_t drop_every = 0;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -111,6 +118,8 @@ int main(int argc, char** argv)
         else if (a == "--loudness") loudness = true;
         else if (a == "--true-peak") true_peak = true;
         else if (a == "--limiter") limiter = true;
+        else if (a == "--conceal") conceal = true;
+        else if (a == "--drop-every") drop_every = (uint32_t)std::atoi(val());
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -139,6 +148,8 @@ int main(int argc, char** argv)
             bytes.insert(bytes.end(), file.begin() + g.byte_offset, file.begin() + g.byte_offset + g.byte_length);
         }
     }
+    uint32_t dropped = 0;                                   /* --drop-every: the entries cut to an ADTS header and two bytes */
+    if (drop_every) for (size_t i = drop_every; i < frames.size(); i += drop_every) if (frames[i].byte_length > 9u) { frames[i].byte_length = 9u; dropped++; }
     std::vector<aacg_code_entry> entries(AACG_STANDARD_CODEBOOK_ENTRIES);
     uint32_t counts[12];
     aacg_standard_codebooks(entries.data(), counts);
@@ -156,6 +167,8 @@ int main(int argc, char** argv)
         if ((rc = aacg_mix_standard(channels, mix, 0.70710678118654752440f, 1, m))) { std::fprintf(stderr, "aacg_mix_standard(%u, %u): %d\n", channels, mix, rc); return 2; }
         if ((rc = aacg_pipeline_set_mix(p, mix, m))) { std::fprintf(stderr, "aacg_pipeline_set_mix: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
+    const aacg_conceal_config conceal_cfg = {2u, 6u};
+    if (conceal && (rc = aacg_pipeline_set_concealment(p, &conceal_cfg))) { std::fprintf(stderr, "aacg_pipeline_set_concealment: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     const uint32_t out_channels = (uint32_t)aacg_pipeline_out_channels(p);      /* what leaves: the mix's rows, or the stream's channels */
     aacg_limiter_config lim_cfg = {0.0f, 0.0f};
     if (limiter) {                                          /* behind the mix, in front of the resampler */
@@ -324,13 +337,21 @@ int main(int argc, char** argv)
                                (double)lim_cfg.ceiling, (double)lim_cfg.release, 2 * resample_in_bytes);
     char features_key[192] = "";                            /* --features only */
     if (features) std::snprintf(features_key, sizeof features_key, "\"features\": \"log-mel\", \"frame_length\": %u, \"hop\": %u, \"n_bins\": %u, \"n_mels\": %u, \"feature_frames_per_stream_most\": %zu, ", ft_K, ft_H, ft_bins, ft_mels, most_ft);
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s%s"
+    char conceal_key[192] = "";                             /* --conceal / --drop-every only */
+    if (conceal || drop_every) {
+        uint64_t concealed = 0;
+        (void)aacg_pipeline_concealed(p, &concealed);
+        std::snprintf(conceal_key, sizeof conceal_key, "\"conceal\": %s, \"conceal_fade_steps\": %u, \"conceal_hold_frames\": %u, \"drop_every\": %u, \"frames_dropped_per_batch\": %u, \"frames_concealed\": %llu, ",
+                      conceal ? "true" : "false", conceal_cfg.fade_steps, conceal_cfg.hold_frames, drop_every, dropped, (unsigned long long)concealed);
+    }
+    if (drop_every) bad = 0;                                /* (the refusals are the dropped frames': expected) */
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s%s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, limiter_key, rate_key, features_key, loudness_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, limiter_key, rate_key, features_key, loudness_key, conceal_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
