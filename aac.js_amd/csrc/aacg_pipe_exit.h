@@ -18,8 +18,11 @@
  *   features   a feature      LANE_RS, LANE_LIM, LANE_MIX CALLER for either device layout (ft_row = stride_frames,    sum ft_out n_mels 4
  *              stage          or LANE_PCM: the last       FEATURE frames, if planar, else 0), else LANE_FT
  *                             written
+ *   trim       a trim and no  LANE_RS, LANE_LIM, LANE_MIX CALLER for either device layout (row = stride_frames x     sum n_keep Oc E
+ *              feature stage  or LANE_PCM: the last       1024 if planar, else 0), else LANE_TRIM
+ *                             written
  *   tail       see `writes`   the last lane buffer        PLANAR_LAUNCH -> CALLER if DEV_PLANAR and neither resampler out_bytes
- *                             written                     nor feature stage; COPY_DOWN -> CALLER (page-locked) or
+ *                             written                     nor trim nor feature stage; COPY_DOWN -> CALLER (page-locked) or
  *                                                         LANE_HOST (pageable, and collect copies it to the caller)
  *                                                         for a host batch; else there is no tail
  *
@@ -31,7 +34,14 @@
  * write lane buffers whatever the destination too — the transform LANE_PCM, the mix LANE_MIX — and the stages behind it read LANE_LIM
  * as the last written.  It emits what it receives: out_bytes, device_need and exit_host_capacity do not know it.
  *
- * out_bytes, what leaves: sum ft_out n_mels 4 with a feature stage, else sum n_out Oc E with a resampler, else n Oc 1024 E.
+ * With a trim (aacg_pipeline_set_trim: each stream's samples cut to its slot's window, sum n_keep of them kept) and no feature stage
+ * the stages in front of it write lane buffers whatever the destination too — the resampler LANE_RS with row 0 — and the trim is the one
+ * that writes the caller's device memory, in either layout: there is no PLANAR_LAUNCH tail.  With a feature stage there is NO trim row:
+ * the feature stage reads each stream's kept range where it lies (its records' in_first and n_in), and ft_most / ft_total follow from
+ * the trimmed counts.  A batch may keep nothing: out_bytes 0, and the walk enqueues neither a launch for a packed destination nor a copy.
+ *
+ * out_bytes, what leaves: sum ft_out n_mels 4 with a feature stage, else sum n_keep Oc E with a trim, else sum n_out Oc E with a
+ * resampler, else n Oc 1024 E.
  * device_need, what a caller's device buffer must hold: n_streams n_mels stride_frames 4 (features) or n_streams Oc stride_frames 1024
  * E planar, out_bytes packed.  The caller's memory is written by exactly one stage, the last.
  *
@@ -50,10 +60,11 @@
 /* a buffer a stage reads or writes: the lane's d_pcm, d_mix, d_rs, its page-locked h_pcm, or the caller's memory (host or device) */
 enum { AACG_EXIT_BUF_NONE = 0, AACG_EXIT_LANE_PCM, AACG_EXIT_LANE_MIX, AACG_EXIT_LANE_RS, AACG_EXIT_LANE_HOST, AACG_EXIT_CALLER,
        AACG_EXIT_LANE_FT,      /* (the lane's d_ft: a host batch's feature frames) */
-       AACG_EXIT_LANE_LIM };   /* (the lane's d_lim: the limiter's PCM wherever it is not the last stage of a packed device batch) */
+       AACG_EXIT_LANE_LIM,     /* (the lane's d_lim: the limiter's PCM wherever it is not the last stage of a packed device batch) */
+       AACG_EXIT_LANE_TRIM };  /* (the lane's d_trim: a host batch's trimmed PCM) */
 /* where the caller wants the batch's PCM */
 enum { AACG_EXIT_HOST_PINNED = 0, AACG_EXIT_HOST_PAGEABLE, AACG_EXIT_DEV_PACKED, AACG_EXIT_DEV_PLANAR };
-enum { AACG_EXIT_XFORM = 0, AACG_EXIT_MIX, AACG_EXIT_RESAMPLE, AACG_EXIT_TAIL, AACG_EXIT_FEATURES, AACG_EXIT_LIMIT };
+enum { AACG_EXIT_XFORM = 0, AACG_EXIT_MIX, AACG_EXIT_RESAMPLE, AACG_EXIT_TAIL, AACG_EXIT_FEATURES, AACG_EXIT_LIMIT, AACG_EXIT_TRIM };
 enum { AACG_EXIT_TAIL_NONE = 0, AACG_EXIT_TAIL_PLANAR_LAUNCH, AACG_EXIT_TAIL_COPY_DOWN };
 
 /* what the pipeline is */
@@ -65,7 +76,8 @@ typedef struct aacg_exit_pipe {
     uint64_t lane_elems;       /* a resampler: elements of the largest batch's output (aacg_pipe::exit_resample_most x Oc)      */
     uint32_t n_mels;           /* a feature stage: floats per feature frame (0: none)                                           */
     uint64_t ft_lane_elems;    /* ... and the floats of the largest batch's output (aacg_pipe::exit_features_most x n_mels)     */
-    uint32_t limited;          /* a limiter is set (the last field: the drivers that build this positionally leave it 0)        */
+    uint32_t limited;          /* a limiter is set (the drivers that build this positionally leave it and what follows 0)       */
+    uint32_t trimmed;          /* a trim is set                                                                                 */
 } aacg_exit_pipe;
 
 /* what the batch is */
@@ -77,6 +89,8 @@ typedef struct aacg_exit_batch {
     uint64_t rs_total;                    /* ... and the sum of them                                                            */
     uint32_t ft_most;                     /* a feature stage: the largest count of feature frames of a stream ...               */
     uint64_t ft_total;                    /* ... and the sum of them                                                            */
+    uint32_t tr_most;                     /* a trim: the largest n_keep of a stream ...                                         */
+    uint64_t tr_total;                    /* ... and the sum of them                                                            */
 } aacg_exit_batch;
 
 typedef struct aacg_exit_stage {
@@ -85,9 +99,9 @@ typedef struct aacg_exit_stage {
 } aacg_exit_stage;
 
 typedef struct aacg_exit_plan {
-    aacg_exit_stage stage[6];             /* in the order they are enqueued; the first is the transform                         */
+    aacg_exit_stage stage[7];             /* in the order they are enqueued; the first is the transform                         */
     uint32_t n_stages;
-    uint32_t row;                         /* a planar resample: elements per row; else 0                                        */
+    uint32_t row;                         /* a planar resample or trim, whichever writes the caller's tensor: elements per row; else 0 */
     uint64_t xform_bytes;                 /* what the transform writes: the clear for unlearnt streams acts on it               */
     uint64_t out_bytes;                   /* what leaves                                                                        */
     uint64_t device_need;                 /* a device batch: the bytes the caller's buffer must hold                            */
@@ -133,25 +147,28 @@ inline aacg_exit_plan exit_plan(const aacg_exit_pipe& P, const aacg_exit_batch& 
     /* (the stages in front of a feature stage see neither device destination: they write lane buffers) */
     const bool packed = B.dest == AACG_EXIT_DEV_PACKED && !ft, planar = B.dest == AACG_EXIT_DEV_PLANAR && !ft, rs = P.resampled != 0;
     const bool lim = P.limited != 0;                     /* (... and so do the stages in front of a limiter) */
+    const bool tr = P.trimmed != 0 && !ft;               /* (... and of a trim; with a feature stage the trim is no stage: it is in that stage's records) */
     aacg_exit_plan X = {};
     uint8_t last = AACG_EXIT_BUF_NONE;                   /* the buffer the stage before wrote */
     auto push = [&](uint8_t what, uint8_t dst, uint64_t bytes, uint8_t tail) { X.stage[X.n_stages++] = {what, last, dst, tail, bytes}; last = dst; };
     X.xform_bytes = (uint64_t)B.n * P.C * 1024u * E;
     const uint64_t mix_bytes = (uint64_t)B.n * Oc * 1024u * E;
-    X.out_bytes = rs ? B.rs_total * Oc * E : mix_bytes;
+    const uint64_t rs_bytes = rs ? B.rs_total * Oc * E : mix_bytes;
+    X.out_bytes = tr ? B.tr_total * Oc * E : rs_bytes;
     X.device_need = planar ? (uint64_t)B.n_streams * Oc * B.stride_frames * 1024u * E : packed ? X.out_bytes : 0u;
-    X.row = rs && planar ? B.stride_frames * 1024u : 0u;
-    push(AACG_EXIT_XFORM, packed && !P.O && !rs && !lim ? AACG_EXIT_CALLER : AACG_EXIT_LANE_PCM, X.xform_bytes, AACG_EXIT_TAIL_NONE);
-    if (P.O) push(AACG_EXIT_MIX, packed && !rs && !lim ? AACG_EXIT_CALLER : AACG_EXIT_LANE_MIX, mix_bytes, AACG_EXIT_TAIL_NONE);
-    if (lim) push(AACG_EXIT_LIMIT, packed && !rs ? AACG_EXIT_CALLER : AACG_EXIT_LANE_LIM, mix_bytes, AACG_EXIT_TAIL_NONE);
-    if (rs) push(AACG_EXIT_RESAMPLE, packed || planar ? AACG_EXIT_CALLER : AACG_EXIT_LANE_RS, X.out_bytes, AACG_EXIT_TAIL_NONE);
+    X.row = (rs || tr) && planar ? B.stride_frames * 1024u : 0u;
+    push(AACG_EXIT_XFORM, packed && !P.O && !rs && !lim && !tr ? AACG_EXIT_CALLER : AACG_EXIT_LANE_PCM, X.xform_bytes, AACG_EXIT_TAIL_NONE);
+    if (P.O) push(AACG_EXIT_MIX, packed && !rs && !lim && !tr ? AACG_EXIT_CALLER : AACG_EXIT_LANE_MIX, mix_bytes, AACG_EXIT_TAIL_NONE);
+    if (lim) push(AACG_EXIT_LIMIT, packed && !rs && !tr ? AACG_EXIT_CALLER : AACG_EXIT_LANE_LIM, mix_bytes, AACG_EXIT_TAIL_NONE);
+    if (rs) push(AACG_EXIT_RESAMPLE, (packed || planar) && !tr ? AACG_EXIT_CALLER : AACG_EXIT_LANE_RS, rs_bytes, AACG_EXIT_TAIL_NONE);
+    if (tr) push(AACG_EXIT_TRIM, packed || planar ? AACG_EXIT_CALLER : AACG_EXIT_LANE_TRIM, X.out_bytes, AACG_EXIT_TAIL_NONE);
     if (ft) {
         X.out_bytes = B.ft_total * P.n_mels * 4u;        /* (the stage in front has its own bytes in its row) */
         X.ft_row = B.dest == AACG_EXIT_DEV_PLANAR ? B.stride_frames : 0u;
         X.device_need = B.dest == AACG_EXIT_DEV_PLANAR ? (uint64_t)B.n_streams * P.n_mels * B.stride_frames * 4u : to_dev ? X.out_bytes : 0u;
         push(AACG_EXIT_FEATURES, to_dev ? AACG_EXIT_CALLER : AACG_EXIT_LANE_FT, X.out_bytes, AACG_EXIT_TAIL_NONE);
     }
-    if (planar && !rs) push(AACG_EXIT_TAIL, AACG_EXIT_CALLER, X.out_bytes, AACG_EXIT_TAIL_PLANAR_LAUNCH);
+    if (planar && !rs && !tr) push(AACG_EXIT_TAIL, AACG_EXIT_CALLER, X.out_bytes, AACG_EXIT_TAIL_PLANAR_LAUNCH);
     else if (!to_dev) {
         X.collect_copy = B.dest == AACG_EXIT_HOST_PAGEABLE;
         push(AACG_EXIT_TAIL, X.collect_copy ? AACG_EXIT_LANE_HOST : AACG_EXIT_CALLER, X.out_bytes, AACG_EXIT_TAIL_COPY_DOWN);
@@ -164,6 +181,7 @@ inline aacg_exit_plan exit_plan(const aacg_exit_pipe& P, const aacg_exit_batch& 
 inline aacg_exit_refusal exit_check(const aacg_exit_pipe& P, const aacg_exit_batch& B, const aacg_exit_plan& X, const aacg_pcm_device_out& out, uint32_t planar_items)
 {
     const bool rs = P.resampled != 0;                    /* the rows hold samples at the new rate */
+    const bool tr = P.trimmed != 0;                      /* the rows hold the kept samples, written by the trim */
     auto no = [](int code, bool late, std::string text) { return aacg_exit_refusal{code, late, "aacg_pipeline_submit_device: " + text}; };
     if ((uintptr_t)out.d_pcm & 15u) return no(AACG_ERR_INVALID_ARG, false, "d_pcm is not 16-byte aligned");
     if (out.layout != AACG_PCM_PACKED && out.layout != AACG_PCM_PLANAR) return no(AACG_ERR_INVALID_ARG, false, "unknown layout (AACG_PCM_PACKED or AACG_PCM_PLANAR)");
@@ -176,13 +194,17 @@ inline aacg_exit_refusal exit_check(const aacg_exit_pipe& P, const aacg_exit_bat
         if ((uint64_t)out.d_pcm_bytes < X.device_need) return no(AACG_ERR_CAPACITY, true, "d_pcm_bytes is smaller than the batch needs (" + std::to_string(X.device_need) + " bytes)");
         return {AACG_OK, false, std::string()};
     }
-    if (out.layout == AACG_PCM_PLANAR && !rs && out.stride_frames < B.longest) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is below the batch's largest frame count");
-    if (out.layout == AACG_PCM_PLANAR && rs) {
+    if (out.layout == AACG_PCM_PLANAR && !rs && !tr && out.stride_frames < B.longest) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is below the batch's largest frame count");
+    if (out.layout == AACG_PCM_PLANAR && rs && !tr) {
         if (!out.stride_frames || out.stride_frames > (1u << 21)) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is not in 1..2^21");
         if ((uint64_t)out.stride_frames * 1024u < B.rs_most) return no(AACG_ERR_INVALID_ARG, false, "stride_frames x 1024 is below a stream's resampled count (aacg_pipeline_out_samples)");
     }
+    if (out.layout == AACG_PCM_PLANAR && tr) {
+        if (!out.stride_frames || out.stride_frames > (1u << 21)) return no(AACG_ERR_INVALID_ARG, false, "stride_frames is not in 1..2^21");
+        if ((uint64_t)out.stride_frames * 1024u < B.tr_most) return no(AACG_ERR_INVALID_ARG, false, "stride_frames x 1024 is below a stream's trimmed count (aacg_pipeline_out_samples)");
+    }
     if ((uint64_t)out.d_pcm_bytes < X.device_need) return no(AACG_ERR_CAPACITY, true, "d_pcm_bytes is smaller than the batch needs (" + std::to_string(X.device_need) + " bytes)");
-    if (out.layout == AACG_PCM_PLANAR && !rs && !planar_items) return no(AACG_ERR_CAPACITY, true, "n_streams x stride_frames is more than one aacg_pcm_planar launch addresses");
+    if (out.layout == AACG_PCM_PLANAR && !rs && !tr && !planar_items) return no(AACG_ERR_CAPACITY, true, "n_streams x stride_frames is more than one aacg_pcm_planar launch addresses");
     return {AACG_OK, false, std::string()};
 }
 

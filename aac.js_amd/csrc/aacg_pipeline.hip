@@ -77,6 +77,7 @@
 #include "aacg_pcm_mix.h"
 #include "aacg_pcm_planar.h"
 #include "aacg_pcm_resample.h"
+#include "aacg_pcm_trim.h"
 #define AACG_FEATURES_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_features.hip's */
 #include "aacg_pcm_features.h"
 #define AACG_LOUDNESS_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_loudness.hip's */
@@ -108,6 +109,8 @@ bool aacg_loudness_launch(const aacg_loudness_args& A, hipStream_t s);
 bool aacg_limit_launch(const aacg_limit_args& A, hipStream_t s);
 /* aacg_engine_truepeak.hip: the true peak of a batch's transform PCM (aacg_pcm_truepeak.h); false: not a launch it serves */
 bool aacg_truepeak_launch(const aacg_truepeak_args& A, hipStream_t s);
+/* aacg_engine_trim.hip: a batch's packed PCM cut to each stream's window (aacg_pcm_trim.h); false: not a launch it serves */
+bool aacg_trim_launch(const aacg_trim_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
  * memory is mapped into the device's address space, and a few workgroups of 16-byte loads and stores move 1.4 MB in 30 us.  The
@@ -213,6 +216,12 @@ struct aacg_pipeline {
         std::vector<uint8_t> parity, fresh;
         uint64_t total = 0;
     } cn;
+    /* aacg_pipeline_set_trim: per slot the window (skip S, keep K) and the position Q, in samples of what the stage receives (on: the
+     * stage is set).  All of it is the host's: the stage has no device state, a batch's kept ranges go up in its records */
+    struct trim_t {
+        bool on = false;
+        std::vector<uint64_t> S, K, Q;
+    } tr;
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -246,6 +255,7 @@ struct aacg_pipeline {
         hipEvent_t ld_done = nullptr;     /* aacg_pipeline_set_loudness: the event behind this lane's latest loudness launch */
         void* d_lim = nullptr;            /* aacg_pipeline_set_limiter: the limited PCM wherever it is not a packed device batch's last stage, max_streams x max_frames x 1024 x Oc elements */
         hipEvent_t lim_done = nullptr;    /* ... and the event behind this lane's latest limiter launch */
+        void* d_trim = nullptr;           /* aacg_pipeline_set_trim: the trimmed PCM of a host batch, the largest batch's untrimmed elements */
         float* ld_user = nullptr; size_t ld_bytes = 0;      /* ... and the batch in flight's records: where they go at collect, and how many bytes */
         float* tp_user = nullptr; size_t tp_bytes = 0;      /* aacg_pipeline_set_true_peak: the same for the batch in flight's true-peak floats */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
@@ -296,7 +306,7 @@ uint32_t out_channels(const aacg_pipeline* p) { return p->O ? p->O : p->C; }
 aacg_exit_pipe exit_pipe(const aacg_pipeline* p)
 {
     return {p->C, p->O, p->rs.L != 0, (uint32_t)pcm_elem(p), (uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.lane_elems,
-            p->ft.K ? p->ft.n_mels : 0u, p->ft.lane_elems, p->lim.on ? 1u : 0u};
+            p->ft.K ? p->ft.n_mels : 0u, p->ft.lane_elems, p->lim.on ? 1u : 0u, p->tr.on ? 1u : 0u};
 }
 /* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M), the first
  * through ceil((q M + n) L / M) = q L + ceil(n L / M) so that the one formula (aacg_resample_ceil) sees the arguments it is made for */
@@ -409,13 +419,17 @@ struct batch_t {
     size_t lim_at;                               /* stage_batch: where those lie, behind the meter's */
     std::vector<aacg_conceal_stream> cn;         /* check_batch, concealment: the batch's records, with the slots' sides as they stand */
     size_t cn_at;                                /* stage_batch: where those lie, behind the limiter's */
+    std::vector<aacg_trim_stream> tr;            /* check_batch, a trim: the batch's records (what each stream keeps, from the host's windows and positions) */
+    std::vector<uint32_t> tr_in;                 /* ... and what each stream brings: its slot's position advances by it in enqueue_out */
+    uint32_t tr_items;                           /* ... and the launch's items */
+    size_t tr_at;                                /* stage_batch: where the records lie, behind the concealment's */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
 /* a buffer of the exit plan, for this lane and this batch */
 void* exit_buf(const aacg_pipeline::lane_t& L, const batch_t& B, uint8_t id)
 {
-    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out, L.d_ft, L.d_lim};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_LANE_LIM */
+    void* const of[] = {nullptr, L.d_pcm, L.d_mix, L.d_rs, L.h_pcm, B.dev ? B.dev->d_pcm : B.pcm_out, L.d_ft, L.d_lim, L.d_trim};      /* AACG_EXIT_BUF_NONE .. AACG_EXIT_LANE_TRIM */
     return of[id];
 }
 
@@ -629,7 +643,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
     }
     for (auto& L : p->lane) {
         /* (d_frames lies in d_bytes, d_refused in d_res; a meter's records lie in front of d_res and h_res, in their blocks) */
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_lim, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_lim, L.d_trim, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
         for (void* h : {L.h_in, L.h_pcm, L.h_res ? (void*)((char*)L.h_res - p->ld.front16) : nullptr}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.rs_done) (void)hipEventDestroy(L.rs_done);
@@ -747,6 +761,7 @@ int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* 
     if (p->rs.L) { p->err = "aacg_pipeline_set_mix: the pipeline has a resampler already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (p->ft.K) { p->err = "aacg_pipeline_set_mix: the pipeline has a feature stage already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (p->lim.on) { p->err = "aacg_pipeline_set_mix: the pipeline has a limiter already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (p->tr.on) { p->err = "aacg_pipeline_set_mix: the pipeline has a trim already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (out_channels < 1 || out_channels > AACG_MIX_MAX_OUT) { p->err = "aacg_pipeline_set_mix: out_channels is not 1 or 2"; return AACG_ERR_INVALID_ARG; }
     if (!matrix) { p->err = "aacg_pipeline_set_mix: no matrix"; return AACG_ERR_INVALID_ARG; }
     for (uint32_t i = 0; i < out_channels * p->C; i++)
@@ -770,6 +785,7 @@ int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_
     if (p->rs.L) { p->err = "aacg_pipeline_set_resample: the pipeline has a resampler already"; return AACG_ERR_INVALID_ARG; }
     if (p->submitted) { p->err = "aacg_pipeline_set_resample: a batch has been submitted (the resampler is set before the first)"; return AACG_ERR_INVALID_ARG; }
     if (p->ft.K) { p->err = "aacg_pipeline_set_resample: the pipeline has a feature stage already (the resampler is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (p->tr.on) { p->err = "aacg_pipeline_set_resample: the pipeline has a trim already (the resampler is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (const int why = aacg_resample_check(L, M, taps)) { p->err = std::string("aacg_pipeline_set_resample: ") + aacg_resample_why(why); return AACG_ERR_INVALID_ARG; }
     if (!table) { p->err = "aacg_pipeline_set_resample: no table"; return AACG_ERR_INVALID_ARG; }
     const size_t n_table = (size_t)L * taps;
@@ -896,6 +912,7 @@ int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
     if (!cfg) { p->err = "aacg_pipeline_set_limiter: no configuration"; return AACG_ERR_INVALID_ARG; }
     if (p->lim.on) { p->err = "aacg_pipeline_set_limiter: the pipeline has a limiter already"; return AACG_ERR_INVALID_ARG; }
     if (p->submitted) { p->err = "aacg_pipeline_set_limiter: a batch has been submitted (the limiter is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (p->tr.on) { p->err = "aacg_pipeline_set_limiter: the pipeline has a trim already (the limiter is set before it)"; return AACG_ERR_INVALID_ARG; }
     if (!(cfg->ceiling > 0.0f) || !std::isfinite(cfg->ceiling)) { p->err = "aacg_pipeline_set_limiter: ceiling is not positive and finite"; return AACG_ERR_INVALID_ARG; }
     if (!(cfg->release > 0.0f) || !(cfg->release <= 1.0f)) { p->err = "aacg_pipeline_set_limiter: release is not in (0, 1]"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
@@ -970,6 +987,48 @@ int aacg_pipeline_gain(const aacg_pipeline* p, uint32_t slot, float* gain)
 {
     if (!p || !gain || !p->lim.on || (int)slot >= p->cfg.max_streams) return AACG_ERR_INVALID_ARG;
     *gain = p->lim.gain[slot];
+    return AACG_OK;
+}
+
+int aacg_pipeline_set_trim(aacg_pipeline* p, const aacg_trim_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    /* every refusal leaves the pipeline exactly as it was */
+    if (!cfg) { p->err = "aacg_pipeline_set_trim: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (p->tr.on) { p->err = "aacg_pipeline_set_trim: the pipeline has a trim already"; return AACG_ERR_INVALID_ARG; }
+    if (p->submitted) { p->err = "aacg_pipeline_set_trim: a batch has been submitted (the trim is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (aacg_trim_check(cfg->skip, cfg->keep)) { p->err = "aacg_pipeline_set_trim: skip or a finite keep is 2^40 or more"; return AACG_ERR_INVALID_ARG; }
+    /* the largest batch's input, samples per channel: the kernel and its records count them in 32 bits */
+    const uint64_t most = p->rs.L ? aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.L, p->rs.M)
+                                  : (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * 1024u;
+    if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_trim: max_streams x max_frames x 1024 (x L / M) is 2^31 samples or more"; return AACG_ERR_INVALID_ARG; }
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    /* (a host batch's trimmed PCM: at most what the stage receives.  With a feature stage the trim writes nothing) */
+    if (!p->ft.K && !lanes_alloc(p, &lane_t::d_trim, (size_t)most * out_channels(p) * pcm_elem(p))) {
+        p->err = "aacg_pipeline_set_trim: no device memory for the lanes' trimmed PCM";
+        return AACG_ERR_OUT_OF_MEMORY;
+    }
+    p->tr.S.assign((size_t)p->cfg.max_streams, cfg->skip); p->tr.K.assign((size_t)p->cfg.max_streams, cfg->keep); p->tr.Q.assign((size_t)p->cfg.max_streams, 0u);
+    p->tr.on = true;
+    return AACG_OK;
+}
+
+int aacg_pipeline_set_stream_trim(aacg_pipeline* p, uint32_t slot, uint64_t skip, uint64_t keep)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    if (!p->tr.on) { p->err = "aacg_pipeline_set_stream_trim: the pipeline has no trim (aacg_pipeline_set_trim)"; return AACG_ERR_INVALID_ARG; }
+    if ((int)slot >= p->cfg.max_streams) { p->err = "aacg_pipeline_set_stream_trim: stream slot out of range"; return AACG_ERR_INVALID_ARG; }
+    if (aacg_trim_check(skip, keep)) { p->err = "aacg_pipeline_set_stream_trim: skip or a finite keep is 2^40 or more"; return AACG_ERR_INVALID_ARG; }
+    p->tr.S[slot] = skip; p->tr.K[slot] = keep; p->tr.Q[slot] = 0;      /* nothing in flight reads them: a batch's ranges went up in its records */
+    return AACG_OK;
+}
+
+int aacg_pipeline_stream_trim(const aacg_pipeline* p, uint32_t slot, uint64_t* skip, uint64_t* keep, uint64_t* position)
+{
+    if (!p || !p->tr.on || (int)slot >= p->cfg.max_streams) return AACG_ERR_INVALID_ARG;
+    if (skip) *skip = p->tr.S[slot];
+    if (keep) *keep = p->tr.K[slot];
+    if (position) *position = p->tr.Q[slot];
     return AACG_OK;
 }
 
@@ -1058,6 +1117,8 @@ int aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uin
         if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "aacg_pipeline_out_samples: a stream brings more frames than max_frames"; return AACG_ERR_INVALID_ARG; }
     }
     for (uint32_t s = 0; s < n_streams; s++) n_out[s] = p->rs.L ? resample_count(p, p->rs.n0[slots[s]], frames_of[s]) : frames_of[s] * 1024u;
+    if (p->tr.on)                                        /* a trim: what the slots' windows keep of them at the slots' positions */
+        for (uint32_t s = 0; s < n_streams; s++) { uint32_t first; aacg_trim_span(p->tr.Q[slots[s]], p->tr.S[slots[s]], p->tr.K[slots[s]], n_out[s], &first, &n_out[s]); }
     if (p->ft.K)                                         /* feature frames: what the samples above complete at the slots' clocks */
         for (uint32_t s = 0; s < n_streams; s++) { aacg_features_stream r; aacg_features_span(p->ft.K, p->ft.H, p->ft.P, p->ft.N[slots[s]], n_out[s], &r); n_out[s] = r.n_out; }
     return AACG_OK;
@@ -1101,6 +1162,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
     if (p->ft.K) { p->ft.N[slot] = 0; p->ft.fresh[slot] = 1; }       /* ... and the feature stage's */
     if (p->ld.hop) { p->ld.N[slot] = 0; p->ld.fresh[slot] = 1; }     /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
+    if (p->tr.on) p->tr.Q[slot] = 0;                                 /* ... and the trim's position; the slot's window is the caller's and stays */
     if (p->cn.on) p->cn.fresh[slot] = 1;                             /* ... and the last good frame: the slot's next batch starts with none */
     if (p->lim.on) p->lim.fresh[slot] = 1;                           /* ... and the limiter's held block and nodes; the slot's gain is the caller's and stays */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
@@ -1147,14 +1209,30 @@ int check_batch(aacg_pipeline* p, batch_t& B)
             if (n_out > b.rs_most) b.rs_most = n_out;
         }
     }
+    if (p->tr.on) {                                      /* what each stream keeps of what the stage receives, from the slots' windows and positions as they stand */
+        const int planar = b.dest == AACG_EXIT_DEV_PLANAR && !p->ft.K;
+        B.tr.resize(B.n_streams); B.tr_in.resize(B.n_streams);
+        B.tr_items = 0;
+        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
+            const uint32_t slot = B.slots[s], n_in = p->rs.L ? B.rs[s].n_out : B.frames_of[s] * 1024u, place = p->rs.L ? B.rs[s].out_first : first * 1024u;
+            uint32_t off, n_keep;
+            aacg_trim_span(p->tr.Q[slot], p->tr.S[slot], p->tr.K[slot], n_in, &off, &n_keep);
+            B.tr[s] = {place + off, n_keep, (uint32_t)b.tr_total, B.tr_items};
+            B.tr_in[s] = n_in;
+            B.tr_items += aacg_trim_items(n_keep, planar);
+            b.tr_total += n_keep;
+            if (n_keep > b.tr_most) b.tr_most = n_keep;
+        }
+    }
     if (p->ft.K) {                                       /* what each stream's samples complete, from the slots' clocks as they stand: one channel, so samples are elements */
         B.ft.resize(B.n_streams);
         uint32_t items = 0;
         for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
             const uint32_t slot = B.slots[s];
             aacg_features_stream& r = B.ft[s];
-            aacg_features_span(p->ft.K, p->ft.H, p->ft.P, p->ft.N[slot], p->rs.L ? B.rs[s].n_out : B.frames_of[s] * 1024u, &r);
-            r.in_first = p->rs.L ? B.rs[s].out_first : first * 1024u;
+            /* (a trim: the stage takes the stream's kept range where it lies, possibly no sample at all, and its clock counts kept samples only) */
+            aacg_features_span(p->ft.K, p->ft.H, p->ft.P, p->ft.N[slot], p->tr.on ? B.tr[s].n_keep : p->rs.L ? B.rs[s].n_out : B.frames_of[s] * 1024u, &r);
+            r.in_first = p->tr.on ? B.tr[s].src_first : p->rs.L ? B.rs[s].out_first : first * 1024u;
             r.out_first = (uint32_t)b.ft_total; r.item_first = items; r.slot = slot;
             r.flags = (uint32_t)p->ft.parity[slot] | (p->ft.fresh[slot] ? 2u : 0u);
             items += aacg_features_items(r.n_out);
@@ -1203,7 +1281,8 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     const size_t ld_bytes = B.ld.size() * sizeof(aacg_loudness_stream);      /* (... and a meter's behind those) */
     const size_t lim_bytes = B.lim.size() * sizeof(aacg_limit_stream);      /* (... and a limiter's behind those: every record is 32 bytes) */
     const size_t cn_bytes = B.cn.size() * sizeof(aacg_conceal_stream);      /* (... and the concealment's behind those, 32 bytes too) */
-    const size_t more = rs_bytes + ft_bytes + ld_bytes + lim_bytes + cn_bytes;
+    const size_t tr_bytes = p->ft.K ? 0u : B.tr.size() * sizeof(aacg_trim_stream);      /* (... and the trim's behind those, 16 bytes; with a feature stage they stay down here) */
+    const size_t more = rs_bytes + ft_bytes + ld_bytes + lim_bytes + cn_bytes + tr_bytes;
     int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, more ? tab16 + more : tab_bytes, B.G);
     if (rc) return rc;
     B.rs_at = B.G.extra_at + tab16;
@@ -1211,6 +1290,8 @@ int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
     B.ld_at = B.ft_at + ft_bytes;
     B.lim_at = B.ld_at + ld_bytes;
     B.cn_at = B.lim_at + lim_bytes;
+    B.tr_at = B.cn_at + cn_bytes;
+    if (tr_bytes) std::memcpy((char*)L.h_in + B.tr_at, B.tr.data(), tr_bytes);
     if (lim_bytes) std::memcpy((char*)L.h_in + B.lim_at, B.lim.data(), lim_bytes);
     if (ld_bytes) std::memcpy((char*)L.h_in + B.ld_at, B.ld.data(), ld_bytes);
     if (rs_bytes) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), rs_bytes);
@@ -1334,7 +1415,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
             /* the packed PCM at the new rate, either layout.  The slots' histories pass from batch to batch, and consecutive batches run on
              * different streams: this launch waits for the one before it, here — behind this lane's parse, transform and mix, which need not wait */
             const aacg_resample_args A = {src, dst, (const aacg_resample_stream*)((const char*)L.d_bytes + B.rs_at), (const float*)p->rs.d_table, (float*)p->rs.d_hist,
-                                          B.n_streams, B.n, p->rs.L, p->rs.M, p->rs.T, B.X.row, Oc, E};
+                                          B.n_streams, B.n, p->rs.L, p->rs.M, p->rs.T, S.dst == AACG_EXIT_CALLER ? B.X.row : 0u, Oc, E};      /* (the row is the stage's that writes the caller's tensor) */
             if (p->rs.last && p->rs.last != L.rs_done) P_TRY(p, hipStreamWaitEvent(L.st, p->rs.last, 0), AACG_ERR_NO_DEVICE);
             if (!aacg_resample_launch(A, L.st)) { p->err = "aacg_pcm_resample: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
             P_TRY(p, hipEventRecord(L.rs_done, L.st), AACG_ERR_NO_DEVICE);
@@ -1350,6 +1431,14 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
             if (!aacg_features_launch(A, L.st)) { p->err = "aacg_pcm_features: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
             P_TRY(p, hipEventRecord(L.ft_done, L.st), AACG_ERR_NO_DEVICE);
             p->ft.last = L.ft_done;
+        } else if (S.what == AACG_EXIT_TRIM) {
+            /* each stream's kept range of the packed PCM, as the stage before left it, either layout.  No state: nothing to wait for and
+             * no event.  A batch that keeps nothing launches nothing for a packed destination; a planar one still gets its zeros */
+            const uint64_t src_elems = (uint64_t)(p->rs.L ? B.rs.back().out_first + B.rs.back().n_out : B.n * 1024u) * Oc;
+            const aacg_trim_args A = {src, dst, (const aacg_trim_stream*)((const char*)L.d_bytes + B.tr_at), src_elems, B.n_streams, B.tr_items, B.X.row, Oc, E};
+            if (B.tr_items && !aacg_trim_launch(A, L.st)) { p->err = "aacg_pcm_trim: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+        } else if (S.tail == AACG_EXIT_TAIL_COPY_DOWN && p->tr.on && !S.bytes) {
+            /* (a trim kept nothing of the batch: no copy of nothing) */
         } else if (S.tail == AACG_EXIT_TAIL_PLANAR_LAUNCH) {
             /* the caller's tensor from the packed PCM and the per-stream table that came up with the bytes (either plan mode's record
              * begins with frame_first and frames), padding included: where the copy down sits for a host batch */
@@ -1401,6 +1490,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     /* ... and the meter's; its destination is this batch's now, and the next submission names its own */
     for (const auto& r : B.ld) { p->ld.N[r.slot] += 1024ull * r.frames; p->ld.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->ld.fresh[r.slot] = 0; }
     for (const auto& r : B.lim) { p->lim.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->lim.fresh[r.slot] = 0; }      /* ... and the limiter's held blocks change sides */
+    for (uint32_t s = 0; s < (uint32_t)B.tr_in.size(); s++) p->tr.Q[B.slots[s]] += B.tr_in[s];      /* ... and the trim's positions advance by what the streams brought */
     /* ... and the last good frames: a stream with units has been through the launch, which wrote the other side of its slot's state */
     if (B.plan) for (const auto& r : B.cn) if ((r.frame_units >> 8) & 0xffu) { p->cn.parity[r.slot] = (uint8_t)((r.state & 1u) ^ 1u); p->cn.fresh[r.slot] = 0; }
     L.ld_user = p->ld.out; L.ld_bytes = B.ld_floats * sizeof(float);

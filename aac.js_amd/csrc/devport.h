@@ -19,6 +19,7 @@
 #include "devport_limit_emu.h"
 #include "devport_truepeak_emu.h"
 #include "devport_conceal_emu.h"
+#include "devport_trim_emu.h"
 #else
 
 #include <hip/hip_runtime.h>
@@ -408,6 +409,13 @@ DP_DEVICE dpf4 dp_load_nt(const dpf4* p)
 {
     const dp_nv4 t = __builtin_nontemporal_load((const dp_nv4*)p);
     dpf4 r; r.x = t[0]; r.y = t[1]; r.z = t[2]; r.w = t[3]; return r;
+}
+/* streaming store of 16 bytes of integers (the trim stage's PCM, aacg_pcm_trim.h: elements moved as the bits they are).  The CPU twin:
+ * tests/emu/devport_trim_emu.h */
+DP_DEVICE void dp_store_nt(dpi4* p, dpi4 v)
+{
+    dp_nv4i t; t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+    __builtin_nontemporal_store(t, (dp_nv4i*)p);
 }
 /* two adjacent floats at an address that is only 4-byte aligned (odd channel counts): one
  * global_store_dwordx2 — gfx950 runs in unaligned-access mode, and the type says align 4 */

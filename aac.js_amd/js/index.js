@@ -343,6 +343,13 @@ GpuAACDecoder.prototype.unitsOfFrame = function (frame, frameSlot, blockBase, tn
  * which is what a caller of the reference sees frame by frame (decoder.js:125-201 throws at exactly that frame). */
 GpuAACDecoder.prototype.readChunk = function () {
     if (!this.queue.length) { if (this.shared && this.group) this.shared.flush(); else this.decodeAhead(); }
+    /* a SharedEngine({ trim }) decoder: a flush whose frames all lie outside the window delivers nothing and is not the stream's end —
+     * on, for as long as flushes still decode something */
+    while (!this.queue.length && this.trimmer && this.shared && this.group) {
+        const st = this.shared.stats, before = st.batches + st.units;
+        this.shared.flush();
+        if (st.batches + st.units === before) break;
+    }
     if (!this.queue.length) return null;
     const next = this.queue.shift();
     if (next instanceof Error) throw next;
@@ -396,15 +403,22 @@ GpuAACDecoder.prototype.fillBatch = function (part, blockBase, q, meta) {
 GpuAACDecoder.prototype.deliver = function (part, pcm, pcmBase, refused) {
     const C = this.config.chanConfig, mix = this.mix;      // mix: a SharedEngine({ downmix }) decoder on the parsing route — the device's rule on the host (mix.js)
     const rs = this.resampler;                             // ... and of a SharedEngine({ sampleRate }): the device's rule again (resample.js), behind the mix
+    const tr = this.trimmer;                               // ... and of a SharedEngine({ trim }): the device's rule once more (trim.js), behind the resampler
     if (part.frames.length) {
         if (refused) {
             this.queue.push(refused);
-            if (rs) for (let i = 0; i < part.frames.length; i++) rs.push(new Float32Array(FRAME * rs.C));      // silence flows through the filter: the clock goes on
+            for (let i = 0; i < part.frames.length && (rs || tr); i++) {       // silence flows through the filter and the window: the clock and the position go on
+                const n = rs ? rs.push(new Float32Array(FRAME * rs.C)).length / rs.C : FRAME;
+                if (tr) tr.position += n;
+            }
         }
         else for (let i = 0; i < part.frames.length; i++) {
             const at = pcmBase + i * FRAME * C;
             const frame = mix ? require('./mix.js').mix(pcm.subarray(at, at + FRAME * C), C, mix.matrix, mix.outChannels) : rs ? pcm.subarray(at, at + FRAME * C) : pcm.slice(at, at + FRAME * C);
-            this.queue.push(rs ? rs.push(frame) : frame);
+            const out = rs ? rs.push(frame) : frame;
+            if (!tr) { this.queue.push(out); continue; }
+            const kept = tr.take(out);                         // a frame that owns no kept sample delivers no chunk
+            if (kept) this.queue.push(kept.length === out.length ? out : kept.slice());
         }
     }
     if (part.failed) this.queue.push(part.failed);

@@ -48,6 +48,13 @@
  * each frame's share of the output, 341 or 342 samples per channel for 1024 at 1 / 3 — a variable length; a decoder on the parsing
  * route is resampled on the host by the same rule (resample.js), bit for bit; format.sampleRate says the new rate either way.  A stream
  * that has the engine's rate already is left alone.
+ * { trim: true } — opt-in; without it nothing differs.  Every decoder of the engine then has decoder.setTrim(skip, length): a window in
+ * samples of the stream's OWN rate (numbers, exact below 2^53; length left out: all of the rest) — the encoder's priming off the front,
+ * the padding off the end.  With sampleRate the engine converts it with the addon's trimDesign (aacg_trim_design: the resampler's
+ * group delay compensated, the residual in decoder.trimResidual).  A resident pipeline trims on the device (aacg_pipeline_set_trim:
+ * only the kept samples come down) and a batch is sliced frame by frame by aacg_trim_counts' rule (trim.js): a frame that owns no
+ * kept sample delivers no chunk, a refused frame's Error is delivered wherever it lies.  Decoders on the parsing route trim on the
+ * host by the same rule, so that both routes deliver the same chunks with the same lengths.
  * { resident: true, ragged: true, devicePlans: true, conceal: true | { fadeSteps, holdFrames } } — a frame the device refuses (a cut
  * packet, a bad scalefactor, a changed layout) repeats its stream's last good frame, fadeSteps scalefactor steps (1.5 dB; default 2)
  * further down per lost frame, for at most holdFrames (default 6) frames in a row (aacg_pipeline_set_concealment: the frame's records
@@ -90,6 +97,7 @@ function SharedEngine(opts) {
         const c = opts.conceal === true ? {} : opts.conceal;
         this.conceal = { fadeSteps: c.fadeSteps === undefined ? 2 : c.fadeSteps | 0, holdFrames: c.holdFrames === undefined ? 6 : c.holdFrames | 0 };
     }
+    this.trim = !!opts.trim;                              // decoder.setTrim(skip, length): trimmed on the device (resident) or by trim.js
     this.stats = { batches: 0, frames: 0, units: 0, engineNs: 0n, retries: 0, flushNs: 0n, concealedFrames: 0 };   // flushNs: resident flushes, host side and native calls
 }
 
@@ -116,6 +124,12 @@ SharedEngine.prototype.attach = function (dec) {
     dec.resampleSpec = this.sampleRate ? require('./resample.js').resolve(this.sampleRate, host.SAMPLE_RATES[cfg.sampleIndex], this.opts.addon || host.loadAddon()) : null;
     dec.resampler = dec.resampleSpec ? new (require('./resample.js').Resampler)(dec.resampleSpec, dec.mix ? dec.mix.outChannels : cfg.chanConfig) : null;
     if (dec.resampleSpec) dec.format.sampleRate = this.sampleRate;
+    /* trim: the decoder's window and position in samples of what it delivers (trim.js) — on the parsing route it cuts the chunks, on
+     * the resident route it mirrors the slot's on the device and says each frame's share of a batch's kept samples.  submitN0: the
+     * resampler's clock where the next batch to be ENQUEUED begins (the decoder's own resampler keeps the one of the next DELIVERED) */
+    dec.trimmer = this.trim ? new (require('./trim.js').Trimmer)(dec.mix ? dec.mix.outChannels : cfg.chanConfig, 0) : null;
+    dec.submitN0 = 0;
+    if (this.trim) { const shared = this; dec.setTrim = function (skip, length) { shared.setTrim(dec, skip, length); }; }
     if (this.takesResident(dec)) return this.attachResident(dec);
     let g = this.groups.get(cfg.sampleIndex);
     if (!g) {
@@ -165,9 +179,10 @@ SharedEngine.prototype.attachResident = function (dec) {
         if (dec.mix) create.mix = { outChannels: dec.mix.outChannels, matrix: dec.mix.matrix };      // mixed on the device: outChannels leave
         if (dec.resampleSpec) create.resample = dec.resampleSpec;      // resampled on the device, behind the mix: ragged PCM comes back
         if (this.conceal) create.conceal = this.conceal;      // refused frames repeat the stream's last good frame on the device
+        if (this.trim) create.trim = true;                    // each slot's window cut on the device, behind the resampler: ragged PCM comes back
         const pipeline = addon.pipelineCreate(create, rec.entries, rec.counts);
         /* channels: of the PCM that comes back — what sizes a flush's PCM and slices it into frames */
-        g = { resident: true, resample: dec.resampleSpec, addon: addon, pipeline: pipeline, channels: dec.mix ? dec.mix.outChannels : cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
+        g = { resident: true, trim: this.trim, resample: dec.resampleSpec, addon: addon, pipeline: pipeline, channels: dec.mix ? dec.mix.outChannels : cfg.chanConfig, outI16: outI16, decoders: [], free: [], next: 0, walks: [] };
         this.groups.set(key, g);
     }
     const slot = g.free.length ? g.free.pop() : g.next++;
@@ -177,8 +192,40 @@ SharedEngine.prototype.attachResident = function (dec) {
     /* 'mp4a': the packets in order, each { bytes, at: first byte not walked yet, ready: its blocks found and not yet taken, done,
      * inflight }; a new object per stream, so that a walk still in flight for the stream before is dropped when it comes back */
     dec.packets = dec.format && dec.format.formatID === 'mp4a' ? { q: [] } : null;
-    dec.engine = { resetStream: function (s) { g.addon.pipelineResetStream(g.pipeline, s); if (dec.resampler) dec.resampler.reset(); } };
+    dec.engine = { resetStream: function (s) { g.addon.pipelineResetStream(g.pipeline, s); if (dec.resampler) dec.resampler.reset(); dec.submitN0 = 0; if (dec.trimmer) dec.trimmer.reset(); } };
+    if (dec.trimmer) g.addon.pipelineSetStreamTrim(g.pipeline, slot, 0);      // a slot handed on starts with the default window
     g.decoders.push(dec);
+};
+
+/* decoder.setTrim(skip, length) of a SharedEngine({ trim: true }): the window in samples of the stream's own rate -> the window of what
+ * the decoder delivers (trimDesign where the engine resamples), set on the decoder's trimmer and, resident, on its slot of the pipeline:
+ * from the next batch enqueued, the position at 0 */
+SharedEngine.prototype.setTrim = function (dec, skip, length) {
+    if (!dec.trimmer) throw new Error('SharedEngine: setTrim needs { trim: true }');
+    let w = { skip: skip, keep: (length === undefined || length === null) ? null : length, residualNum: 0, residualDen: 1 };
+    require('./trim.js').design(w.skip, w.keep, false);      // (the limits, stated once for both routes)
+    if (dec.resampleSpec) w = (this.opts.addon || host.loadAddon()).trimDesign(skip, w.keep === null ? undefined : w.keep, false, dec.resampleSpec.L, dec.resampleSpec.M, dec.resampleSpec.taps);
+    dec.trimmer.set(w.skip, w.keep);
+    dec.trimResidual = { num: w.residualNum, den: w.residualDen };
+    if (dec.resident) dec.group.addon.pipelineSetStreamTrim(dec.group.pipeline, dec.stream, w.skip, w.keep === null ? undefined : w.keep);
+};
+
+/* a trimmed resident batch, in front of its native call: each frame's share of its stream's kept samples, from the decoders' windows
+ * and positions as they stand — which advance here, as the slots' do when the batch is enqueued.  -> what undoes it if the call fails */
+SharedEngine.prototype.trimShares = function (g, b) {
+    const rs = require('./resample.js'), tr = require('./trim.js'), R = g.resample, saved = [];
+    b.kept = new Uint32Array(b.N);
+    for (let s = 0; s < b.S; s++) {
+        const dec = b.part[s], t = dec.trimmer;
+        saved.push([dec, t.position, dec.submitN0]);
+        for (let f = 0, i = b.first[s]; f < b.counts[s]; f++, i++) {
+            const n = R ? rs.count(R.L, R.M, dec.submitN0, 1024) : 1024;
+            if (R) dec.submitN0 = (dec.submitN0 + 1024) % R.M;
+            b.kept[i] = tr.span(t.position, t.skip, t.keep, n).kept;
+            t.position += n;
+        }
+    }
+    return function () { for (const [dec, position, n0] of saved) { dec.trimmer.position = position; dec.submitN0 = n0; } };
 };
 
 SharedEngine.prototype.detach = function (dec) {
@@ -342,6 +389,26 @@ SharedEngine.prototype.deliverResident = function (g, b, out, failed) {
     this.stats.batches++; this.stats.units += b.N;
     if (failed) { for (const dec of part) dec.queue.push(failed); return; }
     const pcm = out.pcm, refused = out.refused, per = 1024 * C;
+    if (g.trim) {
+        /* ragged: stream s's out.lengths[s] kept samples lie behind those of the streams before it, frame f's share of them is
+         * b.kept (trimShares).  A frame that owns no kept sample delivers no chunk; a refused frame's Error is delivered wherever it lies */
+        for (let s = 0, at = 0; s < S; s++) {
+            const q = part[s].queue, r = part[s].resampler;
+            let sum = 0;
+            for (let f = 0, i = b.first[s]; f < b.counts[s]; f++, i++) {
+                const n = b.kept[i];
+                if (r) r.n0 = (r.n0 + 1024) % g.resample.M;      // (the delivered clock goes on, as without the trim)
+                const concealed = (results[8 * i + 3] & PARSE_CONCEALED) !== 0;
+                if (concealed) this.stats.concealedFrames++;
+                if (refused && results[8 * i] && !concealed) q.push(new Error(g.addon.parseStatusString(results[8 * i])));
+                else if (n) q.push(pcm.subarray(at * C, (at + n) * C));
+                at += n; sum += n;
+            }
+            if (sum !== out.lengths[s]) throw new Error('SharedEngine: the device kept ' + out.lengths[s] + ' samples of a stream where trim.js counts ' + sum);
+        }
+        this.stats.frames += b.N;
+        return;
+    }
     if (g.resample) {
         /* ragged: stream s's out.lengths[s] samples lie behind those of the streams before it, and frame f's share of them follows
          * from the stream's clock, which the decoder's resampler keeps (a refused frame was silence: its share is skipped, the clock
@@ -417,7 +484,8 @@ SharedEngine.prototype.flushResidentTimed = function (g) {
         this.walkReady(g, L);
         b = this.prepareResident(g, L);
         if (!b) return;
-        try { out = g.addon.pipelineDecode.apply(null, args(b)); } catch (err) { failed = err instanceof Error ? err : new Error(String(err)); }
+        const undo = g.trim ? this.trimShares(g, b) : null;
+        try { out = g.addon.pipelineDecode.apply(null, args(b)); } catch (err) { failed = err instanceof Error ? err : new Error(String(err)); if (undo) undo(); }
     }
     this.stats.engineNs += process.hrtime.bigint() - t0;
     this.deliverResident(g, b, out, failed);
@@ -425,8 +493,9 @@ SharedEngine.prototype.flushResidentTimed = function (g) {
         this.walkReady(g, 2 * L);
         const nb = this.prepareResident(g, 2 * L);
         if (nb) {
+            const undo = g.trim ? this.trimShares(g, nb) : null;
             try { g.addon.pipelineSubmit.apply(null, args(nb)); g.pending = nb; }
-            catch (err) { this.deliverResident(g, nb, null, err instanceof Error ? err : new Error(String(err))); }
+            catch (err) { if (undo) undo(); this.deliverResident(g, nb, null, err instanceof Error ? err : new Error(String(err))); }
         }
     }
     if (!g.walks.length) this.walkSubmit(g);               // the packets not walked yet: on the device while the caller reads this flush

@@ -69,6 +69,9 @@ static struct {
     int  (*pipeline_out_samples)(aacg_pipeline*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*);
     int  (*resample_design)(uint32_t, uint32_t, uint32_t, double, double, uint32_t*, uint32_t*, float*, size_t);
     int  (*pipeline_set_concealment)(aacg_pipeline*, const aacg_conceal_config*);
+    int  (*pipeline_set_trim)(aacg_pipeline*, const aacg_trim_config*);
+    int  (*pipeline_set_stream_trim)(aacg_pipeline*, uint32_t, uint64_t, uint64_t);
+    int  (*trim_design)(uint64_t, uint64_t, int, uint32_t, uint32_t, uint32_t, uint64_t*, uint64_t*, uint64_t*, uint64_t*);
     void* (*host_alloc)(size_t);
     void (*host_free)(void*);
 } L;
@@ -112,6 +115,7 @@ static int load_lib(napi_env env, const char* path)
     SYM(pipeline_set_mix, "aacg_pipeline_set_mix"); SYM(pipeline_out_channels, "aacg_pipeline_out_channels"); SYM(mix_standard, "aacg_mix_standard");
     SYM(pipeline_set_resample, "aacg_pipeline_set_resample"); SYM(pipeline_out_samples, "aacg_pipeline_out_samples"); SYM(resample_design, "aacg_resample_design");
     SYM(pipeline_set_concealment, "aacg_pipeline_set_concealment");
+    SYM(pipeline_set_trim, "aacg_pipeline_set_trim"); SYM(pipeline_set_stream_trim, "aacg_pipeline_set_stream_trim"); SYM(trim_design, "aacg_trim_design");
     SYM(host_alloc, "aacg_host_alloc"); SYM(host_free, "aacg_host_free");
 #undef SYM
     return 1;
@@ -134,7 +138,7 @@ static int get_i32(napi_env env, napi_value obj, const char* key, int32_t dflt)
 #define BOX_PIPELINE 0x4150504cu /* 'APPL' */
 #define PCM_RING_MAX 16
 typedef struct { uint32_t kind; void* ptr; pthread_mutex_t lock; int out_i16; /* engine / pipeline: AACG_OUTPUT_I16 */
-                 int resampled;   /* pipeline: made with { resample } — a batch's PCM is ragged, sized by aacg_pipeline_out_samples */
+                 int resampled;   /* pipeline: made with { resample } or { trim } — a batch's PCM is ragged, sized by aacg_pipeline_out_samples */
                  /* pipeline, { pcmRing: K }: K page-locked PCM buffers made once and handed out in turn (pipelineDecode) */
                  napi_ref ring_ab[PCM_RING_MAX]; void* ring_ptr[PCM_RING_MAX]; size_t ring_bytes; int ring_n; unsigned ring_next;
                  /* pipeline: the batches submitted and not yet collected, oldest first (pipelineSubmit / pipelineCollect) */
@@ -524,8 +528,10 @@ static void pipeline_finalize(napi_env env, void* data, void* hint)
     free(b);
 }
 
-/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix, resample, conceal}, entries, counts) -> external
- * (conceal: { fadeSteps, holdFrames } — aacg_pipeline_set_concealment before the call returns, with planMode 1: a refused frame repeats its
+/* pipelineCreate({deviceOrdinal, sampleIndex, maxStreams, channels, maxFrames, outputKind, parseOptions, lanes, planMode, stages, mix, resample, conceal, trim}, entries, counts) -> external
+ * (trim: true — aacg_pipeline_set_trim behind the mix and the resampler, before the call returns, every slot's window (0, all) until
+ * pipelineSetStreamTrim says otherwise: only the kept samples come back, ragged per stream (pipelineDecode's lengths), possibly none;
+ * conceal: { fadeSteps, holdFrames } — aacg_pipeline_set_concealment before the call returns, with planMode 1: a refused frame repeats its
  * stream's last good frame, fading, and its result carries AACG_PARSE_CONCEALED in byte 3; a refused setting destroys the pipeline and throws;
  * resample: { L, M, taps, table: Float32Array(L * taps) } — aacg_pipeline_set_resample behind the mix, before the call returns: the PCM leaves
  * at L / M times the streams' rate, ragged per stream (pipelineDecode's lengths); a refused resampler destroys the pipeline and throws;
@@ -608,6 +614,19 @@ static napi_value js_pipeline_create(napi_env env, napi_callback_info info)
             else if ((rc = L.pipeline_set_concealment(p, &cc)))
                 snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_concealment failed (%d): %.800s", rc, L.pipeline_last_error(p));
             if (msg[0]) { L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL; }
+        }
+    }
+    {   /* trim: true — aacg_pipeline_set_trim, behind the mix and the resampler */
+        napi_value tv; bool has = false, on = false;
+        if (napi_has_named_property(env, argv[0], "trim", &has) == napi_ok && has && napi_get_named_property(env, argv[0], "trim", &tv) == napi_ok &&
+            napi_coerce_to_bool(env, tv, &tv) == napi_ok && napi_get_value_bool(env, tv, &on) == napi_ok && on) {
+            const aacg_trim_config tc = {0u, AACG_TRIM_ALL};
+            if ((rc = L.pipeline_set_trim(p, &tc))) {
+                char msg[1024];
+                snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_trim failed (%d): %.800s", rc, L.pipeline_last_error(p));
+                L.pipeline_destroy(p); napi_throw_error(env, NULL, msg); return NULL;
+            }
+            resampled = 1;                              /* ragged: the kept counts */
         }
     }
     handle_box* b = box_new(BOX_PIPELINE, p);
@@ -812,7 +831,7 @@ static pipe_job* pipe_prepare(napi_env env, napi_callback_info info, int keep_ar
         for (size_t s = 0; s < ns; s++) { samples += lengths[s]; cnt[s] = lengths[s]; }
         lengths = cnt;                                  /* (the block's first half now holds them: one allocation, freed as one) */
     }
-    const size_t elems = samples * C, bytes = elems * (pb->out_i16 ? 2u : 4u);
+    const size_t elems = samples * C, bytes = elems ? elems * (pb->out_i16 ? 2u : 4u) : 16u;      /* (a trimmed batch may keep nothing: a buffer all the same) */
     size_t got = 0;
     void* pcm = NULL;
     int slot = -1;
@@ -1103,6 +1122,63 @@ static napi_value js_mix_standard(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* a count of samples from a JavaScript number: an integer in 0 .. 2^53 - 1; `all`: undefined / null mean AACG_TRIM_ALL */
+static int get_samples(napi_env env, napi_value v, int all, uint64_t* out)
+{
+    napi_valuetype vt = napi_undefined;
+    double d = 0.0;
+    if (napi_typeof(env, v, &vt) != napi_ok) return 0;
+    if (all && (vt == napi_undefined || vt == napi_null)) { *out = AACG_TRIM_ALL; return 1; }
+    if (vt != napi_number || napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0.0) || d > 9007199254740991.0 || d != (double)(uint64_t)d) return 0;
+    *out = (uint64_t)d;
+    return 1;
+}
+
+/* pipelineSetStreamTrim(pipeline, slot, skip [, keep]): aacg_pipeline_set_stream_trim — the slot's window (keep absent: all) and position 0,
+ * from the next batch enqueued that holds the slot */
+static napi_value js_pipeline_set_stream_trim(napi_env env, napi_callback_info info)
+{
+    size_t argc = 4; napi_value argv[4], out;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    handle_box* pb = argc >= 3 ? box_of(env, argv[0], BOX_PIPELINE, "aacgpu: bad pipeline handle") : NULL;
+    uint32_t slot = 0; uint64_t skip = 0, keep = AACG_TRIM_ALL;
+    if (!pb) { if (argc < 3) napi_throw_type_error(env, NULL, "pipelineSetStreamTrim(pipeline, slot, skip [, keep])"); return NULL; }
+    if (napi_get_value_uint32(env, argv[1], &slot) != napi_ok || !get_samples(env, argv[2], 0, &skip) || (argc >= 4 && !get_samples(env, argv[3], 1, &keep))) {
+        napi_throw_type_error(env, NULL, "pipelineSetStreamTrim(pipeline, slot, skip [, keep]): counts of samples are integers in 0 .. 2^53 - 1"); return NULL; }
+    pthread_mutex_lock(&pb->lock);
+    const int rc = L.pipeline_set_stream_trim((aacg_pipeline*)pb->ptr, slot, skip, keep);
+    char msg[1024] = "";
+    if (rc) snprintf(msg, sizeof msg, "aacgpu: aacg_pipeline_set_stream_trim failed (%d): %.800s", rc, L.pipeline_last_error((aacg_pipeline*)pb->ptr));
+    pthread_mutex_unlock(&pb->lock);
+    if (rc) { napi_throw_error(env, NULL, msg); return NULL; }
+    CHECK(env, napi_get_undefined(env, &out));
+    return out;
+}
+
+/* trimDesign(skipIn, keepIn | undefined, limiter, L, M, taps) -> { skip, keep | null, residualNum, residualDen }: aacg_trim_design
+ * (include/aacgpu.h) — the window at the trim's input for a window in the stream's own samples; host code, no device */
+static napi_value js_trim_design(napi_env env, napi_callback_info info)
+{
+    size_t argc = 6; napi_value argv[6], out, v;
+    CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (!L.dl) { napi_throw_error(env, NULL, "aacgpu: call load(path) first"); return NULL; }
+    uint64_t skip_in = 0, keep_in = AACG_TRIM_ALL, skip = 0, keep = 0, num = 0, den = 1;
+    uint32_t rl = 1, rm = 1, taps = 0; bool limiter = false;
+    if (argc < 1 || !get_samples(env, argv[0], 0, &skip_in) || (argc >= 2 && !get_samples(env, argv[1], 1, &keep_in)) ||
+        (argc >= 3 && (napi_coerce_to_bool(env, argv[2], &v) != napi_ok || napi_get_value_bool(env, v, &limiter) != napi_ok)) ||
+        (argc >= 6 && (napi_get_value_uint32(env, argv[3], &rl) != napi_ok || napi_get_value_uint32(env, argv[4], &rm) != napi_ok || napi_get_value_uint32(env, argv[5], &taps) != napi_ok))) {
+        napi_throw_type_error(env, NULL, "trimDesign(skipIn, keepIn | undefined, limiter [, L, M, taps])"); return NULL; }
+    const int rc = L.trim_design(skip_in, keep_in, limiter ? 1 : 0, rl, rm, taps, &skip, &keep, &num, &den);
+    if (rc) { char msg[128]; snprintf(msg, sizeof msg, "aacgpu: aacg_trim_design failed (%d)", rc); napi_throw_error(env, NULL, msg); return NULL; }
+    CHECK(env, napi_create_object(env, &out));
+    CHECK(env, napi_create_double(env, (double)skip, &v)); CHECK(env, napi_set_named_property(env, out, "skip", v));
+    if (keep == AACG_TRIM_ALL) CHECK(env, napi_get_null(env, &v)); else CHECK(env, napi_create_double(env, (double)keep, &v));
+    CHECK(env, napi_set_named_property(env, out, "keep", v));
+    CHECK(env, napi_create_double(env, (double)num, &v)); CHECK(env, napi_set_named_property(env, out, "residualNum", v));
+    CHECK(env, napi_create_double(env, (double)den, &v)); CHECK(env, napi_set_named_property(env, out, "residualDen", v));
+    return out;
+}
+
 /* resampleDesign(inRate, outRate, taps [, rolloff, beta]) -> { L, M, taps, table: Float32Array(L * taps) }: the project's default
  * resampling table (aacg_resample_design, include/aacgpu.h), what pipelineCreate({ resample }) takes; host code, no device */
 static napi_value js_resample_design(napi_env env, napi_callback_info info)
@@ -1200,6 +1276,8 @@ static napi_value init(napi_env env, napi_value exports)
         {"pipelineOutChannels", NULL, js_pipeline_out_channels, NULL, NULL, NULL, napi_default, NULL},
         {"mixStandard", NULL, js_mix_standard, NULL, NULL, NULL, napi_default, NULL},
         {"resampleDesign", NULL, js_resample_design, NULL, NULL, NULL, napi_default, NULL},
+        {"pipelineSetStreamTrim", NULL, js_pipeline_set_stream_trim, NULL, NULL, NULL, napi_default, NULL},
+        {"trimDesign", NULL, js_trim_design, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineLaunchCounts", NULL, js_pipeline_launch_counts, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkSubmit", NULL, js_pipeline_walk_submit, NULL, NULL, NULL, napi_default, NULL},
         {"pipelineWalkCollect", NULL, js_pipeline_walk_collect, NULL, NULL, NULL, napi_default, NULL},

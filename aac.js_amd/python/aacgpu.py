@@ -44,7 +44,8 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_loudness_design", "aacg_loudness_integrate",
                "aacg_pipeline_set_limiter", "aacg_pipeline_set_gain", "aacg_pipeline_gain", "aacg_limiter_design",
                "aacg_pipeline_set_true_peak", "aacg_pipeline_true_peak_out", "aacg_true_peak_design",
-               "aacg_conceal_state_bytes", "aacg_plan_conceal_refused", "aacg_pipeline_set_concealment", "aacg_pipeline_concealed"]
+               "aacg_conceal_state_bytes", "aacg_plan_conceal_refused", "aacg_pipeline_set_concealment", "aacg_pipeline_concealed",
+               "aacg_pipeline_set_trim", "aacg_pipeline_set_stream_trim", "aacg_pipeline_stream_trim", "aacg_trim_counts", "aacg_trim_design"]
 # ... and include/aacgpu_tools.h (measurement and diagnostics: bench.py, tools/, tests)
 TOOLS_SYMBOLS = ["aacg_calib_copy", "aacg_timer_create", "aacg_timer_record", "aacg_timer_elapsed_ms", "aacg_timer_destroy",
                  "aacg_pipeline_chained", "aacg_pipeline_concurrent", "aacg_decode_pipelined_timed", "aacg_debug_transform", "aacg_debug_set_route", "aacg_debug_route", "aacg_debug_run_kernel",
@@ -146,6 +147,14 @@ CONCEAL_STREAM_DTYPE = np.dtype([(n, "<u4") for n in ("frame_first", "frames", "
 
 
 LIMIT_BLOCK = 64                                     # AACG_LIMIT_BLOCK: samples of a limiter block, and its delay
+
+
+# aacg_trim_config: the window (skip, keep) every slot of a pipeline with a trim starts with (aacg_pipeline_set_trim)
+class TrimConfig(C.Structure):
+    _fields_ = [("skip", C.c_uint64), ("keep", C.c_uint64)]
+
+
+TRIM_ALL = 2 ** 64 - 1                               # AACG_TRIM_ALL: a window without an end
 
 
 # aacg_shape_stream: one stream of a batch in the table a plan made by aacg_plan_create_shaped is shaped from
@@ -345,6 +354,11 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_set_true_peak.argtypes = [C.c_void_p, C.POINTER(TruePeakConfig)]
     L.aacg_pipeline_true_peak_out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.aacg_true_peak_design.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_size_t]
+    L.aacg_pipeline_set_trim.argtypes = [C.c_void_p, C.POINTER(TrimConfig)]
+    L.aacg_pipeline_set_stream_trim.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]
+    L.aacg_pipeline_stream_trim.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.aacg_trim_counts.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.aacg_trim_design.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint64)] * 4
     _lib = L
     return L
 
@@ -558,12 +572,16 @@ class Pipeline:
     take_true_peak gives a batch's, a list of (n_out[s], in_channels) float32 arrays.  Every other call returns what it returns without it.
     conceal: True, or a dict(fade_steps=, hold_frames=), for set_concealment (aacg_pipeline_set_concealment), with device_plans: a frame
     the parser or the refresh refuses repeats its stream's last good frame, fading, instead of going silent; its result keeps its status
-    and gains PARSE_CONCEALED in `flags`.  concealed() counts such frames of collected batches."""
+    and gains PARSE_CONCEALED in `flags`.  concealed() counts such frames of collected batches.
+    trim: True, or a (skip, keep) pair (keep None: no end), for set_pipeline_trim (aacg_pipeline_set_trim): the last PCM stage, behind the
+    resampler and in front of the feature stage.  Each slot has a window in samples of what the stage receives (set_trim, stream_trim;
+    trim_design converts a window in the stream's own samples and compensates the limiter's and the resampler's delays), and only the
+    kept samples leave, a ragged count per stream: decode, collect and decode_tensor return lengths as for a resampled pipeline."""
 
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
                  carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None, true_peak=None,
-                 conceal=None):
+                 conceal=None, trim=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -585,6 +603,7 @@ class Pipeline:
         self.true_peak, self._tp, self._tp_last, self._tp_armed = None, {}, None, None
         self._keep = {}
         self.conceal = None
+        self.trim = None
         if conceal is not None and conceal is not False:
             try:
                 self.set_concealment(**({} if conceal is True else dict(conceal)))
@@ -617,6 +636,12 @@ class Pipeline:
             try:
                 self.set_resample(*resample)
             except (AacgError, ValueError):
+                self.close()
+                raise
+        if trim is not None and trim is not False:
+            try:
+                self.set_pipeline_trim(*((0, None) if trim is True else trim))
+            except (AacgError, ValueError, TypeError):
                 self.close()
                 raise
         if features is not None:
@@ -731,6 +756,26 @@ class Pipeline:
         if rc != 0:
             raise AacgError(rc, "aacg_pipeline_concealed")
         return int(n.value)
+
+    def set_pipeline_trim(self, skip=0, keep=None):
+        """aacg_pipeline_set_trim: the stage, with the window (skip, keep) every slot starts with (keep None: no end); before the first
+        batch and after the mix, the limiter and the resampler"""
+        cfg = TrimConfig(int(skip), TRIM_ALL if keep is None else int(keep))
+        self._check(self.lib.aacg_pipeline_set_trim(self.handle, C.byref(cfg)))
+        self.trim = (int(skip), None if keep is None else int(keep))
+
+    def set_trim(self, slot, skip, keep=None):
+        """aacg_pipeline_set_stream_trim: the slot's window (keep None: no end) and position 0, from the next batch enqueued that holds
+        the slot; a reset leaves the window and restarts the position"""
+        self._check(self.lib.aacg_pipeline_set_stream_trim(self.handle, int(slot), int(skip), TRIM_ALL if keep is None else int(keep)))
+
+    def stream_trim(self, slot):
+        """aacg_pipeline_stream_trim: (skip, keep, position) of the slot as they stand, keep None: no end"""
+        s, k, q = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.aacg_pipeline_stream_trim(self.handle, int(slot), C.byref(s), C.byref(k), C.byref(q))
+        if rc != 0:
+            raise AacgError(rc, "aacg_pipeline_stream_trim(slot %d): no trim, or no such slot" % int(slot))
+        return int(s.value), None if k.value == TRIM_ALL else int(k.value), int(q.value)
 
     def set_gain(self, slot, gain):
         """aacg_pipeline_set_gain: the slot's gain (0..1024) from the next batch enqueued that holds the slot; a reset leaves it"""
@@ -856,7 +901,7 @@ class Pipeline:
         assert frames.dtype == PARSE_FRAME_DTYPE and len(frames) == total
         n = len(frames)
         # a resampled pipeline: what each stream will emit (the clocks stand still until the batch is enqueued)
-        self._ragged = bool(self.resample or self.features)
+        self._ragged = bool(self.resample or self.features or self.trim)
         self._lengths = self.out_samples(slots, frames_per_stream).astype(np.int64) if self._ragged else None
         samples = int(self._lengths.sum()) if self._ragged else n * 1024
         width, dtype = (self.features["n_mels"], np.float32) if self.features else (self.channels, np.int16 if self.i16 else np.float32)
@@ -934,12 +979,12 @@ class Pipeline:
         slots = np.ascontiguousarray(slots, np.uint32)
         counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
         assert len(counts) == len(slots) and frames.dtype == PARSE_FRAME_DTYPE and len(frames) == int(counts.sum())
-        lengths = self.out_samples(slots, counts).astype(np.int64) if self.resample or self.features else None
+        lengths = self.out_samples(slots, counts).astype(np.int64) if self.resample or self.features or self.trim else None
         if planar and stride_frames is None:
             if self.features:                                     # rows of feature frames: the longest stream's count (at least one)
                 stride_frames = max(int(lengths.max()) if len(lengths) else 0, 1)
             else:
-                stride_frames = (int(counts.max()) if len(counts) else 0) if lengths is None else (int(lengths.max()) + 1023) // 1024
+                stride_frames = (int(counts.max()) if len(counts) else 0) if lengths is None else max((int(lengths.max()) + 1023) // 1024, 1 if self.trim else 0)
         desc = PcmDeviceOut(addr, nbytes, (PCM_PLANAR if planar else PCM_PACKED) if layout is None else int(layout), int(stride_frames or 0))
         res, refused, t = np.zeros(len(frames), PARSE_RESULT_DTYPE), C.c_uint32(0), C.c_uint64()
         loud = self._arm_loudness(slots, counts)
@@ -975,9 +1020,9 @@ class Pipeline:
         slots = np.ascontiguousarray(slots, np.uint32)
         counts = np.ascontiguousarray(frames_per_stream, np.uint32) if np.ndim(frames_per_stream) else np.full(len(slots), int(frames_per_stream), np.uint32)
         shape = (len(slots), self.channels, int(counts.max()) * 1024) if planar else (int(counts.sum()), 1024, self.channels)
-        if self.resample:                                         # rows of whole kilosamples that hold the longest stream; packed: flat (samples, C)
+        if self.resample or self.trim:                            # rows of whole kilosamples that hold the longest stream (a trim: at least one); packed: flat (samples, C)
             n_out = self.out_samples(slots, counts)
-            shape = (len(slots), self.channels, (int(n_out.max()) + 1023) // 1024 * 1024) if planar else (int(n_out.sum()), self.channels)
+            shape = (len(slots), self.channels, max((int(n_out.max()) + 1023) // 1024, 1 if self.trim else 0) * 1024) if planar else (int(n_out.sum()), self.channels)
         if self.features:                                         # (S, n_mels, T) with T the longest stream's feature frames; packed: flat (frames, n_mels)
             n_out = self.out_samples(slots, counts)
             shape = (len(slots), self.features["n_mels"], max(int(n_out.max()), 1)) if planar else (int(n_out.sum()), self.features["n_mels"])
@@ -987,6 +1032,31 @@ class Pipeline:
         self.wait_device(t)
         out, res, refused, *lengths = self.collect(t)
         return out, lengths[0] if lengths else counts.astype(np.int64) * 1024, res, refused
+
+
+def trim_design(skip_in, keep_in=None, limiter=False, resample=None):
+    """aacg_trim_design: the window at the trim's input for a window (skip_in, keep_in) in samples of the stream's own rate and time —
+    (skip, keep, residual) with keep None for no end and residual a fractions.Fraction in [0, 1) output samples.  limiter: the pipeline
+    has one (64 samples of delay); resample: the pipeline's (L, M, table) or (L, M, taps) with a linear-phase table.  Host code, exact."""
+    import fractions
+    L, M, taps = (1, 1, 0) if resample is None else (int(resample[0]), int(resample[1]), int(resample[2]) if np.ndim(resample[2]) == 0 else int(np.shape(resample[2])[1]))
+    s, k, num, den = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = load_library().aacg_trim_design(int(skip_in), TRIM_ALL if keep_in is None else int(keep_in), 1 if limiter else 0, L, M, taps,
+                                         C.byref(s), C.byref(k), C.byref(num), C.byref(den))
+    if rc != 0:
+        raise AacgError(rc, "aacg_trim_design(%d, %r, %d / %d, %d taps)" % (skip_in, keep_in, L, M, taps))
+    return int(s.value), None if k.value == TRIM_ALL else int(k.value), fractions.Fraction(int(num.value), int(den.value))
+
+
+def trim_counts(position, skip, keep, n_in):
+    """aacg_trim_counts: (first_of, kept_of), uint32 arrays — of consecutive pieces of n_in[i] samples, the first at `position`, piece
+    i keeps kept_of[i] samples beginning at its first_of[i]-th under the window (skip, keep), keep None: no end.  Host code."""
+    n_in = np.ascontiguousarray(n_in, np.uint32)
+    first, kept = np.zeros(len(n_in), np.uint32), np.zeros(len(n_in), np.uint32)
+    rc = load_library().aacg_trim_counts(int(position), int(skip), TRIM_ALL if keep is None else int(keep), n_in.ctypes.data, len(n_in), first.ctypes.data, kept.ctypes.data)
+    if rc != 0:
+        raise AacgError(rc, "aacg_trim_counts(%d, %d, %r)" % (position, skip, keep))
+    return first, kept
 
 
 def mix_standard(channels, out_channels, surround_gain=2 ** -0.5, normalise=True):

@@ -1237,6 +1237,69 @@ int  aacg_pipeline_set_concealment(aacg_pipeline* p, const aacg_conceal_config* 
 /* The frames concealed so far in batches that have been collected.  AACG_ERR_INVALID_ARG: a null pipeline or count. */
 int  aacg_pipeline_concealed(const aacg_pipeline* p, uint64_t* count);
 
+/* ---- the resident route: trim, a skip and a length per stream ----------------------------------------------------------------------
+ * Every AAC stream begins with samples that are not programme — the encoder's priming, 2112 samples commonly, 1024 otherwise — and
+ * ends with padding up to a whole frame; containers say how much (MP4 edit lists, iTunSMPB, a server's index), and the CALLER knows it:
+ * nothing here reads it from the bit stream.  A pipeline may carry a TRIM, the last PCM stage of the way out: behind the resampler (or
+ * the limiter, the mix or the transform, whichever wrote last) and in front of the feature stage.  Only the kept samples cross the link.
+ * THE RULE.  Each stream slot has a window (skip S, keep K) and a position Q, all three in samples per channel OF WHAT THE STAGE
+ * RECEIVES — the outgoing rate, after the limiter's delay —, 64-bit, held on the host.  K = AACG_TRIM_ALL: no end; S and a finite K
+ * are below 2^40.  A batch in which the slot's stream brings n_in samples (1024 x frames, or the resampler's n_out) keeps the received
+ * samples with index q in [Q, Q + n_in) n [S, S + K): one contiguous range of n_keep samples, possibly none, copied bit for bit.  Q
+ * advances by n_in when the batch has been enqueued; a refused or failed submission leaves it alone, like the resampler's clock.  A
+ * refused frame, a concealed frame and a frame of an unlearnt stream count their samples like any other.  Any split of a stream's frames
+ * into batches gives the same bits.  A pipeline with the stage and every window at its default (0, AACG_TRIM_ALL) delivers, bit for bit
+ * and count for count, what it delivers without the stage; a pipeline without the stage differs in nothing, call for call.
+ * Output layouts are the resampler's with n_keep[s] in the place of n_out[s]: host PCM and AACG_PCM_PACKED [stream s][n_keep[s]][O],
+ * tight; AACG_PCM_PLANAR [stream][O][stride_frames x 1024] with the padding behind n_keep[s] written as zeros, every element of the block
+ * written exactly once and nothing outside it — stride_frames in 1..2^21, stride_frames x 1024 at least every n_keep[s].  A stream may
+ * emit nothing in a batch and a batch nothing at all (host and packed memory are then untouched, a planar block is zeros); results,
+ * statuses, refusal counts and tickets are the untrimmed batch's.  aacg_pipeline_out_samples reports the trimmed counts — with a feature
+ * stage the feature frames that follow from them: that stage then takes each stream's kept range as its input, its clock counts kept
+ * samples only, and the trim launches nothing.  The meter and the true-peak stage tap the transform's PCM and do not see the trim.
+ * One more launch per batch (aacg_pcm_trim_*) on the lane's stream, with no device state: nothing orders it behind the previous batch's.
+ * Limit: max_streams x max_frames x 1024 (x L / M) below 2^31.  Device memory: every lane gets a buffer for a HOST batch's trimmed PCM, sized
+ * for the largest untrimmed batch (max_streams x max_frames x 1024 (x L / M) x O elements) — device batches do not use it; it is not
+ * made when a feature stage is set already, and stays when one is set afterwards.
+ * aacg_pipeline_set_trim: cfg holds the window every slot starts with.  Called once, before the pipeline's first submitted batch and
+ * after aacg_pipeline_set_mix, aacg_pipeline_set_limiter and aacg_pipeline_set_resample where those are used (they refuse behind it);
+ * its order relative to aacg_pipeline_set_features, _set_loudness and _set_concealment is free.  AACG_ERR_INVALID_ARG, with the reason in
+ * aacg_pipeline_last_error and the pipeline exactly as it was: a null config, a value outside the limits, a call after the first batch,
+ * a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the lanes' trimmed PCM; the pipeline stays as it was.
+ * JavaScript: SharedEngine({ trim: true }) and decoder.setTrim(skip, length) (aac.js_amd/js/shared_engine.js).
+ * Not here: windows of more than one segment, fades at the cuts, a flush of what the limiter and the resampler still hold at a stream's
+ * end, a trim in the stream's own samples in front of those stages (aacg_trim_design converts instead). */
+#define AACG_TRIM_ALL UINT64_MAX
+typedef struct aacg_trim_config {
+    uint64_t skip;             /* S of every slot until aacg_pipeline_set_stream_trim says otherwise */
+    uint64_t keep;             /* K; AACG_TRIM_ALL: no end */
+} aacg_trim_config;
+int  aacg_pipeline_set_trim(aacg_pipeline* p, const aacg_trim_config* cfg);
+/* A slot's window: sets (S, K) and Q = 0.  May be called at any time on a pipeline with a trim; it takes effect with the next batch
+ * ENQUEUED that holds the slot and does not wait for batches in flight (a batch's ranges went up with its launch).
+ * aacg_pipeline_reset_stream sets Q = 0 and LEAVES the window: it is the caller's setting, like a gain.  AACG_ERR_INVALID_ARG: a
+ * pipeline without a trim, a slot out of range, a value outside the limits. */
+int  aacg_pipeline_set_stream_trim(aacg_pipeline* p, uint32_t slot, uint64_t skip, uint64_t keep);
+/* ... and reads the three back (any of the pointers may be null).  AACG_ERR_INVALID_ARG: a pipeline without a trim, a slot out of range. */
+int  aacg_pipeline_stream_trim(const aacg_pipeline* p, uint32_t slot, uint64_t* skip, uint64_t* keep, uint64_t* position);
+/* Host code only (no device, no pipeline): the share of the kept range that each of n consecutive pieces owns, by the rule above — piece
+ * i brings n_in[i] samples, the first at `position`; it keeps kept_of[i] of them beginning at its first_of[i]-th (0 where it keeps
+ * none).  With the frames of a batch as the pieces this is the per-frame slicing of the batch's kept PCM: the kept ranges lie one behind
+ * the other in the output.  AACG_ERR_INVALID_ARG: a null pointer, skip or a finite keep at or above 2^40, a position that would wrap. */
+int  aacg_trim_counts(uint64_t position, uint64_t skip, uint64_t keep, const uint32_t* n_in, uint32_t n, uint32_t* first_of, uint32_t* kept_of);
+/* Host code only, exact integers: the window at the stage's input for a window (skip_in, keep_in) given in samples of the STREAM'S OWN
+ * rate and time, with the route's latencies compensated — the limiter's AACG_LIMIT_BLOCK samples (limiter != 0) and a linear-phase
+ * table's (L taps - 1) / (2 L) input samples.  With A(t) = 2 L t + 128 L limiter + L taps - 1:
+ *     skip = ceil(A(skip_in) / 2M),   keep = ceil(A(skip_in + keep_in) / 2M) - skip   (AACG_TRIM_ALL stays AACG_TRIM_ALL),
+ *     residual = skip - A(skip_in) / 2M = residual_num / residual_den, in [0, 1) output samples: how far behind the exact place of
+ *     sample skip_in the first kept output sample lies (residual_num and residual_den may be null).
+ * Without a resampler pass L = M = 1 and taps = 0; the filter term is then left out: skip = skip_in + 64 limiter, keep = keep_in.  A
+ * caller-supplied table that is NOT linear-phase has whatever delay its designer gave it: compensate that by hand.
+ * AACG_ERR_INVALID_ARG: a null skip or keep, L or M outside 1..1024, taps above 64, skip_in or a finite keep_in at or above 2^40, or a
+ * result there. */
+int  aacg_trim_design(uint64_t skip_in, uint64_t keep_in, int limiter, uint32_t L, uint32_t M, uint32_t taps, uint64_t* skip, uint64_t* keep,
+                      uint64_t* residual_num, uint64_t* residual_den);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,14 @@
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
- *                                         [--loudness [--true-peak]] [--limiter] [--conceal] [--drop-every N]
+ *                                         [--loudness [--true-peak]] [--limiter] [--conceal] [--drop-every N] [--trim SKIP[:KEEP]]
+ *
+ * --trim SKIP[:KEEP]: a trim as the last PCM stage (aacg_pipeline_set_trim: every slot's window skips SKIP samples of what the stage
+ * receives and keeps KEEP, all of the rest if left out): one more launch per batch (aacg_pcm_trim_*) behind the resampler, none with
+ * --features, whose records take the window instead.  The tool feeds every slot one endless stream, so the window's cuts fall into the
+ * warm-up or behind the run and a timed batch keeps ALL it receives: the line's time is the stage's cost at its most, and it carries
+ * the window and a device-to-device aacg_calib_copy of the bytes the trim kernel reads, timed in the same run.  Combines with
+ * everything else.
  *
  * --conceal (with --device-plans): refused frames repeat their stream's last good frame, fading 2 scalefactor steps a frame for at most
  * 6 frames (aacg_pipeline_set_concealment): one more small launch per batch (aacg_units_conceal) between the refresh and the carry.
@@ -94,6 +101,8 @@ int main(int argc, char** argv)
     uint32_t mix = 0, rate = 0;
     bool features = false, loudness = false, limiter = false, true_peak = false, conceal = false;
     uint32_t drop_every = 0;
+    bool trim = false;
+    uint64_t trim_skip = 0, trim_keep = AACG_TRIM_ALL;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) std::exit(2); return argv[++i]; };
@@ -120,6 +129,13 @@ int main(int argc, char** argv)
         else if (a == "--limiter") limiter = true;
         else if (a == "--conceal") conceal = true;
         else if (a == "--drop-every") drop_every = (uint32_t)std::atoi(val());
+        else if (a == "--trim") {
+            const std::string v = val();
+            const size_t colon = v.find(':');
+            trim = true;
+            trim_skip = std::strtoull(v.c_str(), nullptr, 10);
+            if (colon != std::string::npos) trim_keep = std::strtoull(v.c_str() + colon + 1, nullptr, 10);
+        }
         else if (a == "--seed") seed = (uint64_t)std::atoll(val());
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -184,6 +200,10 @@ int main(int argc, char** argv)
         std::vector<float> table(16384);
         if (!rates[sample_index] || (rc = aacg_resample_design(rates[sample_index], rate, 32, 0.0, 0.0, &rs_L, &rs_M, table.data(), table.size()))) { std::fprintf(stderr, "aacg_resample_design(%u -> %u): %d\n", rates[sample_index], rate, rc); return 2; }
         if ((rc = aacg_pipeline_set_resample(p, rs_L, rs_M, 32, table.data()))) { std::fprintf(stderr, "aacg_pipeline_set_resample: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
+    if (trim) {                                             /* behind the resampler, in front of the feature stage */
+        const aacg_trim_config tc = {trim_skip, trim_keep};
+        if ((rc = aacg_pipeline_set_trim(p, &tc))) { std::fprintf(stderr, "aacg_pipeline_set_trim: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
     const uint32_t ft_K = 400, ft_H = 160, ft_bins = 201, ft_mels = 80;
     if (features) {
@@ -311,6 +331,8 @@ int main(int argc, char** argv)
     }
     if (mix) unmixed_copy_us = calib(unmixed_bytes, nullptr);
     const double resample_in_copy_us = rate ? calib(resample_in_bytes, nullptr) : 0.0;
+    const size_t trim_in_bytes = (size_t)S * most * out_channels * (i16 ? 2 : 4);      /* what the trim kernel reads at most: what the stage before it emits */
+    const double trim_in_copy_us = trim && !features ? calib(trim_in_bytes, nullptr) : 0.0;
     bool finite = true, nonzero = false;
     uint32_t bad = 0;
     for (int k = 0; k < n_out; k++) bad += refused[k];
@@ -344,14 +366,17 @@ int main(int argc, char** argv)
         std::snprintf(conceal_key, sizeof conceal_key, "\"conceal\": %s, \"conceal_fade_steps\": %u, \"conceal_hold_frames\": %u, \"drop_every\": %u, \"frames_dropped_per_batch\": %u, \"frames_concealed\": %llu, ",
                       conceal ? "true" : "false", conceal_cfg.fade_steps, conceal_cfg.hold_frames, drop_every, dropped, (unsigned long long)concealed);
     }
+    char trim_key[192] = "";                                /* --trim only */
+    if (trim) std::snprintf(trim_key, sizeof trim_key, "\"trim_skip\": %llu, \"trim_keep\": %s, \"trim_in_bytes_per_batch\": %zu, \"d2d_copy_of_trim_in_us\": %.2f, ", (unsigned long long)trim_skip,
+                            trim_keep == AACG_TRIM_ALL ? "\"all\"" : std::to_string(trim_keep).c_str(), trim_in_bytes, trim_in_copy_us);
     if (drop_every) bad = 0;                                /* (the refusals are the dropped frames': expected) */
-    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s%s%s"
+    std::printf("{\"tool\": \"resident_drive\", \"mode\": \"%s\", \"lanes\": %d, \"streams\": %u, \"frames_per_stream\": %u, \"channels\": %u, \"pcm\": \"%s\", \"pcm_memory\": \"%s\", %s%s%s%s%s%s%s%s"
                 "\"bytes_per_batch\": %zu, \"pcm_bytes_per_batch\": %zu, \"ms_per_batch_median\": %.4f, \"ms_per_batch_min\": %.4f, \"ms_per_batch_max\": %.4f, \"frames_per_s\": %.4g, "
                 "\"pcm_GBs\": %.2f, \"plan_mode\": %d, \"stages\": %d, \"shapes\": \"%s\", \"submit_host_ms_per_batch\": %.4f, \"plan_builds\": %llu, \"batches_shaped_on_device\": %llu, "
                 "\"launches\": %llu, \"launches_continued\": %llu, \"refused\": %u, \"output_ok\": %s}\n",
                 device_pcm ? (sync ? "aacg_pipeline_submit_device + collect, one batch at a time" : "aacg_pipeline_submit_device / collect, batches in flight")
                            : sync ? "aacg_pipeline_decode, one batch at a time" : "aacg_pipeline_submit / collect, batches in flight", sync ? 1 : lanes, S, F, channels, i16 ? "int16" : "f32",
-                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, limiter_key, rate_key, features_key, loudness_key, conceal_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
+                device_pcm ? (planar ? "device, planar" : "device, packed") : pageable ? "pageable" : "page-locked", copy_key, mix_key, limiter_key, rate_key, features_key, loudness_key, conceal_key, trim_key, bytes.size(), pcm_bytes, ms[ms.size() / 2], ms.front(), ms.back(), (new_shapes ? (double)fed / (5.0 * batches) : (double)S * F) / (ms[ms.size() / 2] * 1e-3),
                 (double)pcm_bytes / (ms[ms.size() / 2] * 1e-3) / 1e9, device_plans ? 1 : 0, (int)cfg.stages, new_shapes ? "a new seeded shape per batch, 1..F frames per stream" : "one",
                 new_shapes ? submit_ms : 0.0, (unsigned long long)aacg_pipeline_plan_builds(p), (unsigned long long)shaped, (unsigned long long)launches, (unsigned long long)chained, bad, (finite && nonzero && !bad) ? "true" : "false");
     aacg_pipeline_destroy(p);
