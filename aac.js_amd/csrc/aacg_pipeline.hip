@@ -38,8 +38,7 @@
  * window_shape_prev of the batch's unit records from the frame before and, across batches, from the engine's per-channel state.
  * aacg_pipeline_set_concealment (plan mode 1): one launch of aacg_plan_conceal_refused between the two replaces a refused frame's records by
  * its stream's last good frame, faded; the slots' state — that frame's records, two sides per slot — passes from batch to batch
- * like the resampler's history, its parities advance when a batch has been enqueued, and the per-stream records travel up in the
- * lane's staging block behind the limiter's.
+ * like the resampler's history (SLOT STATE below).
  *
  * THE WAY OUT is a chain: transform -> mix (aacg_pipeline_set_mix: O = 1 or 2 channels leave in the place of C) -> limit
  * (aacg_pipeline_set_limiter: a gain per stream and a look-ahead limiter, sample for sample, state per slot like the resampler's) -> resample
@@ -50,11 +49,15 @@
  * how many bytes is decided ONCE, in check_batch, by aacg_pipe::exit_plan (aacg_pipe_exit.h has the table, tests/test_pipe_exit_plan.py
  * pins it); enqueue_transform and enqueue_out walk that plan.  The two submissions share one body (submit_batch); the results' copy and
  * the lane's `done` event are the same whatever the way out, and aacg_pipeline_wait_device puts a consumer's stream behind that event.
- * The resampler has state per slot — a clock, kept here modulo M, and on the device the last T - 1 samples per channel,
- * double-buffered — which consecutive batches hand on ACROSS lanes: an event behind every resample launch, awaited by the next batch's
- * on its own stream behind that lane's parse and transform.  Clocks and parities advance when a batch has been enqueued, not before;
- * the per-stream records travel up in the lane's one staging block, behind the per-stream table.  The feature stage has the same kind
- * of state — a clock, kept here in 64 bits, and on the device the last K - 1 samples — and is ordered and advanced in the same way.
+ *
+ * SLOT STATE, RECORDS, ORDER.  The resampler has state per slot — a clock, kept here modulo M, and on the device the last T - 1 samples
+ * per channel, double-buffered — and so, each in its kind, have the feature stage, the meter with the true peak, the limiter and the
+ * concealment; the trim has a position.  What the host keeps of it (aacg_pipe_slots.h, host-only, pinned by tests/test_pipe_slots.py;
+ * a stage struct here derives from its slots and adds the device pointers), the batch's per-stream records made from it (check_batch:
+ * build_*), their sections in the lane's one staging block behind the per-stream table (record_block) and the advance when the batch
+ * has been enqueued, not before (enqueue_out: commit_*), are that header's.  Consecutive batches hand device state on ACROSS lanes:
+ * ONE helper, ordered_launch, makes a launch wait for its stage's latest event unless it is this lane's — on the lane's stream behind
+ * its parse and transform — records this lane's event behind it and makes that the latest (lane_t::ordered, aacg_pipeline::last, ORD_*).
  *
  * On a lane's stream, in this order: clear (unlearnt streams) -> copy up -> stale count -> parse -> TNS records -> map / shape ->
  * refresh -> conceal -> carry -> fork -> transform -> join -> mix -> wait / limit / record -> wait / resample / record -> wait / features / record -> planar or copy down -> results copy -> `done`.
@@ -76,17 +79,9 @@
 #include "../../include/aacgpu_tools.h"
 #include "aacg_pcm_mix.h"
 #include "aacg_pcm_planar.h"
-#include "aacg_pcm_resample.h"
-#include "aacg_pcm_trim.h"
-#define AACG_FEATURES_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_features.hip's */
-#include "aacg_pcm_features.h"
-#define AACG_LOUDNESS_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_loudness.hip's */
-#include "aacg_pcm_loudness.h"
-#define AACG_LIMIT_HOST_ONLY                              /* the limits and the records: the body is aacg_engine_limit.hip's */
-#include "aacg_pcm_limit.h"
-#define AACG_TRUEPEAK_HOST_ONLY                           /* the limits and the records: the body is aacg_engine_truepeak.hip's */
+#include "aacg_pipe_slots.h"                              /* ... and with it aacg_pipe_exit.h and the PCM stages' limits and records, host only: the bodies are the engine's */
+#define AACG_TRUEPEAK_HOST_ONLY
 #include "aacg_pcm_truepeak.h"
-#include "aacg_pipe_exit.h"
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
@@ -95,21 +90,16 @@
  * (AACG_PIPELINE_STAGE_WINDOW_SHAPE selects neither: one carry launch behind the refresh, whatever the plan) */
 #define AACG_PIPELINE_SPEC_STAGES (AACG_PIPELINE_STAGE_TNS | AACG_PIPELINE_STAGE_PNS)
 
-/* aacg_engine_planar.hip: a batch's packed PCM into a caller's planar tensor (aacg_pcm_planar.h); false: not a launch it serves */
+/* The side launches on a batch's PCM, each in aacg_engine_<stage>.hip with its kernels and described in aacg_pcm_<stage>.h: into a caller's
+ * planar tensor, mixed to one or two channels, resampled by L / M, to (log-)mel feature frames, metered, gained and limited, its true
+ * peak, cut to each stream's window.  false: not a launch the kernel serves (not_served) */
 bool aacg_planar_launch(const aacg_planar_args& A, hipStream_t s);
-/* aacg_engine_mix.hip: a batch's packed PCM mixed to one or two channels (aacg_pcm_mix.h); false: not a launch it serves */
 bool aacg_mix_launch(const aacg_mix_args& A, hipStream_t s);
-/* aacg_engine_resample.hip: a batch's packed PCM resampled by L / M (aacg_pcm_resample.h); false: not a launch it serves */
 bool aacg_resample_launch(const aacg_resample_args& A, hipStream_t s);
-/* aacg_engine_features.hip: a batch's one-channel PCM to (log-)mel feature frames (aacg_pcm_features.h); false: not a launch it serves */
 bool aacg_features_launch(const aacg_features_args& A, hipStream_t s);
-/* aacg_engine_loudness.hip: a loudness tap on a batch's transform PCM (aacg_pcm_loudness.h); false: not a launch it serves */
 bool aacg_loudness_launch(const aacg_loudness_args& A, hipStream_t s);
-/* aacg_engine_limit.hip: a gain per stream and a look-ahead limiter on a batch's packed PCM (aacg_pcm_limit.h); false: not a launch it serves */
 bool aacg_limit_launch(const aacg_limit_args& A, hipStream_t s);
-/* aacg_engine_truepeak.hip: the true peak of a batch's transform PCM (aacg_pcm_truepeak.h); false: not a launch it serves */
 bool aacg_truepeak_launch(const aacg_truepeak_args& A, hipStream_t s);
-/* aacg_engine_trim.hip: a batch's packed PCM cut to each stream's window (aacg_pcm_trim.h); false: not a launch it serves */
 bool aacg_trim_launch(const aacg_trim_args& A, hipStream_t s);
 
 /* The batch's bytes up (and its few kilobytes of results down) are moved by THIS kernel, not by hipMemcpyAsync: page-locked host
@@ -143,6 +133,10 @@ void aacg_pipe_map(const aacg_pipe_stream* tab, uint32_t n_streams, uint32_t U, 
     aacg_pipe::map_body(tab, n_streams, U, map, gridDim.x);
 }
 
+/* the stages whose slots' device state passes from batch to batch across lanes: their launches are ordered by events (ordered_launch);
+ * the true peak stands inside the meter's */
+enum { ORD_LIMIT, ORD_RESAMPLE, ORD_FEATURES, ORD_METER, ORD_STAGES };
+
 struct aacg_pipeline {
     aacg_pipeline_config cfg;
     aacg_engine* engine = nullptr;
@@ -151,39 +145,29 @@ struct aacg_pipeline {
     uint32_t C = 2;                     /* channels of a frame's PCM (chanConfig) */
     uint32_t O = 0;                     /* aacg_pipeline_set_mix: channels that leave (1 or 2); 0: no mix, C leave */
     float mix[AACG_MIX_MAX_OUT * AACG_MIX_MAX_IN] = {};      /* M[o][c] at mix[o * C + c] */
-    /* aacg_pipeline_set_resample: L / M and the table's taps (L = 0: no resampler), the table and the slots' histories on the device
-     * ([slot][2][T - 1][channels out] floats), and per slot what the host keeps: the clock modulo M, which history buffer the slot's
-     * next batch reads, and whether it has consumed anything since its reset.  last: the event behind the latest resample launch */
-    struct resample_t {
-        uint32_t L = 0, M = 0, T = 0;
+    /* The stages with state per slot: what the host keeps per slot — a clock or a position, and the two sides — and the settings the
+     * batch's records follow from are the base (aacg_pipe_slots.h); here is what the launches need besides.
+     * aacg_pipeline_set_resample: L / M and the table's taps (L = 0: no resampler), the table and the slots' histories on the device
+     * ([slot][2][T - 1][channels out] floats) */
+    struct resample_t : aacg_pipe::resample_slots {
+        uint32_t T = 0;
         void *d_table = nullptr, *d_hist = nullptr;
-        std::vector<uint32_t> n0; std::vector<uint8_t> parity, fresh;
-        hipEvent_t last = nullptr;
         size_t lane_elems = 0;          /* the largest batch's output: elements of a lane's d_rs and h_pcm */
     } rs;
-    /* aacg_pipeline_set_features: the stage's parameters (K = 0: none), its tables and the slots' histories on the device ([slot][2][K - 1]
-     * floats), and per slot what the host keeps: the clock (input samples of the stage since the slot's reset), which history buffer the
-     * slot's next batch reads, and whether it has consumed anything since its reset.  last: the event behind the latest features launch */
-    struct features_t {
-        uint32_t K = 0, H = 0, P = 0, R = 0, n_mels = 0, log = 0;
+    /* aacg_pipeline_set_features: the stage's parameters (K = 0: none), its tables and the slots' histories on the device ([slot][2][K - 1] floats) */
+    struct features_t : aacg_pipe::features_slots {
+        uint32_t R = 0, n_mels = 0, log = 0;
         float floor = 0.0f;
         void *d_basis = nullptr, *d_fb = nullptr, *d_hist = nullptr;
-        std::vector<uint64_t> N; std::vector<uint8_t> parity, fresh;
-        hipEvent_t last = nullptr;
         size_t lane_elems = 0;          /* the largest batch's output: floats of a lane's d_ft and h_pcm */
     } ft;
-    /* aacg_pipeline_set_loudness: the meter's hop (0: none) and sections, the slots' state on the device ([slot][2][C][6] floats), and per
-     * slot what the host keeps: the clock (samples since the slot's reset), which state buffer the slot's next batch reads, and whether
-     * it has consumed anything since its reset.  last: the event behind the latest loudness launch.  front16: the bytes IN FRONT of a
-     * lane's results (d_res, h_res) that take a batch's records, right-aligned, so that the results' copy brings them down too.  out,
-     * out_cap, out_counts: the destination named for the next submission (aacg_pipeline_loudness_out) while `armed` */
-    struct loudness_t {
-        uint32_t hop = 0;
+    /* aacg_pipeline_set_loudness: the meter's hop (0: none) and sections and the slots' state on the device ([slot][2][C][6] floats).
+     * front16: the bytes IN FRONT of a lane's results (d_res, h_res) that take a batch's records, right-aligned, so that the results'
+     * copy brings them down too (results_blocks).  out, out_cap, out_counts: the destination named for the next submission
+     * (aacg_pipeline_loudness_out) while `armed` */
+    struct loudness_t : aacg_pipe::loudness_slots {
         float coeffs[10] = {};
-        void* d_state = nullptr;
-        std::vector<uint64_t> N; std::vector<uint8_t> parity, fresh;
-        hipEvent_t last = nullptr;
-        size_t front16 = 0;
+        void* d_state = nullptr; size_t front16 = 0;
         float* out = nullptr; size_t out_cap = 0; uint32_t* out_counts = nullptr; bool armed = false;
     } ld;
     /* aacg_pipeline_set_true_peak: the table's shape (L 0: none), the table and the slots' state on the device ([slot][2][T x C] words:
@@ -196,32 +180,20 @@ struct aacg_pipeline {
         void *d_table = nullptr, *d_state = nullptr;
         float* out = nullptr; size_t out_cap = 0; bool armed = false;
     } tp;
-    /* aacg_pipeline_set_limiter: the two settings (on: a limiter is set), the slots' state on the device ([slot][2][AACG_LIMIT_STATE(Oc)]
-     * floats), and per slot what the host keeps: the gain (the caller's: a reset leaves it), which state buffer the slot's next batch
-     * reads, and whether it has consumed anything since its reset.  last: the event behind the latest limiter launch */
-    struct limiter_t {
-        bool on = false;
+    /* aacg_pipeline_set_limiter: the two settings (on: a limiter is set) and the slots' state on the device ([slot][2][AACG_LIMIT_STATE(Oc)] floats) */
+    struct limiter_t : aacg_pipe::limiter_slots {
         float ceiling = 0.0f, release = 0.0f;
         void* d_state = nullptr;
-        std::vector<float> gain; std::vector<uint8_t> parity, fresh;
-        hipEvent_t last = nullptr;
     } lim;
-    /* aacg_pipeline_set_concealment: the two settings (on: the stage is set), the slots' state on the device ([slot][2] sides, aacg_conceal_state_bytes),
-     * and per slot what the host keeps: which side the slot's next batch reads, and whether it has been through a batch since its reset.
-     * total: the concealed frames of collected batches */
-    struct conceal_t {
-        bool on = false;
+    /* aacg_pipeline_set_concealment: the two settings (on: the stage is set) and the slots' state on the device ([slot][2] sides,
+     * aacg_conceal_state_bytes).  total: the concealed frames of collected batches */
+    struct conceal_t : aacg_pipe::conceal_slots {
         uint32_t fade_steps = 0, hold_frames = 0;
-        void* d_state = nullptr;
-        std::vector<uint8_t> parity, fresh;
-        uint64_t total = 0;
+        void* d_state = nullptr; uint64_t total = 0;
     } cn;
-    /* aacg_pipeline_set_trim: per slot the window (skip S, keep K) and the position Q, in samples of what the stage receives (on: the
-     * stage is set).  All of it is the host's: the stage has no device state, a batch's kept ranges go up in its records */
-    struct trim_t {
-        bool on = false;
-        std::vector<uint64_t> S, K, Q;
-    } tr;
+    /* aacg_pipeline_set_trim: all of it is the host's — the stage has no device state, a batch's kept ranges go up in its records */
+    aacg_pipe::trim_slots tr;
+    hipEvent_t last[ORD_STAGES] = {};   /* the event behind the latest launch of each ordered stage, whichever lane made it (ordered_launch) */
     uint32_t Cp = 2, U = 1;             /* what the parser is allowed per frame: channels (block stride), elements */
     bool learn = false;                 /* C > 2: layouts are learnt; C <= 2: every frame one SCE / one CPE */
     bool spec_stages = false;           /* cfg.stages has AACG_PIPELINE_STAGE_TNS or _PNS: SPEC engine modes, stages plans, aacg_decode_pipelined_stages */
@@ -249,13 +221,10 @@ struct aacg_pipeline {
         void *d_bytes = nullptr, *d_frames = nullptr, *d_units = nullptr, *d_q = nullptr, *d_meta = nullptr, *d_res = nullptr, *d_pcm = nullptr, *d_refused = nullptr;
         void* d_mix = nullptr;            /* aacg_pipeline_set_mix: the mixed PCM of a host or planar batch, max_streams x max_frames x 1024 x O elements */
         void* d_rs = nullptr;             /* aacg_pipeline_set_resample: the resampled PCM of a host batch, rs.lane_elems elements */
-        hipEvent_t rs_done = nullptr;     /* ... and the event behind this lane's latest resample launch */
         void* d_ft = nullptr;             /* aacg_pipeline_set_features: the feature frames of a host batch, ft.lane_elems floats */
-        hipEvent_t ft_done = nullptr;     /* ... and the event behind this lane's latest features launch */
-        hipEvent_t ld_done = nullptr;     /* aacg_pipeline_set_loudness: the event behind this lane's latest loudness launch */
         void* d_lim = nullptr;            /* aacg_pipeline_set_limiter: the limited PCM wherever it is not a packed device batch's last stage, max_streams x max_frames x 1024 x Oc elements */
-        hipEvent_t lim_done = nullptr;    /* ... and the event behind this lane's latest limiter launch */
         void* d_trim = nullptr;           /* aacg_pipeline_set_trim: the trimmed PCM of a host batch, the largest batch's untrimmed elements */
+        hipEvent_t ordered[ORD_STAGES] = {};      /* the events behind this lane's latest launch of each ordered stage, made at create (ordered_launch) */
         float* ld_user = nullptr; size_t ld_bytes = 0;      /* ... and the batch in flight's records: where they go at collect, and how many bytes */
         float* tp_user = nullptr; size_t tp_bytes = 0;      /* aacg_pipeline_set_true_peak: the same for the batch in flight's true-peak floats */
         void* d_map = nullptr;            /* the batch's refresh map (aacg_pipe_map): max_streams x max_frames x U entries, made at create */
@@ -308,13 +277,30 @@ aacg_exit_pipe exit_pipe(const aacg_pipeline* p)
     return {p->C, p->O, p->rs.L != 0, (uint32_t)pcm_elem(p), (uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.lane_elems,
             p->ft.K ? p->ft.n_mels : 0u, p->ft.lane_elems, p->lim.on ? 1u : 0u, p->tr.on ? 1u : 0u};
 }
-/* the samples a stream of `frames` frames emits at the clock n0 (modulo M): ceil((n0 + 1024 F) L / M) - ceil(n0 L / M), the first
- * through ceil((q M + n) L / M) = q L + ceil(n L / M) so that the one formula (aacg_resample_ceil) sees the arguments it is made for */
-uint32_t resample_count(const aacg_pipeline* p, uint32_t n0, uint32_t frames)
+/* the most samples per channel a batch brings to a stage behind the resampler: what the kernels and their records count in 32 bits */
+uint64_t most_samples(const aacg_pipeline* p)
 {
-    const uint32_t L = p->rs.L, M = p->rs.M;
-    const uint64_t n1 = (uint64_t)n0 + 1024ull * frames;
-    return (uint32_t)(n1 / M * L) + aacg_resample_ceil((uint32_t)(n1 % M), L, M) - aacg_resample_ceil(n0, L, M);
+    return p->rs.L ? aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.L, p->rs.M)
+                   : (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * 1024u;
+}
+/* the most records per channel a batch brings the meter: every stream may complete a hop that earlier batches began */
+uint64_t most_hops(const aacg_pipeline* p, uint32_t hop) { return (uint64_t)p->cfg.max_streams * ((uint64_t)p->cfg.max_frames * 1024u / hop + 1u); }
+
+/* The refusals every aacg_pipeline_set_* begins with, in their order: no configuration, the stage is set already (`has`: "has a mix"), a
+ * batch has been submitted, a stage is set that `what` ("the mix") must be set before.  Every refusal leaves the pipeline exactly as it was */
+struct set_before { bool set; const char* has; };
+int refuse_set(aacg_pipeline* p, const char* fn, bool already, const char* has, const char* what, std::initializer_list<set_before> before = {}, bool no_cfg = false)
+{
+    std::string no = no_cfg ? "no configuration" : already ? std::string("the pipeline ") + has + " already" : p->submitted ? std::string("a batch has been submitted (") + what + " is set before the first)" : "";
+    for (const auto& b : before) if (b.set && no.empty()) no = std::string("the pipeline has ") + b.has + " already (" + what + " is set before it)";
+    if (!no.empty()) p->err = std::string(fn) + ": " + no;
+    return no.empty() ? AACG_OK : AACG_ERR_INVALID_ARG;
+}
+/* the first entry of a caller's table that is not finite, as a refusal: "<what> <i><of> is not finite"; false: every entry is */
+bool not_finite(aacg_pipeline* p, const float* v, size_t n, const char* what, const char* of)
+{
+    for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) { p->err = what + std::to_string(i) + of + " is not finite"; return true; }
+    return false;
 }
 
 /* a slot's layout as plans and callers see it: the learnt one (n = 0: none yet), or, C <= 2, one element of C channels */
@@ -357,25 +343,60 @@ int grow_pair(aacg_pipeline* p, void** h, void** d, size_t* cap, size_t need)
 }
 
 /* The buffers a lane gets after create (aacg_pipeline_set_mix, aacg_pipeline_set_resample): `bytes` of device memory at lane_t::*buf
- * and, if asked for, an event at lane_t::*ev, for EVERY lane — or for none: false leaves the lanes as they were */
+ * for EVERY lane — or for none: false leaves the lanes as they were */
 typedef aacg_pipeline::lane_t lane_t;
-void lanes_release(aacg_pipeline* p, void* lane_t::*buf, hipEvent_t lane_t::*ev)
+void lanes_release(aacg_pipeline* p, void* lane_t::*buf)
 {
-    for (auto& L : p->lane) {
-        if (L.*buf) { (void)hipFree(L.*buf); L.*buf = nullptr; }
-        if (ev && L.*ev) { (void)hipEventDestroy(L.*ev); L.*ev = nullptr; }
-    }
+    for (auto& L : p->lane) if (L.*buf) { (void)hipFree(L.*buf); L.*buf = nullptr; }
 }
-bool lanes_alloc(aacg_pipeline* p, void* lane_t::*buf, size_t bytes, hipEvent_t lane_t::*ev = nullptr)
+bool lanes_alloc(aacg_pipeline* p, void* lane_t::*buf, size_t bytes)
 {
     for (int k = 0; k < p->n_lanes; k++)
-        if (hipMalloc(&(p->lane[k].*buf), bytes) != hipSuccess || (ev && hipEventCreateWithFlags(&(p->lane[k].*ev), hipEventDisableTiming) != hipSuccess)) {
-            (void)hipGetLastError();
-            lanes_release(p, buf, ev);
-            return false;
-        }
+        if (hipMalloc(&(p->lane[k].*buf), bytes) != hipSuccess) { (void)hipGetLastError(); lanes_release(p, buf); return false; }
     return true;
 }
+/* A set-up's allocations did not all succeed: what it made goes — device memory of its own, the lanes' buffers (buf; null: none) —
+ * and the refusal is `what` */
+int no_memory(aacg_pipeline* p, std::initializer_list<void*> made, void* lane_t::*buf, const char* what)
+{
+    (void)hipGetLastError();
+    for (void* d : made) if (d) (void)hipFree(d);
+    if (buf) lanes_release(p, buf);
+    p->err = what;
+    return AACG_ERR_OUT_OF_MEMORY;
+}
+/* Every lane's results block again with front16 bytes IN FRONT of the results for a meter's and a true peak's records, device and
+ * page-locked, cleared — for every lane or for none: false leaves the lanes as they were.  Nothing is in flight yet */
+bool results_blocks(aacg_pipeline* p, size_t front16)
+{
+    const size_t block = front16 + p->res_cap16 + 16;
+    void *d_new[AACG_PIPELINE_MAX_LANES] = {}, *h_new[AACG_PIPELINE_MAX_LANES] = {};
+    bool good = true;
+    for (int k = 0; k < p->n_lanes && good; k++)
+        good = hipMalloc(&d_new[k], block) == hipSuccess && hipMemset(d_new[k], 0, block) == hipSuccess && hipHostMalloc(&h_new[k], block, hipHostMallocDefault) == hipSuccess;
+    for (int k = 0; k < p->n_lanes; k++) {
+        auto& L = p->lane[k];
+        if (!good) { if (d_new[k]) (void)hipFree(d_new[k]); if (h_new[k]) (void)hipHostFree(h_new[k]); continue; }
+        (void)hipFree((char*)L.d_res - p->ld.front16); (void)hipHostFree((char*)L.h_res - p->ld.front16);      /* the old block, at its true base */
+        L.d_res = (char*)d_new[k] + front16; L.h_res = (char*)h_new[k] + front16; L.d_refused = (char*)L.d_res + p->res_cap16;
+        L.count_stale = false;                          /* (the new block's count is zero) */
+    }
+    if (good) p->ld.front16 = front16; else (void)hipGetLastError();
+    return good;
+}
+/* A launch whose slots' device state passes from batch to batch while consecutive batches run on different streams: it waits for the
+ * stage's latest, here — behind this lane's parse, transform and whatever of the way out lies in front, which need not wait — and this
+ * lane's event behind it is the latest from now on.  launch(): AACG_OK, or the refusal with p->err set */
+template <typename F>
+int ordered_launch(aacg_pipeline* p, lane_t& L, int ord, F launch)
+{
+    if (p->last[ord] && p->last[ord] != L.ordered[ord]) P_TRY(p, hipStreamWaitEvent(L.st, p->last[ord], 0), AACG_ERR_NO_DEVICE);
+    if (const int rc = launch()) return rc;
+    P_TRY(p, hipEventRecord(L.ordered[ord], L.st), AACG_ERR_NO_DEVICE);
+    p->last[ord] = L.ordered[ord];
+    return AACG_OK;
+}
+int not_served(aacg_pipeline* p, const char* kernel) { p->err = std::string(kernel) + ": not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
 /* A lane's page-locked PCM staging is made lazily, at the size of the largest batch's output (aacg_pipe::exit_host_capacity).  What a
  * submission that failed half-way left behind has the size of before a mix or a resampler was set: it goes, and is made again */
 void drop_host_staging(aacg_pipeline* p)
@@ -400,29 +421,22 @@ int stage(aacg_pipeline* p, void** h, void** d, size_t* cap, const uint8_t* byte
 }
 
 /* One batch on its way through submit_batch: what the caller gave, then what each step leaves for the steps behind it */
+typedef aacg_pipe::record_block RB;
 struct batch_t {
     const uint8_t* bytes; size_t n_bytes; const aacg_parse_frame* frames; const uint32_t* slots; uint32_t n_streams; const uint32_t* frames_of;
     void* pcm_out; const aacg_pcm_device_out* dev; aacg_parse_result* results; uint32_t* n_refused;
     uint32_t n, longest;                         /* check_batch: the batch's frames, the largest count of a stream */
     uint32_t set;                                /* the lane's index: the set of a plan's unit records that is this lane's */
-    std::vector<aacg_resample_stream> rs;        /* check_batch, a resampler: the batch's records (what each stream emits, from the host's clocks) */
     aacg_exit_plan X;                            /* check_batch: the way out (aacg_pipe_exit.h) — which stage writes which buffer, and how many bytes */
     staging_t G;                                 /* stage_batch (the per-stream table lies at G.extra_at) */
-    size_t rs_at;                                /* stage_batch: where the records lie in the staging block */
-    std::vector<aacg_features_stream> ft;        /* check_batch, a feature stage: the batch's records, from the host's clocks */
-    size_t ft_at;                                /* stage_batch: where those lie, behind the resampler's */
-    std::vector<aacg_loudness_stream> ld;        /* check_batch, a meter: the batch's records, from the host's clocks */
-    size_t ld_at;                                /* stage_batch: where those lie, behind the feature stage's */
-    size_t ld_floats;                            /* check_batch: the floats the batch's loudness records take */
-    size_t tp_floats;                            /* check_batch: ... and its true-peak records, 0 without the stage */
-    std::vector<aacg_limit_stream> lim;          /* check_batch, a limiter: the batch's records, with the slots' gains as they stand */
-    size_t lim_at;                               /* stage_batch: where those lie, behind the meter's */
-    std::vector<aacg_conceal_stream> cn;         /* check_batch, concealment: the batch's records, with the slots' sides as they stand */
-    size_t cn_at;                                /* stage_batch: where those lie, behind the limiter's */
-    std::vector<aacg_trim_stream> tr;            /* check_batch, a trim: the batch's records (what each stream keeps, from the host's windows and positions) */
-    std::vector<uint32_t> tr_in;                 /* ... and what each stream brings: its slot's position advances by it in enqueue_out */
-    uint32_t tr_items;                           /* ... and the launch's items */
-    size_t tr_at;                                /* stage_batch: where the records lie, behind the concealment's */
+    /* check_batch: the records of the stages that are set, from the slots' clocks, windows, gains and sides as they stand (aacg_pipe_slots.h:
+     * build_*; the concealment's are sized there and made in choose_plan, from the plan's table) */
+    std::vector<aacg_resample_stream> rs; std::vector<aacg_features_stream> ft; std::vector<aacg_loudness_stream> ld;
+    std::vector<aacg_limit_stream> lim; std::vector<aacg_conceal_stream> cn; std::vector<aacg_trim_stream> tr;
+    std::vector<uint32_t> tr_in;                 /* ... what each stream brings the trim: its slot's position advances by it in enqueue_out */
+    uint32_t tr_items, ft_items;                 /* ... the trim's and the feature stage's launch items */
+    size_t ld_floats, tp_floats;                 /* ... the floats the batch's loudness and true-peak records take, 0 without the stage */
+    RB R;                                        /* stage_batch: where each stage's records lie in the staging block, behind the per-stream table */
     aacg_plan* plan;                             /* choose_plan: null when no stream of the batch has a layout yet */
 };
 
@@ -646,10 +660,7 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
         for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_lim, L.d_trim, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
         for (void* h : {L.h_in, L.h_pcm, L.h_res ? (void*)((char*)L.h_res - p->ld.front16) : nullptr}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
-        if (L.rs_done) (void)hipEventDestroy(L.rs_done);
-        if (L.ft_done) (void)hipEventDestroy(L.ft_done);
-        if (L.ld_done) (void)hipEventDestroy(L.ld_done);
-        if (L.lim_done) (void)hipEventDestroy(L.lim_done);
+        for (hipEvent_t ev : L.ordered) if (ev) (void)hipEventDestroy(ev);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
     for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state, p->tp.d_table, p->tp.d_state, p->cn.d_state}) if (d) (void)hipFree(d);
@@ -721,8 +732,7 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
          * that and the engine's pipeline streams: other queues again, so that a fifth lane does not wait behind the first */
         const int prio = k < 4 ? least : (least + greatest) / 2;
         good = ok(p, hipStreamCreateWithPriority(&L.st, hipStreamNonBlocking, prio), "hipStreamCreate") &&
-               ok(p, hipEventCreateWithFlags(&L.done, hipEventDisableTiming), "hipEventCreate") &&
-               ok(p, hipMalloc(&L.d_units, n * U * sizeof(aacg_unit_desc)), "hipMalloc") &&
+               ok(p, hipEventCreateWithFlags(&L.done, hipEventDisableTiming), "hipEventCreate") &&               ok(p, hipMalloc(&L.d_units, n * U * sizeof(aacg_unit_desc)), "hipMalloc") &&
                ok(p, hipMalloc(&L.d_map, n * U * sizeof(aacg_refresh_map)), "hipMalloc") &&
                ok(p, hipMalloc(&L.d_q, n * Cp * 2048), "hipMalloc") && ok(p, hipMemsetAsync(L.d_q, 0, n * Cp * 2048, L.st), "hipMemset") &&
                ok(p, hipMalloc(&L.d_meta, n * Cp * sizeof(aacg_band_meta)), "hipMalloc") &&
@@ -734,6 +744,7 @@ int aacg_pipeline_create(const aacg_pipeline_config* cfg, const aacg_code_entry*
                  ok(p, hipMalloc(&L.d_tns, aacg_tns_records_bytes((uint32_t)(n * Cp))), "hipMalloc"))) &&
                ok(p, hipHostMalloc(&L.h_res, p->res_cap16 + 16, hipHostMallocDefault), "hipHostMalloc") &&
                aacg_wait_stream(L.st, p->wait) == hipSuccess;
+        for (hipEvent_t& ev : L.ordered) good = good && ok(p, hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");      /* (a few per lane, whichever stages are set later) */
         if (good) L.d_refused = (char*)L.d_res + p->res_cap16;
     }
     if (!good) { if (p->err.empty()) p->err = "the pipeline's set-up did not complete"; std::fprintf(stderr, "aacgpu: %s\n", p->err.c_str()); aacg_pipeline_destroy(p); return AACG_ERR_OUT_OF_MEMORY; }
@@ -755,20 +766,14 @@ int aacg_pipeline_set_wait_limit_ms(aacg_pipeline* p, uint32_t ms)
 int aacg_pipeline_set_mix(aacg_pipeline* p, uint32_t out_channels, const float* matrix)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (p->O) { p->err = "aacg_pipeline_set_mix: the pipeline has a mix already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_mix: a batch has been submitted (the mix is set before the first)"; return AACG_ERR_INVALID_ARG; }
-    if (p->rs.L) { p->err = "aacg_pipeline_set_mix: the pipeline has a resampler already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
-    if (p->ft.K) { p->err = "aacg_pipeline_set_mix: the pipeline has a feature stage already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
-    if (p->lim.on) { p->err = "aacg_pipeline_set_mix: the pipeline has a limiter already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
-    if (p->tr.on) { p->err = "aacg_pipeline_set_mix: the pipeline has a trim already (the mix is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_mix", p->O != 0, "has a mix", "the mix",
+                                  {{p->rs.L != 0, "a resampler"}, {p->ft.K != 0, "a feature stage"}, {p->lim.on, "a limiter"}, {p->tr.on, "a trim"}})) return no;
     if (out_channels < 1 || out_channels > AACG_MIX_MAX_OUT) { p->err = "aacg_pipeline_set_mix: out_channels is not 1 or 2"; return AACG_ERR_INVALID_ARG; }
     if (!matrix) { p->err = "aacg_pipeline_set_mix: no matrix"; return AACG_ERR_INVALID_ARG; }
-    for (uint32_t i = 0; i < out_channels * p->C; i++)
-        if (!std::isfinite(matrix[i])) { p->err = "aacg_pipeline_set_mix: coefficient " + std::to_string(i) + " of the matrix is not finite"; return AACG_ERR_INVALID_ARG; }
+    if (not_finite(p, matrix, (size_t)out_channels * p->C, "aacg_pipeline_set_mix: coefficient ", " of the matrix")) return AACG_ERR_INVALID_ARG;
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     const size_t bytes = (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * out_channels * 1024u * pcm_elem(p);
-    if (!lanes_alloc(p, &lane_t::d_mix, bytes)) { p->err = "aacg_pipeline_set_mix: no device memory for the lanes' mixed PCM"; return AACG_ERR_OUT_OF_MEMORY; }
+    if (!lanes_alloc(p, &lane_t::d_mix, bytes)) return no_memory(p, {}, nullptr, "aacg_pipeline_set_mix: no device memory for the lanes' mixed PCM");
     drop_host_staging(p);
     std::memset(p->mix, 0, sizeof p->mix);
     std::memcpy(p->mix, matrix, (size_t)out_channels * p->C * sizeof(float));
@@ -781,16 +786,11 @@ int aacg_pipeline_out_channels(const aacg_pipeline* p) { return p ? (int)out_cha
 int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_t taps, const float* table)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (p->rs.L) { p->err = "aacg_pipeline_set_resample: the pipeline has a resampler already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_resample: a batch has been submitted (the resampler is set before the first)"; return AACG_ERR_INVALID_ARG; }
-    if (p->ft.K) { p->err = "aacg_pipeline_set_resample: the pipeline has a feature stage already (the resampler is set before it)"; return AACG_ERR_INVALID_ARG; }
-    if (p->tr.on) { p->err = "aacg_pipeline_set_resample: the pipeline has a trim already (the resampler is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_resample", p->rs.L != 0, "has a resampler", "the resampler", {{p->ft.K != 0, "a feature stage"}, {p->tr.on, "a trim"}})) return no;
     if (const int why = aacg_resample_check(L, M, taps)) { p->err = std::string("aacg_pipeline_set_resample: ") + aacg_resample_why(why); return AACG_ERR_INVALID_ARG; }
     if (!table) { p->err = "aacg_pipeline_set_resample: no table"; return AACG_ERR_INVALID_ARG; }
     const size_t n_table = (size_t)L * taps;
-    for (size_t i = 0; i < n_table; i++)
-        if (!std::isfinite(table[i])) { p->err = "aacg_pipeline_set_resample: coefficient " + std::to_string(i) + " of the table is not finite"; return AACG_ERR_INVALID_ARG; }
+    if (not_finite(p, table, n_table, "aacg_pipeline_set_resample: coefficient ", " of the table")) return AACG_ERR_INVALID_ARG;
     /* the largest batch's output, samples per channel: the kernel and its records count them in 32 bits */
     const uint64_t most = aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, L, M);
     if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_resample: max_streams x max_frames x 1024 x L / M is 2^31 samples or more"; return AACG_ERR_INVALID_ARG; }
@@ -800,17 +800,10 @@ int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_
     void *d_table = nullptr, *d_hist = nullptr;
     /* (the table, synchronously: nothing is in flight yet.  The history needs no clearing: a fresh slot's is not read) */
     if (hipMalloc(&d_table, n_table * sizeof(float)) != hipSuccess || hipMalloc(&d_hist, hist_bytes) != hipSuccess ||
-        !lanes_alloc(p, &lane_t::d_rs, lane_elems * pcm_elem(p), &lane_t::rs_done) ||
-        hipMemcpy(d_table, table, n_table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* d : {d_table, d_hist}) if (d) (void)hipFree(d);
-        lanes_release(p, &lane_t::d_rs, &lane_t::rs_done);
-        p->err = "aacg_pipeline_set_resample: no device memory for the table, the slots' histories and the lanes' resampled PCM";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
+        !lanes_alloc(p, &lane_t::d_rs, lane_elems * pcm_elem(p)) || hipMemcpy(d_table, table, n_table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return no_memory(p, {d_table, d_hist}, &lane_t::d_rs, "aacg_pipeline_set_resample: no device memory for the table, the slots' histories and the lanes' resampled PCM");
     drop_host_staging(p);
-    p->rs.d_table = d_table; p->rs.d_hist = d_hist; p->rs.lane_elems = lane_elems;
-    p->rs.n0.assign((size_t)p->cfg.max_streams, 0u); p->rs.parity.assign((size_t)p->cfg.max_streams, 0); p->rs.fresh.assign((size_t)p->cfg.max_streams, 1);
+    p->rs.make((size_t)p->cfg.max_streams); p->rs.d_table = d_table; p->rs.d_hist = d_hist; p->rs.lane_elems = lane_elems;
     p->rs.M = M; p->rs.T = taps; p->rs.L = L;
     return AACG_OK;
 }
@@ -818,42 +811,27 @@ int aacg_pipeline_set_resample(aacg_pipeline* p, uint32_t L, uint32_t M, uint32_
 int aacg_pipeline_set_features(aacg_pipeline* p, const aacg_features_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (!cfg) { p->err = "aacg_pipeline_set_features: no configuration"; return AACG_ERR_INVALID_ARG; }
-    if (p->ft.K) { p->err = "aacg_pipeline_set_features: the pipeline has a feature stage already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_features: a batch has been submitted (the stage is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_features", p->ft.K != 0, "has a feature stage", "the stage", {}, !cfg)) return no;
     const uint32_t K = cfg->frame_length, H = cfg->hop, R = cfg->n_rows, NM = cfg->n_mels;
     if (const int why = aacg_features_check(K, H, cfg->pad_left, R, NM)) { p->err = std::string("aacg_pipeline_set_features: ") + aacg_features_why(why); return AACG_ERR_INVALID_ARG; }
     if (!(cfg->floor > 0.0f) || !std::isfinite(cfg->floor)) { p->err = "aacg_pipeline_set_features: floor is not positive and finite"; return AACG_ERR_INVALID_ARG; }
     if (out_channels(p) != 1u) { p->err = "aacg_pipeline_set_features: the stage takes ONE channel (channels == 1, or a mix with out_channels 1)"; return AACG_ERR_INVALID_ARG; }
     if (!cfg->basis || !cfg->fb) { p->err = "aacg_pipeline_set_features: no table"; return AACG_ERR_INVALID_ARG; }
     const size_t n_basis = (size_t)R * K, n_fb = (size_t)NM * (R / 2u);
-    for (size_t i = 0; i < n_basis; i++)
-        if (!std::isfinite(cfg->basis[i])) { p->err = "aacg_pipeline_set_features: entry " + std::to_string(i) + " of basis is not finite"; return AACG_ERR_INVALID_ARG; }
-    for (size_t i = 0; i < n_fb; i++)
-        if (!std::isfinite(cfg->fb[i])) { p->err = "aacg_pipeline_set_features: entry " + std::to_string(i) + " of fb is not finite"; return AACG_ERR_INVALID_ARG; }
+    if (not_finite(p, cfg->basis, n_basis, "aacg_pipeline_set_features: entry ", " of basis") || not_finite(p, cfg->fb, n_fb, "aacg_pipeline_set_features: entry ", " of fb")) return AACG_ERR_INVALID_ARG;
     /* the largest batch's output, floats: the kernel and its records count them in 32 bits */
-    const uint64_t samples = p->rs.L ? aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.L, p->rs.M)
-                                     : (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * 1024u;
-    const uint64_t most = aacg_pipe::exit_features_most((uint32_t)p->cfg.max_streams, samples, H) * NM;
+    const uint64_t most = aacg_pipe::exit_features_most((uint32_t)p->cfg.max_streams, most_samples(p), H) * NM;
     if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_features: max_streams x max_frames x 1024 x (L / M) / hop x n_mels is 2^31 or more"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     const size_t hist_bytes = (size_t)p->cfg.max_streams * 2u * (K - 1u) * sizeof(float);
     void *d_basis = nullptr, *d_fb = nullptr, *d_hist = nullptr;
     /* (the tables, synchronously: nothing is in flight yet.  The history needs no clearing: a fresh slot's is not read) */
     if (hipMalloc(&d_basis, n_basis * sizeof(float)) != hipSuccess || hipMalloc(&d_fb, n_fb * sizeof(float)) != hipSuccess || hipMalloc(&d_hist, hist_bytes) != hipSuccess ||
-        !lanes_alloc(p, &lane_t::d_ft, (size_t)most * sizeof(float), &lane_t::ft_done) ||
-        hipMemcpy(d_basis, cfg->basis, n_basis * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_fb, cfg->fb, n_fb * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* d : {d_basis, d_fb, d_hist}) if (d) (void)hipFree(d);
-        lanes_release(p, &lane_t::d_ft, &lane_t::ft_done);
-        p->err = "aacg_pipeline_set_features: no device memory for the tables, the slots' histories and the lanes' feature frames";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
+        !lanes_alloc(p, &lane_t::d_ft, (size_t)most * sizeof(float)) ||
+        hipMemcpy(d_basis, cfg->basis, n_basis * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_fb, cfg->fb, n_fb * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return no_memory(p, {d_basis, d_fb, d_hist}, &lane_t::d_ft, "aacg_pipeline_set_features: no device memory for the tables, the slots' histories and the lanes' feature frames");
     drop_host_staging(p);
-    p->ft.d_basis = d_basis; p->ft.d_fb = d_fb; p->ft.d_hist = d_hist; p->ft.lane_elems = (size_t)most;
-    p->ft.N.assign((size_t)p->cfg.max_streams, 0u); p->ft.parity.assign((size_t)p->cfg.max_streams, 0); p->ft.fresh.assign((size_t)p->cfg.max_streams, 1);
+    p->ft.make((size_t)p->cfg.max_streams); p->ft.d_basis = d_basis; p->ft.d_fb = d_fb; p->ft.d_hist = d_hist; p->ft.lane_elems = (size_t)most;
     p->ft.H = H; p->ft.P = cfg->pad_left; p->ft.R = R; p->ft.n_mels = NM; p->ft.log = cfg->log ? 1u : 0u; p->ft.floor = cfg->floor; p->ft.K = K;
     return AACG_OK;
 }
@@ -861,45 +839,20 @@ int aacg_pipeline_set_features(aacg_pipeline* p, const aacg_features_config* cfg
 int aacg_pipeline_set_loudness(aacg_pipeline* p, const aacg_loudness_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (!cfg) { p->err = "aacg_pipeline_set_loudness: no configuration"; return AACG_ERR_INVALID_ARG; }
-    if (p->ld.hop) { p->err = "aacg_pipeline_set_loudness: the pipeline has a meter already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_loudness: a batch has been submitted (the meter is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_loudness", p->ld.hop != 0, "has a meter", "the meter", {}, !cfg)) return no;
     if (cfg->hop < 1u || cfg->hop > AACG_LOUDNESS_MAX_HOP) { p->err = "aacg_pipeline_set_loudness: hop is not in 1..2^20"; return AACG_ERR_INVALID_ARG; }
-    for (int i = 0; i < 10; i++)
-        if (!std::isfinite(cfg->coeffs[i / 5][i % 5])) { p->err = "aacg_pipeline_set_loudness: coefficient " + std::to_string(i) + " is not finite"; return AACG_ERR_INVALID_ARG; }
-    /* the largest batch's records per channel: every stream may complete a hop that earlier batches began */
-    const uint64_t most = (uint64_t)p->cfg.max_streams * ((uint64_t)p->cfg.max_frames * 1024u / cfg->hop + 1u);
+    if (not_finite(p, &cfg->coeffs[0][0], 10, "aacg_pipeline_set_loudness: coefficient ", "")) return AACG_ERR_INVALID_ARG;
+    const uint64_t most = most_hops(p, cfg->hop);          /* the largest batch's records per channel */
     if (most * p->C >= (1ull << 27)) { p->err = "aacg_pipeline_set_loudness: max_streams x (max_frames x 1024 / hop + 1) x channels is 2^27 records or more"; return AACG_ERR_INVALID_ARG; }
     /* (... and the kernel's lanes count a batch's PCM in 16-byte vectors, in 32 bits) */
     if ((uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * (1024u * p->C * pcm_elem(p) / 16u) > AACG_LOUDNESS_MAX_VECTORS) { p->err = "aacg_pipeline_set_loudness: max_streams x max_frames frames of PCM are 64 GiB or more"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
-    const size_t front16 = ((size_t)most * p->C * 2u * sizeof(float) + 15) & ~(size_t)15, block = front16 + p->res_cap16 + 16;
     const size_t state_bytes = (size_t)p->cfg.max_streams * 2u * p->C * AACG_LOUDNESS_STATE * sizeof(float);
-    /* a lane's results get a block with room for the records in front of them, device and page-locked: new blocks for every lane or
-     * for none (nothing is in flight yet; the state needs no clearing: a fresh slot's is not read) */
-    void *d_state = nullptr, *d_new[AACG_PIPELINE_MAX_LANES] = {}, *h_new[AACG_PIPELINE_MAX_LANES] = {};
-    hipEvent_t ev[AACG_PIPELINE_MAX_LANES] = {};
-    bool good = hipMalloc(&d_state, state_bytes) == hipSuccess;
-    for (int k = 0; k < p->n_lanes && good; k++)
-        good = hipMalloc(&d_new[k], block) == hipSuccess && hipMemset(d_new[k], 0, block) == hipSuccess &&
-               hipHostMalloc(&h_new[k], block, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
-    if (!good) {
-        (void)hipGetLastError();
-        if (d_state) (void)hipFree(d_state);
-        for (int k = 0; k < p->n_lanes; k++) { if (d_new[k]) (void)hipFree(d_new[k]); if (h_new[k]) (void)hipHostFree(h_new[k]); if (ev[k]) (void)hipEventDestroy(ev[k]); }
-        p->err = "aacg_pipeline_set_loudness: no device memory for the slots' state and the lanes' records";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
-    for (int k = 0; k < p->n_lanes; k++) {
-        auto& L = p->lane[k];
-        (void)hipFree(L.d_res); (void)hipHostFree(L.h_res);
-        L.d_res = (char*)d_new[k] + front16; L.h_res = (char*)h_new[k] + front16; L.d_refused = (char*)L.d_res + p->res_cap16;
-        L.count_stale = false;                          /* (the new block's count is zero) */
-        L.ld_done = ev[k];
-    }
-    p->ld.d_state = d_state; p->ld.front16 = front16;
-    p->ld.N.assign((size_t)p->cfg.max_streams, 0u); p->ld.parity.assign((size_t)p->cfg.max_streams, 0); p->ld.fresh.assign((size_t)p->cfg.max_streams, 1);
+    /* a lane's results get a block with room for the records in front of them (the state needs no clearing: a fresh slot's is not read) */
+    void* d_state = nullptr;
+    if (hipMalloc(&d_state, state_bytes) != hipSuccess || !results_blocks(p, ((size_t)most * p->C * 2u * sizeof(float) + 15) & ~(size_t)15))
+        return no_memory(p, {d_state}, nullptr, "aacg_pipeline_set_loudness: no device memory for the slots' state and the lanes' records");
+    p->ld.make((size_t)p->cfg.max_streams); p->ld.d_state = d_state;
     std::memcpy(p->ld.coeffs, cfg->coeffs, sizeof p->ld.coeffs);
     p->ld.hop = cfg->hop;
     return AACG_OK;
@@ -908,11 +861,7 @@ int aacg_pipeline_set_loudness(aacg_pipeline* p, const aacg_loudness_config* cfg
 int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (!cfg) { p->err = "aacg_pipeline_set_limiter: no configuration"; return AACG_ERR_INVALID_ARG; }
-    if (p->lim.on) { p->err = "aacg_pipeline_set_limiter: the pipeline has a limiter already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_limiter: a batch has been submitted (the limiter is set before the first)"; return AACG_ERR_INVALID_ARG; }
-    if (p->tr.on) { p->err = "aacg_pipeline_set_limiter: the pipeline has a trim already (the limiter is set before it)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_limiter", p->lim.on, "has a limiter", "the limiter", {{p->tr.on, "a trim"}}, !cfg)) return no;
     if (!(cfg->ceiling > 0.0f) || !std::isfinite(cfg->ceiling)) { p->err = "aacg_pipeline_set_limiter: ceiling is not positive and finite"; return AACG_ERR_INVALID_ARG; }
     if (!(cfg->release > 0.0f) || !(cfg->release <= 1.0f)) { p->err = "aacg_pipeline_set_limiter: release is not in (0, 1]"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
@@ -921,14 +870,9 @@ int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
     const size_t state_bytes = (size_t)p->cfg.max_streams * 2u * AACG_LIMIT_STATE(Oc) * sizeof(float);
     void* d_state = nullptr;
     /* (the state needs no clearing: a fresh slot's is not read) */
-    if (hipMalloc(&d_state, state_bytes) != hipSuccess || !lanes_alloc(p, &lane_t::d_lim, bytes, &lane_t::lim_done)) {
-        (void)hipGetLastError();
-        if (d_state) (void)hipFree(d_state);
-        p->err = "aacg_pipeline_set_limiter: no device memory for the slots' state and the lanes' limited PCM";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
-    p->lim.d_state = d_state; p->lim.ceiling = cfg->ceiling; p->lim.release = cfg->release;
-    p->lim.gain.assign((size_t)p->cfg.max_streams, 1.0f); p->lim.parity.assign((size_t)p->cfg.max_streams, 0); p->lim.fresh.assign((size_t)p->cfg.max_streams, 1);
+    if (hipMalloc(&d_state, state_bytes) != hipSuccess || !lanes_alloc(p, &lane_t::d_lim, bytes))
+        return no_memory(p, {d_state}, nullptr, "aacg_pipeline_set_limiter: no device memory for the slots' state and the lanes' limited PCM");
+    p->lim.make((size_t)p->cfg.max_streams); p->lim.d_state = d_state; p->lim.ceiling = cfg->ceiling; p->lim.release = cfg->release;
     p->lim.on = true;
     return AACG_OK;
 }
@@ -936,10 +880,7 @@ int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
 int aacg_pipeline_set_concealment(aacg_pipeline* p, const aacg_conceal_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (!cfg) { p->err = "aacg_pipeline_set_concealment: no configuration"; return AACG_ERR_INVALID_ARG; }
-    if (p->cn.on) { p->err = "aacg_pipeline_set_concealment: the pipeline conceals already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_concealment: a batch has been submitted (concealment is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_concealment", p->cn.on, "conceals", "concealment", {}, !cfg)) return no;
     if (cfg->fade_steps > 64u) { p->err = "aacg_pipeline_set_concealment: fade_steps is not in 0..64"; return AACG_ERR_INVALID_ARG; }
     if (cfg->hold_frames < 1u || cfg->hold_frames > 255u) { p->err = "aacg_pipeline_set_concealment: hold_frames is not in 1..255"; return AACG_ERR_INVALID_ARG; }
     if (!p->shaped) {
@@ -954,14 +895,9 @@ int aacg_pipeline_set_concealment(aacg_pipeline* p, const aacg_conceal_config* c
     const size_t state_bytes = aacg_conceal_state_bytes((uint32_t)p->cfg.max_streams, p->Cp);
     void* d_state = nullptr;
     /* (cleared: a slot that has been through no batch is fresh and its side is not read, but the block is small and this is once) */
-    if (hipMalloc(&d_state, state_bytes) != hipSuccess || hipMemset(d_state, 0, state_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_state) (void)hipFree(d_state);
-        p->err = "aacg_pipeline_set_concealment: no device memory for the slots' state";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
-    p->cn.d_state = d_state; p->cn.fade_steps = cfg->fade_steps; p->cn.hold_frames = cfg->hold_frames;
-    p->cn.parity.assign((size_t)p->cfg.max_streams, 0); p->cn.fresh.assign((size_t)p->cfg.max_streams, 1);
+    if (hipMalloc(&d_state, state_bytes) != hipSuccess || hipMemset(d_state, 0, state_bytes) != hipSuccess)
+        return no_memory(p, {d_state}, nullptr, "aacg_pipeline_set_concealment: no device memory for the slots' state");
+    p->cn.side.make((size_t)p->cfg.max_streams); p->cn.d_state = d_state; p->cn.fade_steps = cfg->fade_steps; p->cn.hold_frames = cfg->hold_frames;
     p->cn.on = true;
     return AACG_OK;
 }
@@ -993,22 +929,14 @@ int aacg_pipeline_gain(const aacg_pipeline* p, uint32_t slot, float* gain)
 int aacg_pipeline_set_trim(aacg_pipeline* p, const aacg_trim_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
-    if (!cfg) { p->err = "aacg_pipeline_set_trim: no configuration"; return AACG_ERR_INVALID_ARG; }
-    if (p->tr.on) { p->err = "aacg_pipeline_set_trim: the pipeline has a trim already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_trim: a batch has been submitted (the trim is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_trim", p->tr.on, "has a trim", "the trim", {}, !cfg)) return no;
     if (aacg_trim_check(cfg->skip, cfg->keep)) { p->err = "aacg_pipeline_set_trim: skip or a finite keep is 2^40 or more"; return AACG_ERR_INVALID_ARG; }
-    /* the largest batch's input, samples per channel: the kernel and its records count them in 32 bits */
-    const uint64_t most = p->rs.L ? aacg_pipe::exit_resample_most((uint32_t)p->cfg.max_streams, (uint32_t)p->cfg.max_frames, p->rs.L, p->rs.M)
-                                  : (uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames * 1024u;
+    const uint64_t most = most_samples(p);               /* the largest batch's input, samples per channel */
     if (most >= (1ull << 31)) { p->err = "aacg_pipeline_set_trim: max_streams x max_frames x 1024 (x L / M) is 2^31 samples or more"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     /* (a host batch's trimmed PCM: at most what the stage receives.  With a feature stage the trim writes nothing) */
-    if (!p->ft.K && !lanes_alloc(p, &lane_t::d_trim, (size_t)most * out_channels(p) * pcm_elem(p))) {
-        p->err = "aacg_pipeline_set_trim: no device memory for the lanes' trimmed PCM";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
-    p->tr.S.assign((size_t)p->cfg.max_streams, cfg->skip); p->tr.K.assign((size_t)p->cfg.max_streams, cfg->keep); p->tr.Q.assign((size_t)p->cfg.max_streams, 0u);
+    if (!p->ft.K && !lanes_alloc(p, &lane_t::d_trim, (size_t)most * out_channels(p) * pcm_elem(p))) return no_memory(p, {}, nullptr, "aacg_pipeline_set_trim: no device memory for the lanes' trimmed PCM");
+    p->tr.make((size_t)p->cfg.max_streams, cfg->skip, cfg->keep);
     p->tr.on = true;
     return AACG_OK;
 }
@@ -1044,47 +972,25 @@ int aacg_pipeline_loudness_out(aacg_pipeline* p, float* records, size_t capacity
 int aacg_pipeline_set_true_peak(aacg_pipeline* p, const aacg_true_peak_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
-    /* every refusal leaves the pipeline exactly as it was */
     if (!cfg) { p->err = "aacg_pipeline_set_true_peak: no configuration"; return AACG_ERR_INVALID_ARG; }
     if (!p->ld.hop) { p->err = "aacg_pipeline_set_true_peak: the pipeline has no meter (aacg_pipeline_set_loudness comes first)"; return AACG_ERR_INVALID_ARG; }
-    if (p->tp.L) { p->err = "aacg_pipeline_set_true_peak: the pipeline has a true-peak stage already"; return AACG_ERR_INVALID_ARG; }
-    if (p->submitted) { p->err = "aacg_pipeline_set_true_peak: a batch has been submitted (the stage is set before the first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_true_peak", p->tp.L != 0, "has a true-peak stage", "the stage")) return no;
     if (const int why = aacg_truepeak_check(cfg->phases, cfg->taps)) { p->err = std::string("aacg_pipeline_set_true_peak: ") + aacg_truepeak_why(why); return AACG_ERR_INVALID_ARG; }
     if (!cfg->table) { p->err = "aacg_pipeline_set_true_peak: no table"; return AACG_ERR_INVALID_ARG; }
     const size_t n_table = (size_t)cfg->phases * cfg->taps;
-    for (size_t i = 0; i < n_table; i++)
-        if (!std::isfinite(cfg->table[i])) { p->err = "aacg_pipeline_set_true_peak: coefficient " + std::to_string(i) + " is not finite"; return AACG_ERR_INVALID_ARG; }
+    if (not_finite(p, cfg->table, n_table, "aacg_pipeline_set_true_peak: coefficient ", "")) return AACG_ERR_INVALID_ARG;
     if ((uint64_t)p->cfg.max_streams * (uint64_t)p->cfg.max_frames > AACG_TRUEPEAK_MAX_FRAMES) { p->err = "aacg_pipeline_set_true_peak: max_streams x max_frames is more than 2^21 frames"; return AACG_ERR_INVALID_ARG; }
     P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
     /* the largest batch's floats, one per meter's record and channel (the meter's limit holds: below 2^27), in front of the meter's in
-     * a lane's block: new blocks for every lane or for none, as aacg_pipeline_set_loudness makes them (nothing is in flight yet).  The
-     * state IS cleared: a batch finds the partial maximum it writes to empty (aacg_pcm_truepeak.h) */
-    const uint64_t most = (uint64_t)p->cfg.max_streams * ((uint64_t)p->cfg.max_frames * 1024u / p->ld.hop + 1u);
-    const size_t tp16 = ((size_t)most * p->C * sizeof(float) + 15) & ~(size_t)15, front16 = p->ld.front16 + tp16, block = front16 + p->res_cap16 + 16;
+     * a lane's block, made again as aacg_pipeline_set_loudness made it.  The state IS cleared: a batch finds the partial maximum it
+     * writes to empty (aacg_pcm_truepeak.h) */
+    const size_t tp16 = ((size_t)most_hops(p, p->ld.hop) * p->C * sizeof(float) + 15) & ~(size_t)15;
     const size_t state_bytes = (size_t)p->cfg.max_streams * 2u * AACG_TRUEPEAK_STATE(cfg->taps, p->C) * sizeof(float);
-    void *d_table = nullptr, *d_state = nullptr, *d_new[AACG_PIPELINE_MAX_LANES] = {}, *h_new[AACG_PIPELINE_MAX_LANES] = {};
-    bool good = hipMalloc(&d_table, n_table * sizeof(float)) == hipSuccess && hipMemcpy(d_table, cfg->table, n_table * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-                hipMalloc(&d_state, state_bytes) == hipSuccess && hipMemset(d_state, 0, state_bytes) == hipSuccess;
-    for (int k = 0; k < p->n_lanes && good; k++)
-        good = hipMalloc(&d_new[k], block) == hipSuccess && hipMemset(d_new[k], 0, block) == hipSuccess &&
-               hipHostMalloc(&h_new[k], block, hipHostMallocDefault) == hipSuccess;
-    if (!good) {
-        (void)hipGetLastError();
-        if (d_table) (void)hipFree(d_table);
-        if (d_state) (void)hipFree(d_state);
-        for (int k = 0; k < p->n_lanes; k++) { if (d_new[k]) (void)hipFree(d_new[k]); if (h_new[k]) (void)hipHostFree(h_new[k]); }
-        p->err = "aacg_pipeline_set_true_peak: no device memory for the table, the slots' state and the lanes' records";
-        return AACG_ERR_OUT_OF_MEMORY;
-    }
-    for (int k = 0; k < p->n_lanes; k++) {
-        auto& L = p->lane[k];
-        (void)hipFree((char*)L.d_res - p->ld.front16); (void)hipHostFree((char*)L.h_res - p->ld.front16);
-        L.d_res = (char*)d_new[k] + front16; L.h_res = (char*)h_new[k] + front16; L.d_refused = (char*)L.d_res + p->res_cap16;
-        L.count_stale = false;                          /* (the new block's count is zero) */
-    }
-    p->ld.front16 = front16;
-    p->tp.d_table = d_table; p->tp.d_state = d_state; p->tp.T = cfg->taps;
-    p->tp.L = cfg->phases;
+    void *d_table = nullptr, *d_state = nullptr;
+    if (hipMalloc(&d_table, n_table * sizeof(float)) != hipSuccess || hipMemcpy(d_table, cfg->table, n_table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&d_state, state_bytes) != hipSuccess || hipMemset(d_state, 0, state_bytes) != hipSuccess || !results_blocks(p, p->ld.front16 + tp16))
+        return no_memory(p, {d_table, d_state}, nullptr, "aacg_pipeline_set_true_peak: no device memory for the table, the slots' state and the lanes' records");
+    p->tp.d_table = d_table; p->tp.d_state = d_state; p->tp.T = cfg->taps; p->tp.L = cfg->phases;
     return AACG_OK;
 }
 
@@ -1116,7 +1022,7 @@ int aacg_pipeline_out_samples(aacg_pipeline* p, const uint32_t* slots, const uin
         if ((int)slots[s] >= p->cfg.max_streams) { p->err = "aacg_pipeline_out_samples: stream slot out of range"; return AACG_ERR_INVALID_ARG; }
         if ((int64_t)frames_of[s] > p->cfg.max_frames) { p->err = "aacg_pipeline_out_samples: a stream brings more frames than max_frames"; return AACG_ERR_INVALID_ARG; }
     }
-    for (uint32_t s = 0; s < n_streams; s++) n_out[s] = p->rs.L ? resample_count(p, p->rs.n0[slots[s]], frames_of[s]) : frames_of[s] * 1024u;
+    for (uint32_t s = 0; s < n_streams; s++) n_out[s] = p->rs.L ? aacg_pipe::resample_count(p->rs.L, p->rs.M, p->rs.N[slots[s]], frames_of[s]) : frames_of[s] * 1024u;
     if (p->tr.on)                                        /* a trim: what the slots' windows keep of them at the slots' positions */
         for (uint32_t s = 0; s < n_streams; s++) { uint32_t first; aacg_trim_span(p->tr.Q[slots[s]], p->tr.S[slots[s]], p->tr.K[slots[s]], n_out[s], &first, &n_out[s]); }
     if (p->ft.K)                                         /* feature frames: what the samples above complete at the slots' clocks */
@@ -1159,12 +1065,12 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     for (int k = 0; k < p->n_lanes; k++) { int rc = finish_lane(p, p->lane[k]); if (rc) return rc; }
     int rc = aacg_reset_stream(p->engine, slot);
     if (rc) return engine_fail(p, "", rc);
-    if (p->rs.L) { p->rs.n0[slot] = 0; p->rs.fresh[slot] = 1; }      /* the resampler's clock starts again; the history is zeros by the rule and is not read */
-    if (p->ft.K) { p->ft.N[slot] = 0; p->ft.fresh[slot] = 1; }       /* ... and the feature stage's */
-    if (p->ld.hop) { p->ld.N[slot] = 0; p->ld.fresh[slot] = 1; }     /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
-    if (p->tr.on) p->tr.Q[slot] = 0;                                 /* ... and the trim's position; the slot's window is the caller's and stays */
-    if (p->cn.on) p->cn.fresh[slot] = 1;                             /* ... and the last good frame: the slot's next batch starts with none */
-    if (p->lim.on) p->lim.fresh[slot] = 1;                           /* ... and the limiter's held block and nodes; the slot's gain is the caller's and stays */
+    if (p->rs.L) p->rs.reset(slot);                         /* the resampler's clock starts again; the history is zeros by the rule and is not read */
+    if (p->ft.K) p->ft.reset(slot);                         /* ... and the feature stage's */
+    if (p->ld.hop) p->ld.reset(slot);                       /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
+    if (p->tr.on) p->tr.reset(slot);                        /* ... and the trim's position; the slot's window is the caller's and stays */
+    if (p->cn.on) p->cn.side.reset(slot);                   /* ... and the last good frame: the slot's next batch starts with none */
+    if (p->lim.on) p->lim.side.reset(slot);                     /* ... and the limiter's held block and nodes; the slot's gain is the caller's and stays */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
         drop_plans_with(p, slot);
@@ -1200,71 +1106,20 @@ int check_batch(aacg_pipeline* p, batch_t& B)
      * anything else goes through the lane's own page-locked staging and one host copy at collect */
     aacg_exit_batch b = {B.n, B.n_streams, B.longest, 0u, B.dev ? B.dev->stride_frames : 0u, 0u, 0u};
     b.dest = B.pcm_out ? (is_pinned(B.pcm_out) ? AACG_EXIT_HOST_PINNED : AACG_EXIT_HOST_PAGEABLE) : aacg_pipe::exit_dest_device(B.dev ? B.dev->layout : AACG_PCM_PACKED);
-    if (p->rs.L) {                                       /* what each stream emits, from the slots' clocks as they stand: they advance in enqueue_out */
-        B.rs.resize(B.n_streams);
-        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
-            const uint32_t slot = B.slots[s], n_out = resample_count(p, p->rs.n0[slot], B.frames_of[s]);
-            B.rs[s] = {first, B.frames_of[s], (uint32_t)b.rs_total, n_out, p->rs.n0[slot], slot, p->rs.parity[slot], p->rs.fresh[slot]};
-            b.rs_total += n_out;
-            if (n_out > b.rs_most) b.rs_most = n_out;
-        }
-    }
-    if (p->tr.on) {                                      /* what each stream keeps of what the stage receives, from the slots' windows and positions as they stand */
-        const int planar = b.dest == AACG_EXIT_DEV_PLANAR && !p->ft.K;
-        B.tr.resize(B.n_streams); B.tr_in.resize(B.n_streams);
-        B.tr_items = 0;
-        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
-            const uint32_t slot = B.slots[s], n_in = p->rs.L ? B.rs[s].n_out : B.frames_of[s] * 1024u, place = p->rs.L ? B.rs[s].out_first : first * 1024u;
-            uint32_t off, n_keep;
-            aacg_trim_span(p->tr.Q[slot], p->tr.S[slot], p->tr.K[slot], n_in, &off, &n_keep);
-            B.tr[s] = {place + off, n_keep, (uint32_t)b.tr_total, B.tr_items};
-            B.tr_in[s] = n_in;
-            B.tr_items += aacg_trim_items(n_keep, planar);
-            b.tr_total += n_keep;
-            if (n_keep > b.tr_most) b.tr_most = n_keep;
-        }
-    }
-    if (p->ft.K) {                                       /* what each stream's samples complete, from the slots' clocks as they stand: one channel, so samples are elements */
-        B.ft.resize(B.n_streams);
-        uint32_t items = 0;
-        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
-            const uint32_t slot = B.slots[s];
-            aacg_features_stream& r = B.ft[s];
-            /* (a trim: the stage takes the stream's kept range where it lies, possibly no sample at all, and its clock counts kept samples only) */
-            aacg_features_span(p->ft.K, p->ft.H, p->ft.P, p->ft.N[slot], p->tr.on ? B.tr[s].n_keep : p->rs.L ? B.rs[s].n_out : B.frames_of[s] * 1024u, &r);
-            r.in_first = p->tr.on ? B.tr[s].src_first : p->rs.L ? B.rs[s].out_first : first * 1024u;
-            r.out_first = (uint32_t)b.ft_total; r.item_first = items; r.slot = slot;
-            r.flags = (uint32_t)p->ft.parity[slot] | (p->ft.fresh[slot] ? 2u : 0u);
-            items += aacg_features_items(r.n_out);
-            b.ft_total += r.n_out;
-            if (r.n_out > b.ft_most) b.ft_most = r.n_out;
-        }
-    }
-    if (p->ld.hop) {                                     /* a meter: what each stream's frames complete, and whether the named destination holds it */
+    /* the records of the stages that are set, from the slots' state as it stands (aacg_pipe_slots.h): it advances in enqueue_out.  The
+     * trim in front of the feature stage: that one takes each stream's kept range */
+    if (p->rs.L) aacg_pipe::build_resample(p->rs, B.slots, B.frames_of, B.n_streams, B.rs, b);
+    if (p->tr.on) aacg_pipe::build_trim(p->tr, B.rs, b.dest == AACG_EXIT_DEV_PLANAR && !p->ft.K, B.slots, B.frames_of, B.n_streams, B.tr, B.tr_in, B.tr_items, b);
+    if (p->ft.K) aacg_pipe::build_features(p->ft, B.rs, B.tr, B.slots, B.frames_of, B.n_streams, B.ft, B.ft_items, b);
+    if (p->ld.hop) {                                     /* a meter, and the true-peak stage beside it: whether the named destinations hold the batch's records */
         if (!p->ld.armed) { p->err = "the pipeline has a meter and no destination is named for this submission's records (aacg_pipeline_loudness_out)"; return AACG_ERR_INVALID_ARG; }
-        B.ld.resize(B.n_streams);
-        uint64_t total = 0;
-        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
-            const uint32_t slot = B.slots[s], n_out = (uint32_t)aacg_loudness_emits(p->ld.hop, p->ld.N[slot], 1024ull * B.frames_of[s]);
-            B.ld[s] = {first, B.frames_of[s], (uint32_t)total, n_out, (uint32_t)(p->ld.N[slot] % p->ld.hop), slot, p->ld.parity[slot], p->ld.fresh[slot]};
-            total += n_out;
-        }
-        B.ld_floats = (size_t)total * p->C * 2u;
+        aacg_pipe::build_loudness(p->ld, p->C, p->tp.L != 0, B.slots, B.frames_of, B.n_streams, B.ld, B.ld_floats, B.tp_floats);
         if (B.ld_floats > p->ld.out_cap) { p->err = "the destination named for the loudness records is too small for this submission"; return AACG_ERR_CAPACITY; }
-        if (p->tp.L) {                                   /* ... and the true-peak stage's, a float where the meter has two */
-            if (!p->tp.armed) { p->err = "the pipeline has a true-peak stage and no destination is named for this submission's records (aacg_pipeline_true_peak_out)"; return AACG_ERR_INVALID_ARG; }
-            B.tp_floats = (size_t)total * p->C;
-            if (B.tp_floats > p->tp.out_cap) { p->err = "the destination named for the true-peak records is too small for this submission"; return AACG_ERR_CAPACITY; }
-        }
+        if (p->tp.L && !p->tp.armed) { p->err = "the pipeline has a true-peak stage and no destination is named for this submission's records (aacg_pipeline_true_peak_out)"; return AACG_ERR_INVALID_ARG; }
+        if (p->tp.L && B.tp_floats > p->tp.out_cap) { p->err = "the destination named for the true-peak records is too small for this submission"; return AACG_ERR_CAPACITY; }
     }
-    if (p->lim.on) {                                     /* a limiter: the slots' gains as they stand */
-        B.lim.resize(B.n_streams);
-        for (uint32_t s = 0, first = 0; s < B.n_streams; first += B.frames_of[s], s++) {
-            const uint32_t slot = B.slots[s];
-            B.lim[s] = {first, B.frames_of[s], slot, p->lim.parity[slot], p->lim.fresh[slot], p->lim.gain[slot], {0u, 0u}};
-        }
-    }
-    if (p->cn.on) B.cn.assign(B.n_streams, aacg_conceal_stream());      /* concealment: a record per stream, filled in with the plan's table (choose_plan) */
+    if (p->lim.on) aacg_pipe::build_limiter(p->lim, B.slots, B.frames_of, B.n_streams, B.lim);
+    if (p->cn.on) B.cn.assign(B.n_streams, aacg_conceal_stream());      /* concealment: a record per stream, made from the plan's table (choose_plan) */
     B.X = aacg_pipe::exit_plan(exit_pipe(p), b);
     return B.pcm_out ? AACG_OK : check_device_out(p, B, b);
 }
@@ -1274,28 +1129,14 @@ int check_batch(aacg_pipeline* p, batch_t& B)
  * PCM staging, if the way out goes through it */
 int stage_batch(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
 {
-    /* (a resampler's per-stream records lie behind the per-stream table, 16-byte aligned: one block, one copy up) */
+    /* (the stages' per-stream records lie behind the per-stream table, 16-byte aligned, section behind section: one block, one copy up) */
     const size_t tab_bytes = (size_t)B.n_streams * (p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)), tab16 = (tab_bytes + 15) & ~(size_t)15;
-    /* (... and a feature stage's behind those: both records are 32 bytes) */
-    const size_t rs_bytes = B.rs.size() * sizeof(aacg_resample_stream), ft_bytes = B.ft.size() * sizeof(aacg_features_stream);
-    const size_t ld_bytes = B.ld.size() * sizeof(aacg_loudness_stream);      /* (... and a meter's behind those) */
-    const size_t lim_bytes = B.lim.size() * sizeof(aacg_limit_stream);      /* (... and a limiter's behind those: every record is 32 bytes) */
-    const size_t cn_bytes = B.cn.size() * sizeof(aacg_conceal_stream);      /* (... and the concealment's behind those, 32 bytes too) */
-    const size_t tr_bytes = p->ft.K ? 0u : B.tr.size() * sizeof(aacg_trim_stream);      /* (... and the trim's behind those, 16 bytes; with a feature stage they stay down here) */
-    const size_t more = rs_bytes + ft_bytes + ld_bytes + lim_bytes + cn_bytes + tr_bytes;
+    B.R = RB(B.rs, B.ft, B.ld, B.lim, B.cn, B.tr);
+    const size_t more = B.R.lay(0);
     int rc = stage(p, &L.h_in, &L.d_bytes, &L.bytes_cap, B.bytes, B.n_bytes, B.frames, B.n, more ? tab16 + more : tab_bytes, B.G);
     if (rc) return rc;
-    B.rs_at = B.G.extra_at + tab16;
-    B.ft_at = B.rs_at + rs_bytes;
-    B.ld_at = B.ft_at + ft_bytes;
-    B.lim_at = B.ld_at + ld_bytes;
-    B.cn_at = B.lim_at + lim_bytes;
-    B.tr_at = B.cn_at + cn_bytes;
-    if (tr_bytes) std::memcpy((char*)L.h_in + B.tr_at, B.tr.data(), tr_bytes);
-    if (lim_bytes) std::memcpy((char*)L.h_in + B.lim_at, B.lim.data(), lim_bytes);
-    if (ld_bytes) std::memcpy((char*)L.h_in + B.ld_at, B.ld.data(), ld_bytes);
-    if (rs_bytes) std::memcpy((char*)L.h_in + B.rs_at, B.rs.data(), rs_bytes);
-    if (ft_bytes) std::memcpy((char*)L.h_in + B.ft_at, B.ft.data(), ft_bytes);
+    B.R.lay(B.G.extra_at + tab16);
+    B.R.copy(L.h_in);                                    /* (the concealment's once more when they are made: choose_plan) */
     L.d_frames = (char*)L.d_bytes + B.G.padded;
     if (B.X.collect_copy && !L.h_pcm) P_TRY(p, hipHostMalloc(&L.h_pcm, aacg_pipe::exit_host_capacity(exit_pipe(p)), hipHostMallocDefault), AACG_ERR_OUT_OF_MEMORY);
     return AACG_OK;
@@ -1315,12 +1156,10 @@ int choose_plan(aacg_pipeline* p, const aacg_pipeline::lane_t& L, batch_t& B)
     aacg_pipe::shape_table(p->batch_layout.data(), B.slots, B.frames_of, B.n_streams, (aacg_shape_stream*)tab);
     int rc = aacg_plan_shape_table(p->engine, p->shaped, B.set, (aacg_shape_stream*)tab, B.n_streams, p->Cp, &n_units);
     B.plan = n_units ? p->shaped : nullptr;              /* (no stream of the batch has a layout yet: nothing to transform, as with kept plans) */
-    /* concealment: the stream's words of the table again, with the side of the slot's state this batch reads */
-    for (uint32_t s = 0; s < B.n_streams && !B.cn.empty(); s++) {
-        const aacg_shape_stream& t = ((const aacg_shape_stream*)tab)[s];
-        B.cn[s] = {t.frame_first, t.frames, t.unit_first, t.frame_units, t.slot, t.nch, (uint32_t)p->cn.parity[t.slot] | (p->cn.fresh[t.slot] ? 2u : 0u), 0u};
+    if (p->cn.on) {                                      /* concealment: its records from the completed table, into their section */
+        aacg_pipe::build_conceal(p->cn, (const aacg_shape_stream*)tab, B.n_streams, B.cn);
+        B.R.copy(L.h_in, RB::CN);
     }
-    if (!B.cn.empty()) std::memcpy((char*)L.h_in + B.cn_at, B.cn.data(), B.cn.size() * sizeof(aacg_conceal_stream));
     return rc ? engine_fail(p, "aacg_plan_shape_table: ", rc) : AACG_OK;
 }
 
@@ -1373,7 +1212,7 @@ int enqueue_transform(aacg_pipeline* p, aacg_pipeline::lane_t& L, batch_t& B)
          * shape carried behind a concealed frame is that frame's */
         if (rc == AACG_OK && p->cn.on)
             rc = aacg_plan_conceal_refused(p->engine, B.plan, B.set, (aacg_parse_result*)L.d_res, (int16_t*)L.d_q, (aacg_band_meta*)L.d_meta, p->Cp,
-                                           (const aacg_conceal_stream*)((const char*)L.d_bytes + B.cn_at), B.n_streams, B.longest, p->cn.d_state,
+                                           (const aacg_conceal_stream*)((const char*)L.d_bytes + B.R.at(RB::CN)), B.n_streams, B.longest, p->cn.d_state,
                                            (uint32_t)p->cfg.max_streams, p->cn.fade_steps, p->cn.hold_frames, L.st);
         if (rc == AACG_OK && p->carry_shape) rc = aacg_plan_carry_window_shape(p->engine, B.plan, (const aacg_refresh_map*)L.d_map, B.set, L.st);
         /* the transform: behind this lane's parse and refresh (fork), in front of its copy down (join); consecutive batches of
@@ -1401,42 +1240,28 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
         if (S.what == AACG_EXIT_MIX) {                   /* the packed PCM of C channels into O */
             aacg_mix_args M = {src, dst, B.n, p->C, p->O, E, {}};
             std::memcpy(M.m, p->mix, sizeof M.m);
-            if (!aacg_mix_launch(M, L.st)) { p->err = "aacg_pcm_mix: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+            if (!aacg_mix_launch(M, L.st)) return not_served(p, "aacg_pcm_mix");
         } else if (S.what == AACG_EXIT_LIMIT) {
-            /* the packed PCM of Oc channels, gained and limited, sample for sample.  The slots' held blocks and nodes pass from batch to
-             * batch like the resampler's history: this launch waits for the one before it, here — behind this lane's parse, transform and mix */
-            const aacg_limit_args A = {src, dst, (const aacg_limit_stream*)((const char*)L.d_bytes + B.lim_at), (float*)p->lim.d_state, B.n_streams, B.n,
+            /* the packed PCM of Oc channels, gained and limited, sample for sample; the slots' held blocks and nodes pass from batch to batch */
+            const aacg_limit_args A = {src, dst, (const aacg_limit_stream*)((const char*)L.d_bytes + B.R.at(RB::LIM)), (float*)p->lim.d_state, B.n_streams, B.n,
                                        p->lim.ceiling, p->lim.release, Oc, E};
-            if (p->lim.last && p->lim.last != L.lim_done) P_TRY(p, hipStreamWaitEvent(L.st, p->lim.last, 0), AACG_ERR_NO_DEVICE);
-            if (!aacg_limit_launch(A, L.st)) { p->err = "aacg_pcm_limit: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-            P_TRY(p, hipEventRecord(L.lim_done, L.st), AACG_ERR_NO_DEVICE);
-            p->lim.last = L.lim_done;
+            if (const int rc = ordered_launch(p, L, ORD_LIMIT, [&] { return aacg_limit_launch(A, L.st) ? AACG_OK : not_served(p, "aacg_pcm_limit"); })) return rc;
         } else if (S.what == AACG_EXIT_RESAMPLE) {
-            /* the packed PCM at the new rate, either layout.  The slots' histories pass from batch to batch, and consecutive batches run on
-             * different streams: this launch waits for the one before it, here — behind this lane's parse, transform and mix, which need not wait */
-            const aacg_resample_args A = {src, dst, (const aacg_resample_stream*)((const char*)L.d_bytes + B.rs_at), (const float*)p->rs.d_table, (float*)p->rs.d_hist,
+            /* the packed PCM at the new rate, either layout; the slots' histories pass from batch to batch */
+            const aacg_resample_args A = {src, dst, (const aacg_resample_stream*)((const char*)L.d_bytes + B.R.at(RB::RS)), (const float*)p->rs.d_table, (float*)p->rs.d_hist,
                                           B.n_streams, B.n, p->rs.L, p->rs.M, p->rs.T, S.dst == AACG_EXIT_CALLER ? B.X.row : 0u, Oc, E};      /* (the row is the stage's that writes the caller's tensor) */
-            if (p->rs.last && p->rs.last != L.rs_done) P_TRY(p, hipStreamWaitEvent(L.st, p->rs.last, 0), AACG_ERR_NO_DEVICE);
-            if (!aacg_resample_launch(A, L.st)) { p->err = "aacg_pcm_resample: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-            P_TRY(p, hipEventRecord(L.rs_done, L.st), AACG_ERR_NO_DEVICE);
-            p->rs.last = L.rs_done;
+            if (const int rc = ordered_launch(p, L, ORD_RESAMPLE, [&] { return aacg_resample_launch(A, L.st) ? AACG_OK : not_served(p, "aacg_pcm_resample"); })) return rc;
         } else if (S.what == AACG_EXIT_FEATURES) {
-            /* the one channel of PCM, as the stage before left it, into feature frames, either layout.  The slots' histories pass from batch
-             * to batch like the resampler's: this launch waits for the one before it, here */
-            uint32_t items = 0;
-            for (const auto& r : B.ft) items += aacg_features_items(r.n_out);
-            const aacg_features_args A = {src, (float*)dst, (const aacg_features_stream*)((const char*)L.d_bytes + B.ft_at), (const float*)p->ft.d_basis, (const float*)p->ft.d_fb,
-                                          (float*)p->ft.d_hist, B.n_streams, items, p->ft.K, p->ft.H, p->ft.R, p->ft.n_mels, p->ft.floor, p->ft.log, B.X.ft_row, E};
-            if (p->ft.last && p->ft.last != L.ft_done) P_TRY(p, hipStreamWaitEvent(L.st, p->ft.last, 0), AACG_ERR_NO_DEVICE);
-            if (!aacg_features_launch(A, L.st)) { p->err = "aacg_pcm_features: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-            P_TRY(p, hipEventRecord(L.ft_done, L.st), AACG_ERR_NO_DEVICE);
-            p->ft.last = L.ft_done;
+            /* the one channel of PCM, as the stage before left it, into feature frames, either layout; the slots' histories pass from batch to batch */
+            const aacg_features_args A = {src, (float*)dst, (const aacg_features_stream*)((const char*)L.d_bytes + B.R.at(RB::FT)), (const float*)p->ft.d_basis, (const float*)p->ft.d_fb,
+                                          (float*)p->ft.d_hist, B.n_streams, B.ft_items, p->ft.K, p->ft.H, p->ft.R, p->ft.n_mels, p->ft.floor, p->ft.log, B.X.ft_row, E};
+            if (const int rc = ordered_launch(p, L, ORD_FEATURES, [&] { return aacg_features_launch(A, L.st) ? AACG_OK : not_served(p, "aacg_pcm_features"); })) return rc;
         } else if (S.what == AACG_EXIT_TRIM) {
             /* each stream's kept range of the packed PCM, as the stage before left it, either layout.  No state: nothing to wait for and
              * no event.  A batch that keeps nothing launches nothing for a packed destination; a planar one still gets its zeros */
             const uint64_t src_elems = (uint64_t)(p->rs.L ? B.rs.back().out_first + B.rs.back().n_out : B.n * 1024u) * Oc;
-            const aacg_trim_args A = {src, dst, (const aacg_trim_stream*)((const char*)L.d_bytes + B.tr_at), src_elems, B.n_streams, B.tr_items, B.X.row, Oc, E};
-            if (B.tr_items && !aacg_trim_launch(A, L.st)) { p->err = "aacg_pcm_trim: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+            const aacg_trim_args A = {src, dst, (const aacg_trim_stream*)((const char*)L.d_bytes + B.R.at(RB::TR)), src_elems, B.n_streams, B.tr_items, B.X.row, Oc, E};
+            if (B.tr_items && !aacg_trim_launch(A, L.st)) return not_served(p, "aacg_pcm_trim");
         } else if (S.tail == AACG_EXIT_TAIL_COPY_DOWN && p->tr.on && !S.bytes) {
             /* (a trim kept nothing of the batch: no copy of nothing) */
         } else if (S.tail == AACG_EXIT_TAIL_PLANAR_LAUNCH) {
@@ -1444,7 +1269,7 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
              * begins with frame_first and frames), padding included: where the copy down sits for a host batch */
             const aacg_planar_args A = {src, dst, (const char*)L.d_bytes + B.G.extra_at, (uint32_t)(p->shaped ? sizeof(aacg_shape_stream) : sizeof(aacg_pipe_stream)),
                                         B.n_streams, B.dev->stride_frames, Oc, E};
-            if (!aacg_planar_launch(A, L.st)) { p->err = "aacg_pcm_planar: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
+            if (!aacg_planar_launch(A, L.st)) return not_served(p, "aacg_pcm_planar");
         } else                                           /* AACG_EXIT_TAIL_COPY_DOWN: one SDMA copy per batch (see aacg_pipe_copy) */
             P_TRY(p, hipMemcpyAsync(dst, src, S.bytes, hipMemcpyDeviceToHost, L.st), AACG_ERR_NO_DEVICE);
     }
@@ -1454,52 +1279,39 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
     size_t ld16 = 0, tp16 = 0;
     if (p->ld.hop) {
         /* the meter: the transform's PCM, wherever the exit plan's first stage put it, into records that lie right in front of the lane's
-         * results, so that the one copy below brings both down.  The slots' state passes from batch to batch like the resampler's history:
-         * this launch waits for the one before it, here — behind this lane's parse, transform and way out, which need not wait */
+         * results, so that the one copy below brings both down.  The slots' state passes from batch to batch */
         ld16 = (B.ld_floats * sizeof(float) + 15) & ~(size_t)15;
-        aacg_loudness_args A = {exit_buf(L, B, B.X.stage[0].dst), (float*)((char*)L.d_res - ld16), (const aacg_loudness_stream*)((const char*)L.d_bytes + B.ld_at),
+        tp16 = (B.tp_floats * sizeof(float) + 15) & ~(size_t)15;
+        aacg_loudness_args A = {exit_buf(L, B, B.X.stage[0].dst), (float*)((char*)L.d_res - ld16), (const aacg_loudness_stream*)((const char*)L.d_bytes + B.R.at(RB::LD)),
                                 (float*)p->ld.d_state, B.n_streams, B.n, p->ld.hop, {}, p->C, E};
         std::memcpy(A.coeffs, p->ld.coeffs, sizeof A.coeffs);
-        if (p->ld.last && p->ld.last != L.ld_done) P_TRY(p, hipStreamWaitEvent(L.st, p->ld.last, 0), AACG_ERR_NO_DEVICE);
-        if (!aacg_loudness_launch(A, L.st)) { p->err = "aacg_pcm_loudness: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-        if (p->tp.L) {
+        const int rc = ordered_launch(p, L, ORD_METER, [&]() -> int {
+            if (!aacg_loudness_launch(A, L.st)) return not_served(p, "aacg_pcm_loudness");
+            if (!p->tp.L) return AACG_OK;
             /* the true peak, beside the meter: the same PCM and the same records, into floats that lie in front of the meter's and are
              * cleared first (hops that straddle frames arrive as atomic maxima).  Its slots' state is ordered by the meter's event, which
              * is recorded behind both launches */
-            tp16 = (B.tp_floats * sizeof(float) + 15) & ~(size_t)15;
             uint32_t* const d_tp = (uint32_t*)((char*)L.d_res - ld16 - tp16);
             if (tp16) P_TRY(p, hipMemsetAsync(d_tp, 0, tp16, L.st), AACG_ERR_NO_DEVICE);
             const aacg_truepeak_args Q = {A.src, d_tp, A.rec, (const float*)p->tp.d_table, (float*)p->tp.d_state, B.n_streams, B.n, p->ld.hop, p->tp.L, p->tp.T, p->C, E};
-            if (!aacg_truepeak_launch(Q, L.st)) { p->err = "aacg_pcm_truepeak: not a launch the kernel serves"; return AACG_ERR_INVALID_ARG; }
-        }
-        P_TRY(p, hipEventRecord(L.ld_done, L.st), AACG_ERR_NO_DEVICE);
-        p->ld.last = L.ld_done;
+            return aacg_truepeak_launch(Q, L.st) ? AACG_OK : not_served(p, "aacg_pcm_truepeak");
+        });
+        if (rc) return rc;
     }
     pipe_copy((const char*)L.d_res - ld16 - tp16, (char*)L.h_res - ld16 - tp16, tp16 + ld16 + p->res_cap16 + 16, L.st, true);      /* ... and the count is cleared for the lane's next batch (set to zero at create) */
     P_TRY(p, hipGetLastError(), AACG_ERR_NO_DEVICE);
     P_TRY(p, hipEventRecord(L.done, L.st), AACG_ERR_NO_DEVICE);
     L.busy = true; L.ticket = ++p->submitted; L.collect_pcm = B.pcm_out; L.collect_bytes = B.X.collect_copy ? (size_t)B.X.out_bytes : 0;
     L.user_results = B.results; L.user_refused = B.n_refused; L.n = B.n;
-    /* the batch is enqueued: its streams' resampler clocks advance and their histories change sides (a submission refused or failed
-     * before this point has left them alone, and what its launch wrote lies in the buffers the slots do not read) */
-    for (const auto& r : B.rs) {
-        p->rs.n0[r.slot] = (uint32_t)(((uint64_t)r.n0 + 1024ull * r.frames) % p->rs.M);
-        p->rs.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->rs.fresh[r.slot] = 0;
-    }
-    for (const auto& r : B.ft) { p->ft.N[r.slot] += r.n_in; p->ft.parity[r.slot] = (uint8_t)((r.flags & 1u) ^ 1u); p->ft.fresh[r.slot] = 0; }
-    /* ... and the meter's; its destination is this batch's now, and the next submission names its own */
-    for (const auto& r : B.ld) { p->ld.N[r.slot] += 1024ull * r.frames; p->ld.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->ld.fresh[r.slot] = 0; }
-    for (const auto& r : B.lim) { p->lim.parity[r.slot] = (uint8_t)(r.parity ^ 1u); p->lim.fresh[r.slot] = 0; }      /* ... and the limiter's held blocks change sides */
-    for (uint32_t s = 0; s < (uint32_t)B.tr_in.size(); s++) p->tr.Q[B.slots[s]] += B.tr_in[s];      /* ... and the trim's positions advance by what the streams brought */
-    /* ... and the last good frames: a stream with units has been through the launch, which wrote the other side of its slot's state */
-    if (B.plan) for (const auto& r : B.cn) if ((r.frame_units >> 8) & 0xffu) { p->cn.parity[r.slot] = (uint8_t)((r.state & 1u) ^ 1u); p->cn.fresh[r.slot] = 0; }
+    /* the batch is enqueued: its streams' clocks and positions advance and their device state changes sides (a submission refused or
+     * failed before this point has left them alone, and what its launch wrote lies in the buffers the slots do not read) */
+    aacg_pipe::commit_resample(p->rs, B.rs); aacg_pipe::commit_features(p->ft, B.ft); aacg_pipe::commit_loudness(p->ld, B.ld);
+    aacg_pipe::commit_limiter(p->lim, B.lim); aacg_pipe::commit_trim(p->tr, B.slots, B.tr_in); aacg_pipe::commit_conceal(p->cn, B.cn, B.plan != nullptr);
+    /* the meter's destination is this batch's now, and the next submission names its own */
     L.ld_user = p->ld.out; L.ld_bytes = B.ld_floats * sizeof(float);
     L.tp_user = p->tp.out; L.tp_bytes = B.tp_floats * sizeof(float);
-    if (p->tp.L) p->tp.armed = false;
-    if (p->ld.hop) {
-        if (p->ld.out_counts) for (uint32_t s = 0; s < B.n_streams; s++) p->ld.out_counts[s] = B.ld[s].n_out;
-        p->ld.armed = false;
-    }
+    if (p->ld.hop && p->ld.out_counts) for (uint32_t s = 0; s < B.n_streams; s++) p->ld.out_counts[s] = B.ld[s].n_out;
+    p->ld.armed = p->tp.armed = false;
     *ticket = L.ticket;
     return AACG_OK;
 }
