@@ -82,6 +82,7 @@
 #include "aacg_pipe_slots.h"                              /* ... and with it aacg_pipe_exit.h and the PCM stages' limits and records, host only: the bodies are the engine's */
 #define AACG_TRUEPEAK_HOST_ONLY
 #include "aacg_pcm_truepeak.h"
+#include "aacg_pcm_limit_tp.h"                            /* (host only too: both switches above are set) */
 #include "aacg_plan_shape.h"
 #include "aacg_wait.h"
 
@@ -99,6 +100,7 @@ bool aacg_resample_launch(const aacg_resample_args& A, hipStream_t s);
 bool aacg_features_launch(const aacg_features_args& A, hipStream_t s);
 bool aacg_loudness_launch(const aacg_loudness_args& A, hipStream_t s);
 bool aacg_limit_launch(const aacg_limit_args& A, hipStream_t s);
+bool aacg_limit_tp_launch(const aacg_limit_tp_args& A, hipStream_t s);
 bool aacg_truepeak_launch(const aacg_truepeak_args& A, hipStream_t s);
 bool aacg_trim_launch(const aacg_trim_args& A, hipStream_t s);
 
@@ -180,10 +182,14 @@ struct aacg_pipeline {
         void *d_table = nullptr, *d_state = nullptr;
         float* out = nullptr; size_t out_cap = 0; bool armed = false;
     } tp;
-    /* aacg_pipeline_set_limiter: the two settings (on: a limiter is set) and the slots' state on the device ([slot][2][AACG_LIMIT_STATE(Oc)] floats) */
+    /* aacg_pipeline_set_limiter: the two settings (on: a limiter is set) and the slots' state on the device ([slot][2][AACG_LIMIT_STATE(Oc)] floats).
+     * aacg_pipeline_set_limiter_true_peak: the detector's table (tp_L 0: none) and the slots' histories beside that state
+     * ([slot][2][(tp_T - 1) x Oc] floats), which follow the same parities and fresh flags */
     struct limiter_t : aacg_pipe::limiter_slots {
         float ceiling = 0.0f, release = 0.0f;
         void* d_state = nullptr;
+        uint32_t tp_L = 0, tp_T = 0;
+        void *d_tp_table = nullptr, *d_tp_hist = nullptr;
     } lim;
     /* aacg_pipeline_set_concealment: the two settings (on: the stage is set) and the slots' state on the device ([slot][2] sides,
      * aacg_conceal_state_bytes).  total: the concealed frames of collected batches */
@@ -223,6 +229,7 @@ struct aacg_pipeline {
         void* d_rs = nullptr;             /* aacg_pipeline_set_resample: the resampled PCM of a host batch, rs.lane_elems elements */
         void* d_ft = nullptr;             /* aacg_pipeline_set_features: the feature frames of a host batch, ft.lane_elems floats */
         void* d_lim = nullptr;            /* aacg_pipeline_set_limiter: the limited PCM wherever it is not a packed device batch's last stage, max_streams x max_frames x 1024 x Oc elements */
+        void* d_lim_peak = nullptr;       /* aacg_pipeline_set_limiter_true_peak: the detector's float per block of 64, max_streams x max_frames x 16 floats */
         void* d_trim = nullptr;           /* aacg_pipeline_set_trim: the trimmed PCM of a host batch, the largest batch's untrimmed elements */
         hipEvent_t ordered[ORD_STAGES] = {};      /* the events behind this lane's latest launch of each ordered stage, made at create (ordered_launch) */
         float* ld_user = nullptr; size_t ld_bytes = 0;      /* ... and the batch in flight's records: where they go at collect, and how many bytes */
@@ -657,13 +664,13 @@ void aacg_pipeline_destroy(aacg_pipeline* p)
     }
     for (auto& L : p->lane) {
         /* (d_frames lies in d_bytes, d_refused in d_res; a meter's records lie in front of d_res and h_res, in their blocks) */
-        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_lim, L.d_trim, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
+        for (void* d : {L.d_bytes, L.d_units, L.d_q, L.d_meta, L.d_res ? (void*)((char*)L.d_res - p->ld.front16) : nullptr, L.d_pcm, L.d_mix, L.d_rs, L.d_ft, L.d_lim, L.d_lim_peak, L.d_trim, L.d_map, L.d_tns_info, L.d_tns}) if (d) (void)hipFree(d);
         for (void* h : {L.h_in, L.h_pcm, L.h_res ? (void*)((char*)L.h_res - p->ld.front16) : nullptr}) if (h) (void)hipHostFree(h);
         if (L.done) (void)hipEventDestroy(L.done);
         for (hipEvent_t ev : L.ordered) if (ev) (void)hipEventDestroy(ev);
         if (L.parser) aacg_parser_destroy(L.parser);
     }
-    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state, p->tp.d_table, p->tp.d_state, p->cn.d_state}) if (d) (void)hipFree(d);
+    for (void* d : {p->rs.d_table, p->rs.d_hist, p->ft.d_basis, p->ft.d_fb, p->ft.d_hist, p->ld.d_state, p->lim.d_state, p->lim.d_tp_table, p->lim.d_tp_hist, p->tp.d_table, p->tp.d_state, p->cn.d_state}) if (d) (void)hipFree(d);
     if (p->parser) aacg_parser_destroy(p->parser);
     if (p->engine) aacg_destroy(p->engine);
     for (auto& L : p->lane) if (L.st) (void)hipStreamDestroy(L.st);
@@ -877,6 +884,35 @@ int aacg_pipeline_set_limiter(aacg_pipeline* p, const aacg_limiter_config* cfg)
     return AACG_OK;
 }
 
+int aacg_pipeline_set_limiter_true_peak(aacg_pipeline* p, const aacg_true_peak_config* cfg)
+{
+    if (!p) return AACG_ERR_INVALID_ARG;
+    if (!cfg) { p->err = "aacg_pipeline_set_limiter_true_peak: no configuration"; return AACG_ERR_INVALID_ARG; }
+    if (!p->lim.on) { p->err = "aacg_pipeline_set_limiter_true_peak: the pipeline has no limiter (aacg_pipeline_set_limiter comes first)"; return AACG_ERR_INVALID_ARG; }
+    if (const int no = refuse_set(p, "aacg_pipeline_set_limiter_true_peak", p->lim.tp_L != 0, "has a true-peak detector", "the detector", {{p->tr.on, "a trim"}})) return no;
+    if (const int why = aacg_truepeak_check(cfg->phases, cfg->taps)) { p->err = std::string("aacg_pipeline_set_limiter_true_peak: ") + aacg_truepeak_why(why); return AACG_ERR_INVALID_ARG; }
+    if (!cfg->table) { p->err = "aacg_pipeline_set_limiter_true_peak: no table"; return AACG_ERR_INVALID_ARG; }
+    const size_t n_table = (size_t)cfg->phases * cfg->taps;
+    if (not_finite(p, cfg->table, n_table, "aacg_pipeline_set_limiter_true_peak: coefficient ", "")) return AACG_ERR_INVALID_ARG;
+    P_TRY(p, hipSetDevice(p->cfg.device_ordinal), AACG_ERR_NO_DEVICE);
+    /* (the histories need no clearing: a fresh slot's is not read; the lanes' scratch is written whole by every batch's detector) */
+    const size_t hist_bytes = (size_t)p->cfg.max_streams * 2u * AACG_LIMIT_TP_HIST(cfg->taps, out_channels(p)) * sizeof(float);
+    const size_t peak_bytes = (size_t)p->cfg.max_streams * (size_t)p->cfg.max_frames * AACG_LIMIT_TP_FRAME_BLOCKS * sizeof(float);
+    void *d_table = nullptr, *d_hist = nullptr;
+    if (hipMalloc(&d_table, n_table * sizeof(float)) != hipSuccess || hipMemcpy(d_table, cfg->table, n_table * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&d_hist, hist_bytes) != hipSuccess || !lanes_alloc(p, &lane_t::d_lim_peak, peak_bytes))
+        return no_memory(p, {d_table, d_hist}, nullptr, "aacg_pipeline_set_limiter_true_peak: no device memory for the table, the slots' state and the lanes' scratch");
+    p->lim.d_tp_table = d_table; p->lim.d_tp_hist = d_hist; p->lim.tp_T = cfg->taps; p->lim.tp_L = cfg->phases;
+    return AACG_OK;
+}
+
+int aacg_pipeline_limiter_delay(const aacg_pipeline* p, uint32_t* samples)
+{
+    if (!p || !samples || !p->lim.on) return AACG_ERR_INVALID_ARG;
+    *samples = AACG_LIMIT_BLOCK + p->lim.tp_T / 2u;
+    return AACG_OK;
+}
+
 int aacg_pipeline_set_concealment(aacg_pipeline* p, const aacg_conceal_config* cfg)
 {
     if (!p) return AACG_ERR_INVALID_ARG;
@@ -1070,7 +1106,7 @@ int aacg_pipeline_reset_stream(aacg_pipeline* p, uint32_t slot)
     if (p->ld.hop) p->ld.reset(slot);                       /* ... and the meter's: its filters, energy and peak are zeros by the rule and are not read */
     if (p->tr.on) p->tr.reset(slot);                        /* ... and the trim's position; the slot's window is the caller's and stays */
     if (p->cn.on) p->cn.side.reset(slot);                   /* ... and the last good frame: the slot's next batch starts with none */
-    if (p->lim.on) p->lim.side.reset(slot);                     /* ... and the limiter's held block and nodes; the slot's gain is the caller's and stays */
+    if (p->lim.on) p->lim.side.reset(slot);                     /* ... and the limiter's held block and nodes, and its detector's history; the slot's gain is the caller's and stays */
     if (p->learn && p->layout[slot].n) {                    /* a new stream: its layout is learnt anew; the plans made for the old one go */
         p->layout[slot] = aacg_pipeline::layout_t();
         drop_plans_with(p, slot);
@@ -1245,7 +1281,11 @@ int enqueue_out(aacg_pipeline* p, aacg_pipeline::lane_t& L, const batch_t& B, ui
             /* the packed PCM of Oc channels, gained and limited, sample for sample; the slots' held blocks and nodes pass from batch to batch */
             const aacg_limit_args A = {src, dst, (const aacg_limit_stream*)((const char*)L.d_bytes + B.R.at(RB::LIM)), (float*)p->lim.d_state, B.n_streams, B.n,
                                        p->lim.ceiling, p->lim.release, Oc, E};
-            if (const int rc = ordered_launch(p, L, ORD_LIMIT, [&] { return aacg_limit_launch(A, L.st) ? AACG_OK : not_served(p, "aacg_pcm_limit"); })) return rc;
+            /* ... and with the true-peak detector the histories too: its two launches stand where the plain one stands */
+            const aacg_limit_tp_args Q = {A, (const float*)p->lim.d_tp_table, (float*)p->lim.d_tp_hist, (float*)L.d_lim_peak, p->lim.tp_L, p->lim.tp_T};
+            if (const int rc = ordered_launch(p, L, ORD_LIMIT, [&] {
+                    if (p->lim.tp_L) return aacg_limit_tp_launch(Q, L.st) ? AACG_OK : not_served(p, "aacg_pcm_limit_tp");
+                    return aacg_limit_launch(A, L.st) ? AACG_OK : not_served(p, "aacg_pcm_limit"); })) return rc;
         } else if (S.what == AACG_EXIT_RESAMPLE) {
             /* the packed PCM at the new rate, either layout; the slots' histories pass from batch to batch */
             const aacg_resample_args A = {src, dst, (const aacg_resample_stream*)((const char*)L.d_bytes + B.R.at(RB::RS)), (const float*)p->rs.d_table, (float*)p->rs.d_hist,

@@ -43,6 +43,7 @@ ABI_SYMBOLS = ["aacg_create", "aacg_destroy", "aacg_last_error", "aacg_abi_versi
                "aacg_pipeline_set_loudness", "aacg_pipeline_loudness_out", "aacg_pipeline_loudness_counts", "aacg_loudness_counts",
                "aacg_loudness_design", "aacg_loudness_integrate",
                "aacg_pipeline_set_limiter", "aacg_pipeline_set_gain", "aacg_pipeline_gain", "aacg_limiter_design",
+               "aacg_pipeline_set_limiter_true_peak", "aacg_pipeline_limiter_delay", "aacg_trim_design_delay",
                "aacg_pipeline_set_true_peak", "aacg_pipeline_true_peak_out", "aacg_true_peak_design",
                "aacg_conceal_state_bytes", "aacg_plan_conceal_refused", "aacg_pipeline_set_concealment", "aacg_pipeline_concealed",
                "aacg_pipeline_set_trim", "aacg_pipeline_set_stream_trim", "aacg_pipeline_stream_trim", "aacg_trim_counts", "aacg_trim_design"]
@@ -359,6 +360,9 @@ def load_library(path=LIB_PATH):
     L.aacg_pipeline_stream_trim.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.aacg_trim_counts.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.aacg_trim_design.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint64)] * 4
+    L.aacg_trim_design_delay.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint64)] * 4
+    L.aacg_pipeline_set_limiter_true_peak.argtypes = [C.c_void_p, C.POINTER(TruePeakConfig)]
+    L.aacg_pipeline_limiter_delay.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -567,6 +571,8 @@ class Pipeline:
     limiter: a LimiterConfig or a (ceiling, release) pair for set_limiter (aacg_pipeline_set_limiter; limiter_design makes one from dB and
     milliseconds).  A stage behind the mix and in front of the resampler: every stream's PCM is scaled by its slot's gain (set_gain, 1
     until set) and held below the ceiling, all channels alike, delayed by 64 samples; shapes and counts are what they are without it.
+    limiter_true_peak: True (true_peak_design()'s table), or a (phases, taps, table) triple, for set_limiter_true_peak
+    (aacg_pipeline_set_limiter_true_peak), with limiter: the ceiling holds for the oversampled signal too, and the delay is limiter_delay().
     true_peak: a dict for set_true_peak (aacg_pipeline_set_true_peak; true_peak_design makes the usual table) — phases, taps and table
     (phases, taps) —, on a pipeline with loudness: the oversampled peak of every hop of the meter, beside its records;
     take_true_peak gives a batch's, a list of (n_out[s], in_channels) float32 arrays.  Every other call returns what it returns without it.
@@ -581,7 +587,7 @@ class Pipeline:
     def __init__(self, channels=2, max_streams=1, max_frames=16, sample_index=3, device=0, output_kind=OUTPUT_F32,
                  parse_options=PARSE_REFERENCE_QUIRKS, lanes=0, entries=None, counts=None, device_plans=False, tns_spec=False, pns_spec=False,
                  carry_window_shape=False, mix=None, resample=None, out_rate=None, resample_taps=32, features=None, loudness=None, limiter=None, true_peak=None,
-                 conceal=None, trim=None):
+                 conceal=None, trim=None, limiter_true_peak=None):
         self.lib = load_library()
         if entries is None:
             entries, counts = standard_codebooks()
@@ -599,7 +605,7 @@ class Pipeline:
         self.resample, self.rate = None, SAMPLE_RATES[sample_index]
         self.features = None
         self.loudness, self._loud, self._loud_last = None, {}, None
-        self.limiter = None
+        self.limiter = self.limiter_true_peak = None
         self.true_peak, self._tp, self._tp_last, self._tp_armed = None, {}, None, None
         self._keep = {}
         self.conceal = None
@@ -623,6 +629,13 @@ class Pipeline:
         if limiter is not None:
             try:
                 self.set_limiter(limiter)
+            except (AacgError, ValueError, TypeError):
+                self.close()
+                raise
+        if limiter_true_peak is not None and limiter_true_peak is not False:
+            try:
+                d = true_peak_design() if limiter_true_peak is True else None
+                self.set_limiter_true_peak(*((d["phases"], d["taps"], d["table"]) if d else limiter_true_peak))
             except (AacgError, ValueError, TypeError):
                 self.close()
                 raise
@@ -739,6 +752,24 @@ class Pipeline:
         cfg = config if isinstance(config, LimiterConfig) else LimiterConfig(*[float(v) for v in config])
         self._check(self.lib.aacg_pipeline_set_limiter(self.handle, C.byref(cfg)))
         self.limiter = LimiterConfig(cfg.ceiling, cfg.release)
+
+    def set_limiter_true_peak(self, phases, taps, table):
+        """aacg_pipeline_set_limiter_true_peak: a true-peak detector with the polyphase table (phases, taps) in front of the limiter's
+        recurrence, on a pipeline with a limiter, before the first batch and the trim"""
+        h = np.ascontiguousarray(table, np.float32)
+        if h.shape != (int(phases), int(taps)):
+            raise ValueError("Pipeline: the limiter's true-peak table is not a (phases, taps) matrix")
+        cfg = TruePeakConfig(int(phases), int(taps), h.ctypes.data)
+        self._check(self.lib.aacg_pipeline_set_limiter_true_peak(self.handle, C.byref(cfg)))
+        self.limiter_true_peak = {"phases": int(phases), "taps": int(taps), "table": h}
+
+    def limiter_delay(self):
+        """aacg_pipeline_limiter_delay: the limiter's delay in samples, 64, or 64 + taps / 2 with the true-peak detector"""
+        n = C.c_uint32()
+        rc = self.lib.aacg_pipeline_limiter_delay(self.handle, C.byref(n))
+        if rc != 0:
+            raise AacgError(rc, "aacg_pipeline_limiter_delay: the pipeline has no limiter")
+        return int(n.value)
 
     def set_concealment(self, fade_steps=CONCEAL_FADE_STEPS, hold_frames=CONCEAL_HOLD_FRAMES):
         """aacg_pipeline_set_concealment: refused frames repeat the stream's last good frame, fade_steps scalefactor steps (1.5 dB) down
@@ -1034,15 +1065,20 @@ class Pipeline:
         return out, lengths[0] if lengths else counts.astype(np.int64) * 1024, res, refused
 
 
-def trim_design(skip_in, keep_in=None, limiter=False, resample=None):
+def trim_design(skip_in, keep_in=None, limiter=False, resample=None, delay=None):
     """aacg_trim_design: the window at the trim's input for a window (skip_in, keep_in) in samples of the stream's own rate and time —
     (skip, keep, residual) with keep None for no end and residual a fractions.Fraction in [0, 1) output samples.  limiter: the pipeline
-    has one (64 samples of delay); resample: the pipeline's (L, M, table) or (L, M, taps) with a linear-phase table.  Host code, exact."""
+    has one (64 samples of delay); resample: the pipeline's (L, M, table) or (L, M, taps) with a linear-phase table.  delay: the
+    limiter's delay in samples in the place of `limiter` (Pipeline.limiter_delay(): aacg_trim_design_delay).  Host code, exact."""
     import fractions
     L, M, taps = (1, 1, 0) if resample is None else (int(resample[0]), int(resample[1]), int(resample[2]) if np.ndim(resample[2]) == 0 else int(np.shape(resample[2])[1]))
     s, k, num, den = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-    rc = load_library().aacg_trim_design(int(skip_in), TRIM_ALL if keep_in is None else int(keep_in), 1 if limiter else 0, L, M, taps,
-                                         C.byref(s), C.byref(k), C.byref(num), C.byref(den))
+    if delay is not None:
+        rc = load_library().aacg_trim_design_delay(int(skip_in), TRIM_ALL if keep_in is None else int(keep_in), int(delay), L, M, taps,
+                                                   C.byref(s), C.byref(k), C.byref(num), C.byref(den))
+    else:
+        rc = load_library().aacg_trim_design(int(skip_in), TRIM_ALL if keep_in is None else int(keep_in), 1 if limiter else 0, L, M, taps,
+                                             C.byref(s), C.byref(k), C.byref(num), C.byref(den))
     if rc != 0:
         raise AacgError(rc, "aacg_trim_design(%d, %r, %d / %d, %d taps)" % (skip_in, keep_in, L, M, taps))
     return int(s.value), None if k.value == TRIM_ALL else int(k.value), fractions.Fraction(int(num.value), int(den.value))

@@ -1136,7 +1136,8 @@ int  aacg_loudness_integrate(const float* records, size_t n_hops, uint32_t chann
  * aacg_pipeline_last_error and the pipeline exactly as it was: no meter, a null config or table, phases or taps outside the limits, an
  * entry that is not finite, a call after the first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the table, the
  * slots' state and the lanes' records; the pipeline stays as it was.
- * Not here: short-term windows, a true peak behind the mix or the limiter, a table of more than 8 phases. */
+ * Not here: short-term windows, a metered true peak behind the mix or the limiter (the limiter's own detector is
+ * aacg_pipeline_set_limiter_true_peak, below), a table of more than 8 phases. */
 typedef struct aacg_true_peak_config {
     uint32_t phases;         /* L */
     uint32_t taps;           /* T */
@@ -1194,7 +1195,8 @@ int  aacg_true_peak_design(uint32_t phases, uint32_t taps, double rolloff, doubl
  * aacg_pipeline_last_error and the pipeline exactly as it was: a null config, a ceiling or release outside the limits, a call after
  * the first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the slots' state and the lanes' buffer; the pipeline
  * stays as it was.
- * Not here: true-peak (oversampled) limiting, a limiter behind the resampler, a flush of the last 64 samples. */
+ * A true-peak (oversampled) ceiling: aacg_pipeline_set_limiter_true_peak, below.  Not here: a limiter behind the resampler, a flush of
+ * the last 64 samples. */
 #define AACG_LIMIT_BLOCK 64
 typedef struct aacg_limiter_config {
     float ceiling;
@@ -1212,6 +1214,48 @@ int  aacg_pipeline_gain(const aacg_pipeline* p, uint32_t slot, float* gain);
  * release_ms / 1000)) — the share of the way back to G that a block of 64 samples covers at a time constant of release_ms.
  * AACG_ERR_INVALID_ARG: a rate of 0, a null cfg, a result outside aacg_pipeline_set_limiter's limits. */
 int  aacg_limiter_design(uint32_t rate, double ceiling_db, double release_ms, aacg_limiter_config* cfg);
+/* A TRUE-PEAK ceiling for the limiter: a detector in front of its recurrence, for a consumer whose delivery specification states the
+ * ceiling in dBTP — the plain limiter holds a sample-peak ceiling, and a sine at fs / 4 whose samples are 0.707 passes it with a true
+ * peak of 1.  It takes aacg_pipeline_set_true_peak's configuration and limits:
+ *     phases L: 1..8;  taps T: a multiple of 4 in 4..64;  table: h[L][T], row-major float32, every entry finite (aacg_true_peak_design
+ *     makes the usual one).
+ * THE RULE, bit for bit, in float32 throughout, every operation rounded on its own, nothing fused, subnormals kept.  x[j] is the slot's
+ * limiter input since its reset as aacg_pipeline_set_limiter defines it (after the mix, Oc channels, int16 as the sample times 2^-15),
+ * x[j] = 0 for j < 0.  D = T / 2, and z[j] = x[j - D] is the audio path: x delayed by the detector's group delay rounded up.  For block
+ * k, the indices j = 64 k .. 64 k + 63:
+ *     ps = max over the block's 64 x Oc samples of |z[j][ch]|
+ *     acc_ph[j][ch] = h[ph][0] * x[j][ch]                                      (rounded to float)
+ *     acc_ph[j][ch] = acc_ph[j][ch] + (h[ph][t] * x[j - t][ch])   t = 1 .. T-1  (the product rounded, then the sum rounded, in this order)
+ *     pt = max over the block's 64 x L x Oc values of |acc_ph[j][ch]|           (aacg_pipeline_set_true_peak's accumulation, on x)
+ *     p  = fmaxf(ps, pt)
+ * every maximum an fmaxf from +0 in which a NaN is ignored, as the plain rule ignores a NaN sample.  Then the limiter's rule unchanged
+ * with xk := block k of z and this p: tk, u, a1, the ramp, xh = xk; a0 = a1; th = tk.  A maximum does not depend on order, so nothing in
+ * the result depends on how the device splits the work.  numpy float32 arithmetic reproduces the result exactly.
+ * What follows from the rule.  A batch emits exactly as many samples as it brings, delayed by 64 + T / 2 (aacg_pipeline_limiter_delay);
+ * buffer sizes, aacg_pipeline_out_samples and every copy keep their values.  Any split of a stream's frames into batches gives the same
+ * bits.  A fresh slot (create, aacg_pipeline_reset_stream) holds zeros for the held block and for the T - 1 samples of history, with
+ * a0 = th = G.  Since p >= ps, guarantee (a) of the plain limiter holds: |out| <= c (1 + 2^-21) for finite input.  The detector at block k
+ * covers the signal times [64 k - D + 1 / (2 L), 64 k + 63 - D + 1), which lie inside the span of the audio block it governs, so both node
+ * gains around a held block are <= c / p of that block, as before.  The TRUE-PEAK bound is NOT exact: while the gain moves inside the
+ * filter's window the delivered signal is not a scaled copy of the measured one.  With a gain at rest the delivered true peak, read with
+ * the detector's own table, is <= c (1 + 2^-20); under a moving gain it has been measured a little above c (DESIGN.md section 8 has the
+ * figures), and a reading with another table differs by what the two tables differ.
+ * State per slot: the plain limiter's, and the last T - 1 input samples per channel, on the device, handed from batch to batch across
+ * lanes alike.  Two launches per batch (aacg_pcm_limit_tp_detect_*, aacg_pcm_limit_tp_*) on the lane's stream in the place of the plain
+ * limiter's one, and per lane a scratch of one float per block of 64; it goes with everything the limiter goes with.  The meter's
+ * true-peak stage (aacg_pipeline_set_true_peak) is independent of it: that one taps the transform's PCM, this one sits in the chain.
+ * With the call unused nothing differs, call for call.
+ * Called once, on a pipeline that has a limiter, before the first submitted batch and in front of aacg_pipeline_set_trim, like the
+ * limiter; its order relative to _set_resample, _set_features, _set_loudness and _set_true_peak is free.  AACG_ERR_INVALID_ARG, with the
+ * reason in aacg_pipeline_last_error and the pipeline exactly as it was: no limiter, a null config or table, phases or taps outside the
+ * limits, an entry that is not finite, a call after the first batch, a second call.  AACG_ERR_OUT_OF_MEMORY: no device memory for the
+ * table, the slots' state or the lanes' scratch; the pipeline keeps its plain limiter.
+ * Not here: an exact dBTP bound under a moving gain, a table of more than 8 phases, a limiter behind the resampler, a flush of the held
+ * samples. */
+int  aacg_pipeline_set_limiter_true_peak(aacg_pipeline* p, const aacg_true_peak_config* cfg);
+/* The limiter's delay in samples per channel: AACG_LIMIT_BLOCK = 64, or 64 + T / 2 with the detector (what aacg_trim_design_delay
+ * takes).  AACG_ERR_INVALID_ARG: a pipeline without a limiter, a null pointer. */
+int  aacg_pipeline_limiter_delay(const aacg_pipeline* p, uint32_t* samples);
 
 /* ---- the resident route: refused frames concealed ----------------------------------------------------------------------------------
  * An optional stage in front of the transform: a frame the parser or the refresh refused repeats its stream's last good frame, fading
@@ -1299,6 +1343,11 @@ int  aacg_trim_counts(uint64_t position, uint64_t skip, uint64_t keep, const uin
  * result there. */
 int  aacg_trim_design(uint64_t skip_in, uint64_t keep_in, int limiter, uint32_t L, uint32_t M, uint32_t taps, uint64_t* skip, uint64_t* keep,
                       uint64_t* residual_num, uint64_t* residual_den);
+/* ... with the limiter's delay in samples (aacg_pipeline_limiter_delay: 64, or 64 + T / 2 with the true-peak detector; 0: no limiter) in
+ * the place of 64 x limiter: A(t) = 2 L t + 2 L delay + L taps - 1, the rest unchanged.  delay = 64 gives exactly
+ * aacg_trim_design(..., 1, ...), delay = 0 exactly (..., 0, ...).  The same refusals. */
+int  aacg_trim_design_delay(uint64_t skip_in, uint64_t keep_in, uint32_t delay, uint32_t L, uint32_t M, uint32_t taps, uint64_t* skip, uint64_t* keep,
+                            uint64_t* residual_num, uint64_t* residual_den);
 
 #ifdef __cplusplus
 }

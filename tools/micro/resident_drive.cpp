@@ -7,7 +7,7 @@
  *   tools/micro/resident_drive <file.aac> [--streams S] [--frames F] [--batches N] [--lanes L] [--i16] [--sync] [--pageable]
  *                                         [--device-plans] [--new-shapes [--seed N]] [--tns-spec] [--pns-spec] [--pulses]
  *                                         [--carry-shape] [--device-pcm [--planar]] [--mix 1|2] [--rate OUT] [--features]
- *                                         [--loudness [--true-peak]] [--limiter] [--conceal] [--drop-every N] [--trim SKIP[:KEEP]]
+ *                                         [--loudness [--true-peak]] [--limiter [--limit-tp]] [--conceal] [--drop-every N] [--trim SKIP[:KEEP]]
  *
  * --trim SKIP[:KEEP]: a trim as the last PCM stage (aacg_pipeline_set_trim: every slot's window skips SKIP samples of what the stage
  * receives and keeps KEEP, all of the rest if left out): one more launch per batch (aacg_pcm_trim_*) behind the resampler, none with
@@ -26,6 +26,9 @@
  * rate with a ceiling of -1 dB and a release of 200 ms; aacg_pipeline_set_limiter; slot s gets the gain 0.5 + 0.5 (s mod 8) through
  * aacg_pipeline_set_gain, so that some streams are boosted into the ceiling): one more launch per batch (aacg_pcm_limit_*).  The line
  * then carries the two settings and the bytes that launch reads and writes.  Combines with everything else.
+ * --limit-tp (with --limiter): a true-peak detector in front of the limiter's recurrence (aacg_true_peak_design's four phases of 24 taps
+ * with beta 5; aacg_pipeline_set_limiter_true_peak): two launches per batch (aacg_pcm_limit_tp_detect_*, aacg_pcm_limit_tp_*) in the
+ * place of the limiter's one.  The line then carries the table's shape and the stage's delay (aacg_pipeline_limiter_delay).
  *
  * --true-peak (with --loudness): the oversampled peak of every hop of the meter beside its records (aacg_true_peak_design's four phases
  * of 24 taps with beta 5; aacg_pipeline_set_true_peak): one more launch per batch (aacg_pcm_truepeak_*) over the transform's PCM, and a
@@ -99,7 +102,7 @@ int main(int argc, char** argv)
     bool i16 = false, sync = false, pageable = false, device_plans = false, new_shapes = false, tns_spec = false, pns_spec = false, pulses = false, carry_shape = false, device_pcm = false, planar = false;
     uint64_t seed = 1;
     uint32_t mix = 0, rate = 0;
-    bool features = false, loudness = false, limiter = false, true_peak = false, conceal = false;
+    bool features = false, loudness = false, limiter = false, limit_tp = false, true_peak = false, conceal = false;
     uint32_t drop_every = 0;
     bool trim = false;
     uint64_t trim_skip = 0, trim_keep = AACG_TRIM_ALL;
@@ -127,6 +130,7 @@ int main(int argc, char** argv)
         else if (a == "--loudness") loudness = true;
         else if (a == "--true-peak") true_peak = true;
         else if (a == "--limiter") limiter = true;
+        else if (a == "--limit-tp") limit_tp = true;
         else if (a == "--conceal") conceal = true;
         else if (a == "--drop-every") drop_every = (uint32_t)std::atoi(val());
         else if (a == "--trim") {
@@ -194,6 +198,15 @@ int main(int argc, char** argv)
         for (uint32_t s = 0; s < S; s++)
             if ((rc = aacg_pipeline_set_gain(p, s, 0.5f + 0.5f * (float)(s % 8u)))) { std::fprintf(stderr, "aacg_pipeline_set_gain: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
     }
+    uint32_t lim_delay = 0;
+    if (limit_tp) {                                         /* the detector in front of the limiter's recurrence; in front of the trim, like the limiter */
+        if (!limiter) { std::fprintf(stderr, "--limit-tp goes with --limiter\n"); return 2; }
+        std::vector<float> table(4u * 24u);
+        if ((rc = aacg_true_peak_design(4, 24, 0.95, 5.0, table.data(), table.size()))) { std::fprintf(stderr, "aacg_true_peak_design: %d\n", rc); return 2; }
+        const aacg_true_peak_config tc = {4, 24, table.data()};
+        if ((rc = aacg_pipeline_set_limiter_true_peak(p, &tc))) { std::fprintf(stderr, "aacg_pipeline_set_limiter_true_peak: %d %s\n", rc, aacg_pipeline_last_error(p)); return 2; }
+    }
+    if (limiter && (rc = aacg_pipeline_limiter_delay(p, &lim_delay))) { std::fprintf(stderr, "aacg_pipeline_limiter_delay: %d\n", rc); return 2; }
     uint32_t rs_L = 1, rs_M = 1;
     if (rate) {
         static const uint32_t rates[16] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350, 0, 0, 0};
@@ -354,9 +367,10 @@ int main(int argc, char** argv)
             std::snprintf(loudness_key + at, sizeof loudness_key - (size_t)at, "\"true_peak\": \"kaiser\", \"true_peak_phases\": %u, \"true_peak_taps\": %u, \"true_peak_largest\": %.6g, ", tp_L, tp_T, largest);
         }
     }
-    char limiter_key[192] = "";                             /* --limiter only: what aacg_pcm_limit_* reads and writes is 2 n Oc 1024 E */
+    char limiter_key[320] = "";                             /* --limiter only: what aacg_pcm_limit_* reads and writes is 2 n Oc 1024 E */
     if (limiter) std::snprintf(limiter_key, sizeof limiter_key, "\"limiter\": \"-1 dB, 200 ms\", \"limiter_ceiling\": %.6f, \"limiter_release\": %.6g, \"limiter_bytes_moved_per_batch\": %zu, ",
                                (double)lim_cfg.ceiling, (double)lim_cfg.release, 2 * resample_in_bytes);
+    if (limit_tp) std::snprintf(limiter_key + std::strlen(limiter_key), sizeof limiter_key - std::strlen(limiter_key), "\"limiter_true_peak\": \"kaiser\", \"limiter_true_peak_phases\": 4, \"limiter_true_peak_taps\": 24, \"limiter_delay\": %u, ", lim_delay);
     char features_key[192] = "";                            /* --features only */
     if (features) std::snprintf(features_key, sizeof features_key, "\"features\": \"log-mel\", \"frame_length\": %u, \"hop\": %u, \"n_bins\": %u, \"n_mels\": %u, \"feature_frames_per_stream_most\": %zu, ", ft_K, ft_H, ft_bins, ft_mels, most_ft);
     char conceal_key[192] = "";                             /* --conceal / --drop-every only */
